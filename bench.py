@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: Pippenger MSMs/sec at n = 2^20 (BASELINE.json configs[1]) on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--open-steps J]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--dump-outputs DIR] [--full [--open-steps J] ...]
+
+A plain run sets up, warms up, times exactly K steps once, writes the last step's MSM results if --dump-outputs is given,
+and prints the headline line.  --full adds everything else the benchmark measures or checks: the cold path, the solo latency,
+the kernel-duration passes behind `roofline`, the host-scalar, variable-base, open + check, Fr-kernel and ASDL legs, the CPU
+baselines with their bit-for-bit comparisons, and for N > 1 the sharded open + check and the cross-checks against one GPU.
 
 However it is started it prints one line: under torch.distributed.run (WORLD_SIZE set) it is one rank of N; started plainly
 with --gpus N > 1 it drives the N GPUs from this ONE process through a multi-device context (as with --one-process).
@@ -62,7 +67,13 @@ def main():
                          "auto = index blocks while a rank's block has >= 2^17 points (a fixed-base-table MSM), else windows")
     ap.add_argument("--open-steps", type=int, default=12, help="PCDL open+check repetitions at N=1 (0 = skip)")
     ap.add_argument("--cpu-msms", type=int, default=2, help="oracle MSMs timed for cpu_baseline at N=1 (0 = skip)")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="repeat the K-step timed region until this much time is covered; the median repetition is reported")
+    ap.add_argument("--min-seconds", type=float, default=0.0, help="repeat the K-step timed region until this much time is covered; the median repetition is reported "
+                                                                   "(default 0: the region runs once, exactly K steps)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beyond the headline (see the module docstring); the "
+                                                        "options below that size a leg apply to --full runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the MSM results of the last step to DIR/msm_results.npy: float64, one row per MSM of a "
+                         "launch, the 12 u64 words of the normalised Jacobian point (include/halo_accumulation.h) as 24 little-endian u32 halves")
     ap.add_argument("--one-process", action="store_true",
                     help="--gpus N from ONE process (no torch.distributed): a multi-device context (halo_ctx_create_urs_multi), one "
                          "index-block shard per GPU, partial points added on the host")
@@ -143,7 +154,7 @@ def main():
         # index shard: this rank's block of the key (main.rs:35-45: G_i = hash(i + 2)) and of the scalars
         (lo, hi), part, parts = shard_range(n, rank, world), 0, 1
     cold_path = None
-    if world == 1 and not one_proc and args.open_steps > 0 and args.log_n >= 18:
+    if args.full and world == 1 and not one_proc and args.open_steps > 0 and args.log_n >= 18:
         # THE COLD PATH: a FRESH context in its default configuration does ten open + check pairs, each timed.  The
         # automatic fold table waits for the key's 8th full-size open (csrc/foldtab.hip): a caller with a handful of opens never
         # reserves or pays for it.  Run before the main context exists, closed afterwards: nothing of it is left for the timed legs.
@@ -198,7 +209,7 @@ def main():
     first = ctx.msm_dev(ptrs[0], hi - lo) if not window_mode else None
     t_first = time.perf_counter() - t0
     solo = []
-    if not window_mode:
+    if args.full and not window_mode:
         for _ in range(12):
             t0 = time.perf_counter()
             again = ctx.msm_dev(ptrs[0], hi - lo)
@@ -245,8 +256,9 @@ def main():
 
     run_steps(3 * args.depth * batch)  # untimed: every slot allocates its workspace and captures its launch graph
     run_steps(args.warmup)
-    # The timed region is EXACTLY --steps steps between barrier + synchronize; it is repeated until --min-seconds are covered
-    # (a 20-step region lasts 25 ms: one sample says little) and the median repetition is reported, all of them listed.
+    # The timed region is EXACTLY --steps steps between barrier + synchronize.  By default it runs once; --min-seconds repeats it
+    # until that much time is covered (a 20-step region lasts 25 ms: one sample says little) and the median repetition is
+    # reported, all of them listed.
     reps = []
     while True:
         barrier()
@@ -262,27 +274,34 @@ def main():
             break
     dt = sorted(reps)[len(reps) // 2]
     out = outs[0]
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path received in the last step: one normalised point per MSM of the launch (combined over
+        # the ranks / shards for N > 1), written losslessly as float64 u32 halves
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        pts = np.ascontiguousarray(np.stack([outs[j] for j in range(min(batch, args.steps))]), dtype=np.uint64)
+        np.save(os.path.join(args.dump_outputs, "msm_results.npy"), pts.view(np.uint32).astype(np.float64))
 
-    # Kernel durations for the roofline: HIP events on the stream each kernel is launched on, in two
-    # extra passes of the same loop right after the timed region (the event brackets need individual
-    # launches, the timed region replays the launch sequence as a hipGraph): (a) as timed, several
-    # launches in flight -- kernels of different slots time-share the CUs and every duration stretches;
-    # (b) one launch in flight: the kernel by itself, which is what a roofline fraction is about.
-    prof_steps = max(batch, min(args.steps, 8 * batch) // batch * batch)  # whole launches only
-    ctx.prof_enable(2)
-    ctx.prof_reset()
-    barrier()
-    run_steps(prof_steps)
-    barrier()
-    prof = ctx.prof()
-    cfg["depth"] = 1
-    ctx.prof_reset()
-    barrier()
-    run_steps(prof_steps)
-    barrier()
-    prof_solo = ctx.prof()
-    cfg["depth"] = args.depth
-    ctx.prof_enable(0)
+    if args.full:
+        # Kernel durations for the roofline: HIP events on the stream each kernel is launched on, in two
+        # extra passes of the same loop right after the timed region (the event brackets need individual
+        # launches, the timed region replays the launch sequence as a hipGraph): (a) as timed, several
+        # launches in flight -- kernels of different slots time-share the CUs and every duration stretches;
+        # (b) one launch in flight: the kernel by itself, which is what a roofline fraction is about.
+        prof_steps = max(batch, min(args.steps, 8 * batch) // batch * batch)  # whole launches only
+        ctx.prof_enable(2)
+        ctx.prof_reset()
+        barrier()
+        run_steps(prof_steps)
+        barrier()
+        prof = ctx.prof()
+        cfg["depth"] = 1
+        ctx.prof_reset()
+        barrier()
+        run_steps(prof_steps)
+        barrier()
+        prof_solo = ctx.prof()
+        cfg["depth"] = args.depth
+        ctx.prof_enable(0)
 
     # what the collective layer itself reports: backend, ranks, and how many distinct devices they sit on
     backend_name, world_reported, distinct_gpus, coll_name = "none", 1, 1, "no"
@@ -296,6 +315,32 @@ def main():
         distinct_gpus = len(set(idents))
     result = None
     if rank == 0:
+        result = {
+            "metric": "MSMs/sec (Pippenger, Pallas, n=2^%d random scalars/URS points, bit-exact vs CPU)" % args.log_n,
+            "value": args.steps / dt, "unit": "MSM/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "timed_region": {"repetitions": len(reps), "reported": "median", "seconds_each": [round(x, 6) for x in reps[:32]]},
+            "dtype": "u32x8 (256-bit Montgomery integer)", "data": "synthetic",
+            "config": {"workload": "Pippenger MSM n=2^%d, bases = URS G_i by main.rs rule, scalars SplitMix64 seed 0x48414C4F00000002" % args.log_n,
+                       "sharding": (devices_note + "one process, multi-device context: %d index-block shards on devices %s, partial points added on the host "
+                                    "(no collective)" % (len(devices), devices)) if one_proc and args.gpus > 1 else "single GPU" if world == 1 else
+                                   ("Pippenger windows split over the ranks (key + scalars replicated), %s all-gather of 96 B partials" % coll_name if window_mode
+                                    else "block index shard per rank + %s all-gather of 96 B partials" % coll_name),
+                       "collective_backend": backend_name, "world_size": world_reported,
+                       "distinct_gpus": len(set(devices)) if one_proc else distinct_gpus,
+                       "msms_per_launch": batch, "launches_in_flight": args.depth,
+                       "window_bits": "a rank's block of >= 2^20 points: 20 with fixed-base tables over the context's key (13 windows, one set "
+                                      "of 2^19 buckets); index blocks of 2^17..2^19 points: 17 (15 windows, 2^16 buckets per MSM of a batch); "
+                                      "window shards: 16 (16-window general plan)"},
+            "context_setup_ms": {"key_on_device_and_workspace": t_setup_urs * 1e3,
+                                 "first_msm_incl_table_build": t_first * 1e3,
+                                 "note": "one-time: halo_ctx_create_urs (k_urs over this rank's block + slot-0 workspace), then the first MSM, which "
+                                         "builds the fixed-base table (k_table_step per window) before it runs"},
+            "table_bytes": ((13 if hi - lo >= (1 << 20) else 15) * 128 * (hi - lo) if (not window_mode and hi - lo >= (1 << 17)) else 0),
+            "hbm_roofline_frac_whole_msm": (args.steps / dt) * (96 * n + 64) / (HBM_PEAK_GBS * 1e9),
+        }
+
+    if rank == 0 and args.full:
         dom = "k_msm_accumulate" if "k_msm_accumulate" in prof_solo else "k_smsm_accumulate"  # n <= 2^16: the small-MSM pipeline
         acc_ms, acc_cnt = prof_solo.get(dom, (0.0, 0))
         # per launch sequence: an MSM of more than 1.3 M points runs the kernel once per piece, and the
@@ -343,45 +388,21 @@ def main():
                     valu["clock_ghz_during_kernel"] = k["clock_ghz"]
                     valu["wave_cycles_parked"] = k["wave_parked"]
                     valu["issue_source"] = "static: profiles/%s (rocprofv3 --pmc SQ_INSTS_VALU GRBM_GUI_ACTIVE SQ_WAIT_ANY ..., one MSM in flight)" % os.path.basename(sq)
-        result = {
-            "metric": "MSMs/sec (Pippenger, Pallas, n=2^%d random scalars/URS points, bit-exact vs CPU)" % args.log_n,
-            "value": args.steps / dt, "unit": "MSM/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "timed_region": {"repetitions": len(reps), "reported": "median", "seconds_each": [round(x, 6) for x in reps[:32]]},
-            "dtype": "u32x8 (256-bit Montgomery integer)", "data": "synthetic",
-            "config": {"workload": "Pippenger MSM n=2^%d, bases = URS G_i by main.rs rule, scalars SplitMix64 seed 0x48414C4F00000002" % args.log_n,
-                       "sharding": (devices_note + "one process, multi-device context: %d index-block shards on devices %s, partial points added on the host "
-                                    "(no collective)" % (len(devices), devices)) if one_proc and args.gpus > 1 else "single GPU" if world == 1 else
-                                   ("Pippenger windows split over the ranks (key + scalars replicated), %s all-gather of 96 B partials" % coll_name if window_mode
-                                    else "block index shard per rank + %s all-gather of 96 B partials" % coll_name),
-                       "collective_backend": backend_name, "world_size": world_reported,
-                       "distinct_gpus": len(set(devices)) if one_proc else distinct_gpus,
-                       "msms_per_launch": batch, "launches_in_flight": args.depth,
-                       "window_bits": "a rank's block of >= 2^20 points: 20 with fixed-base tables over the context's key (13 windows, one set "
-                                      "of 2^19 buckets); index blocks of 2^17..2^19 points: 17 (15 windows, 2^16 buckets per MSM of a batch); "
-                                      "window shards: 16 (16-window general plan)"},
-            "roofline": {"bound": "hbm", "kernel": dom, "symbol": "halo::" + str(dom), "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel_ms": kern_s * 1e3, "kernel_ms_while_%d_launches_in_flight" % args.depth: ovl_ms / max(ovl_cnt, 1),
-                         "algorithmic_bytes": alg_bytes, "valu": valu,
-                         "note": "integer-VALU-bound kernel: see DESIGN.md for the VALU roofline"},
-            "solo_latency_ms": (sorted(solo)[len(solo) // 2] * 1e3 if solo else None),
-            "context_setup_ms": {"key_on_device_and_workspace": t_setup_urs * 1e3,
-                                 "first_msm_incl_table_build": t_first * 1e3,
-                                 "note": "one-time: halo_ctx_create_urs (k_urs over this rank's block + slot-0 workspace), then the first MSM, which "
-                                         "builds the fixed-base table (k_table_step per window) before it runs"},
-            "table_bytes": ((13 if hi - lo >= (1 << 20) else 15) * 128 * (hi - lo) if (not window_mode and hi - lo >= (1 << 17)) else 0),
-            "hbm_roofline_frac_whole_msm": (args.steps / dt) * (96 * n + 64) / (HBM_PEAK_GBS * 1e9),
-        }
+        result["roofline"] = {"bound": "hbm", "kernel": dom, "symbol": "halo::" + str(dom), "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                              "kernel_ms": kern_s * 1e3, "kernel_ms_while_%d_launches_in_flight" % args.depth: ovl_ms / max(ovl_cnt, 1),
+                              "algorithmic_bytes": alg_bytes, "valu": valu,
+                              "note": "integer-VALU-bound kernel: see DESIGN.md for the VALU roofline"}
+        result["solo_latency_ms"] = (sorted(solo)[len(solo) // 2] * 1e3 if solo else None)
 
-    if one_proc and args.gpus > 1:
+    if args.full and one_proc and args.gpus > 1:
         # cross-check: the same MSM on a plain one-device context
         full = h._lib.Context(urs_n=n, first_index=2, device=gpu)
         ok = full.msm_dev(ptrs[0], n).tolist() == outs[0].tolist()
         full.close()
         result["sharded_equals_single_gpu"] = ok
         assert ok, "multi-device MSM differs from the single-GPU MSM"
-    elif world == 1:
+    elif args.full and world == 1:
         # Everything below runs on the GPU only; the CPU restatement (oracle/) is touched in ONE leg at the very end, which
         # times it on the host cores as the reported baseline and compares what the GPU produced above with it, bit for bit.
         cpu_model = "unknown"
@@ -927,7 +948,7 @@ def main():
                     "accumulators_bit_exact": True}
         if ctx_small is not None and ctx_small is not ctx:
             ctx_small.close()
-    if (world > 1 or force_dist) and args.open_steps > 0 and world & (world - 1) == 0 and n % world == 0:
+    if args.full and (world > 1 or force_dist) and args.open_steps > 0 and world & (world - 1) == 0 and n % world == 0:
         # BASELINE configs[2] on N GPUs: pcdl::open + check with the key, the coefficients and the z-powers placed cyclically
         # (element i on rank i mod N; sharded.ShardedOpen): per round one all-gather of 256 B per rank, no vector exchange;
         # the check's commitment to h is sharded the same way (halo_pcdl_check_partial).  The same polynomial as at N = 1
@@ -1008,7 +1029,7 @@ def main():
         so.ctx.close()
         if native_gather is not None:
             native_gather.close()
-    if world > 1 and rank == 0:
+    if args.full and world > 1 and rank == 0:
         # cross-check of the sharded results: the same MSMs, unsharded, on this rank's GPU alone
         full = ctx if window_mode else h._lib.Context(urs_n=n, first_index=2, device=gpu)
         ok = True

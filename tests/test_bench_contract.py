@@ -1,4 +1,4 @@
-"""bench.py contract: one JSON line with the driver's keys plus the roofline and cpu_baseline objects."""
+"""bench.py contract: one JSON line with the driver's keys; with --full also the roofline and cpu_baseline objects."""
 import json
 import os
 import subprocess
@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_emits_contract_json():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "14", "--steps", "6", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--log-n", "14", "--steps", "6", "--warmup", "1",
                           "--cpu-msms", "1", "--open-steps", "1", "--asdl-steps", "2", "--min-seconds", "0.05"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -63,6 +63,33 @@ def test_bench_emits_contract_json():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the run times exactly --steps steps once, prints the headline keys and none of the --full legs, and
+    --dump-outputs writes what the timed path returned in its last step: the MSM the CPU restatement computes, bit for bit."""
+    import numpy as np
+    import orc
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "14", "--steps", "6", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "dump")], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, "bench.py must print exactly ONE line on stdout"
+    r = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in r, k
+    assert r["unit"] == "MSM/s" and r["higher_is_better"] is True and r["steps"] == 6 and r["warmup"] == 1
+    assert r["value"] > 0 and abs(r["value"] * r["ms_per_step"] / 1e3 - 1.0) < 1e-6
+    assert r["timed_region"]["repetitions"] == 1
+    for k in ("roofline", "cpu_baseline", "pcdl_open_check", "asdl_chain", "variable_base", "dropin", "cold_path", "solo_latency_ms"):
+        assert k not in r, k
+    got = np.load(tmp_path / "dump" / "msm_results.npy")
+    assert got.dtype == np.float64 and got.shape == (1, 24)
+    assert (got == np.floor(got)).all() and got.min() >= 0 and got.max() < 2.0 ** 32
+    n = 1 << 14
+    want = orc.msm_affine(orc.urs_affine(2, n), orc.rng_scalars(0x48414C4F00000002, n)[0])
+    assert got.astype(np.uint32).view(np.uint64).reshape(12).tolist() == want.tolist()
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_report_msms_and_the_sharded_open():
     """N = 2 as the driver launches it (one process per rank; gloo so that both ranks can share the one GPU of the test box):
     one JSON line from rank 0 with the whole-job MSM rate and open + check over the cyclically sharded key, whose proof the
@@ -71,7 +98,7 @@ def test_bench_two_ranks_report_msms_and_the_sharded_open():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, HALO_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--log-n", "14", "--steps", "8", "--warmup", "2",
+                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--log-n", "14", "--steps", "8", "--warmup", "2",
                           "--open-steps", "2", "--min-seconds", "0"], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -90,7 +117,7 @@ def test_bench_collective_path_over_rccl_with_one_rank():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, HALO_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     env.pop("HALO_BENCH_BACKEND", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "14", "--steps", "6", "--warmup", "1", "--cpu-msms", "0",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--log-n", "14", "--steps", "6", "--warmup", "1", "--cpu-msms", "0",
                           "--open-steps", "2", "--asdl-steps", "0", "--host-steps", "0", "--fr-reps", "0", "--min-seconds", "0"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -109,7 +136,7 @@ def test_bench_gpus_2_runs_without_a_launcher(extra):
     an assert: it takes the one-process path (multi-device context over devices 0..N-1) and says so; with one GPU on the box
     the device ids repeat and the line says REHEARSAL."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "HALO_BENCH_BACKEND", "HALO_BENCH_FORCE_DIST")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--log-n", "17", "--steps", "8", "--warmup", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--log-n", "17", "--steps", "8", "--warmup", "2",
                           "--min-seconds", "0"] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]

@@ -1,59 +1,130 @@
 """The reference-side binding a maintainer applies (integration/*.patch) must apply to the pristine reference tree.
 
-Runs wherever /root/reference exists (the build container); skipped on the GPU box, which never has it.  Nothing of the
-reference is copied into the repository: the tree is copied to a temporary directory for the dry run and removed.
+Self-contained: tests/golden/reference_patch_targets.json pins the four pristine files the patches edit -- line counts, the
+SHA-256 of every region a hunk replaces and how often the strings below occur -- and none of their text enters the
+repository (tests/golden/make_patch_fixture.py writes it from a reference checkout).
 """
+import hashlib
+import json
 import os
+import re
 import shutil
 import subprocess
-
-import pytest
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("HALO_REFERENCE", "/root/reference")
 PATCHES = ["lib_rs.patch", "group_rs.patch", "pcdl_rs.patch", "acc_rs.patch"]
+# what the checks below count in the patched files (single-line strings: a patch changes a file line by line)
+NEEDLES = ["mod ffi;", "ffi::", "crate::ffi::", "msm_unchecked", "ffi::KEY as GS", "ipa.round_lr(&H_prime)", "gs[j + m]",
+           "crate::ffi::h_accumulate(h_0, &xis, alphas)", "crate::ffi::h_eval_batch(&xis, z)", "self.hs[i].get_poly()",
+           "self.hs[i].eval(z)", "let mut h = PallasPoly::zero();"]
 
-needs_ref = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "code", "src")) or shutil.which("patch") is None,
-                               reason="reference tree or patch(1) not present")
+
+def parse_patch(text):
+    """one-file unified diff -> (path, hunks); every hunk's line counts must agree with its header"""
+    lines = text.splitlines(keepends=True)
+    assert lines[0].startswith("--- a/") and lines[1].startswith("+++ b/"), lines[:2]
+    rel = lines[0][6:].rstrip("\n")
+    assert lines[1][6:].rstrip("\n") == rel
+    hunks, i = [], 2
+    while i < len(lines):
+        m = re.fullmatch(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@.*\n", lines[i])
+        assert m, "not a hunk header: %r" % lines[i]
+        h = {"old_start": int(m.group(1)), "old_len": int(m.group(2) or 1), "new_start": int(m.group(3)), "new_len": int(m.group(4) or 1),
+             "old": [], "new": [], "minus": [], "plus": []}
+        i += 1
+        into = {" ": ("old", "new"), "-": ("old", "minus"), "+": ("new", "plus")}
+        prev = ()
+        while i < len(lines) and not lines[i].startswith("@@ "):
+            tag, body = lines[i][0], lines[i][1:]
+            if tag == "\\":  # "\ No newline at end of file": the line before it has none
+                for k in prev:
+                    h[k][-1] = h[k][-1].rstrip("\n")
+            else:
+                assert tag in into, "bad line in a hunk: %r" % lines[i]
+                prev = into[tag]
+                for k in prev:
+                    h[k].append(body)
+            i += 1
+        assert (len(h["old"]), len(h["new"])) == (h["old_len"], h["new_len"]), "hunk header of %s at -%d disagrees with its body" % (rel, h["old_start"])
+        hunks.append(h)
+    assert hunks
+    return rel, hunks
 
 
-@needs_ref
-def test_patches_apply_to_the_pristine_reference(tmp_path):
-    shutil.copytree(os.path.join(REF, "code", "src"), tmp_path / "code" / "src")
+def _fixture():
+    with open(os.path.join(ROOT, "tests", "golden", "reference_patch_targets.json")) as f:
+        return json.load(f)["files"]
+
+
+def _sha(text):
+    return hashlib.sha256(text.encode()).hexdigest()
+
+
+def _write_stand_in(dest):
+    """A stand-in of the pristine tree: every region a hunk replaces as the patch states it, every other line a placeholder."""
+    fx = _fixture()
     for name in PATCHES:
-        with open(os.path.join(ROOT, "integration", name)) as f:
-            r = subprocess.run(["patch", "-p1", "--dry-run"], stdin=f, cwd=tmp_path, capture_output=True, text=True)
-        assert r.returncode == 0, "%s does not apply:\n%s%s" % (name, r.stdout, r.stderr)
-    # and for real, all four in sequence: the result must contain the calls and none of the replaced bodies
+        rel, hunks = parse_patch(open(os.path.join(ROOT, "integration", name)).read())
+        f = fx[rel]
+        lines = ["// line %d of the pristine file (not stored here)\n" % (k + 1) for k in range(f["lines"])]
+        for h in hunks:
+            lines[h["old_start"] - 1: h["old_start"] - 1 + h["old_len"]] = h["old"]
+        assert len(lines) == f["lines"]
+        if not f["ends_with_newline"]:
+            lines[-1] = lines[-1].rstrip("\n")
+        path = os.path.join(dest, rel)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as out:
+            out.write("".join(lines))
+
+
+def test_patches_apply_to_the_pristine_reference():
+    """Every hunk replaces, at the line it names, exactly the pristine lines (their SHA-256 is pinned), so `patch -p1` applies
+    each patch without offset or fuzz; the patched files then contain the calls and none of the replaced bodies."""
+    fx = _fixture()
+    after, added = {}, {}
     for name in PATCHES:
-        with open(os.path.join(ROOT, "integration", name)) as f:
-            subprocess.run(["patch", "-p1", "-s"], stdin=f, cwd=tmp_path, check=True)
-    group = (tmp_path / "code" / "src" / "group.rs").read_text()
-    pcdl = (tmp_path / "code" / "src" / "pcdl.rs").read_text()
-    lib = (tmp_path / "code" / "src" / "lib.rs").read_text()
-    assert "mod ffi;" in lib
-    assert "msm_unchecked" not in group and group.count("crate::ffi::") == 4
-    assert "ffi::KEY as GS" in pcdl and "ipa.round_lr(&H_prime)" in pcdl and "gs[j + m]" not in pcdl
+        rel, hunks = parse_patch(open(os.path.join(ROOT, "integration", name)).read())
+        f = fx[rel]
+        assert [(h["old_start"], h["old_len"]) for h in hunks] == [(x["old_start"], x["old_len"]) for x in f["hunks"]], name
+        end, shift = 0, 0
+        for h, x in zip(hunks, f["hunks"]):
+            assert h["old_start"] > end, "%s: hunks overlap or are out of order" % name
+            end = h["old_start"] + h["old_len"] - 1
+            assert end <= f["lines"], "%s: hunk at -%d runs past the end of the pristine file" % (name, h["old_start"])
+            assert h["new_start"] == h["old_start"] + shift, "%s: hunk at -%d has the wrong new start" % (name, h["old_start"])
+            shift += h["new_len"] - h["old_len"]
+            assert _sha("".join(h["old"])) == x["sha256"], "%s: the lines the hunk at -%d replaces are not the pristine ones" % (name, h["old_start"])
+        # the patched file's count of each string: the pristine count, less what the hunks remove, plus what they add
+        after[os.path.basename(rel)] = {s: f["counts"][s] - sum(l.count(s) for h in hunks for l in h["minus"])
+                                        + sum(l.count(s) for h in hunks for l in h["plus"]) for s in NEEDLES}
+        assert f["counts"]["ffi::"] == 0, rel  # every ffi:: of a patched file comes from the patch
+        added[os.path.basename(rel)] = "".join(l for h in hunks for l in h["plus"])
+    group, pcdl, lib, acc = after["group.rs"], after["pcdl.rs"], after["lib.rs"], after["acc.rs"]
+    assert lib["mod ffi;"] >= 1
+    assert group["msm_unchecked"] == 0 and group["crate::ffi::"] == 4
+    assert pcdl["ffi::KEY as GS"] >= 1 and pcdl["ipa.round_lr(&H_prime)"] >= 1 and pcdl["gs[j + m]"] == 0
     # a13: AccumulatedHPolys::get_poly / eval (acc.rs:85-106) go to halo_h_accumulate / halo_h_eval_batch
-    acc = (tmp_path / "code" / "src" / "acc.rs").read_text()
-    assert "crate::ffi::h_accumulate(h_0, &xis, alphas)" in acc and "crate::ffi::h_eval_batch(&xis, z)" in acc
-    assert "self.hs[i].get_poly()" not in acc and "self.hs[i].eval(z)" not in acc and "let mut h = PallasPoly::zero();" not in acc
+    assert acc["crate::ffi::h_accumulate(h_0, &xis, alphas)"] >= 1 and acc["crate::ffi::h_eval_batch(&xis, z)"] >= 1
+    assert acc["self.hs[i].get_poly()"] == 0 and acc["self.hs[i].eval(z)"] == 0 and acc["let mut h = PallasPoly::zero();"] == 0
     # every ffi:: function a patched file calls exists in ffi.rs
-    import re
     ffi = open(os.path.join(ROOT, "integration", "ffi.rs")).read()
     defined = set(re.findall(r"pub fn (\w+)\s*[(<]", ffi)) | {"KEY", "Ipa"}
-    for text in (group, pcdl, acc):
+    for text in (added["group.rs"], added["pcdl.rs"], added["acc.rs"]):
         for name in re.findall(r"crate::ffi::(\w+)", text) + re.findall(r"ffi::(KEY)", text):
             assert name in defined, name
 
 
-@needs_ref
 def test_patches_are_what_make_patches_writes(tmp_path):
-    """The committed patches are the generator's output (no hand edits: that is how a hunk header went wrong before)."""
+    """The committed patches are the generator's output (no hand edits: that is how a hunk header went wrong before).  The
+    generator runs on the stand-in of the pristine tree, whose replaced regions the test above pins by hash."""
     before = {n: open(os.path.join(ROOT, "integration", n)).read() for n in PATCHES}
+    ref = tmp_path / "reference"
+    _write_stand_in(str(ref))
     out = tmp_path / "integration"
     shutil.copytree(os.path.join(ROOT, "integration"), out)
-    subprocess.run(["python3", str(out / "make_patches.py")], check=True, capture_output=True)
+    subprocess.run([sys.executable, str(out / "make_patches.py")], check=True, capture_output=True, env=dict(os.environ, HALO_REFERENCE=str(ref)))
     for n in PATCHES:
         assert (out / n).read_text() == before[n], n
 

@@ -14,9 +14,9 @@ step() { echo "== $1" | tee -a $OUT/progress.txt; }
 if [ "$PART" != B ]; then
 step pytest;  timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.txt 2>&1 || { tail -5 $OUT/pytest_gpu.txt; exit 1; }
 tail -1 $OUT/pytest_gpu.txt
-step bench;   timeout -k 10 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err || exit 1
-step prof_d4; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_d4 -- python bench.py --steps 40 --warmup 4 --cpu-msms 0 --open-steps 0 --asdl-steps 0 --host-steps 0 --fr-reps 0 --var-steps 0 --min-seconds 0 > $OUT/prof_d4.log 2>&1 || exit 1
-step prof_d1; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_d1 -- python bench.py --steps 40 --warmup 4 --depth 1 --cpu-msms 0 --open-steps 0 --asdl-steps 0 --host-steps 0 --fr-reps 0 --var-steps 0 --min-seconds 0 > $OUT/prof_d1.log 2>&1 || exit 1
+step bench;   timeout -k 10 600 python bench.py --full --min-seconds 1 > $OUT/bench.json 2> $OUT/bench.err || exit 1
+step prof_d4; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_d4 -- python bench.py --full --steps 40 --warmup 4 --cpu-msms 0 --open-steps 0 --asdl-steps 0 --host-steps 0 --fr-reps 0 --var-steps 0 --min-seconds 0 > $OUT/prof_d4.log 2>&1 || exit 1
+step prof_d1; timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_d1 -- python bench.py --full --steps 40 --warmup 4 --depth 1 --cpu-msms 0 --open-steps 0 --asdl-steps 0 --host-steps 0 --fr-reps 0 --var-steps 0 --min-seconds 0 > $OUT/prof_d1.log 2>&1 || exit 1
 step prof_open; FOLD_TABLE=1 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_open -- python3 tools/open_loop.py 20 5 > $OUT/prof_open.log 2>&1 || exit 1
 python tools/trace_timeline.py $(find $OUT/prof_open -name "*kernel_trace.csv" | head -1) > $OUT/open_timeline.txt 2>&1
 step pmc_fetch; timeout -k 10 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- python tools/pipe_loop.py 20 1 6 > $OUT/pmc_fetch.log 2>&1 || exit 1
@@ -50,22 +50,22 @@ fi
 if [ "$PART" = A ]; then step done_A; exit 0; fi
 # BASELINE config 5's size on the one GPU: n = 2^24, the bench line (rate with four in flight, solo latency, roofline), and the
 # same MSM through the multi-device context with the one GPU standing in for eight
-step bench_2_24; timeout -k 10 500 python bench.py --log-n 24 --steps 24 --warmup 2 --cpu-msms 0 --open-steps 0 --asdl-steps 0 --host-steps 0 --fr-reps 0 --var-steps 0 --min-seconds 0.5 > $OUT/bench_2_24.json 2> $OUT/bench_2_24.err || exit 1
-step oneproc8_2_24; timeout -k 10 500 python bench.py --log-n 24 --gpus 8 --devices 0,0,0,0,0,0,0,0 --steps 16 --warmup 2 --min-seconds 0.3 > $OUT/bench_oneproc8_2_24.json 2> $OUT/bench_oneproc8_2_24.err || exit 1
+step bench_2_24; timeout -k 10 500 python bench.py --full --log-n 24 --steps 24 --warmup 2 --cpu-msms 0 --open-steps 0 --asdl-steps 0 --host-steps 0 --fr-reps 0 --var-steps 0 --min-seconds 0.5 > $OUT/bench_2_24.json 2> $OUT/bench_2_24.err || exit 1
+step oneproc8_2_24; timeout -k 10 500 python bench.py --full --log-n 24 --gpus 8 --devices 0,0,0,0,0,0,0,0 --steps 16 --warmup 2 --min-seconds 0.3 > $OUT/bench_oneproc8_2_24.json 2> $OUT/bench_oneproc8_2_24.err || exit 1
 # multi-device context from ONE process (halo_ctx_create_urs_multi), the one GPU of this box standing in for every device
 for N in 2 4 8; do
-  step oneproc$N; timeout -k 10 300 python bench.py --gpus $N --devices $(python -c "print(','.join(['0']*$N))") --steps 64 --min-seconds 0.3 > $OUT/bench_oneproc$N.json 2> $OUT/bench_oneproc$N.err || exit 1
+  step oneproc$N; timeout -k 10 300 python bench.py --full --gpus $N --devices $(python -c "print(','.join(['0']*$N))") --steps 64 --min-seconds 0.3 > $OUT/bench_oneproc$N.json 2> $OUT/bench_oneproc$N.err || exit 1
 done
 # the N > 1 path with its collectives on RCCL, as far as one GPU goes: ONE rank that still runs every all-gather
-step rccl1; HALO_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29540 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout -k 10 400 python bench.py --steps 64 --warmup 8 --cpu-msms 0 --asdl-steps 0 --host-steps 0 --fr-reps 0 --min-seconds 0.3 2> $OUT/bench_rccl1.err | grep '^{' > $OUT/bench_rccl1.json || exit 1
+step rccl1; HALO_BENCH_FORCE_DIST=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29540 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0 timeout -k 10 400 python bench.py --full --steps 64 --warmup 8 --cpu-msms 0 --asdl-steps 0 --host-steps 0 --fr-reps 0 --min-seconds 0.3 2> $OUT/bench_rccl1.err | grep '^{' > $OUT/bench_rccl1.json || exit 1
 export HALO_BENCH_BACKEND=gloo
 for N in 2 4; do
-  step gloo$N; timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 2951$N bench.py --gpus $N --steps 64 --warmup 8 2> $OUT/bench_gloo$N.err | grep '^{' > $OUT/bench_gloo$N.json || exit 1
+  step gloo$N; timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 2951$N bench.py --full --gpus $N --steps 64 --warmup 8 --min-seconds 1 2> $OUT/bench_gloo$N.err | grep '^{' > $OUT/bench_gloo$N.json || exit 1
 done
 # (the default of N > 1 is index blocks through the table plan; the other cut, Pippenger windows, explicitly)
-step gloo2_window; timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 bench.py --gpus 2 --steps 64 --warmup 8 --shard window 2> $OUT/bench_gloo2_window.err | grep '^{' > $OUT/bench_gloo2_window.json || exit 1
+step gloo2_window; timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29519 bench.py --full --gpus 2 --steps 64 --warmup 8 --shard window --min-seconds 1 2> $OUT/bench_gloo2_window.err | grep '^{' > $OUT/bench_gloo2_window.json || exit 1
 # BASELINE config 5 shape: n = 2^24 in index shards (two ranks sharing this GPU: 2^23 points each)
-step gloo2_index_2_24; timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29520 bench.py --gpus 2 --log-n 24 --steps 12 --warmup 2 --shard index --min-seconds 0 2> $OUT/bench_gloo2_index_2_24.err | grep '^{' > $OUT/bench_gloo2_index_2_24.json || exit 1
+step gloo2_index_2_24; timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29520 bench.py --full --gpus 2 --log-n 24 --steps 12 --warmup 2 --shard index --min-seconds 0 2> $OUT/bench_gloo2_index_2_24.err | grep '^{' > $OUT/bench_gloo2_index_2_24.json || exit 1
 unset HALO_BENCH_BACKEND
 step asdl64;  timeout -k 10 600 python tools/time_acc.py 20 64 > $OUT/asdl64.json 2> $OUT/asdl64.err || exit 1
 # keep only the summaries (traces are large)
