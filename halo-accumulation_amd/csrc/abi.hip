@@ -341,7 +341,6 @@ void halo_ctx_destroy(halo_ctx *ctx) {
     (void)hipFree(ctx->d_poly2);
     (void)hipFree(ctx->d_verify);
     for (auto p : ctx->d_slot_scalars) (void)hipFree(p);
-    for (auto p : ctx->d_batch_scalars) (void)hipFree(p);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
     if (ctx->h_wintab) (void)hipHostFree(ctx->h_wintab);
     for (auto &pair : ctx->ev_piece) for (auto e : pair) if (e) (void)hipEventDestroy(e);
@@ -353,10 +352,87 @@ size_t halo_ctx_size(const halo_ctx *ctx) { return ctx ? ctx->n : 0; }
 void *halo_ctx_bases_dev(halo_ctx *ctx) { return ctx ? ctx->d_bases : nullptr; }
 void *halo_ctx_stream(halo_ctx *ctx) { return ctx ? (void *)ctx->stream : nullptr; }
 
+} // extern "C"
+// Every MSM request of the entry points below passes here before any device work: the slot (a synchronous call names slot 0,
+// where it runs) and whether it is busy -- fan: the request fans out over the shards of a multi-device context, which keep
+// their own books per slot --, 1..8 members without null scalar pointers, and GS[off, off + n) inside the key, written so that
+// it cannot wrap around.  Fills `out` with the members.  halo_ctx_read_bases checks its range only (out null).
+static int msm_request(const halo_ctx *ctx, int slot, bool fan, size_t off, size_t n, const void *const *scalars, size_t count, MsmBatch *out) {
+    if (off > ctx->n || n > ctx->n - off) { set_error("msm: bad range or null pointer"); return HALO_E_ARG; }
+    if (!out) return HALO_OK;
+    if (slot < 0 || slot >= HALO_SLOTS) { set_error("msm: slot out of range"); return HALO_E_ARG; }
+    if (fan ? ctx->fan[slot].active : ctx->wss[slot].in_flight) { set_error("msm: slot already has an MSM in flight"); return HALO_E_ARG; }
+    if (count < 1 || count > (size_t)MSM_MAX_BATCH || !scalars) { set_error("msm: batch must be in [1, 8]"); return HALO_E_ARG; }
+    *out = MsmBatch();
+    out->count = (int)count;
+    for (size_t b = 0; b < count; ++b) {
+        if (n && !scalars[b]) { set_error("msm: bad range or null pointer"); return HALO_E_ARG; }
+        out->scalars[b] = static_cast<const uint64_t *>(scalars[b]);
+    }
+    return HALO_OK;
+}
+// Slot `slot`'s scalar staging buffer with room for `members` arrays of max(n, 64) scalars; returns member m's.  Host-scalar MSMs copy
+// into it, the shards of a multi-device context peer-copy device scalars from other GPUs into it.  Allocated on first use and only
+// grown, so its address stays put from call to call: launch graphs are keyed on scalar pointers (MsmWorkspace::GraphKey), and
+// halo_msm / halo_msm_begin replay theirs through this buffer.  Every (re)allocation moves alloc_epoch; the slot's stream is
+// drained before an old buffer goes.
+uint64_t *halo::slot_scalars(halo_ctx *ctx, int slot, int members, int m) {
+    const size_t per = ctx->n < 64 ? 64 : ctx->n, need = (size_t)members * per * 32;
+    if (ctx->slot_scalars_bytes[slot] < need) {
+        alloc_epoch_bump(ctx);
+        if (ctx->d_slot_scalars[slot]) (void)hipStreamSynchronize(ctx->streams[slot]);
+        (void)hipFree(ctx->d_slot_scalars[slot]);
+        ctx->slot_scalars_bytes[slot] = 0;
+        hipError_t e = hipMalloc(&ctx->d_slot_scalars[slot], need);
+        if (e != hipSuccess) { ctx->d_slot_scalars[slot] = nullptr; hip_fail(e, "hipMalloc"); return nullptr; }
+        ctx->slot_scalars_bytes[slot] = need;
+    }
+    return ctx->d_slot_scalars[slot] + (size_t)m * per * 4;
+}
+// scalars in host memory (a checked request: msm_request): copied on the slot's own stream right in front of the launch sequence (no
+// host round trip in between), into the slot's staging buffer so that launches on different slots overlap with each other's copies
+int halo::msm_host_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const uint64_t *scalars, bool mont) {
+    uint64_t *d = slot_scalars(ctx, slot, 1, 0);
+    if (!d) return HALO_E_DEVICE;
+    if (n) HALO_HIP(hipMemcpyAsync(d, scalars, n * 32, hipMemcpyHostToDevice, ctx->streams[slot]));
+    return msm_enqueue(ctx, slot, ctx->d_bases + 32 * off, d, mont, n);
+}
+// The one begin path of the asynchronous forms: device-resident scalars, or host scalars (host: one member), on the context
+// itself or fanned out over the shards of a multi-device context -- window shards (parts != 1) stay on devices[0].  batch:
+// halo_msm_dev_batch_begin, which alone collects a fanned batch.
+static int msm_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const void *const *scalars, size_t count, int mont, int part, int parts,
+                     bool host, bool batch) {
+    HALO_CTX(ctx);
+    const bool fan = !ctx->shards.empty() && parts == 1;
+    MsmBatch members;
+    int rc = msm_request(ctx, slot, fan, off, n, scalars, count, &members);
+    if (rc) return rc;
+    members.part = part;
+    members.parts = parts;
+    if (fan) return multi_batch_begin(ctx, slot, off, n, members, mont != 0, host, batch);
+    if (host) return msm_host_begin(ctx, slot, off, n, members.scalars[0], mont != 0);
+    return msm_enqueue_batch(ctx, slot, ctx->d_bases + 32 * off, members, mont != 0, n);
+}
+// The one end path: `count` results of what `slot` holds (a fanned batch only for the batch call, which is an error for the other)
+static int msm_end(halo_ctx *ctx, int slot, size_t count, bool batch, uint64_t *out) {
+    HALO_CTX(ctx);
+    if (!out || count < 1 || count > (size_t)MSM_MAX_BATCH) { set_error("msm: null output or bad batch"); return HALO_E_ARG; }
+    const bool fanned = !ctx->shards.empty() && slot >= 0 && slot < HALO_SLOTS && ctx->fan[slot].active;
+    if (fanned && ctx->fan[slot].batch && !batch) { set_error("msm: this slot holds a batch (halo_msm_dev_batch_end collects it)"); return HALO_E_ARG; }
+    host::Point r[MSM_MAX_BATCH];
+    int rc = fanned && ctx->fan[slot].batch == batch ? multi_batch_end(ctx, slot, r, (int)count) : msm_finish_batch(ctx, slot, r, (int)count);
+    if (rc) return rc;
+    for (size_t b = 0; b < count; ++b) r[b].store_normalized(out + 12 * b);
+    return HALO_OK;
+}
+extern "C" {
+
 int halo_ctx_read_bases(halo_ctx *ctx, size_t off, size_t n, uint64_t *out) {
     HALO_CTX(ctx);
-    if (off + n > ctx->n || !out) { set_error("read_bases: range"); return HALO_E_ARG; }
-    int rc = aff_native_to_words(ctx, ctx->d_bases + 32 * off, n, ctx->d_tmp_a);
+    if (!out) { set_error("read_bases: range"); return HALO_E_ARG; }
+    int rc = msm_request(ctx, 0, false, off, n, nullptr, 0, nullptr);
+    if (rc) return rc;
+    rc = aff_native_to_words(ctx, ctx->d_bases + 32 * off, n, ctx->d_tmp_a);
     if (rc) return rc;
     return download(ctx, out, ctx->d_tmp_a, n * 8);
 }
@@ -371,91 +447,34 @@ int halo_public_points(uint64_t S_out[12], uint64_t H_out[12]) {
 // ------------------------------------------------------------------ group.rs
 int halo_msm_dev(halo_ctx *ctx, size_t off, size_t n, const void *d_scalars, int mont, uint64_t out[12]) {
     HALO_CTX(ctx);
-    if (off + n > ctx->n || !out || (n && !d_scalars)) { set_error("msm: bad range or null pointer"); return HALO_E_ARG; }
+    if (!out) { set_error("msm: null output"); return HALO_E_ARG; }
+    MsmBatch one;
+    int rc = msm_request(ctx, 0, !ctx->shards.empty() && n >= MULTI_RUN_MIN, off, n, &d_scalars, 1, &one);
+    if (rc) return rc;
     host::Point r;
-    int rc = msm_run(ctx, ctx->d_bases + 32 * off, static_cast<const uint64_t *>(d_scalars), mont != 0, n, &r);
+    rc = msm_run(ctx, ctx->d_bases + 32 * off, one.scalars[0], mont != 0, n, &r);
     if (rc) return rc;
     r.store_normalized(out);
     return HALO_OK;
 }
 
 int halo_msm_dev_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const void *d_scalars, int mont) {
-    HALO_CTX(ctx);
-    if (off + n > ctx->n || (n && !d_scalars)) { set_error("msm: bad range or null pointer"); return HALO_E_ARG; }
-    if (!ctx->shards.empty()) return multi_begin(ctx, slot, off, n, nullptr, static_cast<const uint64_t *>(d_scalars), mont != 0);
-    return msm_enqueue(ctx, slot, ctx->d_bases + 32 * off, static_cast<const uint64_t *>(d_scalars), mont != 0, n);
+    return msm_begin(ctx, slot, off, n, &d_scalars, 1, mont, 0, 1, false, false);
 }
 int halo_msm_dev_begin_part(halo_ctx *ctx, int slot, size_t off, size_t n, const void *d_scalars, int mont, int part, int parts) {
-    HALO_CTX(ctx);
-    if (off + n > ctx->n || (n && !d_scalars)) { set_error("msm: bad range or null pointer"); return HALO_E_ARG; }
-    MsmBatch one;
-    one.count = 1;
-    one.scalars[0] = static_cast<const uint64_t *>(d_scalars);
-    one.part = part;
-    one.parts = parts;
-    return msm_enqueue_batch(ctx, slot, ctx->d_bases + 32 * off, one, mont != 0, n);
+    return msm_begin(ctx, slot, off, n, &d_scalars, 1, mont, part, parts, false, false);
 }
-int halo_msm_dev_end(halo_ctx *ctx, int slot, uint64_t out[12]) {
-    HALO_CTX(ctx);
-    if (!out) { set_error("msm: null output"); return HALO_E_ARG; }
-    host::Point r;
-    bool fanned = !ctx->shards.empty() && slot >= 0 && slot < HALO_SLOTS && ctx->fan[slot].active;
-    if (fanned && ctx->fan[slot].batch > 0) { set_error("msm: this slot holds a batch (halo_msm_dev_batch_end collects it)"); return HALO_E_ARG; }
-    int rc = fanned ? multi_end(ctx, slot, &r) : msm_finish(ctx, slot, &r);
-    if (rc) return rc;
-    r.store_normalized(out);
-    return HALO_OK;
-}
+int halo_msm_dev_end(halo_ctx *ctx, int slot, uint64_t out[12]) { return msm_end(ctx, slot, 1, false, out); }
 
 int halo_msm_dev_batch_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const void *const *d_scalars, size_t batch, int mont, int part,
                              int parts) {
-    HALO_CTX(ctx);
-    if (batch < 1 || batch > (size_t)MSM_MAX_BATCH || !d_scalars) { set_error("msm: batch must be in [1, 8]"); return HALO_E_ARG; }
-    if (off + n > ctx->n) { set_error("msm: bad range"); return HALO_E_ARG; }
-    MsmBatch members;
-    members.count = (int)batch;
-    members.part = part;
-    members.parts = parts;
-    for (size_t b = 0; b < batch; ++b) {
-        if (n && !d_scalars[b]) { set_error("msm: null scalar pointer in batch"); return HALO_E_ARG; }
-        members.scalars[b] = static_cast<const uint64_t *>(d_scalars[b]);
-    }
-    if (!ctx->shards.empty() && parts == 1) return multi_batch_begin(ctx, slot, off, n, members, mont != 0);
-    return msm_enqueue_batch(ctx, slot, ctx->d_bases + 32 * off, members, mont != 0, n);
+    return msm_begin(ctx, slot, off, n, d_scalars, batch, mont, part, parts, false, true);
 }
-int halo_msm_dev_batch_end(halo_ctx *ctx, int slot, size_t batch, uint64_t *out) {
-    HALO_CTX(ctx);
-    if (!out || batch < 1 || batch > (size_t)MSM_MAX_BATCH) { set_error("msm: null output or bad batch"); return HALO_E_ARG; }
-    host::Point r[MSM_MAX_BATCH];
-    bool fanned = !ctx->shards.empty() && slot >= 0 && slot < HALO_SLOTS && ctx->fan[slot].active && ctx->fan[slot].batch > 0;
-    int rc = fanned ? multi_batch_end(ctx, slot, r, (int)batch) : msm_finish_batch(ctx, slot, r, (int)batch);
-    if (rc) return rc;
-    for (size_t b = 0; b < batch; ++b) r[b].store_normalized(out + 12 * b);
-    return HALO_OK;
-}
+int halo_msm_dev_batch_end(halo_ctx *ctx, int slot, size_t batch, uint64_t *out) { return msm_end(ctx, slot, batch, true, out); }
 
-// scalars in host memory: copied on the slot's own stream right in front of the launch sequence (no host round trip in
-// between), into a per-slot device buffer so that launches on different slots overlap with each other's copies
-} // extern "C"
-int halo::msm_host_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const uint64_t *scalars, int mont) {
-    if (slot < 0 || slot >= HALO_SLOTS) { set_error("msm: slot out of range"); return HALO_E_ARG; }
-    if (off + n > ctx->n || (n && !scalars)) { set_error("msm: bad range or null pointer"); return HALO_E_ARG; }
-    if (ctx->wss[slot].in_flight) { set_error("msm: slot already has an MSM in flight"); return HALO_E_ARG; }
-    if (!ctx->d_slot_scalars[slot]) {
-        alloc_epoch_bump(ctx);
-        HALO_HIP(hipMalloc(&ctx->d_slot_scalars[slot], (ctx->n < 64 ? 64 : ctx->n) * 32));
-    }
-    if (n) HALO_HIP(hipMemcpyAsync(ctx->d_slot_scalars[slot], scalars, n * 32, hipMemcpyHostToDevice, ctx->streams[slot]));
-    return msm_enqueue(ctx, slot, ctx->d_bases + 32 * off, ctx->d_slot_scalars[slot], mont != 0, n);
-}
-extern "C" {
 int halo_msm_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const uint64_t *scalars, int mont) {
-    HALO_CTX(ctx);
-    if (!ctx->shards.empty()) {
-        if (off + n > ctx->n || (n && !scalars)) { set_error("msm: bad range or null pointer"); return HALO_E_ARG; }
-        return multi_begin(ctx, slot, off, n, scalars, nullptr, mont != 0);
-    }
-    return msm_host_begin(ctx, slot, off, n, scalars, mont);
+    const void *p = scalars;
+    return msm_begin(ctx, slot, off, n, &p, 1, mont, 0, 1, true, false);
 }
 int halo_msm_end(halo_ctx *ctx, int slot, uint64_t out[12]) { return halo_msm_dev_end(ctx, slot, out); }
 
@@ -501,22 +520,18 @@ static int msm_host_pieces(halo_ctx *ctx, int P, size_t off, size_t n, const uin
             at += lens[k];
         }
     }
+    uint64_t *stage[HALO_SLOTS];
+    for (int k = 0; k < P; ++k)  // (every stretch's buffer is there before the first stretch goes out)
+        if (!(stage[k] = slot_scalars(ctx, k, 1, 0))) return HALO_E_DEVICE;
     int rc = HALO_OK, started = 0;
     for (int k = 0; k < P && !rc; ++k) {
         const size_t len = lens[k];
         const size_t have = valid > offs[k] ? (valid - offs[k] < len ? valid - offs[k] : len) : 0;  // scalars of this stretch the caller has
-        if (!ctx->d_slot_scalars[k]) {
-            alloc_epoch_bump(ctx);
-            hipError_t e = hipMalloc(&ctx->d_slot_scalars[k], (ctx->n < 64 ? 64 : ctx->n) * 32);
-            if (e != hipSuccess) { rc = hip_fail(e, "hipMalloc"); break; }
-        }
         hipError_t e = hipSuccess;
-        if (have < len) e = hipMemsetAsync(ctx->d_slot_scalars[k] + 4 * have, 0, (len - have) * 32, ctx->streams[k]);
-        if (e == hipSuccess && have) e = hipMemcpyAsync(ctx->d_slot_scalars[k], scalars + 4 * offs[k], have * 32, hipMemcpyHostToDevice, ctx->streams[k]);
+        if (have < len) e = hipMemsetAsync(stage[k] + 4 * have, 0, (len - have) * 32, ctx->streams[k]);
+        if (e == hipSuccess && have) e = hipMemcpyAsync(stage[k], scalars + 4 * offs[k], have * 32, hipMemcpyHostToDevice, ctx->streams[k]);
         if (e != hipSuccess) { rc = hip_fail(e, "hipMemcpyAsync"); break; }
-        MsmBatch one;
-        one.count = 1;
-        one.scalars[0] = ctx->d_slot_scalars[k];
+        MsmBatch one = msm_one(stage[k]);
         one.sub = true;
         rc = msm_enqueue_batch(ctx, k, ctx->d_bases + 32 * (off + offs[k]), one, mont != 0, len);
         if (!rc) started = k + 1;
@@ -535,31 +550,27 @@ static int msm_host_pieces(halo_ctx *ctx, int P, size_t off, size_t n, const uin
 // that pays (above), else one copy in front of one launch sequence on slot 0.  halo_msm and pcdl::commit / pedersen::commit with host
 // coefficients (pcdl_acc.hip) both end here.
 int halo::msm_host_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars, size_t valid, int mont, host::Point *out) {
-    if (off + n > ctx->n || valid > n || (valid && !scalars)) { set_error("msm: bad range or null pointer"); return HALO_E_ARG; }
-    const int P = ctx->shards.empty() ? host_pieces_wanted(ctx, n) : 1;
-    if (P > 1) return msm_host_pieces(ctx, P, off, n, scalars, valid, mont, out);
-    if (!ctx->shards.empty() && valid == n) return multi_host_run(ctx, off, n, scalars, mont != 0, out);
-    if (ctx->wss[0].in_flight) { set_error("msm: slot already has an MSM in flight"); return HALO_E_ARG; }
-    if (!ctx->d_slot_scalars[0]) {
-        alloc_epoch_bump(ctx);
-        HALO_HIP(hipMalloc(&ctx->d_slot_scalars[0], (ctx->n < 64 ? 64 : ctx->n) * 32));
-    }
-    if (valid < n) HALO_HIP(hipMemsetAsync(ctx->d_slot_scalars[0] + 4 * valid, 0, (n - valid) * 32, ctx->streams[0]));
-    if (valid) HALO_HIP(hipMemcpyAsync(ctx->d_slot_scalars[0], scalars, valid * 32, hipMemcpyHostToDevice, ctx->streams[0]));
-    if (!ctx->shards.empty()) {  // (a multi-device context with a short polynomial: the padded scalars are device-resident now)
-        HALO_HIP(hipStreamSynchronize(ctx->streams[0]));
-        return msm_run(ctx, ctx->d_bases + 32 * off, ctx->d_slot_scalars[0], mont != 0, n, out);
-    }
-    BorrowScope scope(ctx);  // synchronous: a large MSM may alternate its pieces over slot 1's workspace
-    int rc = msm_enqueue(ctx, 0, ctx->d_bases + 32 * off, ctx->d_slot_scalars[0], mont != 0, n);
+    if (valid > n) { set_error("msm: bad range or null pointer"); return HALO_E_ARG; }
+    const bool fan = !ctx->shards.empty() && valid == n;
+    const void *p = scalars;
+    MsmBatch one;
+    int rc = msm_request(ctx, 0, fan, off, n, &p, 1, &one);
     if (rc) return rc;
-    return msm_finish(ctx, 0, out);
+    if (fan) return multi_host_run(ctx, off, n, scalars, mont != 0, out);
+    const int P = host_pieces_wanted(ctx, n);
+    if (P > 1) return msm_host_pieces(ctx, P, off, n, scalars, valid, mont, out);
+    uint64_t *d = slot_scalars(ctx, 0, 1, 0);
+    if (!d) return HALO_E_DEVICE;
+    if (valid < n) HALO_HIP(hipMemsetAsync(d + 4 * valid, 0, (n - valid) * 32, ctx->streams[0]));
+    if (valid) HALO_HIP(hipMemcpyAsync(d, scalars, valid * 32, hipMemcpyHostToDevice, ctx->streams[0]));
+    // (a multi-device context with a short polynomial: the padded scalars are device-resident now, for its shards to read)
+    if (!ctx->shards.empty()) HALO_HIP(hipStreamSynchronize(ctx->streams[0]));
+    return msm_run(ctx, ctx->d_bases + 32 * off, d, mont != 0, n, out);
 }
 extern "C" {
 int halo_msm(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars, int mont, uint64_t out[12]) {
     if (!out) { set_error("msm: null output"); return HALO_E_ARG; }
     HALO_CTX(ctx);
-    if (off + n > ctx->n || (n && !scalars)) { set_error("msm: bad range or null pointer"); return HALO_E_ARG; }
     host::Point r;
     int rc = msm_host_run(ctx, off, n, scalars, n, mont, &r);
     if (rc) return rc;

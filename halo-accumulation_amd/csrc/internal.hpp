@@ -104,6 +104,7 @@ struct MsmBatch {
     bool sub = false;
 };
 inline int msm_outputs(const MsmBatch &m) { return m.tagged ? 2 : m.count; }
+inline MsmBatch msm_one(const uint64_t *scalars) { MsmBatch one; one.scalars[0] = scalars; return one; }
 MsmPlan msm_plan(size_t n, int forced_c);
 uint32_t msm_spread(const MsmPlan &p, uint32_t *top_bit);  // top-window spread of the recode (0: none)
 
@@ -322,9 +323,8 @@ struct halo_ctx {
     size_t tmp_words = 0;
     uint64_t *h_pinned = nullptr;  // small pinned staging (4 KiB)
     uint64_t *h_wintab = nullptr;  // pinned staging of a window table of powers (ipa.hip upload_window_table), 8 KiB
-    uint64_t *d_batch_scalars[HALO_SLOTS] = {};  // a shard's peer copies of a batch's scalar arrays (multi.hip), grown on demand
-    size_t batch_scalars_bytes[HALO_SLOTS] = {};
-    uint64_t *d_slot_scalars[HALO_SLOTS] = {};  // host-scalar MSMs (halo_msm, halo_msm_begin): one staging buffer of n x 4 words per slot, first use
+    uint64_t *d_slot_scalars[HALO_SLOTS] = {};  // scalar staging per slot (abi.hip slot_scalars): host scalars, a shard's peer copies
+    size_t slot_scalars_bytes[HALO_SLOTS] = {};
     uint64_t *d_verify = nullptr;  // staging of the batched verifier (points, scalars, challenges, results), grown on demand
     size_t verify_words = 0;
     // lazily allocated n x 4 polynomial buffers for pcdl::open / acc::prover
@@ -338,8 +338,10 @@ struct halo_ctx {
     std::vector<halo_ctx *> shards;
     std::vector<size_t> shard_lo;  // shards.size() + 1 block boundaries
     halo_ctx *parent = nullptr;    // set on a shard
-    struct Fan { bool active = false; int batch = 0; std::vector<char> used; };  // batch: members of a batched launch (0: a single MSM)
-    Fan fan[HALO_SLOTS];           // which shards hold a stretch of the MSM in flight on each slot
+    // the MSM(s) in flight over the shards on each slot: `count` members over GS[off, off + n); batch: begun by
+    // halo_msm_dev_batch_begin, which alone collects it
+    struct Fan { bool active = false, batch = false; int count = 0; size_t off = 0, n = 0; };
+    Fan fan[HALO_SLOTS];
 };
 
 struct halo_ipa {
@@ -448,14 +450,16 @@ void fold_digits_host(const host::Fr &s, int8_t out[44]);
 int multi_attach_shards(halo_ctx *ctx, const int *devices, int n_dev, const uint64_t *bases_affine, uint64_t first_index);
 void multi_destroy(halo_ctx *ctx);
 bool multi_takes(const halo_ctx *ctx, const uint32_t *d_bases, size_t n);  // a stretch of the parent's own key?
-int multi_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const uint64_t *host_scalars, const uint64_t *dev_scalars, bool mont);
-int multi_end(halo_ctx *ctx, int slot, host::Point *out);
-int multi_batch_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const MsmBatch &members, bool mont);
+constexpr size_t MULTI_RUN_MIN = (size_t)1 << 16;  // synchronous MSMs over the key fan out from this many points (msm_run)
+// members over GS[off, off + n) on every shard's slot `slot` (host: one member in host memory); collected by count
+int multi_batch_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const MsmBatch &members, bool mont, bool host, bool batch);
 int multi_batch_end(halo_ctx *ctx, int slot, host::Point *out, int count);
 int multi_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *dev_scalars, bool mont, host::Point *out);
 int multi_host_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars, bool mont, host::Point *out);  // synchronous, host scalars, per shard msm_host_run
-int msm_host_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const uint64_t *scalars, int mont);  // abi.hip
-int msm_host_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars, size_t valid, int mont, host::Point *out);  // abi.hip: synchronous, host scalars, zero-padded beyond `valid`
+// ---- abi.hip: host-scalar MSMs and the scalar staging buffers
+uint64_t *slot_scalars(halo_ctx *ctx, int slot, int members, int m);  // member m's array in slot `slot`'s buffer (null: allocation failed)
+int msm_host_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const uint64_t *scalars, bool mont);
+int msm_host_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars, size_t valid, int mont, host::Point *out);  // synchronous, zero-padded beyond `valid`
 
 // ---- smsm.hip: the 4-launch pipeline for MSMs of up to 2^16 points (digits already in ws.d_canon)
 // (winsum / winsum_plain may be pinned host memory; done: the counter to publish to, or null)

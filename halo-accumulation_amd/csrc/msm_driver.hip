@@ -109,7 +109,7 @@ void msm_workspace_free(halo_ctx *ctx) {
 // ------------------------------------------------------------------------------ driver
 int msm_run(halo_ctx *ctx, const uint32_t *d_bases, const uint64_t *d_scalars, bool mont, size_t n, host::Point *out) {
     // a multi-device context: a large MSM over its own key goes to the shards (multi.hip); short ones are not worth the fan-out
-    if (n >= ((size_t)1 << 16) && multi_takes(ctx, d_bases, n))
+    if (n >= MULTI_RUN_MIN && multi_takes(ctx, d_bases, n))
         return multi_run(ctx, (size_t)(d_bases - ctx->d_bases) / AFF_STRIDE, n, d_scalars, mont, out);
     BorrowScope scope(ctx);  // synchronous: a large MSM may alternate its pieces over slot 1's workspace (tmsm_enqueue_launches)
     int rc = msm_enqueue(ctx, 0, d_bases, d_scalars, mont, n);
@@ -155,10 +155,7 @@ static bool batch_need(const halo_ctx *ctx, const MsmWorkspace &ws, size_t n, in
 }
 
 int msm_enqueue(halo_ctx *ctx, int slot, const uint32_t *d_bases, const uint64_t *d_scalars, bool mont, size_t n) {
-    MsmBatch one;
-    one.count = 1;
-    one.scalars[0] = d_scalars;
-    return msm_enqueue_batch(ctx, slot, d_bases, one, mont, n);
+    return msm_enqueue_batch(ctx, slot, d_bases, msm_one(d_scalars), mont, n);
 }
 
 int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const MsmBatch &members, bool mont, size_t n) {

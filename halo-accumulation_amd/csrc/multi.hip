@@ -68,216 +68,132 @@ static int device_of(const void *p, int fallback) {
     return fallback;
 }
 
-// Enqueue the stretches of GS[off, off + n) on the shards' slot `slot`.  Exactly one of host_scalars / dev_scalars is set.
-int multi_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const uint64_t *host_scalars, const uint64_t *dev_scalars, bool mont) {
-    if (slot < 0 || slot >= HALO_SLOTS) { set_error("msm: slot out of range"); return HALO_E_ARG; }
-    halo_ctx::Fan &fan = ctx->fan[slot];
-    if (fan.active) { set_error("msm: slot already has an MSM in flight"); return HALO_E_ARG; }
-    const int P = (int)ctx->shards.size();
-    fan.used.assign((size_t)P, 0);
-    int src_dev = dev_scalars ? device_of(dev_scalars, ctx->device) : -1;
-    int rc = HALO_OK;
-    std::vector<int> rcs((size_t)P, HALO_OK);
-    std::vector<std::string> errs((size_t)P);
-    for (int k = 0; k < P && !rc; ++k) {
-        size_t lo = ctx->shard_lo[k], hi = ctx->shard_lo[k + 1];
-        size_t a = std::max(off, lo), b = std::min(off + n, hi);
+// fn(k, a, b) for every shard k whose block meets GS[off, off + n), [a, b) being the common stretch (indices into the key), in
+// block order; stops at the first failure
+template <class F>
+static int for_blocks(const halo_ctx *ctx, size_t off, size_t n, F fn) {
+    for (int k = 0; k + 1 < (int)ctx->shard_lo.size(); ++k) {
+        size_t a = std::max(off, ctx->shard_lo[k]), b = std::min(off + n, ctx->shard_lo[k + 1]);
         if (a >= b) continue;
-        halo_ctx *s = ctx->shards[k];
-        fan.used[k] = 1;
-        if (host_scalars) {
-            // every device has its own PCIe link: the copies run in parallel, each issued by its shard's helper thread
-            const uint64_t *src = host_scalars + 4 * (a - off);
-            s->worker.submit([s, slot, a, b, lo, src, mont, &rcs, &errs, k] {
-                (void)hipSetDevice(s->device);
-                rcs[k] = msm_host_begin(s, slot, a - lo, b - a, src, mont ? 1 : 0);
-                if (rcs[k]) errs[k] = halo_last_error();
-            });
-            continue;
-        }
-        // (no early return in here: whatever has been enqueued on other shards is drained below if this one fails)
-        const uint64_t *src = dev_scalars + 4 * (a - off);
-        hipError_t e = hipSetDevice(s->device);
-        const bool staged = src_dev != s->device || dev_hooks().force_peer_copy;  // (development library's hook: the copy path on a one-GPU box)
-        if (e == hipSuccess && staged) {  // the scalars live on another GPU: peer copy on this shard's stream, in front of its launches
-            if (!s->d_slot_scalars[slot]) {
-                alloc_epoch_bump(s);
-                e = hipMalloc(&s->d_slot_scalars[slot], (s->n < 64 ? 64 : s->n) * 32);
-            }
-            if (e == hipSuccess) e = hipMemcpyPeerAsync(s->d_slot_scalars[slot], s->device, src, src_dev, (b - a) * 32, s->streams[slot]);
-            src = s->d_slot_scalars[slot];
-        }
-        // (same device: the shard reads the caller's buffer in place; as for halo_msm_dev on a plain context the caller has
-        // synchronised whatever wrote it)
-        rc = e != hipSuccess ? hip_fail(e, "multi-device MSM: peer copy of the scalars") : msm_enqueue(s, slot, s->d_bases + 32 * (a - lo), src, mont, b - a);
+        int rc = fn(k, a, b);
+        if (rc) return rc;
     }
-    if (host_scalars)
-        for (int k = 0; k < P; ++k)
-            if (fan.used[k]) {
-                ctx->shards[k]->worker.wait();
-                if (rcs[k] && !rc) { rc = rcs[k]; set_error(errs[k]); }
-            }
-    (void)hipSetDevice(ctx->device);
-    fan.active = true;  // (also after a failure: multi_end drains whatever was enqueued)
-    fan.batch = 0;
-    if (rc) { host::Point dummy; std::string keep = halo_last_error(); (void)multi_end(ctx, slot, &dummy); set_error(keep); }
-    return rc;
+    return HALO_OK;
 }
 
-// Wait for the shards, combine their window sums (each on its own helper thread), add the partials in block order.
-int multi_end(halo_ctx *ctx, int slot, host::Point *out) {
-    if (slot < 0 || slot >= HALO_SLOTS || !ctx->fan[slot].active) { set_error("msm: nothing in flight on this slot"); return HALO_E_ARG; }
-    halo_ctx::Fan &fan = ctx->fan[slot];
+// The same fn(k, a, b) on every such shard's helper thread (on the shard's device), all at once; waits for them in block order
+// and returns the first failure with its message
+template <class F>
+static int on_shards(halo_ctx *ctx, size_t off, size_t n, F fn) {
     const int P = (int)ctx->shards.size();
-    std::vector<host::Point> part((size_t)P, host::Point::infinity());
     std::vector<int> rcs((size_t)P, HALO_OK);
     std::vector<std::string> errs((size_t)P);
-    for (int k = 0; k < P; ++k) {
-        if (!fan.used[k]) continue;
+    (void)for_blocks(ctx, off, n, [&](int k, size_t a, size_t b) {
         halo_ctx *s = ctx->shards[k];
-        if (!s->wss[slot].in_flight) { fan.used[k] = 0; continue; }  // (its enqueue failed)
-        s->worker.submit([s, slot, k, &part, &rcs, &errs] {
+        s->worker.submit([s, k, a, b, &fn, &rcs, &errs] {
             (void)hipSetDevice(s->device);
-            rcs[k] = msm_finish(s, slot, &part[k]);
+            rcs[k] = fn(k, a, b);
             if (rcs[k]) errs[k] = halo_last_error();
         });
-    }
+        return HALO_OK;
+    });
     int rc = HALO_OK;
-    host::Point acc = host::Point::infinity();
-    for (int k = 0; k < P; ++k) {
-        if (!fan.used[k]) continue;
+    (void)for_blocks(ctx, off, n, [&](int k, size_t, size_t) {
         ctx->shards[k]->worker.wait();
         if (rcs[k] && !rc) { rc = rcs[k]; set_error(errs[k]); }
-        acc = acc + part[k];  // block order 0 .. P-1
-    }
-    fan.active = false;
+        return HALO_OK;
+    });
     (void)hipSetDevice(ctx->device);
-    *out = acc;
     return rc;
 }
 
-// Batched form (halo_msm_dev_batch_begin/_end): `members.count` MSMs over GS[off, off + n), one resident scalar array each.
-// Every shard runs ITS stretch of all members as one batched launch sequence (which is what makes a 2^17-point block a full
-// launch: msm.hip, small-key table plan), and the shards' per-member partials are added in block order.
-int multi_batch_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const MsmBatch &members, bool mont) {
-    if (slot < 0 || slot >= HALO_SLOTS) { set_error("msm: slot out of range"); return HALO_E_ARG; }
+// Enqueue the stretches of `members.count` MSMs over GS[off, off + n) on the shards' slot `slot`: every shard runs ITS stretch of
+// all members as one batched launch sequence (which is what makes a 2^17-point block a full launch: msm.hip, small-key table
+// plan).  host: the one member's scalars are in host memory -- every device has its own PCIe link, so each shard's helper
+// thread copies its stretch (msm_host_begin); else the shard on the scalars' device reads them in place and the others copy
+// theirs peer-to-peer (xGMI) into member m's place in their slot's staging buffer, in front of their launches.  batch: begun by
+// halo_msm_dev_batch_begin, which alone collects it.
+int multi_batch_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const MsmBatch &members, bool mont, bool host, bool batch) {
     halo_ctx::Fan &fan = ctx->fan[slot];
     if (fan.active) { set_error("msm: slot already has an MSM in flight"); return HALO_E_ARG; }
-    if (members.parts != 1) { set_error("msm: window shards are not split over the devices of a multi-device context"); return HALO_E_ARG; }
-    const int P = (int)ctx->shards.size();
-    fan.used.assign((size_t)P, 0);
-    int rc = HALO_OK;
-    for (int k = 0; k < P && !rc; ++k) {
-        size_t lo = ctx->shard_lo[k], hi = ctx->shard_lo[k + 1];
-        size_t a = std::max(off, lo), b = std::min(off + n, hi);
-        if (a >= b) continue;
-        halo_ctx *s = ctx->shards[k];
-        fan.used[k] = 1;
-        hipError_t e = hipSetDevice(s->device);
-        MsmBatch mine = members;
-        for (int m = 0; m < members.count && e == hipSuccess; ++m) {
-            const uint64_t *src = members.scalars[m] + 4 * (a - off);
-            int src_dev = device_of(src, ctx->device);
-            if (src_dev != s->device || dev_hooks().force_peer_copy) {  // (as multi_begin: peer copy in front of the launches)
-                size_t need = (size_t)members.count * (s->n < 64 ? 64 : s->n) * 32;
-                if (s->batch_scalars_bytes[slot] < need) {
-                    alloc_epoch_bump(s);
-                    (void)hipStreamSynchronize(s->streams[slot]);
-                    (void)hipFree(s->d_batch_scalars[slot]);
-                    s->d_batch_scalars[slot] = nullptr;
-                    s->batch_scalars_bytes[slot] = 0;
-                    e = hipMalloc(&s->d_batch_scalars[slot], need);
-                    if (e == hipSuccess) s->batch_scalars_bytes[slot] = need;
-                }
-                uint64_t *dst = s->d_batch_scalars[slot] + (size_t)m * (s->n < 64 ? 64 : s->n) * 4;
-                if (e == hipSuccess) e = hipMemcpyPeerAsync(dst, s->device, src, src_dev, (b - a) * 32, s->streams[slot]);
-                src = dst;
+    int rc;
+    if (host) {
+        rc = on_shards(ctx, off, n, [&](int k, size_t a, size_t b) {
+            halo_ctx *s = ctx->shards[k];
+            return msm_host_begin(s, slot, a - ctx->shard_lo[k], b - a, members.scalars[0] + 4 * (a - off), mont);
+        });
+    } else {
+        int src_dev[MSM_MAX_BATCH];
+        for (int m = 0; m < members.count; ++m) src_dev[m] = device_of(members.scalars[m], ctx->device);
+        // (a failure stops the loop; whatever the shards before it have enqueued is drained below)
+        rc = for_blocks(ctx, off, n, [&](int k, size_t a, size_t b) {
+            halo_ctx *s = ctx->shards[k];
+            hipError_t e = hipSetDevice(s->device);
+            MsmBatch mine = members;
+            for (int m = 0; m < members.count && e == hipSuccess; ++m) {
+                mine.scalars[m] = members.scalars[m] + 4 * (a - off);
+                mine.base_off[m] = 0;
+                if (src_dev[m] == s->device && !dev_hooks().force_peer_copy) continue;  // (development library's hook: the copy path on a one-GPU box)
+                uint64_t *dst = slot_scalars(s, slot, members.count, m);
+                if (!dst) return HALO_E_DEVICE;
+                e = hipMemcpyPeerAsync(dst, s->device, mine.scalars[m], src_dev[m], (b - a) * 32, s->streams[slot]);
+                mine.scalars[m] = dst;
             }
-            mine.scalars[m] = src;
-            mine.base_off[m] = 0;
-        }
-        rc = e != hipSuccess ? hip_fail(e, "multi-device MSM: peer copy of the scalars") : msm_enqueue_batch(s, slot, s->d_bases + 32 * (a - lo), mine, mont, b - a);
+            // (same device: the shard reads the caller's buffer in place; as for halo_msm_dev on a plain context the caller has
+            // synchronised whatever wrote it)
+            if (e != hipSuccess) return hip_fail(e, "multi-device MSM: peer copy of the scalars");
+            return msm_enqueue_batch(s, slot, s->d_bases + 32 * (a - ctx->shard_lo[k]), mine, mont, b - a);
+        });
+        (void)hipSetDevice(ctx->device);
     }
-    (void)hipSetDevice(ctx->device);
-    fan.active = true;
-    fan.batch = members.count;
+    fan.active = true;  // (also after a failure: multi_batch_end drains whatever was enqueued)
+    fan.batch = batch;
+    fan.count = members.count;
+    fan.off = off;
+    fan.n = n;
     if (rc) { host::Point dummy[MSM_MAX_BATCH]; std::string keep = halo_last_error(); (void)multi_batch_end(ctx, slot, dummy, members.count); set_error(keep); }
     return rc;
 }
+
+// Wait for the shards, combine their window sums (each on its own helper thread), add the per-member partials in block order.
+// A wrong count is reported and leaves the MSMs in flight.
 int multi_batch_end(halo_ctx *ctx, int slot, host::Point *out, int count) {
     if (slot < 0 || slot >= HALO_SLOTS || !ctx->fan[slot].active) { set_error("msm: nothing in flight on this slot"); return HALO_E_ARG; }
     halo_ctx::Fan &fan = ctx->fan[slot];
-    if (fan.batch != count) { set_error("msm: this slot holds a batch of a different size"); return HALO_E_ARG; }
-    const int P = (int)ctx->shards.size();
-    std::vector<host::Point> part((size_t)P * MSM_MAX_BATCH, host::Point::infinity());
-    std::vector<int> rcs((size_t)P, HALO_OK);
-    std::vector<std::string> errs((size_t)P);
-    for (int k = 0; k < P; ++k) {
-        if (!fan.used[k]) continue;
+    if (fan.count != count) { set_error("msm: this slot holds a batch of a different size"); return HALO_E_ARG; }
+    std::vector<host::Point> part(ctx->shards.size() * MSM_MAX_BATCH, host::Point::infinity());
+    int rc = on_shards(ctx, fan.off, fan.n, [&](int k, size_t, size_t) {
         halo_ctx *s = ctx->shards[k];
-        if (!s->wss[slot].in_flight) { fan.used[k] = 0; continue; }
-        s->worker.submit([s, slot, k, count, &part, &rcs, &errs] {
-            (void)hipSetDevice(s->device);
-            rcs[k] = msm_finish_batch(s, slot, &part[(size_t)k * MSM_MAX_BATCH], count);
-            if (rcs[k]) errs[k] = halo_last_error();
-        });
-    }
-    int rc = HALO_OK;
+        if (!s->wss[slot].in_flight) return (int)HALO_OK;  // (its begin failed or never came: it adds nothing)
+        return msm_finish_batch(s, slot, &part[(size_t)k * MSM_MAX_BATCH], count);
+    });
     for (int m = 0; m < count; ++m) out[m] = host::Point::infinity();
-    for (int k = 0; k < P; ++k) {
-        if (!fan.used[k]) continue;
-        ctx->shards[k]->worker.wait();
-        if (rcs[k] && !rc) { rc = rcs[k]; set_error(errs[k]); }
-        for (int m = 0; m < count; ++m) out[m] = out[m] + part[(size_t)k * MSM_MAX_BATCH + m];  // block order 0 .. P-1
-    }
+    for (size_t k = 0; k < ctx->shards.size(); ++k)
+        for (int m = 0; m < count; ++m) out[m] = out[m] + part[k * MSM_MAX_BATCH + m];  // block order 0 .. P-1
     fan.active = false;
-    fan.batch = 0;
-    (void)hipSetDevice(ctx->device);
     return rc;
 }
 
 int multi_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *dev_scalars, bool mont, host::Point *out) {
     // the library's own synchronous MSMs have just written their scalars on the parent's stream
     HALO_HIP(hipStreamSynchronize(ctx->stream));
-    int rc = multi_begin(ctx, 0, off, n, nullptr, dev_scalars, mont);
+    int rc = multi_batch_begin(ctx, 0, off, n, msm_one(dev_scalars), mont, false, false);
     if (rc) return rc;
-    return multi_end(ctx, 0, out);
+    return multi_batch_end(ctx, 0, out, 1);
 }
 
 // The synchronous host-scalar form (halo_msm, pcdl::commit with host coefficients): every shard's helper thread runs its block of
 // GS[off, off + n) through msm_host_run on its own device -- its scalars over its own PCIe link, in stretches where that pays
 // (abi.hip: a shard's block of 2^21 points of an n = 2^24 MSM copies under its own kernels) -- and the partial points are added in
-// block order.  Same point as multi_begin + multi_end give.
+// block order.  Same point as multi_batch_begin + multi_batch_end give.
 int multi_host_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars, bool mont, host::Point *out) {
-    if (ctx->fan[0].active) { set_error("msm: slot already has an MSM in flight"); return HALO_E_ARG; }
-    const int P = (int)ctx->shards.size();
-    std::vector<host::Point> part((size_t)P, host::Point::infinity());
-    std::vector<int> rcs((size_t)P, HALO_OK);
-    std::vector<char> used((size_t)P, 0);
-    std::vector<std::string> errs((size_t)P);
-    for (int k = 0; k < P; ++k) {
-        size_t lo = ctx->shard_lo[k], hi = ctx->shard_lo[k + 1];
-        size_t a = std::max(off, lo), b = std::min(off + n, hi);
-        if (a >= b) continue;
-        halo_ctx *s = ctx->shards[k];
-        used[k] = 1;
-        const uint64_t *src = scalars + 4 * (a - off);
-        s->worker.submit([s, a, b, lo, src, mont, &rcs, &errs, &part, k] {
-            (void)hipSetDevice(s->device);
-            rcs[k] = msm_host_run(s, a - lo, b - a, src, b - a, mont ? 1 : 0, &part[k]);
-            if (rcs[k]) errs[k] = halo_last_error();
-        });
-    }
-    int rc = HALO_OK;
-    for (int k = 0; k < P; ++k)
-        if (used[k]) {
-            ctx->shards[k]->worker.wait();
-            if (rcs[k] && !rc) { rc = rcs[k]; set_error(errs[k]); }
-        }
-    (void)hipSetDevice(ctx->device);
+    std::vector<host::Point> part(ctx->shards.size(), host::Point::infinity());
+    int rc = on_shards(ctx, off, n, [&](int k, size_t a, size_t b) {
+        return msm_host_run(ctx->shards[k], a - ctx->shard_lo[k], b - a, scalars + 4 * (a - off), b - a, mont ? 1 : 0, &part[k]);
+    });
     if (rc) return rc;
     host::Point acc = host::Point::infinity();
-    for (int k = 0; k < P; ++k) acc = acc + part[k];  // block order
+    for (const host::Point &p : part) acc = acc + p;  // block order
     *out = acc;
     return HALO_OK;
 }

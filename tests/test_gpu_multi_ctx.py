@@ -206,10 +206,20 @@ def test_multi_ctx_from_host_bases_and_full_api(hal, urs4096):
 
 
 def test_multi_ctx_argument_errors(hal):
+    import torch
     with pytest.raises(hal.HaloError):
         hal.Context(urs_n=4096, devices=[0, 99])
     with pytest.raises(hal.HaloError):
         hal.Context(urs_n=4096, devices=[])
+    c = hal.Context(urs_n=4096, devices=[0, 0])
+    try:
+        d = torch.zeros(64 * 4, dtype=torch.int64, device="cuda")
+        with pytest.raises(hal.HaloError):
+            c.msm_dev_begin(0, d.data_ptr(), 64, off=2**64 - 32)     # off + n wraps around: refused before any shard sees it
+        c.msm_dev_begin(0, d.data_ptr(), 64)                         # nothing was left in flight
+        assert c.msm_dev_end(0).tolist() == orc.msm_affine(c.read_bases(0, 64), np.zeros((64, 4), dtype=np.uint64)).tolist()
+    finally:
+        c.close()
 
 
 @pytest.mark.parametrize("n,P", [(10, 8), (64, 8), (1000, 3), (4097, 5)])

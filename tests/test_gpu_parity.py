@@ -909,6 +909,18 @@ def test_api_misuse_is_reported_not_crashed(hal, ctx16k):
     with pytest.raises(hal.HaloError):
         ctx16k.msm_dev_begin(1, d.data_ptr(), 64)       # slot busy
     assert canon(ctx16k.msm_dev_end(1)) is None         # all-zero scalars
+    wrap = 2**64 - 32                                   # off + n wraps around to 32: refused before any device work
+    for call in (lambda: ctx16k.msm(sc[:64], off=wrap),
+                 lambda: ctx16k.msm_begin(0, sc[:64], off=wrap),
+                 lambda: ctx16k.msm_dev(d.data_ptr(), 64, off=wrap),
+                 lambda: ctx16k.msm_dev_begin(0, d.data_ptr(), 64, off=wrap),
+                 lambda: ctx16k.msm_dev_begin(0, d.data_ptr(), 64, off=wrap, part=0, parts=2),
+                 lambda: ctx16k.msm_dev_batch_begin(0, [d.data_ptr()], 64, off=wrap),
+                 lambda: ctx16k.read_bases(off=wrap, n=64)):
+        with pytest.raises(hal.HaloError):
+            call()
+    ctx16k.msm_dev_begin(0, d.data_ptr(), 64)           # nothing was left in flight
+    assert canon(ctx16k.msm_dev_end(0)) is None
     with pytest.raises(hal.HaloError):
         ctx16k.set_window_bits(3)
     ipa = hal.Ipa(ctx16k, 4, sc[:4], sc[0])
