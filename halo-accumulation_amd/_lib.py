@@ -101,6 +101,9 @@ _SIGS = {
     "halo_pcdl_open_sharded": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), u64p, C.c_size_t, C.c_size_t, u64p, C.c_size_t,
                                          u64p, u64p, C.c_void_p, C.c_void_p, u64p, u64p]),
     "halo_pcdl_check_sharded": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, u64p, C.c_size_t, u64p, u64p, u64p, C.c_void_p, C.c_void_p]),
+    "halo_msm_sharded": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_size_t, u64p, C.c_int, C.c_void_p, C.c_void_p, u64p]),
+    "halo_msm_dev_sharded": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, u64p]),
+    "halo_msm_end_sharded": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, u64p]),
     "halo_acc_prover": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, u64p, C.c_size_t, u64p]),
     "halo_acc_verifier": (C.c_int, [C.c_void_p, C.c_size_t, u64p, C.c_size_t, u64p]),
     "halo_acc_decider": (C.c_int, [C.c_void_p, u64p]),
@@ -341,6 +344,35 @@ class Context:
     def msm_dev_batch_end(self, slot: int, batch: int):
         out = np.zeros((batch, 12), dtype=np.uint64)
         check(self.lib.halo_msm_dev_batch_end(self.h, slot, batch, ptr(out)))
+        return out
+
+    # ---- group.rs sharded over one process per GPU: this rank's share, one all-gather (halo_msm_sharded and its forms).
+    # allgather: None (world 1, no collective), an object with .fn / .user (rccl.RcclGather: passed as it is) or a Python
+    # callable arr -> (world, len) uint64, whose exception is raised here after the call.
+    def msm_sharded(self, scalars, world: int, rank: int, allgather, off=0, mont=True):
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        out = np.zeros(12, dtype=np.uint64)
+        cb, fn, user = allgather_args(allgather, world)
+        rc = self.lib.halo_msm_sharded(self.h, world, rank, off, scalars.shape[0], ptr(scalars), int(mont), fn, user, ptr(out))
+        _raise_callback(cb)
+        check(rc)
+        return out
+
+    def msm_dev_sharded(self, dptr: int, n: int, world: int, rank: int, allgather, off=0, mont=True):
+        out = np.zeros(12, dtype=np.uint64)
+        cb, fn, user = allgather_args(allgather, world)
+        rc = self.lib.halo_msm_dev_sharded(self.h, world, rank, off, n, C.c_void_p(dptr), int(mont), fn, user, ptr(out))
+        _raise_callback(cb)
+        check(rc)
+        return out
+
+    def msm_end_sharded(self, slot: int, batch: int, world: int, rank: int, allgather):
+        """collect what `slot` holds (any msm*_begin; batch = its member count) and sum it across ranks -> (batch, 12)"""
+        out = np.zeros((batch, 12), dtype=np.uint64)
+        cb, fn, user = allgather_args(allgather, world)
+        rc = self.lib.halo_msm_end_sharded(self.h, slot, batch, world, rank, fn, user, ptr(out))
+        _raise_callback(cb)
+        check(rc)
         return out
 
     def msm_points(self, pts_jac, scalars):
@@ -622,6 +654,23 @@ def make_allgather_callback(allgather, world: int):
     cb = ALLGATHER_FN(_cb)
     cb.error = None
     return cb
+
+
+def allgather_args(allgather, world: int):
+    """-> (object to keep alive, function pointer, user pointer) for the sharded entry points.  An all-gather that brings its own
+    C entry point (rccl.RcclGather: .fn = halo_allgather_rccl, .user = its handle) is passed as it is -- no Python frame in the
+    collective path; a Python callable is wrapped (make_allgather_callback); None stays None (one rank, no collective)."""
+    if allgather is None:
+        return None, None, None
+    if hasattr(allgather, "fn") and hasattr(allgather, "user"):
+        return None, allgather.fn, allgather.user
+    cb = make_allgather_callback(allgather, world)
+    return cb, C.cast(cb, C.c_void_p), None
+
+
+def _raise_callback(cb):
+    if cb is not None and cb.error is not None:
+        raise cb.error
 
 
 def open_tail(recs, Hp, xi_prev):

@@ -425,6 +425,12 @@ static int msm_end(halo_ctx *ctx, int slot, size_t count, bool batch, uint64_t *
     for (size_t b = 0; b < count; ++b) r[b].store_normalized(out + 12 * b);
     return HALO_OK;
 }
+// halo_msm_end_sharded's local half: whichever begin started `slot` -- a fanned single MSM is collected as halo_msm_dev_end
+// collects it, everything else (one context's slot, a fanned batch) as halo_msm_dev_batch_end; `count` must match either way
+int halo::msm_end_slot(halo_ctx *ctx, int slot, size_t count, uint64_t *out) {
+    const bool fanned_one = ctx && !ctx->shards.empty() && slot >= 0 && slot < HALO_SLOTS && ctx->fan[slot].active && !ctx->fan[slot].batch;
+    return msm_end(ctx, slot, count, !fanned_one, out);
+}
 extern "C" {
 
 int halo_ctx_read_bases(halo_ctx *ctx, size_t off, size_t n, uint64_t *out) {

@@ -167,7 +167,7 @@ int halo_dev_hook(const char *name, long value) {
     if (!std::strcmp(name, "table_fail")) h.table_fail = (int)value;
     else if (!std::strcmp(name, "force_peer_copy")) h.force_peer_copy = (int)value;
     else if (!std::strcmp(name, "shard_fail_rank")) h.shard_fail_rank = (int)value;
-    else if (!std::strcmp(name, "shard_fail_at")) h.shard_fail_at = (int)value;
+    else if (!std::strcmp(name, "shard_fail_at")) h.shard_fail_at = (int)value;  // >= 0: a sharded open's collective, -2: check, -3: MSM
     else if (!std::strcmp(name, "reset")) h = DevHooks();
     else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, reset)"); return HALO_E_ARG; }
     return HALO_OK;

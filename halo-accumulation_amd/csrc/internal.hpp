@@ -8,6 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -460,6 +461,7 @@ int multi_host_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars,
 uint64_t *slot_scalars(halo_ctx *ctx, int slot, int members, int m);  // member m's array in slot `slot`'s buffer (null: allocation failed)
 int msm_host_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const uint64_t *scalars, bool mont);
 int msm_host_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars, size_t valid, int mont, host::Point *out);  // synchronous, zero-padded beyond `valid`
+int msm_end_slot(halo_ctx *ctx, int slot, size_t count, uint64_t *out);  // `count` results of whatever begin started `slot` (halo_msm_end_sharded)
 
 // ---- smsm.hip: the 4-launch pipeline for MSMs of up to 2^16 points (digits already in ws.d_canon)
 // (winsum / winsum_plain may be pinned host memory; done: the counter to publish to, or null)
@@ -509,6 +511,59 @@ const host::FixedBaseTable &public_s_table();  // (k S and k H from the process-
 int ipa_begin_dev(halo_ctx *ctx, size_t n, const uint64_t *d_coeffs_padded, const host::Fr &z, halo_ipa **out);
 int upload_words(halo_ctx *ctx, uint64_t *dst, const uint64_t *src, size_t words);
 int download_words(halo_ctx *ctx, uint64_t *dst, const uint64_t *src, size_t words);
+
+
+// ---- pcdl_acc.hip, msm_sharded.hip: the collectives of the sharded entry points (include/halo_accumulation.h, "sharded open /
+// check"): the caller's all-gather with ONE status word behind every rank's record
+// The development library's hooks "shard_fail_rank" / "shard_fail_at" (DevHooks; never the environment): the rank with that
+// offset fails locally (HALO_E_DEVICE) before collective number `at` of a sharded open (0 = the share of p(z), 1.. = the rounds,
+// then the tail), or, with at = SHARD_AT_CHECK, in a sharded check, or, with at = SHARD_AT_MSM, before the collective of a
+// sharded MSM -- what tests/test_sharded_gloo.py, tests/test_gpu_pcdl_acc.py and tests/test_gpu_msm_sharded.py use to drive
+// the failure path
+constexpr long SHARD_AT_CHECK = -2, SHARD_AT_MSM = -3;
+inline int shard_test_failure(uint64_t offset, long step) {
+    const DevHooks &h = dev_hooks();
+    if (h.shard_fail_rank < 0 || (uint64_t)h.shard_fail_rank != offset) return HALO_OK;
+    if ((long)h.shard_fail_at != step) return HALO_OK;
+    set_error("sharded call: local failure injected by the development library's shard_fail hook");
+    return HALO_E_DEVICE;
+}
+struct StatusGather {
+    size_t P;
+    uint64_t offset;
+    halo_allgather_fn fn;
+    void *user;
+    const char *who;
+    std::vector<uint64_t> sbuf, rbuf;
+    // all-gather of `words` record words + this rank's status; recv = P x words.  Returns the first non-zero status in rank
+    // order (the same value on every rank), HALO_E_ARG if the collective itself failed, else 0.
+    int run(const uint64_t *rec, size_t words, int local_rc, std::vector<uint64_t> &recv) {
+        recv.assign(P * words, 0);
+        if (!fn) {  // one rank, no callback: nothing to agree on
+            if (local_rc) return local_rc;
+            std::memcpy(recv.data(), rec, words * 8);
+            return HALO_OK;
+        }
+        sbuf.assign(words + 1, 0);
+        if (!local_rc) std::memcpy(sbuf.data(), rec, words * 8);
+        sbuf[words] = (uint64_t)(int64_t)local_rc;
+        rbuf.assign(P * (words + 1), 0);
+        std::string own = local_rc ? halo_last_error() : "";
+        if (fn(user, sbuf.data(), words + 1, rbuf.data())) {
+            set_error(std::string(who) + ": the caller's all-gather failed (abort the process group: the ranks are no longer in step)");
+            return HALO_E_ARG;
+        }
+        for (size_t r = 0; r < P; ++r) {
+            int st = (int)(int64_t)rbuf[r * (words + 1) + words];
+            if (!st) continue;
+            if (r == offset || local_rc == st) set_error(own);  // (a rejection every rank found by itself keeps its own wording)
+            else set_error(std::string(who) + ": rank " + std::to_string(r) + " failed locally (code " + std::to_string(st) + "); every rank returns its code");
+            return st;
+        }
+        for (size_t r = 0; r < P; ++r) std::memcpy(&recv[r * words], &rbuf[r * (words + 1)], words * 8);
+        return HALO_OK;
+    }
+};
 
 }  // namespace halo
 

@@ -712,56 +712,7 @@ int halo_pcdl_check_partial(halo_ctx *ctx, const uint64_t C[12], size_t d, const
 // all of them return the first non-zero one in rank order, at the same collective.  No rank is left waiting in an
 // all-gather its peers never enter.  (A collective that itself fails -- the callback returns non-zero -- is the caller's
 // fabric failing: the call returns HALO_E_ARG on the ranks that see it and the caller must abort its process group.)
-namespace {
-// The development library's hooks "shard_fail_rank" / "shard_fail_at" (tuning.hpp DevHooks; never the environment): the rank with
-// that offset fails locally (HALO_E_DEVICE) before collective number `at` of a sharded open (0 = the share of p(z), 1.. = the
-// rounds, then the tail), or, with at = -2, in a sharded check -- what tests/test_sharded_gloo.py and
-// tests/test_gpu_pcdl_acc.py use to drive the failure path above
-int shard_test_failure(uint64_t offset, long step, bool in_check) {
-    const DevHooks &h = dev_hooks();
-    if (h.shard_fail_rank < 0 || (uint64_t)h.shard_fail_rank != offset) return HALO_OK;
-    const bool hit = in_check ? h.shard_fail_at == -2 : (h.shard_fail_at >= 0 && (long)h.shard_fail_at == step);
-    if (!hit) return HALO_OK;
-    set_error("sharded call: local failure injected by the development library's shard_fail hook");
-    return HALO_E_DEVICE;
-}
-struct StatusGather {
-    size_t P;
-    uint64_t offset;
-    halo_allgather_fn fn;
-    void *user;
-    const char *who;
-    std::vector<uint64_t> sbuf, rbuf;
-    // all-gather of `words` record words + this rank's status; recv = P x words.  Returns the first non-zero status in rank
-    // order (the same value on every rank), HALO_E_ARG if the collective itself failed, else 0.
-    int run(const uint64_t *rec, size_t words, int local_rc, std::vector<uint64_t> &recv) {
-        recv.assign(P * words, 0);
-        if (!fn) {  // one rank, no callback: nothing to agree on
-            if (local_rc) return local_rc;
-            std::memcpy(recv.data(), rec, words * 8);
-            return HALO_OK;
-        }
-        sbuf.assign(words + 1, 0);
-        if (!local_rc) std::memcpy(sbuf.data(), rec, words * 8);
-        sbuf[words] = (uint64_t)(int64_t)local_rc;
-        rbuf.assign(P * (words + 1), 0);
-        std::string own = local_rc ? halo_last_error() : "";
-        if (fn(user, sbuf.data(), words + 1, rbuf.data())) {
-            set_error(std::string(who) + ": the caller's all-gather failed (abort the process group: the ranks are no longer in step)");
-            return HALO_E_ARG;
-        }
-        for (size_t r = 0; r < P; ++r) {
-            int st = (int)(int64_t)rbuf[r * (words + 1) + words];
-            if (!st) continue;
-            if (r == offset || local_rc == st) set_error(own);  // (a rejection every rank found by itself keeps its own wording)
-            else set_error(std::string(who) + ": rank " + std::to_string(r) + " failed locally (code " + std::to_string(st) + "); every rank returns its code");
-            return st;
-        }
-        for (size_t r = 0; r < P; ++r) std::memcpy(&recv[r * words], &rbuf[r * (words + 1)], words * 8);
-        return HALO_OK;
-    }
-};
-}  // namespace
+// (StatusGather and the development hook shard_test_failure live in internal.hpp: halo_msm_sharded shares them.)
 
 int halo_pcdl_open_sharded(halo_ctx *ctx, uint64_t stride, uint64_t offset, uint64_t *rng_state, const uint64_t *coeffs_local, size_t len_local,
                            size_t deg, const uint64_t C_w[12], size_t d, const uint64_t z_w[4], const uint64_t *w_w, halo_allgather_fn allgather,
@@ -793,7 +744,7 @@ int halo_pcdl_open_sharded(halo_ctx *ctx, uint64_t stride, uint64_t offset, uint
     if (!lrc) lrc = halo_ipa_dot_cz(st, send);  // this shard's share of p(z)   (:135)
     uint64_t Cm[12];
     std::memcpy(Cm, C_w, sizeof Cm);
-    if (!lrc) lrc = shard_test_failure(offset, step, false);
+    if (!lrc) lrc = shard_test_failure(offset, step);
     if (w_w) {  // :137-164
         if (!lrc) lrc = halo_ipa_hiding_partial(st, *rng_state, deg, z_w, stride, offset, send + 4);
         rc = sg.run(send, 16, lrc, recv);
@@ -818,7 +769,7 @@ int halo_pcdl_open_sharded(halo_ctx *ctx, uint64_t stride, uint64_t offset, uint
     if (rc) return rc;
     for (size_t round = 0; round < lg_l; ++round) {
         ++step;
-        if (!lrc) lrc = shard_test_failure(offset, step, false);
+        if (!lrc) lrc = shard_test_failure(offset, step);
         if (!lrc) lrc = halo_ipa_round_lr_partial(st, send, send + 12, send + 24);
         rc = sg.run(send, 32, lrc, recv);
         if (rc) return rc;
@@ -830,7 +781,7 @@ int halo_pcdl_open_sharded(halo_ctx *ctx, uint64_t stride, uint64_t offset, uint
     }
     uint64_t last[20] = {};
     ++step;
-    if (!lrc) lrc = shard_test_failure(offset, step, false);
+    if (!lrc) lrc = shard_test_failure(offset, step);
     if (!lrc) lrc = halo_ipa_finish_z(st, last, last + 12, last + 16);
     if (P == 1) {
         if (lrc) return lrc;
@@ -862,7 +813,7 @@ int halo_pcdl_check_sharded(halo_ctx *ctx, uint64_t stride, uint64_t offset, con
     Point U, part;
     // The succinct check is host arithmetic on the same proof on every rank: its HALO_E_REJECT is the same everywhere, but it
     // goes through the status word like any other outcome, so that the collective count stays fixed (one).
-    int lrc = shard_test_failure(offset, 0, true);
+    int lrc = shard_test_failure(offset, SHARD_AT_CHECK);
     if (!lrc) lrc = pcdl_check_partial_host(ctx, Point::load(C), d, Fr::load(z), Fr::load(v), proof, stride, offset, &U, &part);
     uint64_t send[12] = {};
     if (!lrc) part.store_normalized(send);

@@ -50,7 +50,7 @@ struct DevHooks {
     int table_fail = 0;        // "table_fail"       the allocation of a fixed-base / fold table reports out-of-memory
     int force_peer_copy = 0;   // "force_peer_copy"  multi-device contexts stage device scalars through a peer copy even on the same GPU
     int shard_fail_rank = -1;  // "shard_fail_rank" / "shard_fail_at": that rank fails locally before its collective number `at`
-    int shard_fail_at = -1;
+    int shard_fail_at = -1;    //   (at = -2: in a sharded check, -3: before a sharded MSM's collective)
 };
 DevHooks &dev_hooks();
 

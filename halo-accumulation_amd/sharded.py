@@ -168,12 +168,7 @@ class ShardedOpen:
         """-> (object to keep alive, function pointer, user pointer) for halo_pcdl_open_sharded / _check_sharded.  An all-gather
         that brings its own C entry point (rccl.RcclGather: .fn = halo_allgather_rccl, .user = its handle) is passed as it is --
         no Python frame in the collective path; anything else is wrapped."""
-        if self.allgather is None:
-            return None, None, None
-        if hasattr(self.allgather, "fn") and hasattr(self.allgather, "user"):
-            return None, self.allgather.fn, self.allgather.user
-        cb = self.lib.make_allgather_callback(self.allgather, self.world)
-        return cb, C.cast(cb, C.c_void_p), None
+        return self.lib.allgather_args(self.allgather, self.world)
 
     def open(self, coeffs_local, Cm, z, w=None, rng=None, deg=None):
         """pcdl::open over the sharded key in ONE library call (halo_pcdl_open_sharded): the round loop runs in the library,

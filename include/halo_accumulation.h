@@ -271,6 +271,24 @@ int halo_pcdl_open_sharded(halo_ctx *ctx, uint64_t stride, uint64_t offset, uint
  * with U; HALO_E_REJECT -- or the code of a rank whose half failed -- on every rank alike */
 int halo_pcdl_check_sharded(halo_ctx *ctx, uint64_t stride, uint64_t offset, const uint64_t C[12], size_t d, const uint64_t z[4],
                             const uint64_t v[4], const uint64_t *proof, halo_allgather_fn allgather, void *user);
+/* point_dot_affine (group.rs:24-26) sharded over `world` processes, one per GPU.  Each rank passes ITS share of the MSM:
+ * sum_i scalars[i] * G[off + i] over its own ctx (halo_msm / halo_msm_dev underneath; a multi-device ctx fans out as usual).
+ * The partition is the caller's: an index block over halo_ctx_create_urs(2 + lo, hi - lo), a cyclic shard, anything else.
+ * n may be 0 (the point at infinity).  One all-gather of 12 + 1 words per rank, then P - 1 additions in rank order on the host:
+ * out_jac is normalised and the same limbs on every rank, and equals halo_msm over the whole key when the shares partition it.
+ * world in 1..64, rank below it; world == 1 with allgather == NULL: no collective, exactly halo_msm.  Failure safety as above:
+ * world, rank, a missing all-gather and a null out_jac return HALO_E_ARG before the collective; a null ctx, a range past this
+ * rank's key, null scalars or a device failure on one rank enter it as that rank's status, and every rank returns that code. */
+int halo_msm_sharded(halo_ctx *ctx, uint64_t world, uint64_t rank, size_t off, size_t n, const uint64_t *scalars, int scalars_are_mont,
+                     halo_allgather_fn allgather, void *user, uint64_t out_jac[12]);
+int halo_msm_dev_sharded(halo_ctx *ctx, uint64_t world, uint64_t rank, size_t off, size_t n, const void *d_scalars, int scalars_are_mont,
+                         halo_allgather_fn allgather, void *user, uint64_t out_jac[12]);
+/* The asynchronous end: collect what `slot` holds and combine it across ranks with ONE collective of 12 * batch + 1 words.
+ * The slot was started by halo_msm_begin, halo_msm_dev_begin, halo_msm_dev_begin_part (window shards: part = rank,
+ * parts = world, every rank holding the whole key) or halo_msm_dev_batch_begin.  batch (1..8) must match what the slot
+ * holds; an idle slot or a different batch is that rank's failure and rides into the collective.  out_jac = batch x 12 limbs. */
+int halo_msm_end_sharded(halo_ctx *ctx, int slot, size_t batch, uint64_t world, uint64_t rank, halo_allgather_fn allgather, void *user,
+                         uint64_t *out_jac);
 /* acc::prover / verifier / decider (acc.rs:190-255); instances = m contiguous Instance blobs */
 int halo_acc_prover(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *instances, size_t m, uint64_t *acc_out);
 int halo_acc_verifier(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, const uint64_t *acc);

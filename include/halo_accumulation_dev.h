@@ -20,7 +20,8 @@ extern "C" {
 /* Fault injectors / forced paths, process-wide.  name: "table_fail" (value != 0: the allocation of a fixed-base or fold table
  * reports out-of-memory), "force_peer_copy" (multi-device contexts stage device scalars through a peer copy even on one GPU),
  * "shard_fail_rank" + "shard_fail_at" (the rank with that offset fails locally before collective number `at` of a sharded open:
- * 0 = the share of p(z), 1.. = the rounds, then the tail; at = -2: in a sharded check), "reset" (all off). */
+ * 0 = the share of p(z), 1.. = the rounds, then the tail; at = -2: in a sharded check; at = -3: the rank with that `rank`
+ * before the collective of halo_msm_sharded / _dev_sharded / _end_sharded), "reset" (all off). */
 int halo_dev_hook(const char *name, long value);
 /* What the library read from the environment at its first use (csrc/tuning.hip), by field: "host_split_set", "host_pieces", "host_split0".."host_split3",
  * "fold_table_after", "graph_cache", "pow_e", "spin_us", "graphs", "memory_budget" (MiB, -1 unset), "trace", "tagged"; -1 for an

@@ -61,6 +61,13 @@ extern "C" {
                                   user: *mut c_void, proof_out: *mut u64, v_out: *mut u64) -> c_int;
     pub fn halo_pcdl_check_sharded(ctx: *mut HaloCtx, stride: u64, offset: u64, c: *const u64, d: usize, z: *const u64, v: *const u64,
                                    proof: *const u64, allgather: HaloAllgatherFn, user: *mut c_void) -> c_int;
+    // point_dot_affine sharded the same way: this rank's share over its own ctx, one all-gather of the partial points
+    pub fn halo_msm_sharded(ctx: *mut HaloCtx, world: u64, rank: u64, off: usize, n: usize, scalars: *const u64, mont: c_int,
+                            allgather: HaloAllgatherFn, user: *mut c_void, out_jac: *mut u64) -> c_int;
+    pub fn halo_msm_dev_sharded(ctx: *mut HaloCtx, world: u64, rank: u64, off: usize, n: usize, d_scalars: *const c_void, mont: c_int,
+                                allgather: HaloAllgatherFn, user: *mut c_void, out_jac: *mut u64) -> c_int;
+    pub fn halo_msm_end_sharded(ctx: *mut HaloCtx, slot: c_int, batch: usize, world: u64, rank: u64, allgather: HaloAllgatherFn,
+                                user: *mut c_void, out_jac: *mut u64) -> c_int;
 }
 
 // ---- limbs: exactly what `main.rs:47-53` prints (`x.0 .0` is the `[u64; 4]` Montgomery representation).

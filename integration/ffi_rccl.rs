@@ -1,7 +1,8 @@
 // code/src/ffi_rccl.rs -- optional: the sharded entry points' all-gather over RCCL, native (include/halo_rccl.h,
 // libhalo_rccl.so).  Uncompiled source, like ffi.rs (no Rust toolchain in the build image); tests/test_integration_patches.py
 // lints it structurally against the header.  A multi-GPU host adds `pub mod ffi_rccl;` next to `pub mod ffi;` and passes
-// `RcclGather::callback()` / `.user()` to `ffi::halo_pcdl_open_sharded` / `halo_pcdl_check_sharded`; one rank per GPU.
+// `RcclGather::callback()` / `.user()` to `ffi::halo_pcdl_open_sharded` / `halo_pcdl_check_sharded`, and to the sharded MSM
+// (`ffi::halo_msm_sharded` / `halo_msm_dev_sharded` / `halo_msm_end_sharded`, point_dot_affine over the ranks' shares); one rank per GPU.
 use std::os::raw::{c_char, c_int, c_void};
 
 pub const HALO_RCCL_ID_BYTES: usize = 128;
