@@ -97,6 +97,7 @@ _SIGS = {
     "halo_pcdl_succinct_check": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, u64p, u64p, u64p, u64p]),
     "halo_pcdl_succinct_check_batch": (C.c_int, [C.c_void_p, C.c_size_t, u64p, C.c_size_t, u64p, u64p, C.POINTER(C.c_int)]),
     "halo_pcdl_check": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, u64p, u64p]),
+    "halo_pcdl_check_batch": (C.c_int, [C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_int)]),
     "halo_pcdl_check_partial": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, u64p, u64p, C.c_uint64, C.c_uint64, u64p, u64p]),
     "halo_pcdl_open_sharded": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), u64p, C.c_size_t, C.c_size_t, u64p, C.c_size_t,
                                          u64p, u64p, C.c_void_p, C.c_void_p, u64p, u64p]),
@@ -107,6 +108,7 @@ _SIGS = {
     "halo_acc_prover": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, u64p, C.c_size_t, u64p]),
     "halo_acc_verifier": (C.c_int, [C.c_void_p, C.c_size_t, u64p, C.c_size_t, u64p]),
     "halo_acc_decider": (C.c_int, [C.c_void_p, u64p]),
+    "halo_acc_decider_batch": (C.c_int, [C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_int)]),
     "halo_random_instance": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, u64p]),
     "halo_proof_encoded_size": (C.c_size_t, [C.c_size_t, C.c_int]),
     "halo_instance_encoded_size": (C.c_size_t, [C.c_size_t, C.c_int]),
@@ -152,6 +154,7 @@ _DEV_SIGS = {
     "halo_test_fold_digits": (C.c_int, [u64p, C.POINTER(C.c_int8)]),
     "halo_test_field_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, u64p, u64p, C.c_size_t, u64p]),
     "halo_test_point_op": (C.c_int, [C.c_void_p, C.c_int, u64p, u64p, C.c_size_t, u64p]),
+    "halo_dev_h_coeffs_batch": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_size_t, u64p]),
 }
 
 

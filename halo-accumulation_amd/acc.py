@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from halo_accumulation_amd._lib import check, ptr
-from halo_accumulation_amd.pcdl import lg_of
+from halo_accumulation_amd.pcdl import _check_batch, lg_of
 
 
 def _cat(qs):
@@ -42,3 +42,9 @@ def verifier(ctx, d, qs, acc):
 def decider(ctx, acc):
     """acc.rs:245-255"""
     check(ctx.lib.halo_acc_decider(ctx.h, ptr(np.ascontiguousarray(acc, dtype=np.uint64))))
+
+
+def decider_batch(ctx, d, accs):
+    """acc::decider (acc.rs:245-255) of m accumulators of degree bound d at once (benches/acc.rs:100-106 in one call) -> status
+    list; raises HaloReject as pcdl.check_batch does"""
+    return _check_batch(ctx, ctx.lib.halo_acc_decider_batch, d, accs)

@@ -321,6 +321,11 @@ void halo_ctx_destroy(halo_ctx *ctx) {
     msm_workspace_free(ctx);
     foldtab_release(ctx);
     ipa_bufs_release(ctx);
+    if (ctx->d_check_stage) {  // (optional memory of the check batch: off the budget's books before the key's remainder goes)
+        (void)hipFree(ctx->d_check_stage);
+        if (ctx->share) table_budget_release(ctx, ctx->check_stage_bytes);
+        ctx->d_check_stage = nullptr;
+    }
     if (ctx->share) {  // the key itself: freed by its last user (the tables went above, the same way)
         bool last;
         { std::lock_guard<std::mutex> lk(ctx->share->mu); last = --ctx->share->users == 0; }

@@ -168,9 +168,32 @@ int halo_dev_hook(const char *name, long value) {
     else if (!std::strcmp(name, "force_peer_copy")) h.force_peer_copy = (int)value;
     else if (!std::strcmp(name, "shard_fail_rank")) h.shard_fail_rank = (int)value;
     else if (!std::strcmp(name, "shard_fail_at")) h.shard_fail_at = (int)value;  // >= 0: a sharded open's collective, -2: check, -3: MSM
+    else if (!std::strcmp(name, "batch_stage_fail")) h.batch_stage_fail = (int)value;
+    else if (!std::strcmp(name, "check_batch_group")) h.check_group = (int)value;
     else if (!std::strcmp(name, "reset")) h = DevHooks();
-    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, reset)"); return HALO_E_ARG; }
+    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, reset)"); return HALO_E_ARG; }
     return HALO_OK;
+}
+
+// the check batch's h expansion on its own (tests/test_gpu_check_batch.py holds it against halo_h_coeffs): temporary device
+// buffers of this call only
+int halo_dev_h_coeffs_batch(halo_ctx *ctx, const uint64_t *xis, size_t m, size_t lg_n, uint64_t *out) {
+    HALO_CTX(ctx);
+    if (m == 0) return HALO_OK;
+    if (!xis || !out) { set_error("h_coeffs_batch: null pointer"); return HALO_E_ARG; }
+    if (lg_n > 24 || ((size_t)1 << lg_n) > (ctx->n < 64 ? 64 : ctx->n)) { set_error("h_coeffs_batch: 2^lg_n exceeds context size"); return HALO_E_ARG; }
+    if (m > 65535) { set_error("h_coeffs_batch: at most 65535 members"); return HALO_E_ARG; }
+    const size_t n = (size_t)1 << lg_n, xw = (lg_n + 1) * 4;
+    uint64_t *d = nullptr;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d, (m * (xw + H_TABLES_WORDS + n * 4)) * 8));
+    uint64_t *d_xis = d, *d_tabs = d + m * xw, *d_out = d_tabs + m * H_TABLES_WORDS;
+    hipError_t e = hipMemcpy(d_xis, xis, m * xw * 8, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? h_coeffs_batch_dev(ctx, d_xis, m, lg_n, d_tabs, d_out, n * 4) : hip_fail(e, "hipMemcpy");
+    if (!rc && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    if (!rc && (e = hipMemcpy(out, d_out, m * n * 32, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d);
+    return rc;
 }
 
 int halo_bench_fr_kernel(halo_ctx *ctx, int which, size_t n, int reps) {

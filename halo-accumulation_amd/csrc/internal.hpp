@@ -328,6 +328,10 @@ struct halo_ctx {
     size_t slot_scalars_bytes[HALO_SLOTS] = {};
     uint64_t *d_verify = nullptr;  // staging of the batched verifier (points, scalars, challenges, results), grown on demand
     size_t verify_words = 0;
+    // staging of halo_pcdl_check_batch / halo_acc_decider_batch (pcdl_acc.hip): h coefficients and tables of the members in flight.
+    // Optional memory (on the budget of halo_set_memory_budget; released at destroy), only grown, so its address stays put
+    uint64_t *d_check_stage = nullptr;
+    size_t check_stage_bytes = 0;
     // lazily allocated n x 4 polynomial buffers for pcdl::open / acc::prover
     uint64_t *d_poly = nullptr, *d_poly2 = nullptr;
     halo::HostWorker worker;      // host arithmetic overlapped with the caller's (see HostWorker; multi.hip also runs a shard's HIP calls on it)
@@ -487,6 +491,10 @@ int fr_scale(halo_ctx *ctx, uint64_t *d_v, size_t n, const host::Fr &a);
 int fr_poly_eval(halo_ctx *ctx, const uint64_t *d_coeffs, size_t len, const host::Fr &z, host::Fr *out);
 // d_out[k] (+)= scale * prod_{bit i of k} xis[lg_n - i]
 int h_coeffs_dev(halo_ctx *ctx, const host::Fr *xis, size_t lg_n, const host::Fr &scale, bool accumulate, uint64_t *d_out);
+// m of them at once, scale one: tables (d_tabs, m x 3072 words) built on the device from d_xis (m x (lg_n + 1) x 4), member b's
+// coefficients at d_out + b * out_stride (bit-identical to h_coeffs_dev per member)
+int h_coeffs_batch_dev(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg_n, uint64_t *d_tabs, uint64_t *d_out, size_t out_stride);
+constexpr size_t H_TABLES_WORDS = 3 * 256 * 4;
 int h_eval_batch(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg_n, const host::Fr &z, uint64_t *d_out);
 // m polynomials h_i at their own points z_i; m sums of K scalar multiples (canonical scalars, affine points) -> m Jacobian points
 int h_eval_each(halo_ctx *ctx, const uint64_t *d_xis, const uint64_t *d_zs, size_t m, size_t lg_n, uint64_t *d_out);

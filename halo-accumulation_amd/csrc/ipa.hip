@@ -443,10 +443,11 @@ __global__ __launch_bounds__(256) void k_poly_eval_partial(const uint64_t *__res
 }
 
 // ------------------------------------------------------------------ K7: h coefficients from three 256-entry tables
+constexpr size_t H_TAB_WORDS = H_TABLES_WORDS;  // one polynomial's low | mid | high tables
 // tab = low (A-form) | mid | high (N-form), 256 x 4 words each; coefficient k = low[k & 255] * mid[(k >> 8) & 255] * high[k >> 16].
 // Lane l of a wave takes k = base + l + 64 j: (k >> 8) is the same for the whole wave and changes every fourth step,
 // so mid * high is one product per four elements and low * (mid high) the only product per element.
-__global__ __launch_bounds__(256) void k_h_coeffs(const uint64_t *__restrict__ tab, uint32_t n, int E, int accumulate, uint64_t *__restrict__ out) {
+HALO_DEV void h_coeffs_wave(const uint64_t *__restrict__ tab, uint32_t n, int E, int accumulate, uint64_t *__restrict__ out) {
     uint32_t wave = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
     uint32_t k = wave * (64u * (uint32_t)E) + lane;
     if (k >= n) return;
@@ -460,6 +461,39 @@ __global__ __launch_bounds__(256) void k_h_coeffs(const uint64_t *__restrict__ t
         Fs<2> v = fs_mul(fs_load(tab + 4 * (size_t)(k & 255u)), hm);
         if (accumulate) fs_store(out + 4 * (size_t)k, fs_add(v, fs_load(out + 4 * (size_t)k)));
         else fs_store(out + 4 * (size_t)k, v);
+    }
+}
+__global__ __launch_bounds__(256) void k_h_coeffs(const uint64_t *__restrict__ tab, uint32_t n, int E, int accumulate, uint64_t *__restrict__ out) {
+    h_coeffs_wave(tab, n, E, accumulate, out);
+}
+// The same for a batch of polynomials: blockIdx.y = member, its own table (3 x 256 x 4 words) and its own n x 4 output words
+__global__ __launch_bounds__(256) void k_h_coeffs_batch(const uint64_t *__restrict__ tabs, uint32_t n, int E, uint64_t *__restrict__ outs, uint64_t out_stride) {
+    h_coeffs_wave(tabs + (size_t)blockIdx.y * H_TAB_WORDS, n, E, 0, outs + (size_t)blockIdx.y * out_stride);
+}
+// The three tables of k_h_coeffs built on the device, one block per member (challenges: lg_n + 1 Montgomery elements per
+// member, contiguous).  Thread k of level L (bits 8L .. 8L + 7 of the coefficient index) multiplies the challenges of the set
+// bits of k, xis[lg_n - (8L + b)] -- the same field element the host's doubling construction in h_coeffs_dev reaches, and both
+// are canonical Montgomery limbs, so the tables are bit-identical.  Entries past a level's 2^bits stay one as on the host; the
+// mid and high levels are N-form multipliers (32 x, five doublings), the low one A-form.
+__global__ __launch_bounds__(256) void k_h_tables(const uint64_t *__restrict__ xis, int lg_n, uint64_t *__restrict__ tabs) {
+    const uint64_t *x = xis + (size_t)blockIdx.x * 4 * (size_t)(lg_n + 1);
+    uint64_t *tab = tabs + (size_t)blockIdx.x * H_TAB_WORDS;
+    const uint32_t k = threadIdx.x;
+#pragma unroll 1
+    for (int level = 0; level < 3; level++) {
+        int bits = lg_n - 8 * level;
+        bits = bits < 0 ? 0 : (bits > 8 ? 8 : bits);
+        Fe t = fe_one<FrCfg>();
+        if ((k >> bits) == 0) {
+#pragma unroll 1
+            for (int b = 0; b < bits; b++)
+                if ((k >> b) & 1u) t = fe_mul<FrCfg>(t, fe_load(x + 4 * (size_t)(lg_n - (8 * level + b))));
+        }
+        if (level > 0) {
+#pragma unroll
+            for (int d = 0; d < 5; d++) t = fe_dbl<FrCfg>(t);
+        }
+        fe_store(tab + 4 * (size_t)(256 * level + k), t);
     }
 }
 
@@ -905,6 +939,22 @@ int bench_fr_kernel(halo_ctx *ctx, int which, size_t n, int reps) {
     HALO_HIP(hipGetLastError());
     HALO_HIP(hipStreamSynchronize(ctx->stream));
     if (ctx->prof.on) ctx->prof.collect();
+    return HALO_OK;
+}
+
+// m polynomials at once (scale one, no accumulation): member b's coefficients go to d_out + b * out_stride words, bit-identical
+// to h_coeffs_dev(xis_b, lg_n, 1, false).  Two launches on ctx->stream whatever m is: the tables (d_tabs: m x H_TAB_WORDS) from
+// the challenges already in device memory (d_xis: m x (lg_n + 1) x 4 words), then the coefficients.
+int h_coeffs_batch_dev(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg_n, uint64_t *d_tabs, uint64_t *d_out, size_t out_stride) {
+    if (lg_n > 24) { set_error("h_coeffs: lg_n > 24 unsupported"); return HALO_E_ARG; }
+    if (m == 0) return HALO_OK;
+    if (m > 65535) { set_error("h_coeffs_batch: at most 65535 members per launch"); return HALO_E_ARG; }
+    size_t n = (size_t)1 << lg_n;
+    int E = pow_chain_len(n, 4);
+    HALO_LAUNCH(ctx, "k_h_tables", k_h_tables, dim3((unsigned)m), dim3(256), 0, d_xis, (int)lg_n, d_tabs);
+    HALO_LAUNCH(ctx, "k_h_coeffs_batch", k_h_coeffs_batch, dim3(wave_blocks(n, E), (unsigned)m), dim3(256), 0, d_tabs, (uint32_t)n, E, d_out,
+                (uint64_t)out_stride);
+    HALO_HIP(hipGetLastError());
     return HALO_OK;
 }
 

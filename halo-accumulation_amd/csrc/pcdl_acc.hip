@@ -299,9 +299,10 @@ static int verify_staging(halo_ctx *ctx, size_t words) {
     return HALO_OK;
 }
 struct BatchCheck { int rc = HALO_OK; std::string err; SuccinctState st; };
-// instances: m blobs at stride instance_words(lg(d+1)); res[i].rc / .err / .st filled; returns a device / argument error only
-static int succinct_check_batch(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t m, std::vector<BatchCheck> &res) {
-    size_t lg = ilog2(d + 1), iw = instance_words(lg), K = 2 * lg + 2;
+// instances: m blobs at stride `stride` words (0: instance_words(lg(d+1)); an Accumulator's Instance prefix at acc_words);
+// res[i].rc / .err / .st filled; returns a device / argument error only
+static int succinct_check_batch(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t m, std::vector<BatchCheck> &res, size_t stride = 0) {
+    size_t lg = ilog2(d + 1), iw = stride ? stride : instance_words(lg), K = 2 * lg + 2;
     res.assign(m, BatchCheck());
     if (K > 64) { set_error("batched succinct check: lg n too large"); return HALO_E_ARG; }
     pool_run(m, [&](size_t i) {
@@ -392,6 +393,172 @@ static int pcdl_check_host(halo_ctx *ctx, const Point &C, size_t d, const Fr &z,
     if (rc) return rc;
     if (st.U != comm) return fail_reject("U != CM.Commit(ck, h_vec)");  // :339
     return HALO_OK;
+}
+
+// ------------------------------------------------------------------ pcdl::check of m instances at once
+// The succinct half of every member as halo_pcdl_succinct_check_batch runs it (the relations on the device from kBatchVerifyMin
+// members on, on the host pool below); then the accepted members in groups of up to MSM_MAX_BATCH: their h coefficients expanded
+// on the device (k_h_tables + k_h_coeffs_batch: two launches per group) into the group's staging, and the group's n-point MSMs
+// as ONE batched launch sequence over the key.  Groups rotate over the slots that were idle at entry; when a slot comes round
+// again its group is collected and every member's point compared with its U (pcdl.rs:338-339) on the host while the other slots'
+// groups run.  Every member gets its own exact MSM.  A multi-device context runs the groups on its own device (devices[0], which
+// holds the whole key), as halo_pcdl_check does: no fan-out, the same points.
+//
+// Members per launch (check_group_size): the small pipeline (smsm.hip, n <= 2^16) takes batches of 8 within its bucket limit
+// (windows x batch x buckets <= 2^22); a key of 2^20 points or more runs its MSMs of >= 2^20 points through the fixed-base table,
+// which takes single members only, so there each member is a group of its own.  Measured: DESIGN.md "Batched checks".
+static int check_group_size(const halo_ctx *ctx, size_t n) {
+    const int forced = dev_hooks().check_group;  // (development library: the sweep of tools/time_decider_batch.py)
+    int g = forced >= 1 && forced <= MSM_MAX_BATCH ? forced : MSM_MAX_BATCH;
+    if (forced <= 0 && n >= ((size_t)1 << 20) && ctx->n >= ((size_t)1 << 20) && ctx->table_mode != 0) g = 1;
+    MsmPlan p = msm_plan(n, ctx->window_bits);
+    while (g > 1 && (size_t)p.W * (size_t)g * p.B > ((size_t)1 << 22)) --g;
+    return g;
+}
+// Member buffers of n coefficients + one set of tables each in the context's check staging: grown to `want` buffers if the
+// memory budget and the device allow (optional memory: halo_set_memory_budget), never shrunk.  Returns how many buffers it
+// holds (0: none -- the caller runs one member at a time in ctx->d_tmp_a; never an error).
+static size_t check_stage(halo_ctx *ctx, size_t want, size_t per_bytes) {
+    if (dev_hooks().batch_stage_fail) return 0;  // (development library: the fallback path)
+    const size_t bytes = want * per_bytes;
+    if (ctx->check_stage_bytes < bytes && table_budget_reserve(ctx, bytes)) {
+        uint64_t *p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            table_budget_release(ctx, bytes);
+        } else {
+            alloc_epoch_bump(ctx);  // (cached launch graphs name the old buffer)
+            if (ctx->d_check_stage) {
+                for (int k = 0; k < HALO_SLOTS; ++k)
+                    if (!ctx->wss[k].in_flight) (void)hipStreamSynchronize(ctx->streams[k]);
+                (void)hipFree(ctx->d_check_stage);
+                table_budget_release(ctx, ctx->check_stage_bytes);
+            }
+            ctx->d_check_stage = p;
+            ctx->check_stage_bytes = bytes;
+        }
+    }
+    return ctx->check_stage_bytes / per_bytes;
+}
+// blobs: m Instances (or Accumulators, whose Instance prefix is checked) at `stride` words, all of degree bound d (checked by
+// the caller); status[i] (nullable) = what halo_pcdl_check returns for member i alone
+static int pcdl_check_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t stride, size_t m, int *status) {
+    const size_t n = d + 1, lg = ilog2(n);
+    int slots[HALO_SLOTS], S = 0;
+    for (int k = 0; k < HALO_SLOTS; ++k)
+        if (!ctx->wss[k].in_flight && ctx->wss[k].lent_from < 0 && !ctx->fan[k].active) slots[S++] = k;
+    if (!S) { set_error("check_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
+    // 1. the succinct half (pcdl.rs:333)
+    std::vector<BatchCheck> res;
+    if (m >= kBatchVerifyMin && ctx->batch_verify) {
+        int rc = succinct_check_batch(ctx, d, qs, m, res, stride);
+        if (rc) return rc;
+    } else {
+        res.assign(m, BatchCheck());
+        pool_run(m, [&](size_t i) {
+            const uint64_t *q = qs + i * stride;
+            res[i].rc = succinct_challenges(ctx, Point::load(q), d, Fr::load(q + 13), Fr::load(q + 17), q + 21, &res[i].st);
+            if (!res[i].rc) res[i].rc = succinct_relation(res[i].st, Fr::load(q + 13), Fr::load(q + 17), q + 21);
+            if (res[i].rc) res[i].err = halo_last_error();
+        });
+    }
+    std::vector<size_t> ok;  // the accepted members, in order
+    for (size_t i = 0; i < m; ++i)
+        if (!res[i].rc) ok.push_back(i);
+    const size_t A = ok.size();
+    if (A) {
+        if (lg > 24) { set_error("h_coeffs: lg_n > 24 unsupported"); return HALO_E_ARG; }
+        // 2. their challenges in device memory, in that order (one copy)
+        const size_t xw = (lg + 1) * 4;
+        std::vector<uint64_t> xis(A * xw);
+        for (size_t a = 0; a < A; ++a)
+            for (size_t k = 0; k <= lg; ++k) res[ok[a]].st.xis[k].store(&xis[a * xw + 4 * k]);
+        int rc = verify_staging(ctx, xis.size());
+        if (rc) return rc;
+        HALO_HIP(hipMemcpy(ctx->d_verify, xis.data(), xis.size() * 8, hipMemcpyHostToDevice));
+        // 3. groups of G members over S slots, G x S member buffers in the staging (fewer if it cannot grow; none: d_tmp_a)
+        size_t G = (size_t)check_group_size(ctx, n);
+        if (G > A) G = A;
+        size_t ng = (A + G - 1) / G;
+        if ((size_t)S > ng) S = (int)ng;
+        const size_t per = n * 4 + H_TABLES_WORDS;  // words of one member buffer
+        size_t have = check_stage(ctx, G * (size_t)S, per * 8);
+        const bool scratch = have == 0;
+        if (scratch) { G = 1; S = 1; }
+        else if (have < G * (size_t)S) {
+            if (G > have) G = have;
+            if ((size_t)S > have / G) S = (int)(have / G);
+        }
+        ng = (A + G - 1) / G;
+        auto coeffs_of = [&](size_t j) { return scratch ? ctx->d_tmp_a : ctx->d_check_stage + j * G * n * 4; };
+        auto tables_of = [&](size_t j) { return scratch ? ctx->d_tmp_c + 8 * 1024 + 1024 : ctx->d_check_stage + (size_t)S * G * n * 4 + j * G * H_TABLES_WORDS; };
+        std::vector<long> flight(S, -1);  // the group in flight on slots[j]
+        auto collect = [&](size_t j) -> int {
+            long g = flight[j];
+            if (g < 0) return HALO_OK;
+            flight[j] = -1;
+            size_t first = (size_t)g * G, cnt = A - first < G ? A - first : G;
+            Point pts[MSM_MAX_BATCH];
+            int rc2 = msm_finish_batch(ctx, slots[j], pts, (int)cnt);
+            if (rc2) return rc2;
+            for (size_t b = 0; b < cnt; ++b) {
+                BatchCheck &r = res[ok[first + b]];
+                if (r.st.U != pts[b]) { r.rc = HALO_E_REJECT; r.err = "U != CM.Commit(ck, h_vec)"; }  // :339
+            }
+            return HALO_OK;
+        };
+        auto abandon = [&]() {  // (a device error: nothing of this call stays in flight)
+            std::string err = halo_last_error();
+            for (int j = 0; j < S; ++j)
+                if (flight[j] >= 0) {
+                    Point pts[MSM_MAX_BATCH];
+                    size_t first = (size_t)flight[j] * G;
+                    (void)msm_finish_batch(ctx, slots[j], pts, (int)(A - first < G ? A - first : G));
+                    flight[j] = -1;
+                }
+            set_error(err);
+        };
+        for (size_t g = 0; g < ng; ++g) {
+            const size_t j = g % (size_t)S, first = g * G, cnt = A - first < G ? A - first : G;
+            rc = collect(j);
+            if (!rc) {
+                hipStream_t saved = ctx->stream;  // (the launch macro uses ctx->stream: the slot's own)
+                ctx->stream = ctx->streams[slots[j]];
+                rc = h_coeffs_batch_dev(ctx, ctx->d_verify + first * xw, cnt, lg, tables_of(j), coeffs_of(j), n * 4);  // h.get_poly().coeffs
+                ctx->stream = saved;
+            }
+            if (!rc) {
+                MsmBatch mb;
+                mb.count = (int)cnt;
+                for (size_t b = 0; b < cnt; ++b) mb.scalars[b] = coeffs_of(j) + b * n * 4;
+                rc = msm_enqueue_batch(ctx, slots[j], ctx->d_bases, mb, true, n);  // :338, asynchronous
+            }
+            if (rc) { abandon(); return rc; }
+            flight[j] = (long)g;
+        }
+        for (size_t g = ng > (size_t)S ? ng - (size_t)S : 0; g < ng; ++g) {
+            rc = collect(g % (size_t)S);
+            if (rc) { abandon(); return rc; }
+        }
+    }
+    int first = -1;
+    for (size_t i = 0; i < m; ++i) {
+        if (status) status[i] = res[i].rc;
+        if (res[i].rc && first < 0) first = (int)i;
+    }
+    if (first >= 0) { set_error("instance " + std::to_string(first) + ": " + res[first].err); return res[first].rc; }
+    return HALO_OK;
+}
+// the argument checks of both entry points (halo_pcdl_succinct_check_batch's), then the batch; acc: Accumulator blobs
+static int check_batch_entry(halo_ctx *ctx, size_t d, const uint64_t *blobs, size_t m, int *status, bool acc) {
+    if (m && !blobs) { set_error("check_batch: null pointer"); return HALO_E_ARG; }
+    if (!is_pow2(d + 1)) return fail_reject("d+1 is not a power of 2!");
+    size_t lg = ilog2(d + 1), stride = acc ? acc_words(lg) : instance_words(lg);
+    for (size_t i = 0; i < m; ++i)
+        if ((size_t)(blobs + i * stride)[12] != d || (blobs + i * stride)[22] != lg) return fail_reject("d_i != d");
+    if (m == 0) return HALO_OK;
+    return pcdl_check_batch_host(ctx, d, blobs, stride, m, status);
 }
 
 // One rank's half of pcdl::check when the key is sharded cyclically (point i on rank i mod P): the succinct check (host
@@ -685,6 +852,12 @@ int halo_pcdl_check(halo_ctx *ctx, const uint64_t C[12], size_t d, const uint64_
     return pcdl_check_host(ctx, Point::load(C), d, Fr::load(z), Fr::load(v), proof);
 }
 
+// pcdl::check of m instances at once (see pcdl_check_batch_host)
+int halo_pcdl_check_batch(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, int *status) {
+    HALO_CTX2(ctx);
+    return check_batch_entry(ctx, d, instances, m, status, false);
+}
+
 int halo_pcdl_check_partial(halo_ctx *ctx, const uint64_t C[12], size_t d, const uint64_t z[4], const uint64_t v[4], const uint64_t *proof,
                             uint64_t stride, uint64_t offset, uint64_t U_out[12], uint64_t part_out[12]) {
     HALO_CTX2(ctx);
@@ -901,6 +1074,12 @@ int halo_acc_verifier(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t m, con
 int halo_acc_decider(halo_ctx *ctx, const uint64_t *acc) {
     HALO_CTX2(ctx);
     return pcdl_check_host(ctx, Point::load(acc), (size_t)acc[12], Fr::load(acc + 13), Fr::load(acc + 17), acc + 21);
+}
+
+// acc::decider of m accumulators at once (benches/acc.rs:100-106 in one call): the check batch over their Instance prefixes
+int halo_acc_decider_batch(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, int *status) {
+    HALO_CTX2(ctx);
+    return check_batch_entry(ctx, d, accs, m, status, true);
 }
 
 // benches/acc.rs:15-29 random_instance (workload generator for BASELINE config 4)

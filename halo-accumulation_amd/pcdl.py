@@ -84,6 +84,24 @@ def check_proof(ctx, Cm, d, z, v, pi):
     check(ctx.lib.halo_pcdl_check(ctx.h, ptr(_a(Cm)), d, ptr(_a(z)), ptr(_a(v)), ptr(_a(pi))))
 
 
+def _check_batch(ctx, fn, d, blobs):
+    qs = np.ascontiguousarray(np.concatenate(blobs), dtype=np.uint64) if len(blobs) else np.zeros(0, dtype=np.uint64)
+    m = len(blobs)
+    status = (C.c_int * max(m, 1))()
+    rc = fn(ctx.h, d, ptr(qs), m, status)
+    st = [status[i] for i in range(m)]
+    if rc == _lib.HALO_E_REJECT:
+        raise _lib.HaloReject(ctx.lib.halo_last_error().decode(), st)
+    check(rc)
+    return st
+
+
+def check_batch(ctx, d, instances):
+    """pcdl::check (pcdl.rs:323-342) of m instances of degree bound d at once -> status list (all 0); raises HaloReject if any
+    instance fails, with the status list (what halo_pcdl_check returns for each alone) as its second argument"""
+    return _check_batch(ctx, ctx.lib.halo_pcdl_check_batch, d, instances)
+
+
 def check_partial(ctx, Cm, d, z, v, pi, stride, offset):
     """One rank's half of pcdl::check over a cyclically sharded key (halo_pcdl_check_partial): -> (U, this rank's share of
     CM.Commit(ck, h)).  The caller adds the shares in rank order and accepts iff the sum is U (sharded.ShardedOpen.check)."""

@@ -238,6 +238,16 @@ int halo_pcdl_succinct_check_batch(halo_ctx *ctx, size_t d, const uint64_t *inst
                                    int *status);
 /* pcdl::check (pcdl.rs:323-342) */
 int halo_pcdl_check(halo_ctx *ctx, const uint64_t C[12], size_t d, const uint64_t z[4], const uint64_t v[4], const uint64_t *proof);
+/* pcdl::check (pcdl.rs:323-342) of m instances at once.  instances = m Instance blobs at stride halo_instance_words(lg(d+1)),
+ * all of degree bound d.  The succinct checks run as in halo_pcdl_succinct_check_batch; the accepted members' h coefficients
+ * are expanded on the device and their n-point MSMs (pcdl.rs:338) run in batched launches of up to 8, rotating over the slots
+ * that are idle on entry (a caller's MSM in flight on another slot is left alone; no idle slot: HALO_E_ARG).  Every member gets
+ * its own exact MSM.  status[i] (nullable) = what halo_pcdl_check returns for member i alone; returns 0 if every member was
+ * accepted, else the first non-zero status in member order, halo_last_error() = "instance i: <its message>".  A null ctx, or a
+ * null `instances` with m > 0: HALO_E_ARG.  d + 1 not a power of two, or a member whose d or proof length differs from d:
+ * HALO_E_REJECT ("d_i != d") before any work, status not written.  m = 0: HALO_OK.  The staging of the members in flight is
+ * optional memory (halo_set_memory_budget): without it the members run one at a time, same results. */
+int halo_pcdl_check_batch(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, int *status /*nullable*/);
 /* One rank's half of pcdl::check over a key sharded cyclically (halo_ctx_create_urs_strided: point i on rank i mod stride,
  * offset = the rank): the succinct check (pcdl.rs:333, the same on every rank; d + 1 may be up to stride * the shard's size)
  * and this rank's share of CM.Commit(ck, h) (pcdl.rs:338) over its own points.  U_out = the proof's U after the succinct
@@ -293,6 +303,9 @@ int halo_msm_end_sharded(halo_ctx *ctx, int slot, size_t batch, uint64_t world, 
 int halo_acc_prover(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *instances, size_t m, uint64_t *acc_out);
 int halo_acc_verifier(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, const uint64_t *acc);
 int halo_acc_decider(halo_ctx *ctx, const uint64_t *acc);
+/* acc::decider (acc.rs:245-255) of m accumulators at once: benches/acc.rs:100-106 in one call.  accs = m Accumulator blobs at
+ * stride halo_accumulator_words(lg(d+1)); halo_pcdl_check_batch over their Instance prefixes, with its conventions. */
+int halo_acc_decider_batch(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, int *status /*nullable*/);
 /* benches/acc.rs:15-29 random_instance: the workload generator of the reference's benchmark */
 int halo_random_instance(halo_ctx *ctx, uint64_t *rng_state, size_t d, uint64_t *instance_out);
 

@@ -21,7 +21,10 @@ extern "C" {
  * reports out-of-memory), "force_peer_copy" (multi-device contexts stage device scalars through a peer copy even on one GPU),
  * "shard_fail_rank" + "shard_fail_at" (the rank with that offset fails locally before collective number `at` of a sharded open:
  * 0 = the share of p(z), 1.. = the rounds, then the tail; at = -2: in a sharded check; at = -3: the rank with that `rank`
- * before the collective of halo_msm_sharded / _dev_sharded / _end_sharded), "reset" (all off). */
+ * before the collective of halo_msm_sharded / _dev_sharded / _end_sharded), "batch_stage_fail" (value != 0: the staging of
+ * halo_pcdl_check_batch / halo_acc_decider_batch is refused, as over the memory budget: one member at a time in the context's
+ * scratch on one slot), "check_batch_group" (members per MSM launch of those calls, 1..8; 0: the measured default),
+ * "reset" (all off). */
 int halo_dev_hook(const char *name, long value);
 /* What the library read from the environment at its first use (csrc/tuning.hip), by field: "host_split_set", "host_pieces", "host_split0".."host_split3",
  * "fold_table_after", "graph_cache", "pow_e", "spin_us", "graphs", "memory_budget" (MiB, -1 unset), "trace", "tagged"; -1 for an
@@ -33,6 +36,11 @@ long halo_dev_tuning(const char *name);
  * (the two pairs of an IPA round, m = n / 2), 4 k_h_coeffs, 5 k_fold_scalars (m = n / 2), 6 k_axpy.  For rocprofv3 / the
  * event profiler: steady-state kernel durations, the figures of bench.py's hbm_kernels block. */
 int halo_bench_fr_kernel(halo_ctx *ctx, int which, size_t n, int reps);
+
+/* The batched h expansion of halo_pcdl_check_batch (k_h_tables + k_h_coeffs_batch) on its own: xis = m x (lg_n + 1) x 4
+ * Montgomery words, out = m x 2^lg_n x 4 words; member b's block equals halo_h_coeffs(xis_b, lg_n).  2^lg_n <= the context's
+ * size (64 at least). */
+int halo_dev_h_coeffs_batch(halo_ctx *ctx, const uint64_t *xis, size_t m, size_t lg_n, uint64_t *out);
 
 /* replay cached hipGraphs of the MSM launch sequence when the same shape repeats (default on) */
 int halo_set_graphs(halo_ctx *ctx, int on);  /* also: environment HALO_GRAPHS=0 at context creation; HALO_TRACE=1 logs every launch */

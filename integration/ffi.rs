@@ -48,6 +48,9 @@ extern "C" {
     pub fn halo_h_coeffs(ctx: *mut HaloCtx, xis: *const u64, lg_n: usize, out: *mut u64) -> c_int;
     pub fn halo_h_commit(ctx: *mut HaloCtx, xis: *const u64, lg_n: usize, out_jac: *mut u64) -> c_int;
     pub fn halo_h_eval_batch(ctx: *mut HaloCtx, xis: *const u64, m: usize, lg_n: usize, z: *const u64, out: *mut u64) -> c_int;
+    // pcdl::check / acc::decider of m blobs at once (status: m codes, may be null)
+    pub fn halo_pcdl_check_batch(ctx: *mut HaloCtx, d: usize, instances: *const u64, m: usize, status: *mut c_int) -> c_int;
+    pub fn halo_acc_decider_batch(ctx: *mut HaloCtx, d: usize, accs: *const u64, m: usize, status: *mut c_int) -> c_int;
     pub fn halo_h_accumulate(ctx: *mut HaloCtx, h0: *const u64, xis: *const u64, alphas: *const u64, m: usize, lg_n: usize, out: *mut u64) -> c_int;
     pub fn halo_ipa_begin(ctx: *mut HaloCtx, n: usize, coeffs: *const u64, len: usize, z: *const u64, out: *mut *mut HaloIpa) -> c_int;
     pub fn halo_ipa_round_lr(st: *mut HaloIpa, h_prime: *const u64, l: *mut u64, r: *mut u64) -> c_int;
