@@ -25,6 +25,16 @@ def random_instance(ctx, rng, d):
     return inst
 
 
+def random_instance_batch(ctx, rng, d, m):
+    """benches/acc.rs:15-29, m times in one call (halo_random_instance_batch) -> the m Instances random_instance returns in turn,
+    rng[0] updated as it would update it"""
+    st = C.c_uint64(rng[0])
+    out = np.zeros((max(m, 1), ctx.lib.halo_instance_words(lg_of(d))), dtype=np.uint64)
+    check(ctx.lib.halo_random_instance_batch(ctx.h, C.byref(st), d, m, ptr(out)))
+    rng[0] = st.value
+    return [out[i].copy() for i in range(m)]
+
+
 def prover(ctx, rng, d, qs):
     """acc.rs:190-220"""
     st = C.c_uint64(rng[0])

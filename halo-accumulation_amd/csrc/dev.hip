@@ -170,8 +170,9 @@ int halo_dev_hook(const char *name, long value) {
     else if (!std::strcmp(name, "shard_fail_at")) h.shard_fail_at = (int)value;  // >= 0: a sharded open's collective, -2: check, -3: MSM
     else if (!std::strcmp(name, "batch_stage_fail")) h.batch_stage_fail = (int)value;
     else if (!std::strcmp(name, "check_batch_group")) h.check_group = (int)value;
+    else if (!std::strcmp(name, "open_batch_group")) h.open_group = (int)value;
     else if (!std::strcmp(name, "reset")) h = DevHooks();
-    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, reset)"); return HALO_E_ARG; }
+    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, reset)"); return HALO_E_ARG; }
     return HALO_OK;
 }
 

@@ -332,6 +332,9 @@ struct halo_ctx {
     // Optional memory (on the budget of halo_set_memory_budget; released at destroy), only grown, so its address stays put
     uint64_t *d_check_stage = nullptr;
     size_t check_stage_bytes = 0;
+    // (the same staging holds the member state of halo_pcdl_open_batch / halo_random_instance_batch; these are their per-slot
+    // constants and results in pinned memory, allocated at the first batched open)
+    uint64_t *h_open_pinned = nullptr;
     // lazily allocated n x 4 polynomial buffers for pcdl::open / acc::prover
     uint64_t *d_poly = nullptr, *d_poly2 = nullptr;
     halo::HostWorker worker;      // host arithmetic overlapped with the caller's (see HostWorker; multi.hip also runs a shard's HIP calls on it)
@@ -509,6 +512,41 @@ int bench_fr_kernel(halo_ctx *ctx, int which, size_t n, int reps);
 int nofold_expand(halo_ctx *ctx, const uint64_t *d_c, const uint64_t *d_s, size_t m, size_t M, uint64_t *d_L, uint64_t *d_R);
 int nofold_expand_tagged(halo_ctx *ctx, const uint64_t *d_c, const uint64_t *d_s, size_t m, size_t M, uint64_t *d_F);  // one array for a tagged launch
 int nofold_s_update(halo_ctx *ctx, const uint64_t *d_s_in, size_t len, const host::Fr &xi, uint64_t *d_s_out);
+
+// ---- ipa.hip: the member-batched kernels of halo_pcdl_open_batch (pcdl_acc.hip).  G <= OPEN_MAX_GROUP members per launch,
+// blockIdx.y = member.  Member b's vectors sit at b * ms words from the base pointers; its window table, constants, partial sums
+// and results at b * OPEN_*_WORDS in the group's own regions.
+constexpr int OPEN_MAX_GROUP = 4;
+constexpr size_t OPEN_TAB_WORDS = 1024, OPEN_CONST_WORDS = 32, OPEN_PART_WORDS = 1024, OPEN_OUT_WORDS = 32;
+constexpr size_t OPEN_MAX_N = (size_t)1 << 16;  // the batched kernels' partial sums and window tables are sized for this
+// One member's constants in device memory (uploaded once per step of a group, never kernel arguments): N-form multipliers
+// (ipa.hip FsArg: 9 x 29-bit limbs) and Montgomery limbs (FeArg: 8 x 32 bits)
+struct OpenConst {
+    uint32_t xi_n[9], xi_inv_n[9], alpha_n[9], z64_n[9];
+    uint32_t xi_m[8], z_m[8];
+    uint64_t s_q;  // rng state before q of p_bar (deg scalars)
+    uint64_t s_p;  // rng state before p of random_instance (deg + 1 scalars)
+    uint32_t deg;  // the member's degree
+    uint32_t len;  // axpy: coefficients of p' = p + alpha p_bar (deg + 1)
+    uint32_t pad[6];
+};
+// (the host fills an array of these and the kernels index records of OPEN_CONST_WORDS: the two strides must agree)
+static_assert(sizeof(OpenConst) == OPEN_CONST_WORDS * 8, "OpenConst record");
+// host: member's window table of z (powers and p(z) over n coefficients) into h_tab (OPEN_TAB_WORDS), z and z^64 into k
+int open_batch_table(const host::Fr &z, size_t n, uint64_t *h_tab, OpenConst *k);
+void open_const_xi(OpenConst *k, const host::Fr &xi, const host::Fr &xi_inv);
+void open_const_alpha(OpenConst *k, const host::Fr &alpha);
+// on ctx->stream; outs: the group's result records (OPEN_OUT_WORDS each): v at +0, dot_l / dot_r at +4 / +8
+int open_batch_eval(halo_ctx *ctx, int G, const uint64_t *d_coeffs, size_t ms, size_t n, const uint64_t *d_tabs, uint64_t *d_parts, uint64_t *d_outs);
+int open_batch_powers(halo_ctx *ctx, int G, const uint64_t *d_tabs, const uint64_t *d_consts, size_t n, uint64_t *d_z, size_t ms);
+int open_batch_pbar(halo_ctx *ctx, int G, const uint64_t *d_consts, size_t n, uint64_t *d_out, size_t ms);
+int open_batch_rng(halo_ctx *ctx, int G, const uint64_t *d_consts, size_t n, uint64_t *d_out, size_t ms);
+int open_batch_axpy(halo_ctx *ctx, int G, uint64_t *d_y, const uint64_t *d_x, size_t ms, size_t n, const uint64_t *d_consts);
+int open_batch_expand(halo_ctx *ctx, int G, const uint64_t *d_c, const uint64_t *d_s, size_t ms, size_t m, size_t M, uint64_t *d_L, uint64_t *d_R);
+int open_batch_dots(halo_ctx *ctx, int G, const uint64_t *d_c, const uint64_t *d_z, size_t ms, size_t m, uint64_t *d_parts, uint64_t *d_outs);
+// s_out[2t + u] = s_in[t] xi^u (t < s_len), then c' = c_l + xi^-1 c_r, z' = z_l + xi z_r over m
+int open_batch_fold(halo_ctx *ctx, int G, uint64_t *d_c, uint64_t *d_z, const uint64_t *d_s_in, uint64_t *d_s_out, size_t ms, size_t m,
+                    size_t s_len, const uint64_t *d_consts);
 
 // ---- abi.hip (device-pointer forms used by pcdl_acc.hip)
 // H' = xi0 * H for this state (pcdl.rs:181): lets the rounds use the process-wide window table of H

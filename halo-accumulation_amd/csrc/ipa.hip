@@ -304,10 +304,8 @@ HALO_DEV Fs<2> dot_step(const Fs<2> &acc, const DotOps &o) {
     return fs_tighten(fs_add(acc, fs_mul_add_mul(fs_from_fe(o.x), fs_from_fe(o.y), fs_from_fe(o.x2), fs_from_fe(o.y2))));
 }
 template <bool HAS1>
-__global__ __launch_bounds__(256) void k_dot2_partial(const uint64_t *__restrict__ xs0, const uint64_t *__restrict__ ys0,
-                                                      const uint64_t *__restrict__ xs1, const uint64_t *__restrict__ ys1, uint32_t m,
-                                                      uint64_t *__restrict__ partial) {
-    __shared__ Fe lds[8];
+HALO_DEV void dot2_partial_body(const uint64_t *__restrict__ xs0, const uint64_t *__restrict__ ys0, const uint64_t *__restrict__ xs1,
+                                const uint64_t *__restrict__ ys1, uint32_t m, uint64_t *__restrict__ partial, Fe *lds /* 8 */) {
     Fs<2> a0 = fs_zero<2>(), a1 = fs_zero<2>();
     const uint32_t stride = gridDim.x * 256;
     uint32_t i = blockIdx.x * 256 + threadIdx.x;
@@ -335,11 +333,17 @@ __global__ __launch_bounds__(256) void k_dot2_partial(const uint64_t *__restrict
         fe_store(partial + 8 * (size_t)blockIdx.x + 4, s1);
     }
 }
+template <bool HAS1>
+__global__ __launch_bounds__(256) void k_dot2_partial(const uint64_t *__restrict__ xs0, const uint64_t *__restrict__ ys0,
+                                                      const uint64_t *__restrict__ xs1, const uint64_t *__restrict__ ys1, uint32_t m,
+                                                      uint64_t *__restrict__ partial) {
+    __shared__ Fe lds[8];
+    dot2_partial_body<HAS1>(xs0, ys0, xs1, ys1, m, partial, lds);
+}
 // sums `count` partial records of `width` Fr each into out[width]; times32: the records are sums of A(x) A(y) products
 // (1/32 of the A-form value): the total is multiplied by 32 (fr29.hpp C266)
-__global__ __launch_bounds__(256) void k_sum_partials(const uint64_t *__restrict__ partial, uint32_t count, uint32_t width, int times32,
-                                                      uint64_t *__restrict__ out) {
-    __shared__ Fe lds[4];
+HALO_DEV void sum_partials_body(const uint64_t *__restrict__ partial, uint32_t count, uint32_t width, int times32, uint64_t *__restrict__ out,
+                                Fe *lds /* 4 */) {
     for (uint32_t k = 0; k < width; k++) {
         Fe a = fe_zero();
         for (uint32_t i = threadIdx.x; i < count; i += 256) a = fe_add<FrCfg>(a, fe_load(partial + 4 * ((size_t)i * width + k)));
@@ -350,6 +354,11 @@ __global__ __launch_bounds__(256) void k_sum_partials(const uint64_t *__restrict
         }
         __syncthreads();
     }
+}
+__global__ __launch_bounds__(256) void k_sum_partials(const uint64_t *__restrict__ partial, uint32_t count, uint32_t width, int times32,
+                                                      uint64_t *__restrict__ out) {
+    __shared__ Fe lds[4];
+    sum_partials_body(partial, count, width, times32, out, lds);
 }
 
 // ---- powers of one scalar: the window table the host prepares (upload_window_table)
@@ -391,17 +400,19 @@ static int pow_chain_len(size_t n, int best) {
 // ------------------------------------------------------------------ K6: out[i] = z^i
 // One product per 32 bytes written: VALU-bound (fr29.hpp: 5.3 TB/s if nothing else ran).  Lane l of a wave writes the
 // elements base + l + 64 k: every store instruction of the wave covers 2 KiB of consecutive addresses.
-__global__ __launch_bounds__(256) void k_powers(const uint64_t *__restrict__ tab, int nwin, int E, uint32_t n, FsArg z64, uint64_t *__restrict__ out) {
+HALO_DEV void powers_body(const uint64_t *__restrict__ tab, int nwin, int E, uint32_t n, const Fs<1> &step, uint64_t *__restrict__ out) {
     uint32_t wave = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
     uint32_t e = wave * (64u * (uint32_t)E) + lane;
     if (e >= n) return;
     Fs<2> cur = fs_tighten(window_power(tab, e, nwin, true));
-    Fs<1> step = from_nform(z64);
 #pragma unroll 1
     for (int k = 0; k < E && e < n; k++, e += 64) {
         fs_store(out + 4 * (size_t)e, cur);  // (a product's result is below 2 r: one conditional subtraction)
         cur = fs_mul(cur, step);
     }
+}
+__global__ __launch_bounds__(256) void k_powers(const uint64_t *__restrict__ tab, int nwin, int E, uint32_t n, FsArg z64, uint64_t *__restrict__ out) {
+    powers_body(tab, nwin, E, n, from_nform(z64), out);
 }
 
 // ------------------------------------------------------------------ K9: p(z)
@@ -411,9 +422,8 @@ __global__ __launch_bounds__(256) void k_powers(const uint64_t *__restrict__ tab
 // r3 weak #7: 1.34 TB/s, half of the kernel's own VALU bound) was E dependent products on a grid of one wave per SIMD, i.e.
 // one product in flight per SIMD; here the next pair's operands are in flight and its products issue while the current
 // reduction runs.
-__global__ __launch_bounds__(256) void k_poly_eval_partial(const uint64_t *__restrict__ coeffs, uint32_t len, const uint64_t *__restrict__ tab,
-                                                           int nwin, int E, const uint64_t *__restrict__ zpow, uint64_t *__restrict__ partial) {
-    __shared__ Fe lds[4];
+HALO_DEV void poly_eval_partial_body(const uint64_t *__restrict__ coeffs, uint32_t len, const uint64_t *__restrict__ tab, int nwin, int E,
+                                     const uint64_t *__restrict__ zpow, uint64_t *__restrict__ partial, Fe *lds /* 4 */) {
     Fs<2> acc = fs_zero<2>();
     uint32_t lane = threadIdx.x & 63u, nwaves = gridDim.x * 4;
     for (uint32_t wave = (blockIdx.x * 256 + threadIdx.x) >> 6; (size_t)wave * (64u * (uint32_t)E) < len; wave += nwaves) {
@@ -440,6 +450,11 @@ __global__ __launch_bounds__(256) void k_poly_eval_partial(const uint64_t *__res
     }
     Fe s = block_sum_fr(fs_to_fe(acc), lds);
     if (threadIdx.x == 0) fe_store(partial + 4 * (size_t)blockIdx.x, s);
+}
+__global__ __launch_bounds__(256) void k_poly_eval_partial(const uint64_t *__restrict__ coeffs, uint32_t len, const uint64_t *__restrict__ tab,
+                                                           int nwin, int E, const uint64_t *__restrict__ zpow, uint64_t *__restrict__ partial) {
+    __shared__ Fe lds[4];
+    poly_eval_partial_body(coeffs, len, tab, nwin, E, zpow, partial, lds);
 }
 
 // ------------------------------------------------------------------ K7: h coefficients from three 256-entry tables
@@ -699,6 +714,118 @@ __global__ __launch_bounds__(256) void k_scale(uint64_t *__restrict__ v, uint32_
     fe_store(v + 4 * (size_t)i, fe_mul<FrCfg>(fe_load(v + 4 * (size_t)i), from_arg(aarg)));
 }
 
+// ================================================================== member-batched forms (halo_pcdl_open_batch)
+// The kernels of one open above with blockIdx.y = member (as k_h_coeffs_batch is to k_h_coeffs): member b's vectors at b * ms words
+// from the base pointers, its window table / partial sums / results at b * OPEN_TAB_WORDS / OPEN_PART_WORDS / OPEN_OUT_WORDS, its
+// field constants in record b of `consts` (OpenConst, device memory).  Everything a block reads of its member is the same for all
+// of its lanes: control flow stays wave-uniform over the member index.
+HALO_DEV const OpenConst &open_const(const uint64_t *consts) { return *(const OpenConst *)(consts + OPEN_CONST_WORDS * (size_t)blockIdx.y); }
+HALO_DEV Fs<1> fs_from_n9(const uint32_t (&v)[9]) {
+    Fs<1> r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.v[i] = v[i];
+    return r;
+}
+HALO_DEV Fe fe_from_m8(const uint32_t (&v)[8]) {
+    Fe r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.v[i] = v[i];
+    return r;
+}
+// v_b = p_b(z_b): k_poly_eval_partial over each member's coefficients with its own table (zpow behind the window entries)
+__global__ __launch_bounds__(256) void k_poly_eval_partial_batch(const uint64_t *__restrict__ coeffs, uint64_t ms, uint32_t len,
+                                                                 const uint64_t *__restrict__ tabs, int nwin, int E, uint64_t *__restrict__ parts) {
+    __shared__ Fe lds[4];
+    const uint64_t *tab = tabs + OPEN_TAB_WORDS * (size_t)blockIdx.y;
+    poly_eval_partial_body(coeffs + ms * blockIdx.y, len, tab, nwin, E, tab + 4 * (size_t)(16 * (1 + nwin)), parts + OPEN_PART_WORDS * (size_t)blockIdx.y, lds);
+}
+// one block per member: k_sum_partials into the member's result record
+__global__ __launch_bounds__(256) void k_sum_partials_batch(const uint64_t *__restrict__ parts, uint32_t count, uint32_t width, int times32,
+                                                            uint64_t *__restrict__ outs) {
+    __shared__ Fe lds[4];
+    sum_partials_body(parts + OPEN_PART_WORDS * (size_t)blockIdx.y, count, width, times32, outs + OPEN_OUT_WORDS * (size_t)blockIdx.y, lds);
+}
+// z_b^i, i < n
+__global__ __launch_bounds__(256) void k_powers_batch(const uint64_t *__restrict__ tabs, const uint64_t *__restrict__ consts, int nwin, int E,
+                                                      uint32_t n, uint64_t *__restrict__ out, uint64_t ms) {
+    powers_body(tabs + OPEN_TAB_WORDS * (size_t)blockIdx.y, nwin, E, n, fs_from_n9(open_const(consts).z64_n), out + ms * blockIdx.y);
+}
+// p_bar_b = q_b (X - z_b) over all n coefficients (zero past deg), q_b = deg scalars of the stream after s_q (k_rng_scalars + k_pbar
+// in one pass: the same elements, the same products)
+__global__ __launch_bounds__(256) void k_pbar_batch(const uint64_t *__restrict__ consts, uint32_t n, uint64_t *__restrict__ out, uint64_t ms) {
+    uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const OpenConst &k = open_const(consts);
+    Fe r = fe_zero();
+    if (i <= k.deg) {
+        Fe lo = (i >= 1) ? rng_scalar_at(k.s_q, i - 1) : fe_zero();
+        Fe hi = (i < k.deg) ? rng_scalar_at(k.s_q, i) : fe_zero();
+        r = fe_sub<FrCfg>(lo, fe_mul<FrCfg>(fe_from_m8(k.z_m), hi));
+    }
+    fe_store(out + ms * blockIdx.y + 4 * (size_t)i, r);
+}
+// p_b = deg + 1 scalars of the stream after s_p, zero-padded to n (random_instance's PallasPoly::rand)
+__global__ __launch_bounds__(256) void k_rng_batch(const uint64_t *__restrict__ consts, uint32_t n, uint64_t *__restrict__ out, uint64_t ms) {
+    uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const OpenConst &k = open_const(consts);
+    fe_store(out + ms * blockIdx.y + 4 * (size_t)i, i <= k.deg ? rng_scalar_at(k.s_p, i) : fe_zero());
+}
+// y_b[i] += alpha_b x_b[i], i < len_b
+__global__ __launch_bounds__(256) void k_axpy_batch(uint64_t *__restrict__ y, const uint64_t *__restrict__ x, uint64_t ms, const uint64_t *__restrict__ consts) {
+    uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    const OpenConst &k = open_const(consts);
+    if (i >= k.len) return;
+    size_t o = ms * blockIdx.y + 4 * (size_t)i;
+    Fe yv = fe_load(y + o), xv = fe_load(x + o);
+    fs_store(y + o, fs_add(fs_from_fe(yv), fs_mul(fs_from_fe(xv), fs_from_n9(k.alpha_n))));
+}
+// k_nofold_expand of each member from its own c and s
+__global__ __launch_bounds__(256) void k_nofold_expand_batch(const uint64_t *__restrict__ c, const uint64_t *__restrict__ sv, uint64_t ms, uint32_t m,
+                                                             int log2m, uint32_t M, uint64_t *__restrict__ outL, uint64_t *__restrict__ outR) {
+    uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= M) return;
+    const size_t o = ms * blockIdx.y;
+    uint32_t u = b & (m - 1), t = b >> log2m, h = m >> 1;
+    Fe sc = fe_load(sv + o + 4 * (size_t)t);
+    if (u < h) {
+        fe_store(outL + o + 4 * (size_t)b, fe_mul<FrCfg>(fe_load(c + o + 4 * (size_t)(u + h)), sc));
+        fe_store(outR + o + 4 * (size_t)b, fe_zero());
+    } else {
+        fe_store(outR + o + 4 * (size_t)b, fe_mul<FrCfg>(fe_load(c + o + 4 * (size_t)(u - h)), sc));
+        fe_store(outL + o + 4 * (size_t)b, fe_zero());
+    }
+}
+// <c_r, z_l> and <c_l, z_r> of each member (k_dot2_partial<true>)
+__global__ __launch_bounds__(256) void k_dot2_partial_batch(const uint64_t *__restrict__ c, const uint64_t *__restrict__ z, uint64_t ms, uint32_t m,
+                                                            uint64_t *__restrict__ parts) {
+    __shared__ Fe lds[8];
+    const size_t o = ms * blockIdx.y;
+    dot2_partial_body<true>(c + o + 4 * (size_t)m, z + o, c + o, z + o + 4 * (size_t)m, m, parts + OPEN_PART_WORDS * (size_t)blockIdx.y, lds);
+}
+// k_fold_scalars with each member's xi, xi^-1
+__global__ __launch_bounds__(256) void k_fold_scalars_batch(uint64_t *__restrict__ c, uint64_t *__restrict__ z, uint64_t ms, uint32_t m,
+                                                            const uint64_t *__restrict__ consts) {
+    uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= m) return;
+    const OpenConst &k = open_const(consts);
+    const size_t o = ms * blockIdx.y;
+    Fe cl = fe_load(c + o + 4 * (size_t)j), cr = fe_load(c + o + 4 * (size_t)(j + m));
+    Fe zl = fe_load(z + o + 4 * (size_t)j), zr = fe_load(z + o + 4 * (size_t)(j + m));
+    fs_store(c + o + 4 * (size_t)j, fs_add(fs_from_fe(cl), fs_mul(fs_from_fe(cr), fs_from_n9(k.xi_inv_n))));
+    fs_store(z + o + 4 * (size_t)j, fs_add(fs_from_fe(zl), fs_mul(fs_from_fe(zr), fs_from_n9(k.xi_n))));
+}
+// k_nofold_s_update with each member's xi
+__global__ __launch_bounds__(256) void k_nofold_s_update_batch(const uint64_t *__restrict__ s_in, uint64_t *__restrict__ s_out, uint64_t ms, uint32_t len,
+                                                               const uint64_t *__restrict__ consts) {
+    uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 2 * len) return;
+    const size_t o = ms * blockIdx.y;
+    Fe v = fe_load(s_in + o + 4 * (size_t)(i >> 1));
+    if (i & 1) v = fe_mul<FrCfg>(v, fe_from_m8(open_const(consts).xi_m));
+    fe_store(s_out + o + 4 * (size_t)i, v);
+}
+
 // ================================================================== host launchers
 int ipa_fold_points(halo_ctx *ctx, uint32_t *d_G, size_t m, const host::Fr &xi_mont) {
     if (m == 0) return HALO_OK;
@@ -799,8 +926,8 @@ static int bits_for(size_t n) {
     return b < 1 ? 1 : b;
 }
 // zpows > 0: N(z^(64 k)), k < zpows, behind the window table (k_poly_eval_partial's per-element multipliers)
-static int upload_window_table(halo_ctx *ctx, const host::Fr &z, int nwin, uint64_t *d_tab, host::Fr *z64, int zpows = 0) {
-    uint64_t *h = ctx->h_wintab;  // pinned, 1024 words: nwin <= 15
+// fills h (16 (1 + nwin) + zpows entries of 4 words); -1 if that is more than 256 entries
+static long fill_window_table(const host::Fr &z, int nwin, uint64_t *h, host::Fr *z64, int zpows) {
     const host::Fr k32 = host::Fr::from_u64(32);
     host::Fr base = z;  // z^(16^k)
     for (int k = 0; k < nwin; ++k) {
@@ -816,13 +943,19 @@ static int upload_window_table(halo_ctx *ctx, const host::Fr &z, int nwin, uint6
     for (int i = 0; i < 6; ++i) t = t.sqr();
     *z64 = t;
     size_t entries = (size_t)16 * (1 + nwin);
-    if (entries + (size_t)zpows > 256) { set_error("window table: too many entries"); return HALO_E_ARG; }  // (h_wintab: 256 entries)
+    if (entries + (size_t)zpows > 256) return -1;  // (h_wintab: 256 entries)
     host::Fr cur = host::Fr::one();
     for (int k = 0; k < zpows; ++k) {
         (cur * k32).store(h + 4 * (entries + (size_t)k));
         cur = cur * t;
     }
-    HALO_HIP(hipMemcpyAsync(d_tab, h, (entries + (size_t)zpows) * 32, hipMemcpyHostToDevice, ctx->stream));
+    return (long)(entries + (size_t)zpows);
+}
+static int upload_window_table(halo_ctx *ctx, const host::Fr &z, int nwin, uint64_t *d_tab, host::Fr *z64, int zpows = 0) {
+    uint64_t *h = ctx->h_wintab;  // pinned, 1024 words: nwin <= 15
+    long entries = fill_window_table(z, nwin, h, z64, zpows);
+    if (entries < 0) { set_error("window table: too many entries"); return HALO_E_ARG; }
+    HALO_HIP(hipMemcpyAsync(d_tab, h, (size_t)entries * 32, hipMemcpyHostToDevice, ctx->stream));
     HALO_HIP(hipStreamSynchronize(ctx->stream));  // the staging memory is reused by the next call
     return HALO_OK;
 }
@@ -1032,6 +1165,88 @@ int pbar_stream_dev(halo_ctx *ctx, uint64_t state0, size_t deg, const host::Fr &
     if (n_local == 0) return HALO_OK;
     HALO_LAUNCH(ctx, "k_pbar_stream", k_pbar_stream, dim3((unsigned)((n_local + 255) / 256)), dim3(256), 0, state0, (uint32_t)deg, to_arg(z),
                 (uint32_t)stride, (uint32_t)offset, (uint32_t)n_local, d_out);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
+
+// ---- member-batched launchers (halo_pcdl_open_batch)
+// One window table per member serves both of its uses: powers of z over n (window part) and p(z) over n coefficients (the
+// zpow entries behind it); fr_powers / fr_poly_eval build the same entries.
+int open_batch_table(const host::Fr &z, size_t n, uint64_t *h_tab, OpenConst *k) {
+    const int nwin = (bits_for(n) + 3) / 4;
+    host::Fr z64;
+    if (fill_window_table(z, nwin, h_tab, &z64, pow_chain_len(n, POLY_EVAL_E)) < 0) { set_error("window table: too many entries"); return HALO_E_ARG; }
+    FsArg a = to_nform(z64);
+    FeArg b = to_arg(z);
+    for (int i = 0; i < 9; ++i) k->z64_n[i] = a.v[i];
+    for (int i = 0; i < 8; ++i) k->z_m[i] = b.v[i];
+    return HALO_OK;
+}
+void open_const_xi(OpenConst *k, const host::Fr &xi, const host::Fr &xi_inv) {
+    FsArg a = to_nform(xi), b = to_nform(xi_inv);
+    FeArg c = to_arg(xi);
+    for (int i = 0; i < 9; ++i) { k->xi_n[i] = a.v[i]; k->xi_inv_n[i] = b.v[i]; }
+    for (int i = 0; i < 8; ++i) k->xi_m[i] = c.v[i];
+}
+void open_const_alpha(OpenConst *k, const host::Fr &alpha) {
+    FsArg a = to_nform(alpha);
+    for (int i = 0; i < 9; ++i) k->alpha_n[i] = a.v[i];
+}
+int open_batch_eval(halo_ctx *ctx, int G, const uint64_t *d_coeffs, size_t ms, size_t n, const uint64_t *d_tabs, uint64_t *d_parts, uint64_t *d_outs) {
+    const int nwin = (bits_for(n) + 3) / 4, E = pow_chain_len(n, POLY_EVAL_E);
+    unsigned nb = wave_blocks(n, E);
+    if (nb > OPEN_PART_WORDS / 4) { set_error("open_batch: polynomial too long for the batched evaluation"); return HALO_E_ARG; }
+    HALO_LAUNCH(ctx, "k_poly_eval_partial_batch", k_poly_eval_partial_batch, dim3(nb, (unsigned)G), dim3(256), 0, d_coeffs, (uint64_t)ms, (uint32_t)n,
+                d_tabs, nwin, E, d_parts);
+    HALO_LAUNCH(ctx, "k_sum_partials_batch", k_sum_partials_batch, dim3(1, (unsigned)G), dim3(256), 0, d_parts, nb, 1u, 0, d_outs);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+int open_batch_powers(halo_ctx *ctx, int G, const uint64_t *d_tabs, const uint64_t *d_consts, size_t n, uint64_t *d_z, size_t ms) {
+    const int nwin = (bits_for(n) + 3) / 4, E = pow_chain_len(n, 8);
+    HALO_LAUNCH(ctx, "k_powers_batch", k_powers_batch, dim3(wave_blocks(n, E), (unsigned)G), dim3(256), 0, d_tabs, d_consts, nwin, E, (uint32_t)n, d_z,
+                (uint64_t)ms);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+int open_batch_pbar(halo_ctx *ctx, int G, const uint64_t *d_consts, size_t n, uint64_t *d_out, size_t ms) {
+    HALO_LAUNCH(ctx, "k_pbar_batch", k_pbar_batch, dim3((unsigned)((n + 255) / 256), (unsigned)G), dim3(256), 0, d_consts, (uint32_t)n, d_out, (uint64_t)ms);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+int open_batch_rng(halo_ctx *ctx, int G, const uint64_t *d_consts, size_t n, uint64_t *d_out, size_t ms) {
+    HALO_LAUNCH(ctx, "k_rng_batch", k_rng_batch, dim3((unsigned)((n + 255) / 256), (unsigned)G), dim3(256), 0, d_consts, (uint32_t)n, d_out, (uint64_t)ms);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+int open_batch_axpy(halo_ctx *ctx, int G, uint64_t *d_y, const uint64_t *d_x, size_t ms, size_t n, const uint64_t *d_consts) {
+    HALO_LAUNCH(ctx, "k_axpy_batch", k_axpy_batch, dim3((unsigned)((n + 255) / 256), (unsigned)G), dim3(256), 0, d_y, d_x, (uint64_t)ms, d_consts);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+int open_batch_expand(halo_ctx *ctx, int G, const uint64_t *d_c, const uint64_t *d_s, size_t ms, size_t m, size_t M, uint64_t *d_L, uint64_t *d_R) {
+    int log2m = 0;
+    while (((size_t)1 << log2m) < m) log2m++;
+    HALO_LAUNCH(ctx, "k_nofold_expand_batch", k_nofold_expand_batch, dim3((unsigned)((M + 255) / 256), (unsigned)G), dim3(256), 0, d_c, d_s, (uint64_t)ms,
+                (uint32_t)m, log2m, (uint32_t)M, d_L, d_R);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+int open_batch_dots(halo_ctx *ctx, int G, const uint64_t *d_c, const uint64_t *d_z, size_t ms, size_t m, uint64_t *d_parts, uint64_t *d_outs) {
+    unsigned nb = dot_blocks(m);
+    if (nb > OPEN_PART_WORDS / 8) nb = OPEN_PART_WORDS / 8;  // (the sums are exact: any grid gives the same field elements)
+    HALO_LAUNCH(ctx, "k_dot2_partial_batch", k_dot2_partial_batch, dim3(nb, (unsigned)G), dim3(256), 0, d_c, d_z, (uint64_t)ms, (uint32_t)m, d_parts);
+    HALO_LAUNCH(ctx, "k_sum_partials_batch", k_sum_partials_batch, dim3(1, (unsigned)G), dim3(256), 0, d_parts, nb, 2u, 1, d_outs + 4);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+int open_batch_fold(halo_ctx *ctx, int G, uint64_t *d_c, uint64_t *d_z, const uint64_t *d_s_in, uint64_t *d_s_out, size_t ms, size_t m, size_t s_len,
+                    const uint64_t *d_consts) {
+    HALO_LAUNCH(ctx, "k_nofold_s_update_batch", k_nofold_s_update_batch, dim3((unsigned)((2 * s_len + 255) / 256), (unsigned)G), dim3(256), 0, d_s_in,
+                d_s_out, (uint64_t)ms, (uint32_t)s_len, d_consts);
+    HALO_LAUNCH(ctx, "k_fold_scalars_batch", k_fold_scalars_batch, dim3((unsigned)((m + 255) / 256), (unsigned)G), dim3(256), 0, d_c, d_z, (uint64_t)ms,
+                (uint32_t)m, d_consts);
     HALO_HIP(hipGetLastError());
     return HALO_OK;
 }

@@ -691,6 +691,435 @@ static int common_subroutine(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t
 
 using namespace halo;
 
+// the body of halo_pcdl_open after its argument checks (deg = host_poly_degree(coeffs) <= d)
+static int pcdl_open_host(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *coeffs, size_t deg, const uint64_t C[12], size_t d, const uint64_t z[4],
+                          const uint64_t *w, uint64_t *proof_out) {
+    int rc = ensure_poly_buffers(ctx);
+    if (rc) return rc;
+    HALO_HIP(hipMemsetAsync(ctx->d_poly, 0, (d + 1) * 32, ctx->stream));
+    rc = upload_words(ctx, ctx->d_poly, coeffs, (deg + 1) * 4);
+    if (rc) return rc;
+    host::Rng rng{rng_state ? *rng_state : 0};
+    Fr wf = w ? Fr::load(w) : Fr::zero();
+    rc = pcdl_open_dev(ctx, &rng, deg, Point::load(C), d, Fr::load(z), w ? &wf : nullptr, proof_out);
+    if (rng_state) *rng_state = rng.state;
+    return rc;
+}
+
+// the body of halo_random_instance after its argument checks
+static int random_instance_one(halo_ctx *ctx, uint64_t *rng_state, size_t d, uint64_t *inst) {
+    size_t lg = ilog2(d + 1), n = d + 1;
+    host::Rng rng{rng_state ? *rng_state : 0};
+    size_t lo = d / 2, d_prime = lo + (size_t)(rng.next() % (uint64_t)(d - lo));
+    if (d_prime == 0) d_prime = 1;
+    Fr w = rng.scalar();
+    int rc = ensure_poly_buffers(ctx);
+    if (rc) return rc;
+    // p = PallasPoly::rand(d_prime): d_prime + 1 scalars of the stream, generated on the device
+    HALO_HIP(hipMemsetAsync(ctx->d_poly, 0, n * 32, ctx->stream));
+    rc = rng_scalars_dev(ctx, rng.state, d_prime + 1, ctx->d_poly);
+    if (rc) return rc;
+    rng.state += 4 * (uint64_t)(d_prime + 1) * 0x9E3779B97F4A7C15ULL;
+    Point C;
+    rc = pedersen_commit_dev(ctx, &w, ctx->d_poly, n, &C);
+    if (rc) return rc;
+    C = C.normalized();
+    Fr z = rng.scalar(), v;
+    rc = fr_poly_eval(ctx, ctx->d_poly, d_prime + 1, z, &v);
+    if (rc) return rc;
+    std::memset(inst, 0, 8 * instance_words(lg));
+    C.store(inst);
+    inst[12] = d;
+    z.store(inst + 13);
+    v.store(inst + 17);
+    // the leading coefficient is non-zero with overwhelming probability: degree = d_prime
+    rc = pcdl_open_dev(ctx, &rng, d_prime, C, d, z, &w, inst + 21);
+    if (rng_state) *rng_state = rng.state;
+    return rc;
+}
+
+// ------------------------------------------------------------------ pcdl::open of m polynomials at once
+// The randomness of every member is known before any device work: the counter-based stream's draws depend only on the members'
+// degrees (a hiding open draws deg scalars for q, then w_bar; random_instance draws d', w, the d' + 1 coefficients, z, then the
+// open's draws).  So the host computes every member's start state first, and the members run side by side.
+//
+// Device path (2 <= n <= the context's no-fold size, at most OPEN_MAX_N): the open in its no-fold form (abi.hip ipa_round_lr_points:
+// the key is never folded, every round's L and R are two MSMs over the same n points with expanded scalars) for a GROUP of up to
+// OPEN_MAX_GROUP members at a time.  Each step of a group is one set of member-batched launches (ipa.hip *_batch, blockIdx.y =
+// member) and ONE batched MSM launch sequence over the key (L and R of every member: up to 8 scalar arrays; the C_bar commits of the
+// hiding branch, and random_instance's commits, likewise).  Groups rotate over the slots that were idle on entry: while this
+// thread waits for one group's step and runs its host half -- window combines, H' terms, Fiat-Shamir hashes, xi^-1, on the host
+// pool for the group's members -- the other slots' groups run on the device.  Every group runs through all its rounds before
+// its slot takes the next one, so the staging holds G x S members.  Host arithmetic is the single open's, term for term
+// (pcdl_open_dev, halo_ipa_finish's last-round U), so every proof word is the one halo_pcdl_open writes.
+struct OpenJob {
+    size_t idx = 0, deg = 0;
+    uint64_t s_start = 0;                // rng state before the member's first draw (the single call's *rng_state)
+    uint64_t s_p = 0, s_q = 0;           // rng state before p's coefficients (random_instance) / before q's (hiding)
+    const uint64_t *coeffs = nullptr;    // the caller's n coefficients (null: p generated on the device)
+    bool hiding = false;
+    Point C, last_L, last_R;
+    Fr z, v, w, w_bar, xi0, xi, c0, c1, last_xi, last_xi_inv;
+    uint64_t *proof = nullptr;
+    int rc = HALO_OK;
+    std::string err;
+};
+// members per launch: 4 (8 scalar arrays per round) within the small pipeline's bucket limit; "open_batch_group" forces 1..4
+static size_t open_group_size(const halo_ctx *ctx, size_t n) {
+    const int forced = dev_hooks().open_group;  // (development library: the sweep of tools/time_open_batch.py)
+    int g = forced >= 1 && forced <= OPEN_MAX_GROUP ? forced : OPEN_MAX_GROUP;
+    MsmPlan p = msm_plan(n, ctx->window_bits);
+    while (g > 1 && (size_t)p.W * (size_t)(2 * g) * p.B > ((size_t)1 << 22)) --g;
+    return (size_t)g;
+}
+constexpr size_t OPEN_AUX_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS + OPEN_PART_WORDS + OPEN_OUT_WORDS);
+constexpr size_t OPEN_PIN_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS + OPEN_OUT_WORDS) + 4;  // per slot; + the element one
+
+// jobs: the members that do not fail up front, in member order.  *ran = false: the device path does not apply (nothing done)
+static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, bool gen, const int *slots_in, int S, bool *ran) {
+    *ran = false;
+    const size_t n = d + 1, lg = ilog2(n), A = jobs.size();
+    if (A == 0 || n < 2 || n > ctx->nofold_size || n > OPEN_MAX_N) return HALO_OK;
+    size_t G = open_group_size(ctx, n);
+    if (G > A) G = A;
+    size_t ng = (A + G - 1) / G;
+    if ((size_t)S > ng) S = (int)ng;
+    const size_t ms = 7 * 4 * n;  // words of one member's vectors: c | z | s | s' | F_L | F_R | p_bar
+    const size_t per = G * ms + OPEN_AUX_WORDS;  // words of one slot's group
+    size_t have = check_stage(ctx, (size_t)S, per * 8);
+    if (have == 0) return HALO_OK;
+    if ((size_t)S > have) S = (int)have;
+    if (!ctx->h_open_pinned) {
+        if (hipHostMalloc(&ctx->h_open_pinned, HALO_SLOTS * OPEN_PIN_WORDS * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->h_open_pinned = nullptr;
+            return HALO_OK;
+        }
+        for (int k = 0; k < HALO_SLOTS; ++k) Fr::one().store(ctx->h_open_pinned + k * OPEN_PIN_WORDS + OPEN_PIN_WORDS - 4);
+    }
+    *ran = true;
+    const bool hiding = jobs[0].hiding;  // (the same for every member of a batch)
+    const bool u_from_last_round = tuning().u_from_last_round;
+    struct Flight { long g = -1; size_t first = 0, cnt = 0, step = 0; int msm = 0; bool flip = false; std::vector<size_t> need_u; };
+    std::vector<Flight> fl(S);
+    // slot j's regions: the group's member vectors, then its window tables | constants | partial sums | results; in pinned memory
+    // the tables | constants (one upload) | results (one download) | the element one
+    auto dev = [&](int j) { return ctx->d_check_stage + (size_t)j * per; };
+    auto vec = [&](int j, int k) { return dev(j) + 4 * n * (size_t)k; };  // member 0's vector k; member b at + b * ms
+    auto aux = [&](int j) { return dev(j) + G * ms; };
+    auto d_tabs = [&](int j) { return aux(j); };
+    auto d_consts = [&](int j) { return aux(j) + OPEN_MAX_GROUP * OPEN_TAB_WORDS; };
+    auto d_parts = [&](int j) { return d_consts(j) + OPEN_MAX_GROUP * OPEN_CONST_WORDS; };
+    auto d_outs = [&](int j) { return d_parts(j) + OPEN_MAX_GROUP * OPEN_PART_WORDS; };
+    auto h_tabs = [&](int j) { return ctx->h_open_pinned + (size_t)j * OPEN_PIN_WORDS; };
+    auto h_consts = [&](int j) { return (OpenConst *)(h_tabs(j) + OPEN_MAX_GROUP * OPEN_TAB_WORDS); };
+    auto h_outs = [&](int j) { return h_tabs(j) + OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS); };
+    auto h_one = [&](int j) { return h_tabs(j) + OPEN_PIN_WORDS - 4; };
+    auto out_of = [&](int j, size_t b) { return h_outs(j) + OPEN_OUT_WORDS * b; };
+    auto s_cur = [&](int j) { return vec(j, fl[j].flip ? 3 : 2); };
+    // the launches of one step of slot j's group on the slot's stream (the launch macro uses ctx->stream)
+    auto on_slot = [&](int j, const std::function<int(hipStream_t)> &body) -> int {
+        hipStream_t saved = ctx->stream;
+        ctx->stream = ctx->streams[slots_in[j]];
+        int rc = body(ctx->stream);
+        ctx->stream = saved;
+        return rc;
+    };
+    auto msm_out = [&](int j, int count, const std::function<const uint64_t *(int)> &scalars) -> int {
+        MsmBatch mb;
+        mb.count = count;
+        for (int k = 0; k < count; ++k) mb.scalars[k] = scalars(k);
+        int rc = msm_enqueue_batch(ctx, slots_in[j], ctx->d_bases, mb, true, n);
+        if (!rc) fl[j].msm = count;
+        return rc;
+    };
+    auto download_outs = [&](int j, hipStream_t st) -> int {
+        HALO_HIP(hipMemcpyAsync(h_outs(j), d_outs(j), fl[j].cnt * OPEN_OUT_WORDS * 8, hipMemcpyDeviceToHost, st));
+        return HALO_OK;
+    };
+    auto upload_consts = [&](int j, hipStream_t st) -> int {
+        HALO_HIP(hipMemcpyAsync(d_consts(j), h_consts(j), fl[j].cnt * OPEN_CONST_WORDS * 8, hipMemcpyHostToDevice, st));
+        return HALO_OK;
+    };
+    // round r of slot j's group: F_L, F_R from c and s, the dot products, L and R of every member as one batched MSM
+    auto enqueue_round = [&](int j, size_t r) -> int {
+        Flight &f = fl[j];
+        const size_t mcur = n >> r;
+        int rc = on_slot(j, [&](hipStream_t st) -> int {
+            int rc2 = open_batch_expand(ctx, (int)f.cnt, vec(j, 0), s_cur(j), ms, mcur, n, vec(j, 4), vec(j, 5));
+            if (!rc2) rc2 = open_batch_dots(ctx, (int)f.cnt, vec(j, 0), vec(j, 1), ms, mcur / 2, d_parts(j), d_outs(j));
+            if (rc2) return rc2;
+            if (mcur == 2)  // the last round: c0, c1 travel with its results (halo_ipa_finish's U from this round's MSMs)
+                for (size_t b = 0; b < f.cnt; ++b)
+                    HALO_HIP(hipMemcpyAsync(d_outs(j) + OPEN_OUT_WORDS * b + 12, vec(j, 0) + b * ms, 64, hipMemcpyDeviceToDevice, st));
+            return download_outs(j, st);
+        });
+        if (!rc) rc = msm_out(j, 2 * (int)f.cnt, [&](int k) { return vec(j, 4 + (k & 1)) + (size_t)(k >> 1) * ms; });
+        f.step = 1 + r;
+        return rc;
+    };
+    // step 0: coefficients (copied, or generated), p(z), the powers of z, p_bar; the commits as one batched MSM
+    auto start = [&](int j, size_t g) -> int {
+        Flight &f = fl[j];
+        f.g = (long)g;
+        f.first = g * G;
+        f.cnt = A - f.first < G ? A - f.first : G;
+        f.step = 0;
+        f.msm = 0;
+        f.flip = false;
+        for (size_t b = 0; b < f.cnt; ++b) {
+            const OpenJob &jb = jobs[f.first + b];
+            OpenConst &k = h_consts(j)[b];
+            std::memset(&k, 0, sizeof k);
+            int rc = open_batch_table(jb.z, n, h_tabs(j) + OPEN_TAB_WORDS * b, &k);
+            if (rc) return rc;
+            k.s_q = jb.s_q;
+            k.s_p = jb.s_p;
+            k.deg = (uint32_t)jb.deg;
+            k.len = (uint32_t)(jb.deg + 1);
+        }
+        int rc = on_slot(j, [&](hipStream_t st) -> int {
+            HALO_HIP(hipMemcpyAsync(d_tabs(j), h_tabs(j), OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS) * 8, hipMemcpyHostToDevice, st));
+            int rc2 = HALO_OK;
+            if (gen) rc2 = open_batch_rng(ctx, (int)f.cnt, d_consts(j), n, vec(j, 0), ms);  // p = PallasPoly::rand(d')
+            else
+                for (size_t b = 0; b < f.cnt; ++b)
+                    HALO_HIP(hipMemcpyAsync(vec(j, 0) + b * ms, jobs[f.first + b].coeffs, n * 32, hipMemcpyHostToDevice, st));
+            if (!rc2) rc2 = open_batch_eval(ctx, (int)f.cnt, vec(j, 0), ms, n, d_tabs(j), d_parts(j), d_outs(j));  // :135
+            if (!rc2) rc2 = open_batch_powers(ctx, (int)f.cnt, d_tabs(j), d_consts(j), n, vec(j, 1), ms);
+            if (!rc2 && hiding) rc2 = open_batch_pbar(ctx, (int)f.cnt, d_consts(j), n, vec(j, 6), ms);  // :140-142
+            for (size_t b = 0; b < f.cnt && !rc2; ++b)  // s = (1)
+                HALO_HIP(hipMemcpyAsync(vec(j, 2) + b * ms, h_one(j), 32, hipMemcpyHostToDevice, st));
+            if (!rc2) rc2 = download_outs(j, st);
+            return rc2;
+        });
+        const int commits = (gen ? (int)f.cnt : 0) + (hiding ? (int)f.cnt : 0);  // random_instance's C, then C_bar (:150)
+        if (!rc && commits)
+            rc = msm_out(j, commits, [&](int k) { return (gen && (size_t)k < f.cnt) ? vec(j, 0) + (size_t)k * ms : vec(j, 6) + (k % f.cnt) * ms; });
+        return rc;
+    };
+    // slot j's step is done: its results through the host half, then the next step (or the group is through)
+    auto advance = [&](int j, bool *through) -> int {
+        Flight &f = fl[j];
+        *through = false;
+        Point pts[MSM_MAX_BATCH];
+        if (f.msm) {
+            int rc = msm_finish_batch(ctx, slots_in[j], pts, f.msm);
+            f.msm = 0;
+            if (rc) return rc;
+        }
+        HALO_HIP(hipStreamSynchronize(ctx->streams[slots_in[j]]));
+        if (f.step == 0) {
+            pool_run(f.cnt, [&](size_t b) {
+                OpenJob &jb = jobs[f.first + b];
+                jb.v = Fr::load(out_of(j, b));
+                if (gen) jb.C = (public_s_table().mul(jb.w) + pts[b]).normalized();
+                Point C_prime = jb.C;
+                if (hiding) {
+                    Point C_bar = public_s_table().mul(jb.w_bar) + pts[(gen ? f.cnt : 0) + b];
+                    Fr a = rho0_C_z_v_Cbar(jb.C, jb.z, jb.v, C_bar);  // :153
+                    Fr w_prime = jb.w_bar * a + jb.w;                  // :159
+                    C_prime = jb.C + C_bar.mul(a) - public_s_table().mul(w_prime);  // :162
+                    jb.proof[0] = 1;
+                    C_bar.store_normalized(pf_Cbar(jb.proof, lg));
+                    w_prime.store(pf_wp(jb.proof, lg));
+                    open_const_alpha(&h_consts(j)[b], a);
+                } else {
+                    Point::infinity().store(pf_Cbar(jb.proof, lg));
+                }
+                jb.xi0 = jb.xi = rho0_C_z_v(C_prime, jb.z, jb.v);  // :180
+            });
+            int rc = HALO_OK;
+            if (hiding)
+                rc = on_slot(j, [&](hipStream_t st) -> int {
+                    int rc2 = upload_consts(j, st);
+                    return rc2 ? rc2 : open_batch_axpy(ctx, (int)f.cnt, vec(j, 0), vec(j, 6), ms, n, d_consts(j));  // :156
+                });
+            return rc ? rc : enqueue_round(j, 0);
+        }
+        if (f.step <= lg) {  // round r = step - 1 (:203-224)
+            const size_t r = f.step - 1;
+            const bool last = r + 1 == lg;
+            pool_run(f.cnt, [&](size_t b) {
+                OpenJob &jb = jobs[f.first + b];
+                const uint64_t *o = out_of(j, b);
+                Fr dl = Fr::load(o + 4), dr = Fr::load(o + 8);
+                if (last) { jb.last_L = pts[2 * b]; jb.last_R = pts[2 * b + 1]; jb.c0 = Fr::load(o + 12); jb.c1 = Fr::load(o + 16); }
+                uint64_t *Lw = pf_L(jb.proof, r), *Rw = pf_R(jb.proof, lg, r);
+                (pts[2 * b] + public_h_table().mul(dl * jb.xi0)).normalized().store(Lw);
+                (pts[2 * b + 1] + public_h_table().mul(dr * jb.xi0)).normalized().store(Rw);
+                Fr xi_next = rho0_xi_L_R(jb.xi, Point::load(Lw), Point::load(Rw));  // :212
+                if (xi_next.is_zero() && !jb.rc) { jb.rc = HALO_E_ASSERT; jb.err = "open: challenge is zero (inverse().unwrap())"; }
+                Fr xi_inv = xi_next.inv();  // :213
+                jb.xi = xi_next;
+                if (last) { jb.last_xi = xi_next; jb.last_xi_inv = xi_inv; }
+                open_const_xi(&h_consts(j)[b], xi_next, xi_inv);
+            });
+            int rc = on_slot(j, [&](hipStream_t st) -> int {  // :216-224
+                int rc2 = upload_consts(j, st);
+                const uint64_t *s_in = s_cur(j);
+                f.flip = !f.flip;
+                return rc2 ? rc2 : open_batch_fold(ctx, (int)f.cnt, vec(j, 0), vec(j, 1), s_in, s_cur(j), ms, n >> (r + 1), (size_t)1 << r, d_consts(j));
+            });
+            if (rc) return rc;
+            if (!last) return enqueue_round(j, r + 1);
+            // :230-231 as halo_ipa_finish: U from the last round's MSMs where both coefficients are non-zero, else U = <s, G>
+            f.need_u.clear();
+            pool_run(f.cnt, [&](size_t b) {
+                OpenJob &jb = jobs[f.first + b];
+                if (!(u_from_last_round && !jb.c0.is_zero() && !jb.c1.is_zero())) return;
+                Fr inv01 = (jb.c0 * jb.c1).inv();
+                Fr a = inv01 * jb.c0, bb = inv01 * jb.c1 * jb.last_xi;  // 1 / c1, xi / c0
+                (jb.last_L.mul(a) + jb.last_R.mul(bb)).store_normalized(pf_U(jb.proof, lg));
+                (jb.c0 + jb.last_xi_inv * jb.c1).store(pf_c(jb.proof, lg));
+            });
+            for (size_t b = 0; b < f.cnt; ++b) {
+                const OpenJob &jb = jobs[f.first + b];
+                if (!(u_from_last_round && !jb.c0.is_zero() && !jb.c1.is_zero())) f.need_u.push_back(b);
+            }
+            if (f.need_u.empty()) { *through = true; return HALO_OK; }
+            rc = on_slot(j, [&](hipStream_t st) -> int {
+                for (size_t k = 0; k < f.need_u.size(); ++k)
+                    HALO_HIP(hipMemcpyAsync(d_outs(j) + OPEN_OUT_WORDS * f.need_u[k] + 20, vec(j, 0) + f.need_u[k] * ms, 32, hipMemcpyDeviceToDevice, st));
+                return download_outs(j, st);
+            });
+            if (!rc) rc = msm_out(j, (int)f.need_u.size(), [&](int k) { return s_cur(j) + f.need_u[(size_t)k] * ms; });
+            f.step = lg + 1;
+            return rc;
+        }
+        for (size_t k = 0; k < f.need_u.size(); ++k) {  // U = <s, G> and c = c[0] (halo_ipa_finish)
+            OpenJob &jb = jobs[f.first + f.need_u[k]];
+            pts[k].store_normalized(pf_U(jb.proof, lg));
+            std::memcpy(pf_c(jb.proof, lg), out_of(j, f.need_u[k]) + 20, 32);
+        }
+        *through = true;
+        return HALO_OK;
+    };
+    auto abandon = [&]() {  // (a device error: nothing of this call stays in flight)
+        std::string err = halo_last_error();
+        for (int j = 0; j < S; ++j) {
+            if (fl[j].msm) {
+                Point pts[MSM_MAX_BATCH];
+                (void)msm_finish_batch(ctx, slots_in[j], pts, fl[j].msm);
+                fl[j].msm = 0;
+            }
+            (void)hipStreamSynchronize(ctx->streams[slots_in[j]]);
+        }
+        set_error(err);
+    };
+    size_t next = 0;
+    int rc = HALO_OK, active = 0;
+    for (int j = 0; j < S && next < ng && !rc; ++j, ++active) rc = start(j, next++);
+    while (!rc && active) {
+        for (int j = 0; j < S && !rc; ++j) {
+            if (fl[j].g < 0) continue;
+            bool through = false;
+            rc = advance(j, &through);
+            if (rc || !through) continue;
+            fl[j].g = -1;
+            --active;
+            if (next < ng) { rc = start(j, next++); ++active; }
+        }
+    }
+    if (rc) { abandon(); return rc; }
+    return HALO_OK;
+}
+
+// halo_pcdl_open_batch (coeffs != null) and halo_random_instance_batch (coeffs == null: `out` holds Instance blobs) after their
+// argument checks: the members' draws, then the device path or, where it does not apply, the members one at a time
+static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *Cs, const uint64_t *zs,
+                            const uint64_t *ws, uint64_t *out, int *status) {
+    const size_t n = d + 1, lg = ilog2(n);
+    const bool gen = coeffs == nullptr, hiding = gen || ws != nullptr;
+    const size_t stride = gen ? instance_words(lg) : proof_words(lg);
+    constexpr uint64_t GAMMA = 0x9E3779B97F4A7C15ULL;
+    int slots[HALO_SLOTS], S = 0;
+    for (int k = 0; k < HALO_SLOTS; ++k)
+        if (!ctx->wss[k].in_flight && ctx->wss[k].lent_from < 0 && !ctx->fan[k].active) slots[S++] = k;
+    if (!S) { set_error("open_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
+    // 1. every member's draws, in member order (the loop's order)
+    host::Rng rng{rng_state ? *rng_state : 0};
+    std::vector<OpenJob> jobs;
+    std::vector<int> pre(m, HALO_OK);  // members that fail before any draw (a hiding open of a constant polynomial)
+    jobs.reserve(m);
+    for (size_t i = 0; i < m; ++i) {
+        OpenJob jb;
+        jb.idx = i;
+        jb.hiding = hiding;
+        jb.proof = out + i * stride + (gen ? 21 : 0);
+        jb.s_start = rng.state;
+        if (gen) {
+            size_t lo = d / 2;
+            jb.deg = lo + (size_t)(rng.next() % (uint64_t)(d - lo));
+            if (jb.deg == 0) jb.deg = 1;
+            jb.w = rng.scalar();
+            jb.s_p = rng.state;
+            rng.state += 4 * (uint64_t)(jb.deg + 1) * GAMMA;
+            jb.z = rng.scalar();
+        } else {
+            jb.coeffs = coeffs + i * n * 4;
+            jb.deg = host_poly_degree(jb.coeffs, n);
+            jb.C = Point::load(Cs + 12 * i);
+            jb.z = Fr::load(zs + 4 * i);
+            if (ws) jb.w = Fr::load(ws + 4 * i);
+            if (hiding && jb.deg == 0) { pre[i] = HALO_E_ASSERT; continue; }  // pcdl_open_dev: before any draw
+        }
+        if (hiding) {
+            jb.s_q = rng.state;
+            rng.state += 4 * (uint64_t)jb.deg * GAMMA;
+            jb.w_bar = rng.scalar();
+        }
+        jobs.push_back(jb);
+    }
+    // 2. the device path; where it does not apply, the loop itself (the single calls' bodies, from the same states)
+    bool ran = false;
+    int rc = HALO_OK;
+    if (!jobs.empty()) {
+        for (OpenJob &jb : jobs) {
+            std::memset(jb.proof, 0, 8 * proof_words(lg));
+            jb.proof[1] = lg;
+        }
+        rc = open_batch_dev(ctx, d, jobs, gen, slots, S, &ran);
+        if (rc) return rc;
+    }
+    if (!ran) {
+        for (OpenJob &jb : jobs) {
+            uint64_t st = jb.s_start;
+            if (gen) rc = random_instance_one(ctx, &st, d, out + jb.idx * stride);
+            else rc = pcdl_open_host(ctx, &st, jb.coeffs, jb.deg, Cs + 12 * jb.idx, d, zs + 4 * jb.idx, ws ? ws + 4 * jb.idx : nullptr, jb.proof);
+            if (rc == HALO_E_ASSERT) { jb.rc = rc; jb.err = halo_last_error(); }
+            else if (rc) return rc;
+        }
+    }
+    // 3. outcomes in member order
+    std::vector<int> codes(pre);
+    std::vector<std::string> errs(m);
+    for (size_t i = 0; i < m; ++i)
+        if (pre[i]) errs[i] = "open: hiding needs p.degree() >= 1";
+    for (OpenJob &jb : jobs) {
+        codes[jb.idx] = jb.rc;
+        errs[jb.idx] = jb.err;
+        if (gen && !jb.rc && ran) {  // the Instance around the proof (random_instance_one writes its own)
+            uint64_t *inst = out + jb.idx * stride;
+            jb.C.store(inst);
+            inst[12] = d;
+            jb.z.store(inst + 13);
+            jb.v.store(inst + 17);
+        }
+    }
+    int first = -1;
+    for (size_t i = 0; i < m; ++i) {
+        if (codes[i]) {
+            std::memset(out + i * stride, 0, 8 * stride);
+            if (first < 0) first = (int)i;
+        }
+        if (status) status[i] = codes[i];
+    }
+    if (rng_state) *rng_state = rng.state;
+    if (first >= 0) { set_error("member " + std::to_string(first) + ": " + errs[first]); return codes[first]; }
+    return HALO_OK;
+}
+
 #define HALO_CTX2(ctx)                                                   \
     do {                                                                 \
         if (!(ctx)) { halo::set_error("null context"); return HALO_E_ARG; } \
@@ -749,16 +1178,7 @@ int halo_pcdl_open(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *coeffs, s
     size_t deg = host_poly_degree(coeffs, len);
     if (deg > d) return fail_assert("open: p.degree() > d");                   // pcdl.rs:131
     if (n > ctx->n) return fail_assert("open: d > D");                         // pcdl.rs:132
-    int rc = ensure_poly_buffers(ctx);
-    if (rc) return rc;
-    HALO_HIP(hipMemsetAsync(ctx->d_poly, 0, n * 32, ctx->stream));
-    rc = upload_words(ctx, ctx->d_poly, coeffs, (deg + 1) * 4);
-    if (rc) return rc;
-    host::Rng rng{rng_state ? *rng_state : 0};
-    Fr wf = w ? Fr::load(w) : Fr::zero();
-    rc = pcdl_open_dev(ctx, &rng, deg, Point::load(C), d, Fr::load(z), w ? &wf : nullptr, proof_out);
-    if (rng_state) *rng_state = rng.state;
-    return rc;
+    return pcdl_open_host(ctx, rng_state, coeffs, deg, C, d, z, w, proof_out);
 }
 
 // pcdl::open for a polynomial that already lives in device memory (the coefficients are copied, not clobbered)
@@ -1087,34 +1507,29 @@ int halo_random_instance(halo_ctx *ctx, uint64_t *rng_state, size_t d, uint64_t 
     HALO_CTX2(ctx);
     if (!is_pow2(d + 1) || d < 2) return fail_assert("random_instance: bad d");
     if (d + 1 > ctx->n) return fail_assert("random_instance: d > D");
-    size_t lg = ilog2(d + 1), n = d + 1;
-    host::Rng rng{rng_state ? *rng_state : 0};
-    size_t lo = d / 2, d_prime = lo + (size_t)(rng.next() % (uint64_t)(d - lo));
-    if (d_prime == 0) d_prime = 1;
-    Fr w = rng.scalar();
-    int rc = ensure_poly_buffers(ctx);
-    if (rc) return rc;
-    // p = PallasPoly::rand(d_prime): d_prime + 1 scalars of the stream, generated on the device
-    HALO_HIP(hipMemsetAsync(ctx->d_poly, 0, n * 32, ctx->stream));
-    rc = rng_scalars_dev(ctx, rng.state, d_prime + 1, ctx->d_poly);
-    if (rc) return rc;
-    rng.state += 4 * (uint64_t)(d_prime + 1) * 0x9E3779B97F4A7C15ULL;
-    Point C;
-    rc = pedersen_commit_dev(ctx, &w, ctx->d_poly, n, &C);
-    if (rc) return rc;
-    C = C.normalized();
-    Fr z = rng.scalar(), v;
-    rc = fr_poly_eval(ctx, ctx->d_poly, d_prime + 1, z, &v);
-    if (rc) return rc;
-    std::memset(inst, 0, 8 * instance_words(lg));
-    C.store(inst);
-    inst[12] = d;
-    z.store(inst + 13);
-    v.store(inst + 17);
-    // the leading coefficient is non-zero with overwhelming probability: degree = d_prime
-    rc = pcdl_open_dev(ctx, &rng, d_prime, C, d, z, &w, inst + 21);
-    if (rng_state) *rng_state = rng.state;
-    return rc;
+    return random_instance_one(ctx, rng_state, d, inst);
+}
+
+// pcdl::open of m polynomials at once (see open_batch_dev)
+int halo_pcdl_open_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *Cs, const uint64_t *zs,
+                         const uint64_t *ws, uint64_t *proofs_out, int *status) {
+    HALO_CTX2(ctx);
+    if (m == 0) return HALO_OK;
+    if (!coeffs || !Cs || !zs || !proofs_out) { set_error("open_batch: null pointer"); return HALO_E_ARG; }
+    const size_t n = d + 1;
+    if (!is_pow2(n)) return fail_assert("open: d + 1 is not a power of two");  // pcdl.rs:130 (p.degree() <= d: the arrays hold d + 1)
+    if (n > ctx->n) return fail_assert("open: d > D");                         // pcdl.rs:132
+    return open_batch_entry(ctx, rng_state, d, coeffs, m, Cs, zs, ws, proofs_out, status);
+}
+
+// benches/acc.rs:15-29 random_instance, m times (see open_batch_dev)
+int halo_random_instance_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, size_t m, uint64_t *instances_out) {
+    HALO_CTX2(ctx);
+    if (m == 0) return HALO_OK;
+    if (!instances_out) { set_error("random_instance_batch: null pointer"); return HALO_E_ARG; }
+    if (!is_pow2(d + 1) || d < 2) return fail_assert("random_instance: bad d");
+    if (d + 1 > ctx->n) return fail_assert("random_instance: d > D");
+    return open_batch_entry(ctx, rng_state, d, nullptr, m, nullptr, nullptr, nullptr, instances_out, nullptr);
 }
 
 }  // extern "C"

@@ -51,8 +51,9 @@ struct DevHooks {
     int force_peer_copy = 0;   // "force_peer_copy"  multi-device contexts stage device scalars through a peer copy even on the same GPU
     int shard_fail_rank = -1;  // "shard_fail_rank" / "shard_fail_at": that rank fails locally before its collective number `at`
     int shard_fail_at = -1;    //   (at = -2: in a sharded check, -3: before a sharded MSM's collective)
-    int batch_stage_fail = 0;  // "batch_stage_fail"   the staging of halo_pcdl_check_batch is refused: one member at a time in the scratch
+    int batch_stage_fail = 0;  // "batch_stage_fail"   the staging of the check and open batches is refused: one member at a time
     int check_group = 0;       // "check_batch_group"  members per MSM launch of halo_pcdl_check_batch (1..8; 0: the measured default)
+    int open_group = 0;        // "open_batch_group"   members per launch of halo_pcdl_open_batch (1..4; 0: the measured default)
 };
 DevHooks &dev_hooks();
 

@@ -38,6 +38,31 @@ def open(ctx, rng, p, Cm, d, z, w=None):
     return proof
 
 
+def open_batch(ctx, rng, ps, Cs, d, zs, ws=None):
+    """pcdl::open of m polynomials of degree bound d at once (halo_pcdl_open_batch) -> list of EvalProof blobs: what m pcdl.open
+    calls in member order return, rng[0] updated as they would update it.  A failing member raises as pcdl.open does, with the
+    status list (what halo_pcdl_open returns for each member alone) as the exception's second argument."""
+    m, lg = len(ps), max(lg_of(d), 0)
+    coeffs = np.zeros((max(m, 1), d + 1, 4), dtype=np.uint64)
+    for i, p in enumerate(ps):
+        p = _a(p).reshape(-1, 4)
+        nz = np.nonzero(p.any(axis=1))[0]
+        k = int(nz[-1]) + 1 if len(nz) else 1
+        if k > d + 1:
+            raise AssertionError("open: p.degree() > d")
+        coeffs[i, :k] = p[:k]
+    st = C.c_uint64(rng[0])
+    out = np.zeros((max(m, 1), ctx.lib.halo_proof_words(lg)), dtype=np.uint64)
+    status = (C.c_int * max(m, 1))()
+    rc = ctx.lib.halo_pcdl_open_batch(ctx.h, C.byref(st), d, ptr(coeffs), m, ptr(_a(Cs)), ptr(_a(zs)), ptr(_a(ws)), ptr(out), status)
+    if rc in (_lib.HALO_OK, _lib.HALO_E_ASSERT):
+        rng[0] = st.value
+    if rc == _lib.HALO_E_ASSERT:
+        raise AssertionError(ctx.lib.halo_last_error().decode(), [status[i] for i in range(m)])
+    check(rc)
+    return [out[i].copy() for i in range(m)]
+
+
 def commit_dev(ctx, dptr, length, d, w=None):
     """pcdl::commit for `length` coefficients resident in device memory"""
     out = np.zeros(12, dtype=np.uint64)

@@ -309,6 +309,32 @@ int halo_acc_decider_batch(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t
 /* benches/acc.rs:15-29 random_instance: the workload generator of the reference's benchmark */
 int halo_random_instance(halo_ctx *ctx, uint64_t *rng_state, size_t d, uint64_t *instance_out);
 
+/* pcdl::open (pcdl.rs:120-242) of m polynomials of degree bound d at once.  coeffs = m x (d + 1) x 4 words (member i at
+ * i * (d + 1) * 4, zero-padded; its degree is that of the padded array, found as halo_pcdl_open finds it), Cs = m x 12,
+ * zs = m x 4, ws = m x 4 or NULL (NULL: no member hides; otherwise every member hides with its own w).  proofs_out = m
+ * EvalProof blobs at stride halo_proof_words(lg(d+1)).
+ * - Same results as a loop: every proof word and the final *rng_state equal m calls of halo_pcdl_open in member order with the
+ *   same rng_state pointer (NULL: state 0, as there).  The stream is counter-based, so every member's draws (a hiding open: deg
+ *   scalars for q, then w_bar) depend only on the earlier members' degrees: the host knows every start state before any device work.
+ * - A member fails as the single call would (today only a hiding open of a constant polynomial: HALO_E_ASSERT, "open: hiding needs
+ *   p.degree() >= 1"): it consumes no randomness, status[i] (nullable) gets its code and its blob is zero-filled; the other members
+ *   are unaffected.  Returns 0 if every member succeeded, else the first non-zero status in member order, halo_last_error() =
+ *   "member i: <message>".
+ * - Before any work (status not written, *rng_state unchanged): a null ctx or a null array with m > 0: HALO_E_ARG; d + 1 not a
+ *   power of two or above the key: HALO_E_ASSERT with the single call's messages.  m = 0: HALO_OK, nothing touched.
+ * - Where the single open takes its no-fold form (2 <= d + 1 <= the no-fold size, 2^14 by default) groups of up to 4 members run
+ *   in member-batched launches: one batched MSM per round for the L and R of the whole group.  Groups rotate over the slots that
+ *   are idle on entry (a caller's MSM in flight on another slot is left alone; no idle slot: HALO_E_ARG).  Their device state is
+ *   optional memory (halo_set_memory_budget; it only grows and goes with the context): without it, and above the no-fold size,
+ *   the members run one at a time as halo_pcdl_open runs them, with the same results.  A multi-device context runs the batch
+ *   on its first device, with the proofs halo_pcdl_open gives there. */
+int halo_pcdl_open_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *Cs,
+                         const uint64_t *zs, const uint64_t *ws /*nullable*/, uint64_t *proofs_out, int *status /*nullable*/);
+/* benches/acc.rs:15-29 random_instance, m times: instances_out = m Instance blobs at stride halo_instance_words(lg(d+1)), every
+ * word and the final *rng_state as m calls of halo_random_instance in order (draws per member: d', w, the d' + 1 coefficients,
+ * z, then its hiding open's).  The conventions of halo_pcdl_open_batch; d < 2: the single call's assert. */
+int halo_random_instance_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, size_t m, uint64_t *instances_out);
+
 /* ---- wire format (host only; no device needed) ----------------------------------------------
  * EvalProof (pcdl.rs:22-30), Instance (acc.rs:21-28) and Accumulator (acc.rs:43-59) in the byte layout a derived
  * ark-serialize `CanonicalSerialize` (compressed) writes: fields in declaration order; Fr = 32 bytes LE canonical;

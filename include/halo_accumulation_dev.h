@@ -22,9 +22,9 @@ extern "C" {
  * "shard_fail_rank" + "shard_fail_at" (the rank with that offset fails locally before collective number `at` of a sharded open:
  * 0 = the share of p(z), 1.. = the rounds, then the tail; at = -2: in a sharded check; at = -3: the rank with that `rank`
  * before the collective of halo_msm_sharded / _dev_sharded / _end_sharded), "batch_stage_fail" (value != 0: the staging of
- * halo_pcdl_check_batch / halo_acc_decider_batch is refused, as over the memory budget: one member at a time in the context's
- * scratch on one slot), "check_batch_group" (members per MSM launch of those calls, 1..8; 0: the measured default),
- * "reset" (all off). */
+ * halo_pcdl_check_batch / halo_acc_decider_batch / halo_pcdl_open_batch / halo_random_instance_batch is refused, as over the
+ * memory budget: one member at a time), "check_batch_group" (members per MSM launch of the check batch, 1..8; 0: the measured
+ * default), "open_batch_group" (members per launch of the open batch, 1..4; 0: the measured default), "reset" (all off). */
 int halo_dev_hook(const char *name, long value);
 /* What the library read from the environment at its first use (csrc/tuning.hip), by field: "host_split_set", "host_pieces", "host_split0".."host_split3",
  * "fold_table_after", "graph_cache", "pow_e", "spin_us", "graphs", "memory_budget" (MiB, -1 unset), "trace", "tagged"; -1 for an

@@ -51,6 +51,10 @@ extern "C" {
     // pcdl::check / acc::decider of m blobs at once (status: m codes, may be null)
     pub fn halo_pcdl_check_batch(ctx: *mut HaloCtx, d: usize, instances: *const u64, m: usize, status: *mut c_int) -> c_int;
     pub fn halo_acc_decider_batch(ctx: *mut HaloCtx, d: usize, accs: *const u64, m: usize, status: *mut c_int) -> c_int;
+    // pcdl::open / random_instance of m members at once (ws, status may be null)
+    pub fn halo_pcdl_open_batch(ctx: *mut HaloCtx, rng_state: *mut u64, d: usize, coeffs: *const u64, m: usize, cs: *const u64, zs: *const u64,
+                                ws: *const u64, proofs_out: *mut u64, status: *mut c_int) -> c_int;
+    pub fn halo_random_instance_batch(ctx: *mut HaloCtx, rng_state: *mut u64, d: usize, m: usize, instances_out: *mut u64) -> c_int;
     pub fn halo_h_accumulate(ctx: *mut HaloCtx, h0: *const u64, xis: *const u64, alphas: *const u64, m: usize, lg_n: usize, out: *mut u64) -> c_int;
     pub fn halo_ipa_begin(ctx: *mut HaloCtx, n: usize, coeffs: *const u64, len: usize, z: *const u64, out: *mut *mut HaloIpa) -> c_int;
     pub fn halo_ipa_round_lr(st: *mut HaloIpa, h_prime: *const u64, l: *mut u64, r: *mut u64) -> c_int;

@@ -1,0 +1,147 @@
+"""pcdl::open of k polynomials timed two ways: the serial halo_pcdl_open loop and ONE halo_pcdl_open_batch, with hiding (as
+random_instance and acc::prover open), alternating in the same process after a warm-up of each shape; and k x
+halo_random_instance against one halo_random_instance_batch.  A 2^14-point URS context; n in {512 .. 16384} at full degree,
+k in {10, 100, 1000}; a sweep of the members per launch (the development hook open_batch_group) at k = 100; with --big a k = 4
+leg at n = 2^20 on a 2^20-point context with the fold table fixed off (halo_set_fold_table 0), so that no table build lands
+inside a timed run.  The proofs, instances and final RNG states of both ways must be equal.  Prints one JSON line; every time
+is the median of --reps alternating runs, in ms."""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+
+import halo_accumulation_amd as h  # noqa: E402
+from halo_accumulation_amd import pcdl  # noqa: E402
+from halo_accumulation_amd._lib import ptr  # noqa: E402
+
+SIZES = [512, 1024, 2048, 4096, 8192, 16384]
+
+
+def scalars(g, shape):
+    """canonical field elements (< 2^253 < r) as 4 words each"""
+    a = g.integers(0, 2 ** 63, size=tuple(shape) + (4,), dtype=np.uint64)
+    a[..., 3] &= np.uint64((1 << 61) - 1)
+    return a
+
+
+def inputs(ctx, n, k, seed):
+    g = np.random.default_rng(seed)
+    ps, zs, ws = scalars(g, (k, n)), scalars(g, (k,)), scalars(g, (k,))
+    Cs = np.stack([pcdl.commit(ctx, ps[i], n - 1, ws[i]) for i in range(k)])
+    return ps, Cs, zs, ws
+
+
+def serial(ctx, d, args, k, state):
+    ps, Cs, zs, ws = args
+    out = np.zeros((k, ctx.lib.halo_proof_words((d + 1).bit_length() - 1)), dtype=np.uint64)
+    calls = [(ptr(ps[i]), ptr(Cs[i]), ptr(zs[i]), ptr(ws[i]), ptr(out[i])) for i in range(k)]
+    st = C.c_uint64(state)
+    t = time.perf_counter()
+    for p, c, z, w, o in calls:
+        assert ctx.lib.halo_pcdl_open(ctx.h, C.byref(st), p, d + 1, c, d, z, w, o) == 0
+    return (time.perf_counter() - t) * 1e3, out, st.value
+
+
+def batched(ctx, d, args, k, state):
+    ps, Cs, zs, ws = (np.ascontiguousarray(a[:k]) for a in args)
+    out = np.zeros((k, ctx.lib.halo_proof_words((d + 1).bit_length() - 1)), dtype=np.uint64)
+    status = (C.c_int * k)()
+    st = C.c_uint64(state)
+    t = time.perf_counter()
+    rc = ctx.lib.halo_pcdl_open_batch(ctx.h, C.byref(st), d, ptr(ps), k, ptr(Cs), ptr(zs), ptr(ws), ptr(out), status)
+    ms = (time.perf_counter() - t) * 1e3
+    assert rc == 0, ctx.lib.halo_last_error()
+    return ms, out, st.value
+
+
+def ri_serial(ctx, d, k, state):
+    out = np.zeros((k, ctx.lib.halo_instance_words((d + 1).bit_length() - 1)), dtype=np.uint64)
+    rows = [ptr(out[i]) for i in range(k)]
+    st = C.c_uint64(state)
+    t = time.perf_counter()
+    for o in rows:
+        assert ctx.lib.halo_random_instance(ctx.h, C.byref(st), d, o) == 0
+    return (time.perf_counter() - t) * 1e3, out, st.value
+
+
+def ri_batched(ctx, d, k, state):
+    out = np.zeros((k, ctx.lib.halo_instance_words((d + 1).bit_length() - 1)), dtype=np.uint64)
+    st = C.c_uint64(state)
+    t = time.perf_counter()
+    rc = ctx.lib.halo_random_instance_batch(ctx.h, C.byref(st), d, k, ptr(out))
+    ms = (time.perf_counter() - t) * 1e3
+    assert rc == 0, ctx.lib.halo_last_error()
+    return ms, out, st.value
+
+
+def alternate(one, two, reps):
+    """a warm-up of each, then `reps` alternating runs; both ways must give the same outputs and final state"""
+    a, b = one(), two()
+    assert a[1].tolist() == b[1].tolist() and a[2] == b[2], "the two ways differ"
+    s_ms, b_ms = [], []
+    for _ in range(reps):
+        s_ms.append(one()[0])
+        b_ms.append(two()[0])
+    return statistics.median(s_ms), statistics.median(b_ms)
+
+
+def row(n, k, s, b, what):
+    return {"n": n, "k": k, "serial_ms": round(s, 3), "batch_ms": round(b, 3), "speedup": round(s / b, 2),
+            "serial_ms_per_" + what: round(s / k, 4), "batch_ms_per_" + what: round(b / k, 4)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--sizes", default=",".join(map(str, SIZES)))
+    ap.add_argument("--ks", default="10,100,1000")
+    ap.add_argument("--sweep", type=int, default=1, help="members-per-launch sweep at k = 100 (0: off)")
+    ap.add_argument("--big", action="store_true", help="add the 2^20-point leg (k = 4)")
+    a = ap.parse_args()
+    ks = [int(x) for x in a.ks.split(",")]
+    ctx = h._lib.Context(urs_n=1 << 14)
+    rows, ri_rows, sweep = [], [], []
+    for n in [int(x) for x in a.sizes.split(",")]:
+        d = n - 1
+        args = inputs(ctx, n, max(ks), 0x48414C4F00000300 + n)
+        for k in ks:
+            s, b = alternate(lambda: serial(ctx, d, args, k, 7 + k), lambda: batched(ctx, d, args, k, 7 + k), a.reps)
+            rows.append(row(n, k, s, b, "open"))
+            s, b = alternate(lambda: ri_serial(ctx, d, k, 11 + k), lambda: ri_batched(ctx, d, k, 11 + k), a.reps)
+            ri_rows.append(row(n, k, s, b, "instance"))
+        if a.sweep and 100 in ks:
+            for g in (1, 2, 4):
+                h._lib.dev_hook("open_batch_group", g)
+                try:
+                    s, b = alternate(lambda: serial(ctx, d, args, 100, 5), lambda: batched(ctx, d, args, 100, 5), a.reps)
+                finally:
+                    h._lib.dev_hook("reset", 0)
+                sweep.append({"n": n, "k": 100, "members_per_launch": g, "serial_ms": round(s, 3), "batch_ms": round(b, 3)})
+        print(json.dumps({"progress_n": n}), file=sys.stderr, flush=True)
+    ctx.close()
+    big = []
+    if a.big:
+        n = 1 << 20
+        c = h._lib.Context(urs_n=n)
+        try:
+            c.set_fold_table(0)
+            args = inputs(c, n, 4, 0x48414C4F00000400)
+            s, b = alternate(lambda: serial(c, n - 1, args, 4, 3), lambda: batched(c, n - 1, args, 4, 3), a.reps)
+            big.append(row(n, 4, s, b, "open"))
+        finally:
+            c.close()
+    print(json.dumps({"tool": "tools/time_open_batch.py", "workload": "k x pcdl::open with hiding (full-degree polynomials) and k x "
+                      "random_instance (benches/acc.rs:15-29), 1 GPU, context of 2^14 points", "reps": a.reps, "statistic": "median",
+                      "open": rows, "random_instance": ri_rows, "members_per_launch_sweep": sweep, "full_size": big,
+                      "equal": "proofs, instances and final RNG states: loop == batch for every row"}))
+
+
+if __name__ == "__main__":
+    main()
