@@ -3,6 +3,7 @@ import ctypes as C
 
 import numpy as np
 
+from halo_accumulation_amd import _lib
 from halo_accumulation_amd._lib import check, ptr
 from halo_accumulation_amd.pcdl import _check_batch, lg_of
 
@@ -47,6 +48,24 @@ def prover(ctx, rng, d, qs):
 def verifier(ctx, d, qs, acc):
     """acc.rs:223-243"""
     check(ctx.lib.halo_acc_verifier(ctx.h, d, ptr(_cat(qs)), len(qs), ptr(np.ascontiguousarray(acc, dtype=np.uint64))))
+
+
+def verifier_batch(ctx, d, qss, accs):
+    """acc::verifier (acc.rs:223-243) of k accumulators at once (benches/acc.rs:64-74's loop in one call): qss[j] = the Instances
+    accs[j] is verified against (may be empty) -> status list; raises HaloReject as decider_batch does"""
+    k = len(accs)
+    if len(qss) != k:
+        raise ValueError("verifier_batch: one list of instances per accumulator")
+    counts = (C.c_size_t * max(k, 1))(*[len(qs) for qs in qss])
+    qs = _cat([q for qs in qss for q in qs])
+    blob = _cat(accs) if k else np.zeros(0, dtype=np.uint64)
+    status = (C.c_int * max(k, 1))()
+    rc = ctx.lib.halo_acc_verifier_batch(ctx.h, d, ptr(qs), counts, k, ptr(blob), status)
+    st = [status[i] for i in range(k)]
+    if rc == _lib.HALO_E_REJECT:
+        raise _lib.HaloReject(ctx.lib.halo_last_error().decode(), st)
+    check(rc)
+    return st
 
 
 def decider(ctx, acc):

@@ -171,8 +171,9 @@ int halo_dev_hook(const char *name, long value) {
     else if (!std::strcmp(name, "batch_stage_fail")) h.batch_stage_fail = (int)value;
     else if (!std::strcmp(name, "check_batch_group")) h.check_group = (int)value;
     else if (!std::strcmp(name, "open_batch_group")) h.open_group = (int)value;
+    else if (!std::strcmp(name, "verifier_batch_min")) h.verifier_min = (int)value;
     else if (!std::strcmp(name, "reset")) h = DevHooks();
-    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, reset)"); return HALO_E_ARG; }
+    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, verifier_batch_min, reset)"); return HALO_E_ARG; }
     return HALO_OK;
 }
 
@@ -193,6 +194,37 @@ int halo_dev_h_coeffs_batch(halo_ctx *ctx, const uint64_t *xis, size_t m, size_t
     int rc = e == hipSuccess ? h_coeffs_batch_dev(ctx, d_xis, m, lg_n, d_tabs, d_out, n * 4) : hip_fail(e, "hipMemcpy");
     if (!rc && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
     if (!rc && (e = hipMemcpy(out, d_out, m * n * 32, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d);
+    return rc;
+}
+
+// the verifier batch's segmented sums on their own (tests/test_gpu_verifier_batch.py holds them against the oracle): one
+// k_small_msm_seg launch over nsums sums of lens[s] in 1..64 terms, temporary device buffers of this call only
+int halo_dev_small_msm_seg(halo_ctx *ctx, const uint64_t *points, const uint64_t *scalars, const size_t *lens, size_t nsums, uint64_t *out_jac) {
+    HALO_CTX(ctx);
+    if (nsums == 0) return HALO_OK;
+    if (!points || !scalars || !lens || !out_jac) { set_error("small_msm_seg: null pointer"); return HALO_E_ARG; }
+    if (nsums >= ((size_t)1 << 20)) { set_error("small_msm_seg: too many sums"); return HALO_E_ARG; }
+    std::vector<uint32_t> off{0};
+    for (size_t s = 0; s < nsums; ++s) {
+        if (lens[s] < 1 || lens[s] > 64) { set_error("small_msm_seg: 1..64 terms per sum"); return HALO_E_ARG; }
+        off.push_back(off.back() + (uint32_t)lens[s]);
+    }
+    const size_t nterms = off.back();
+    std::vector<uint32_t> desc;
+    const size_t waves = small_msm_seg_plan(off.data(), nsums, desc);
+    uint64_t *d = nullptr;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d, nterms * 96 + nsums * 96 + off.size() * 4 + desc.size() * 4));
+    uint64_t *d_pts = d, *d_sc = d_pts + nterms * 8, *d_out = d_sc + nterms * 4;
+    uint32_t *d_off = reinterpret_cast<uint32_t *>(d_out + nsums * 12), *d_desc = d_off + off.size();
+    hipError_t e = hipMemcpy(d_pts, points, nterms * 64, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_sc, scalars, nterms * 32, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_desc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? small_msm_seg(ctx, d_pts, d_sc, d_off, d_desc, waves, d_out) : hip_fail(e, "hipMemcpy");
+    if (!rc && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    if (!rc && (e = hipMemcpy(out_jac, d_out, nsums * 96, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d);
     return rc;
 }

@@ -502,6 +502,11 @@ int h_eval_batch(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg_n, co
 // m polynomials h_i at their own points z_i; m sums of K scalar multiples (canonical scalars, affine points) -> m Jacobian points
 int h_eval_each(halo_ctx *ctx, const uint64_t *d_xis, const uint64_t *d_zs, size_t m, size_t lg_n, uint64_t *d_out);
 int batch_small_msm(halo_ctx *ctx, const uint64_t *d_points, const uint64_t *d_scalars, size_t m, size_t K, uint64_t *d_out);
+// sums of 1..64 terms each, several to a wave (k_small_msm_seg): sum s holds terms sum_off[s] .. sum_off[s + 1] (same term
+// format as above).  plan: the lane descriptor (64 words per wave) -> the number of waves; the launch writes nsums Jacobian points
+size_t small_msm_seg_plan(const uint32_t *sum_off, size_t nsums, std::vector<uint32_t> &desc);
+int small_msm_seg(halo_ctx *ctx, const uint64_t *d_points, const uint64_t *d_scalars, const uint32_t *d_sum_off, const uint32_t *d_desc, size_t waves,
+                  uint64_t *d_out);
 // SplitMix64 stream -> n Montgomery scalars (element i = draws 4i+1..4i+4 after state0)
 int rng_scalars_dev(halo_ctx *ctx, uint64_t state0, size_t n, uint64_t *d_out);
 int pbar_dev(halo_ctx *ctx, const uint64_t *d_q, size_t deg, const host::Fr &z, uint64_t *d_out);

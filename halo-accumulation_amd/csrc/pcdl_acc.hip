@@ -299,6 +299,32 @@ static int verify_staging(halo_ctx *ctx, size_t words) {
     return HALO_OK;
 }
 struct BatchCheck { int rc = HALO_OK; std::string err; SuccinctState st; };
+// The 2 lg n + 2 terms of one instance's relation (q: its blob, hz = h(z) of its challenges, st: its accepted transcript) whose
+// sum is -C' exactly when pcdl.rs:288-310 accepts: points arkworks affine ((0, 0) = infinity), scalars canonical
+static void relation_terms(const SuccinctState &st, const uint64_t *q, const Fr &hz, uint64_t *pts, uint64_t *sc) {
+    const size_t lg = st.lg_n;
+    uint64_t *proof = const_cast<uint64_t *>(q + 21);
+    auto put_point = [&](size_t slot, const Point &p) {
+        host::Affine a = p.to_affine();
+        if (!a.inf) { a.x.store(pts + 8 * slot); a.y.store(pts + 8 * slot + 4); }
+    };
+    // challenge inverses with one inversion (Montgomery's trick)
+    std::vector<Fr> pref(lg + 1, Fr::one()), inv(lg + 1);
+    for (size_t j = 0; j < lg; ++j) pref[j + 1] = pref[j] * st.xis[j + 1];
+    Fr run = lg ? pref[lg].inv() : Fr::one();
+    for (size_t j = lg; j-- > 0;) { inv[j + 1] = run * pref[j]; run = run * st.xis[j + 1]; }
+    for (size_t j = 0; j < lg; ++j) {
+        put_point(j, Point::load(pf_L(proof, j)));
+        inv[j + 1].from_mont().store(sc + 4 * j);
+        put_point(lg + j, Point::load(pf_R(proof, lg, j)));
+        st.xis[j + 1].from_mont().store(sc + 4 * (lg + j));
+    }
+    Fr c = Fr::load(pf_c(proof, lg)), v = Fr::load(q + 17);
+    put_point(2 * lg, public_points().H);
+    ((v - c * hz) * st.xis[0]).from_mont().store(sc + 4 * (2 * lg));      // (v - v') xi_0 on H: the two H' terms of :288 and :307
+    put_point(2 * lg + 1, st.U);
+    (-c).from_mont().store(sc + 4 * (2 * lg + 1));
+}
 // instances: m blobs at stride `stride` words (0: instance_words(lg(d+1)); an Accumulator's Instance prefix at acc_words);
 // res[i].rc / .err / .st filled; returns a device / argument error only
 static int succinct_check_batch(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t m, std::vector<BatchCheck> &res, size_t stride = 0) {
@@ -326,34 +352,9 @@ static int succinct_check_batch(halo_ctx *ctx, size_t d, const uint64_t *qs, siz
     if (rc) return rc;
     HALO_HIP(hipMemcpyAsync(&host[o_hz], ctx->d_verify + o_hz, m * 32, hipMemcpyDeviceToHost, ctx->stream));
     HALO_HIP(hipStreamSynchronize(ctx->stream));
-    const PublicPoints &pp = public_points();
-    host::Affine Ha = pp.H.to_affine();
     pool_run(m, [&](size_t i) {
         if (res[i].rc) return;
-        const uint64_t *q = qs + i * iw;
-        uint64_t *proof = const_cast<uint64_t *>(q + 21);
-        const SuccinctState &st = res[i].st;
-        uint64_t *pts = &host[o_pts + i * K * 8], *sc = &host[o_sc + i * K * 4];
-        auto put_point = [&](size_t slot, const Point &p) {
-            host::Affine a = p.to_affine();
-            if (!a.inf) { a.x.store(pts + 8 * slot); a.y.store(pts + 8 * slot + 4); }
-        };
-        // challenge inverses with one inversion (Montgomery's trick)
-        std::vector<Fr> pref(lg + 1, Fr::one()), inv(lg + 1);
-        for (size_t j = 0; j < lg; ++j) pref[j + 1] = pref[j] * st.xis[j + 1];
-        Fr run = lg ? pref[lg].inv() : Fr::one();
-        for (size_t j = lg; j-- > 0;) { inv[j + 1] = run * pref[j]; run = run * st.xis[j + 1]; }
-        for (size_t j = 0; j < lg; ++j) {
-            put_point(j, Point::load(pf_L(proof, j)));
-            inv[j + 1].from_mont().store(sc + 4 * j);
-            put_point(lg + j, Point::load(pf_R(proof, lg, j)));
-            st.xis[j + 1].from_mont().store(sc + 4 * (lg + j));
-        }
-        Fr c = Fr::load(pf_c(proof, lg)), v = Fr::load(q + 17), hz = Fr::load(&host[o_hz + 4 * i]);
-        Ha.x.store(pts + 8 * (2 * lg)); Ha.y.store(pts + 8 * (2 * lg) + 4);
-        ((v - c * hz) * st.xis[0]).from_mont().store(sc + 4 * (2 * lg));      // (v - v') xi_0 on H: the two H' terms of :288 and :307
-        put_point(2 * lg + 1, st.U);
-        (-c).from_mont().store(sc + 4 * (2 * lg + 1));
+        relation_terms(res[i].st, qs + i * iw, Fr::load(&host[o_hz + 4 * i]), &host[o_pts + i * K * 8], &host[o_sc + i * K * 4]);
     });
     HALO_HIP(hipMemcpyAsync(ctx->d_verify + o_pts, &host[o_pts], (o_out - o_pts) * 8, hipMemcpyHostToDevice, ctx->stream));
     rc = batch_small_msm(ctx, ctx->d_verify + o_pts, ctx->d_verify + o_sc, m, K, ctx->d_verify + o_out);
@@ -615,6 +616,26 @@ struct AccHPolys {  // acc.rs:61-66
     }
 };
 
+// :173  alpha = rho_1(hs): h_0 Some(poly), hs Vec<HPoly>, alpha None, alphas empty; then alpha^0 .. alpha^m
+static void set_alphas(AccHPolys *hs) {
+    const Fr *h0 = hs->h0;
+    const size_t lg = hs->lg_n, m = hs->xis.size();
+    Transcript t;
+    size_t h0len = h0[1].is_zero() ? (h0[0].is_zero() ? 0 : 1) : 2;
+    t.byte(1); t.u64le(h0len);
+    for (size_t k = 0; k < h0len; ++k) t.scalar(h0[k]);
+    t.u64le(m);
+    for (size_t i = 0; i < m; ++i) { t.u64le(lg + 1); for (size_t k = 0; k <= lg; ++k) t.scalar(hs->xis[i][k]); }
+    t.byte(0); t.u64le(0);
+    hs->alpha = t.finish(1);
+    hs->alphas.assign(m + 1, Fr::one());
+    for (size_t i = 1; i <= m; ++i) hs->alphas[i] = hs->alphas[i - 1] * hs->alpha;
+}
+// :181  z = rho_1(C, alpha)
+static Fr rho1_C_alpha(const Point &C, const Fr &alpha) {
+    Transcript t; t.point(C); t.scalar(alpha); return t.finish(1);
+}
+
 // acc.rs:135-188
 static int common_subroutine(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t m, const Fr h0[2], const Point &U0, const Fr &w,
                              Point *C_bar_out, Fr *z_out, AccHPolys *hs) {
@@ -668,22 +689,187 @@ static int common_subroutine(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t
         hs->xis.push_back(std::move(res[i].xis));
         Us.push_back(res[i].U);
     }
-    // :173  alpha = rho_1(hs): h_0 Some(poly), hs Vec<HPoly>, alpha None, alphas empty
-    Transcript t;
-    size_t h0len = h0[1].is_zero() ? (h0[0].is_zero() ? 0 : 1) : 2;
-    t.byte(1); t.u64le(h0len);
-    for (size_t k = 0; k < h0len; ++k) t.scalar(h0[k]);
-    t.u64le(m);
-    for (size_t i = 0; i < m; ++i) { t.u64le(lg + 1); for (size_t k = 0; k <= lg; ++k) t.scalar(hs->xis[i][k]); }
-    t.byte(0); t.u64le(0);
-    hs->alpha = t.finish(1);
-    hs->alphas.assign(m + 1, Fr::one());
-    for (size_t i = 1; i <= m; ++i) hs->alphas[i] = hs->alphas[i - 1] * hs->alpha;
+    set_alphas(hs);  // :173
     Point C = host::small_msm(Us, hs->alphas);  // :178  (m + 1 points)
-    Transcript t2;
-    t2.point(C); t2.scalar(hs->alpha);
-    *z_out = t2.finish(1);                       // :181
+    *z_out = rho1_C_alpha(C, hs->alpha);         // :181
     *C_bar_out = C + public_s_table().mul(w);   // :184
+    return HALO_OK;
+}
+
+// ------------------------------------------------------------------ acc::verifier of k accumulators at once
+// (halo_acc_verifier_batch; acc.rs:223-243 per member, each member's outcome the single call's)
+//  1. the transcripts: one pool pass over the instances of every member that reaches its succinct checks -- C', the
+//     challenges (succinct_challenges) and h_i(z_i), i.e. the relation's terms (relation_terms); then one pass over the members:
+//     alpha = rho_1(hs) (:173), its powers, and the terms of h_0[0] G_0 + h_0[1] G_1 (:152-155) and C = sum_i alpha^i U_i (:178).
+//  2. every sum of the batch at once: ONE k_small_msm_seg launch on a slot idle at entry, from kVerifierBatchMin relations on;
+//     below that, without an idle slot or without staging (optional memory: check_stage), the host pool, sum by sum.
+//  3. one pass over the members: z' = rho_1(C, alpha) (:181), C_bar' = C + w S (:184), h(z), and the status in the single
+//     call's order (fields, U_0, d_i, the succinct checks in instance order, C_bar', z', d', h(z)).
+constexpr size_t kVerifierBatchMin = 64;  // relations; measured: tools/time_verifier_batch.py
+constexpr size_t kSegMaxTerms = 64;      // terms per sum of k_small_msm_seg (a longer C is summed in parts)
+
+struct VerifierMember {
+    int rc = HALO_OK;
+    std::string err;
+    size_t first = 0, m = 0;  // its instances in the flat list
+    bool sums = false;        // reaches the U_0 check (fields valid, deg h_0 <= d)
+    bool reach = false;       // ... and its succinct checks (every d_i == d)
+    bool all_ok = false;      // ... and every transcript held: C is summed
+    size_t s_u0 = 0, s_c = 0, n_c = 0;  // its sums: h_0 against U_0, the n_c parts of C
+    AccHPolys hs;
+};
+
+static int acc_verifier_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, const size_t *counts, size_t k, const uint64_t *accs, int *status) {
+    const size_t lg = ilog2(d + 1), iw = instance_words(lg), aw = acc_words(lg), K = 2 * lg + 2;
+    if (K > kSegMaxTerms) { set_error("verifier_batch: lg n too large"); return HALO_E_ARG; }
+    std::vector<VerifierMember> mem(k);
+    size_t total = 0;
+    for (size_t j = 0; j < k; ++j) { mem[j].first = total; mem[j].m = counts[j]; total += counts[j]; }
+    // 0. what the single call checks before any arithmetic, and the sums' layout (sum_off: term offsets)
+    std::vector<uint32_t> sum_off{0};
+    auto add_sum = [&](size_t terms) { sum_off.push_back(sum_off.back() + (uint32_t)terms); return sum_off.size() - 2; };
+    std::vector<size_t> rel_sum(total, 0), work;  // relation sum of each instance; the instances whose transcripts run
+    const size_t u0_terms = d ? 2 : 1;            // (d = 0: h_0 is a constant, or the assert below)
+    for (size_t j = 0; j < k; ++j) {
+        VerifierMember &M = mem[j];
+        const uint64_t *acc = accs + j * aw, *piV = acc + iw;
+        M.hs.h0[0] = Fr::load(piV);
+        M.hs.h0[1] = Fr::load(piV + 4);
+        M.hs.lg_n = lg;
+        if (!Point::load(piV + 8).on_curve() || !Point::load(acc).on_curve() || !scalar_ok(M.hs.h0[0]) || !scalar_ok(M.hs.h0[1]) ||
+            !scalar_ok(Fr::load(piV + 20)) || !scalar_ok(Fr::load(acc + 13)) || !scalar_ok(Fr::load(acc + 17))) {
+            M.rc = HALO_E_REJECT;
+            M.err = "accumulator holds an invalid point or scalar";
+            continue;
+        }
+        if (host_poly_degree(piV, 2) > d) { M.rc = HALO_E_ASSERT; M.err = "commit: p.degree() > d"; continue; }  // pcdl_commit_host
+        M.sums = true;
+        M.s_u0 = add_sum(u0_terms);
+        M.reach = true;
+        for (size_t i = 0; i < M.m && M.reach; ++i) {
+            const uint64_t *q = qs + (M.first + i) * iw;
+            if ((size_t)q[12] != d || q[22] != lg) M.reach = false;  // :169
+        }
+        if (!M.reach) continue;
+        for (size_t i = 0; i < M.m; ++i) {
+            rel_sum[M.first + i] = add_sum(K);
+            work.push_back(M.first + i);
+        }
+        M.n_c = (M.m + 1 + kSegMaxTerms - 1) / kSegMaxTerms;
+        M.s_c = sum_off.size() - 1;
+        for (size_t c = 0; c < M.n_c; ++c) add_sum(c + 1 < M.n_c ? kSegMaxTerms : M.m + 1 - c * kSegMaxTerms);
+    }
+    const size_t nsums = sum_off.size() - 1, nterms = sum_off.back();
+    if (nterms >= ((size_t)1 << 31) || nsums >= ((size_t)1 << 28)) { set_error("verifier_batch: too many terms"); return HALO_E_ARG; }
+    std::vector<uint64_t> pts(nterms * 8, 0), sc(nterms * 4, 0);
+    // 1. the transcripts and the relations' terms
+    std::vector<BatchCheck> res(total);
+    pool_run(work.size(), [&](size_t w) {
+        const size_t i = work[w];
+        const uint64_t *q = qs + i * iw;
+        BatchCheck &r = res[i];
+        const Fr z = Fr::load(q + 13);
+        r.rc = succinct_challenges(ctx, Point::load(q), d, z, Fr::load(q + 17), q + 21, &r.st, false);
+        if (r.rc) { r.err = halo_last_error(); return; }
+        const std::vector<Fr> &x = r.st.xis;  // h(z) as k_h_eval_z computes it (pcdl.rs:301-304)
+        Fr hz = Fr::one() + x[lg] * z, zi = z;
+        for (size_t t = 1; t < lg; ++t) { zi = zi.sqr(); hz = hz * (Fr::one() + x[lg - t] * zi); }
+        const size_t o = sum_off[rel_sum[i]];
+        relation_terms(r.st, q, hz, &pts[8 * o], &sc[4 * o]);
+    });
+    uint64_t g01[16] = {};  // G_0, G_1
+    auto put_affine = [&](size_t t, const Point &p) {
+        host::Affine a = p.to_affine();
+        if (!a.inf) { a.x.store(&pts[8 * t]); a.y.store(&pts[8 * t + 4]); }
+    };
+    auto member_terms = [&](size_t j) {  // alpha, its powers, the terms of the U_0 check and of C
+        VerifierMember &M = mem[j];
+        const uint64_t *piV = accs + j * aw + iw;
+        const size_t u = sum_off[M.s_u0];
+        for (size_t t = 0; t < u0_terms; ++t) {
+            std::memcpy(&pts[8 * (u + t)], g01 + 8 * t, 64);
+            M.hs.h0[t].from_mont().store(&sc[4 * (u + t)]);
+        }
+        if (!M.reach) return;
+        for (size_t i = 0; i < M.m; ++i)
+            if (res[M.first + i].rc) return;
+        M.all_ok = true;
+        for (size_t i = 0; i < M.m; ++i) M.hs.xis.push_back(res[M.first + i].st.xis);
+        set_alphas(&M.hs);
+        const size_t c0 = sum_off[M.s_c];  // the parts of C are consecutive: term t of C is term c0 + t
+        for (size_t t = 0; t <= M.m; ++t) {
+            put_affine(c0 + t, t ? res[M.first + t - 1].st.U : Point::load(piV + 8));
+            M.hs.alphas[t].from_mont().store(&sc[4 * (c0 + t)]);
+        }
+    };
+    // 2. every sum: on the device in one launch, or on the host pool
+    std::vector<Point> sums(nsums, Point::infinity());
+    int slot = -1;
+    for (int s = 0; s < HALO_SLOTS && slot < 0; ++s)
+        if (!ctx->wss[s].in_flight && ctx->wss[s].lent_from < 0 && !ctx->fan[s].active) slot = s;
+    std::vector<uint32_t> desc;
+    const size_t waves = small_msm_seg_plan(sum_off.data(), nsums, desc);
+    // staging (bytes): points nterms x 64 | scalars nterms x 32 | results nsums x 96 | sum_off (nsums + 1) x 4 | desc waves x 256
+    const size_t bytes = nterms * 96 + nsums * 96 + (nsums + 1) * 4 + desc.size() * 4;
+    const int forced = dev_hooks().verifier_min;  // (development library: the threshold sweep of tools/time_verifier_batch.py)
+    const size_t min_rel = forced >= 1 ? (size_t)forced : kVerifierBatchMin;
+    const bool device = slot >= 0 && ctx->batch_verify && work.size() >= min_rel && check_stage(ctx, 1, bytes) >= 1;
+    hipStream_t saved = ctx->stream;
+    if (device) ctx->stream = ctx->streams[slot];  // (the launch macro and the reads below use ctx->stream: the slot's own)
+    int rc = nsums ? halo_ctx_read_bases(ctx, 0, u0_terms, g01) : HALO_OK;
+    if (!rc) pool_run(k, [&](size_t j) { if (mem[j].sums) member_terms(j); });
+    if (!rc && device) {
+        uint64_t *d_pts = ctx->d_check_stage, *d_sc = d_pts + nterms * 8, *d_out = d_sc + nterms * 4;
+        uint32_t *d_off = reinterpret_cast<uint32_t *>(d_out + nsums * 12), *d_desc = d_off + nsums + 1;
+        hipError_t e = hipMemcpyAsync(d_pts, pts.data(), nterms * 64, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_sc, sc.data(), nterms * 32, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_off, sum_off.data(), (nsums + 1) * 4, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_desc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+        rc = e == hipSuccess ? small_msm_seg(ctx, d_pts, d_sc, d_off, d_desc, waves, d_out) : hip_fail(e, "hipMemcpyAsync");
+        std::vector<uint64_t> out(nsums * 12);
+        if (!rc && (e = hipMemcpyAsync(out.data(), d_out, nsums * 96, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+        if (!rc && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+        if (!rc)
+            for (size_t s = 0; s < nsums; ++s) sums[s] = Point::load(&out[12 * s]);
+    } else if (!rc) {
+        pool_run(nsums, [&](size_t s) {
+            const size_t lo = sum_off[s], len = sum_off[s + 1] - lo;
+            std::vector<Point> p(len);
+            std::vector<Fr> kk(len);
+            for (size_t t = 0; t < len; ++t) { p[t] = Point::load_affine(&pts[8 * (lo + t)]); kk[t] = Fr::load(&sc[4 * (lo + t)]).to_mont(); }
+            sums[s] = host::small_msm(p, kk);
+        });
+    }
+    ctx->stream = saved;
+    if (rc) return rc;
+    // 3. the tail and every member's status in the single call's order
+    pool_run(k, [&](size_t j) {
+        VerifierMember &M = mem[j];
+        if (M.rc) return;
+        const uint64_t *acc = accs + j * aw, *piV = acc + iw;
+        if (sums[M.s_u0] != Point::load(piV + 8)) { M.rc = HALO_E_REJECT; M.err = "U_0 != PCDL.Commit(h_0)"; return; }
+        if (!M.reach) { M.rc = HALO_E_REJECT; M.err = "d_i != d"; return; }  // :169
+        for (size_t i = 0; i < M.m; ++i) {  // :158-170 in instance order
+            const BatchCheck &r = res[M.first + i];
+            if (r.rc) { M.rc = r.rc; M.err = r.err; return; }
+            if (sums[rel_sum[M.first + i]] != -r.st.C_prime) { M.rc = HALO_E_REJECT; M.err = "C_(log_n) != CM.Commit_Sigma(c || v')"; return; }  // :307-310
+        }
+        Point C = Point::infinity();
+        for (size_t c = 0; c < M.n_c; ++c) C = C + sums[M.s_c + c];
+        const Fr z_p = rho1_C_alpha(C, M.hs.alpha);                         // :181
+        const Point C_bar_p = C + public_s_table().mul(Fr::load(piV + 20));  // :184
+        const Fr z = Fr::load(acc + 13), v = Fr::load(acc + 17);
+        if (C_bar_p != Point::load(acc)) { M.rc = HALO_E_REJECT; M.err = "C_bar' != C_bar"; }
+        else if (z_p != z) { M.rc = HALO_E_REJECT; M.err = "z' != z"; }
+        else if ((size_t)acc[12] != d) { M.rc = HALO_E_REJECT; M.err = "d' != d"; }
+        else if (M.hs.eval(z) != v) { M.rc = HALO_E_REJECT; M.err = "h(z) != v"; }
+    });
+    int first = -1;
+    for (size_t j = 0; j < k; ++j) {
+        if (status) status[j] = mem[j].rc;
+        if (mem[j].rc && first < 0) first = (int)j;
+    }
+    if (first >= 0) { set_error("member " + std::to_string(first) + ": " + mem[first].err); return mem[first].rc; }
     return HALO_OK;
 }
 
@@ -1488,6 +1674,24 @@ int halo_acc_verifier(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t m, con
     if ((size_t)acc[12] != d) return fail_reject("d' != d");
     if (hs.eval(z) != v) return fail_reject("h(z) != v");
     return HALO_OK;
+}
+
+// acc::verifier of k accumulators at once (benches/acc.rs:64-74's loop in one call; see acc_verifier_batch_host).  The argument
+// checks are the whole call's and come before any work: d + 1 above the key is the assert the single call meets in
+// pcdl_commit_host.  A multi-device context runs the batch on its own device (devices[0]) like the other batches.
+int halo_acc_verifier_batch(halo_ctx *ctx, size_t d, const uint64_t *instances, const size_t *counts, size_t k, const uint64_t *accs, int *status) {
+    HALO_CTX2(ctx);
+    if (k && (!accs || !counts)) { set_error("verifier_batch: null pointer"); return HALO_E_ARG; }
+    size_t total = 0;
+    for (size_t j = 0; j < k; ++j) {
+        if (counts[j] > ((size_t)1 << 32) - total) { set_error("verifier_batch: too many instances"); return HALO_E_ARG; }
+        total += counts[j];
+    }
+    if (total && !instances) { set_error("verifier_batch: null pointer"); return HALO_E_ARG; }
+    if (!is_pow2(d + 1)) return fail_reject("d+1 is not a power of 2!");
+    if (d + 1 > ctx->n) return fail_assert("commit: d > D");
+    if (k == 0) return HALO_OK;
+    return acc_verifier_batch_host(ctx, d, instances, counts, k, accs, status);
 }
 
 // acc.rs:245-255

@@ -54,6 +54,7 @@ struct DevHooks {
     int batch_stage_fail = 0;  // "batch_stage_fail"   the staging of the check and open batches is refused: one member at a time
     int check_group = 0;       // "check_batch_group"  members per MSM launch of halo_pcdl_check_batch (1..8; 0: the measured default)
     int open_group = 0;        // "open_batch_group"   members per launch of halo_pcdl_open_batch (1..4; 0: the measured default)
+    int verifier_min = 0;      // "verifier_batch_min" relations from which halo_acc_verifier_batch launches (>= 1; 0: the measured default)
 };
 DevHooks &dev_hooks();
 

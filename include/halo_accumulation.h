@@ -306,6 +306,21 @@ int halo_acc_decider(halo_ctx *ctx, const uint64_t *acc);
 /* acc::decider (acc.rs:245-255) of m accumulators at once: benches/acc.rs:100-106 in one call.  accs = m Accumulator blobs at
  * stride halo_accumulator_words(lg(d+1)); halo_pcdl_check_batch over their Instance prefixes, with its conventions. */
 int halo_acc_decider_batch(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, int *status /*nullable*/);
+/* acc::verifier (acc.rs:223-243) of k accumulators at once: benches/acc.rs:64-74's loop in one call.  accs = k Accumulator blobs
+ * at stride halo_accumulator_words(lg(d+1)); counts[j] = the number of Instances member j verifies against accs[j] (0 allowed);
+ * instances = sum(counts) Instance blobs at stride halo_instance_words(lg(d+1)), member j's right after member j - 1's.
+ * status[j] = what halo_acc_verifier(ctx, d, <member j's instances>, counts[j], accs[j]) returns alone: each member's checks
+ * resolve in that call's order (accumulator fields, U_0 == commit(h_0), every instance's d and proof length, the succinct
+ * checks in instance order, C_bar' == C_bar, z' == z, d' == d, h(z) == v).  Returns 0 if every member is accepted, else the
+ * first non-zero status in member order with halo_last_error() = "member j: <the single call's message>".  Whole-call errors
+ * come first and leave status untouched: a null ctx, k > 0 with null accs or counts, or a non-zero total with null instances
+ * (HALO_E_ARG); d + 1 not a power of two (HALO_E_REJECT); d + 1 above the key (HALO_E_ASSERT "commit: d > D"); k = 0 is OK.
+ * A device failure returns its code.  The transcripts run on a host thread pool; every relation and member sum goes to the
+ * device in one launch, on a slot idle on entry (a caller's MSM in flight is left alone), from 64 relations on.  Fewer, no
+ * idle slot or no staging memory (optional memory, halo_set_memory_budget): the host pool, with the same results.  A
+ * multi-device context runs the batch on devices[0]. */
+int halo_acc_verifier_batch(halo_ctx *ctx, size_t d, const uint64_t *instances, const size_t *counts, size_t k,
+                            const uint64_t *accs, int *status /*nullable*/);
 /* benches/acc.rs:15-29 random_instance: the workload generator of the reference's benchmark */
 int halo_random_instance(halo_ctx *ctx, uint64_t *rng_state, size_t d, uint64_t *instance_out);
 

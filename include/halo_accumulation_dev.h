@@ -23,8 +23,9 @@ extern "C" {
  * 0 = the share of p(z), 1.. = the rounds, then the tail; at = -2: in a sharded check; at = -3: the rank with that `rank`
  * before the collective of halo_msm_sharded / _dev_sharded / _end_sharded), "batch_stage_fail" (value != 0: the staging of
  * halo_pcdl_check_batch / halo_acc_decider_batch / halo_pcdl_open_batch / halo_random_instance_batch is refused, as over the
- * memory budget: one member at a time), "check_batch_group" (members per MSM launch of the check batch, 1..8; 0: the measured
- * default), "open_batch_group" (members per launch of the open batch, 1..4; 0: the measured default), "reset" (all off). */
+ * memory budget: one member at a time; halo_acc_verifier_batch: its sums on the host pool), "check_batch_group" (members per MSM launch of the check batch, 1..8; 0: the measured
+ * default), "open_batch_group" (members per launch of the open batch, 1..4; 0: the measured default), "verifier_batch_min" (relations
+ * from which halo_acc_verifier_batch runs its sums on the device, >= 1; 0: the measured default), "reset" (all off). */
 int halo_dev_hook(const char *name, long value);
 /* What the library read from the environment at its first use (csrc/tuning.hip), by field: "host_split_set", "host_pieces", "host_split0".."host_split3",
  * "fold_table_after", "graph_cache", "pow_e", "spin_us", "graphs", "memory_budget" (MiB, -1 unset), "trace", "tagged"; -1 for an
@@ -79,6 +80,12 @@ int halo_set_small_path(halo_ctx *ctx, int mode);
 
 /* MSM tuning: longest chain of mixed additions one lane runs in the bucket kernel (0 = automatic; 8, 16, 32, 64) */
 int halo_set_task_len(halo_ctx *ctx, int len);
+
+/* The verifier batch's segmented small MSM (k_small_msm_seg) on its own, in one launch: nsums sums, sum s of lens[s] in 1..64
+ * terms; points = the terms' arkworks affine points (8 words, (0, 0) = infinity), scalars = their canonical scalars (4 words),
+ * sum after sum; out_jac = nsums x 12 Jacobian words */
+int halo_dev_small_msm_seg(halo_ctx *ctx, const uint64_t *points, const uint64_t *scalars, const size_t *lens, size_t nsums,
+                           uint64_t *out_jac);
 
 /* ---- primitive hooks used by the parity tests (elementwise over n) ----------------------- */
 /* host-only: base-2 expansion of the fold scalar over the Eisenstein units (host_math.hpp glv_digits):
