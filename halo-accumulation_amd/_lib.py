@@ -110,6 +110,7 @@ _SIGS = {
     "halo_acc_decider": (C.c_int, [C.c_void_p, u64p]),
     "halo_acc_decider_batch": (C.c_int, [C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_int)]),
     "halo_acc_verifier_batch": (C.c_int, [C.c_void_p, C.c_size_t, u64p, C.POINTER(C.c_size_t), C.c_size_t, u64p, C.POINTER(C.c_int)]),
+    "halo_acc_prover_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, u64p, C.POINTER(C.c_size_t), C.c_size_t, u64p, C.POINTER(C.c_int)]),
     "halo_random_instance": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, u64p]),
     "halo_pcdl_open_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, u64p, C.c_size_t, u64p, u64p, u64p, u64p, C.POINTER(C.c_int)]),
     "halo_random_instance_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.c_size_t, u64p]),
@@ -158,6 +159,7 @@ _DEV_SIGS = {
     "halo_test_field_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, u64p, u64p, C.c_size_t, u64p]),
     "halo_test_point_op": (C.c_int, [C.c_void_p, C.c_int, u64p, u64p, C.c_size_t, u64p]),
     "halo_dev_h_coeffs_batch": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_size_t, u64p]),
+    "halo_dev_h_accumulate_batch": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.c_size_t, u64p]),
     "halo_dev_small_msm_seg": (C.c_int, [C.c_void_p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, u64p]),
 }
 

@@ -45,6 +45,26 @@ def prover(ctx, rng, d, qs):
     return acc
 
 
+def prover_batch(ctx, rng, d, qss):
+    """acc::prover (acc.rs:190-220) of k members at once (halo_acc_prover_batch): qss[j] = member j's Instances (may be empty) ->
+    (accs, status), the accumulators prover returns in turn (a failed member's is zero-filled), rng[0] updated as the loop would
+    update it; raises HaloReject with the status list as verifier_batch does"""
+    k = len(qss)
+    counts = (C.c_size_t * max(k, 1))(*[len(qs) for qs in qss])
+    qs = _cat([q for qs in qss for q in qs])
+    st = C.c_uint64(rng[0])
+    out = np.zeros((max(k, 1), ctx.lib.halo_accumulator_words(lg_of(d))), dtype=np.uint64)
+    status = (C.c_int * max(k, 1))()
+    rc = ctx.lib.halo_acc_prover_batch(ctx.h, C.byref(st), d, ptr(qs), counts, k, ptr(out), status)
+    codes = [status[i] for i in range(k)]
+    if rc == _lib.HALO_E_REJECT:
+        rng[0] = st.value
+        raise _lib.HaloReject(ctx.lib.halo_last_error().decode(), codes)
+    check(rc)
+    rng[0] = st.value
+    return [out[i].copy() for i in range(k)], codes
+
+
 def verifier(ctx, d, qs, acc):
     """acc.rs:223-243"""
     check(ctx.lib.halo_acc_verifier(ctx.h, d, ptr(_cat(qs)), len(qs), ptr(np.ascontiguousarray(acc, dtype=np.uint64))))

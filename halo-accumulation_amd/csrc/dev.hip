@@ -198,6 +198,49 @@ int halo_dev_h_coeffs_batch(halo_ctx *ctx, const uint64_t *xis, size_t m, size_t
     return rc;
 }
 
+// the prover batch's accumulated polynomials on their own (tests/test_gpu_prover_batch.py holds them against the oracle's
+// h_coeffs): temporary device and pinned buffers of this call only
+int halo_dev_h_accumulate_batch(halo_ctx *ctx, const uint64_t *h0s, const uint64_t *xis, const uint64_t *alphas, const size_t *counts, size_t members,
+                                size_t lg_n, size_t max_tables, uint64_t *out) {
+    HALO_CTX(ctx);
+    if (members == 0) return HALO_OK;
+    if (!h0s || !counts || !out) { set_error("h_accumulate_batch: null pointer"); return HALO_E_ARG; }
+    if (lg_n < 1 || lg_n > 24 || ((size_t)1 << lg_n) > (ctx->n < 64 ? 64 : ctx->n)) { set_error("h_accumulate_batch: 2^lg_n exceeds context size"); return HALO_E_ARG; }
+    if (members > 65535) { set_error("h_accumulate_batch: at most 65535 members"); return HALO_E_ARG; }
+    const size_t n = (size_t)1 << lg_n, xw = (lg_n + 1) * 4;
+    size_t total = 0;
+    for (size_t j = 0; j < members; ++j) {
+        if (counts[j] > 65535 - total) { set_error("h_accumulate_batch: at most 65535 polynomials"); return HALO_E_ARG; }
+        total += counts[j];
+    }
+    if (total && (!xis || !alphas)) { set_error("h_accumulate_batch: null pointer"); return HALO_E_ARG; }
+    std::vector<host::Fr> h0(2 * members), x(total * (lg_n + 1)), a(total);
+    for (size_t i = 0; i < h0.size(); ++i) h0[i] = host::Fr::load(h0s + 4 * i);
+    for (size_t i = 0; i < x.size(); ++i) x[i] = host::Fr::load(xis + 4 * i);
+    for (size_t i = 0; i < total; ++i) a[i] = host::Fr::load(alphas + 4 * i);
+    std::vector<HAccMember> mem(members);
+    for (size_t j = 0, t = 0; j < members; t += counts[j], ++j) {
+        mem[j].h0 = &h0[2 * j];
+        mem[j].count = counts[j];
+        mem[j].scales = a.data() + t;
+        for (size_t i = 0; i < counts[j]; ++i) mem[j].xis.push_back(x.data() + (t + i) * (xw / 4));
+    }
+    const size_t cap = max_tables ? max_tables : (total ? total : 1);
+    uint64_t *d = nullptr, *h = nullptr;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d, (hacc_stage_words(members, lg_n, cap) + members * n * 4) * 8));
+    hipError_t e = hipHostMalloc(&h, hacc_pin_words(members, lg_n, cap) * 8);
+    if (e != hipSuccess) { (void)hipFree(d); return hip_fail(e, "hipHostMalloc"); }
+    uint64_t *d_out = d + hacc_stage_words(members, lg_n, cap);
+    int rc = h_accumulate_group(ctx, mem.data(), members, lg_n, cap, h, d, d_out, n * 4);
+    if (!rc && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    if (!rc && (e = hipMemcpy(out, d_out, members * n * 32, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (rc) (void)hipStreamSynchronize(ctx->stream);
+    (void)hipHostFree(h);
+    (void)hipFree(d);
+    return rc;
+}
+
 // the verifier batch's segmented sums on their own (tests/test_gpu_verifier_batch.py holds them against the oracle): one
 // k_small_msm_seg launch over nsums sums of lens[s] in 1..64 terms, temporary device buffers of this call only
 int halo_dev_small_msm_seg(halo_ctx *ctx, const uint64_t *points, const uint64_t *scalars, const size_t *lens, size_t nsums, uint64_t *out_jac) {

@@ -498,6 +498,20 @@ int h_coeffs_dev(halo_ctx *ctx, const host::Fr *xis, size_t lg_n, const host::Fr
 // coefficients at d_out + b * out_stride (bit-identical to h_coeffs_dev per member)
 int h_coeffs_batch_dev(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg_n, uint64_t *d_tabs, uint64_t *d_out, size_t out_stride);
 constexpr size_t H_TABLES_WORDS = 3 * 256 * 4;
+// h(X) = h_0 + sum_i scale_i h_i(X) of several members at once (k_h_tables with scales + k_h_accumulate_batch; acc.rs:85-94):
+// member b's polynomials are xis[i] (lg_n + 1 challenges each) with scales[i], i < count
+struct HAccMember {
+    const host::Fr *h0 = nullptr;  // two coefficients
+    std::vector<const host::Fr *> xis;
+    const host::Fr *scales = nullptr;
+    size_t count = 0;
+};
+constexpr size_t HACC_REC_WORDS = 10;  // a member's record: first table | count << 32, mode, h_0
+// words of the pinned / device staging of one call with G members and room for `cap` tables per pass
+inline size_t hacc_pin_words(size_t G, size_t lg_n, size_t cap) { return G * HACC_REC_WORDS + cap * (lg_n + 2) * 4; }
+inline size_t hacc_stage_words(size_t G, size_t lg_n, size_t cap) { return hacc_pin_words(G, lg_n, cap) + cap * H_TABLES_WORDS; }
+int h_accumulate_group(halo_ctx *ctx, const HAccMember *mem, size_t G, size_t lg_n, size_t cap, uint64_t *h_stage, uint64_t *d_stage, uint64_t *d_out,
+                       size_t out_stride);
 int h_eval_batch(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg_n, const host::Fr &z, uint64_t *d_out);
 // m polynomials h_i at their own points z_i; m sums of K scalar multiples (canonical scalars, affine points) -> m Jacobian points
 int h_eval_each(halo_ctx *ctx, const uint64_t *d_xis, const uint64_t *d_zs, size_t m, size_t lg_n, uint64_t *d_out);

@@ -942,7 +942,8 @@ struct OpenJob {
     size_t idx = 0, deg = 0;
     uint64_t s_start = 0;                // rng state before the member's first draw (the single call's *rng_state)
     uint64_t s_p = 0, s_q = 0;           // rng state before p's coefficients (random_instance) / before q's (hiding)
-    const uint64_t *coeffs = nullptr;    // the caller's n coefficients (null: p generated on the device)
+    const uint64_t *coeffs = nullptr;    // the caller's n coefficients (null: p generated or accumulated on the device)
+    const AccHPolys *hs = nullptr;       // acc::prover's h_0, challenges and alpha powers: p = h.get_poly() accumulated on the device
     bool hiding = false;
     Point C, last_L, last_R;
     Fr z, v, w, w_bar, xi0, xi, c0, c1, last_xi, last_xi_inv;
@@ -959,9 +960,14 @@ static size_t open_group_size(const halo_ctx *ctx, size_t n) {
     return (size_t)g;
 }
 constexpr size_t OPEN_AUX_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS + OPEN_PART_WORDS + OPEN_OUT_WORDS);
-constexpr size_t OPEN_PIN_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS + OPEN_OUT_WORDS) + 4;  // per slot; + the element one
+// (the prover batch's third coefficient source: up to HACC_TABLES polynomials h_i per pass of a group, see h_accumulate_group)
+constexpr size_t HACC_TABLES = 32;
+constexpr size_t HACC_PIN_WORDS = OPEN_MAX_GROUP * HACC_REC_WORDS + HACC_TABLES * (16 + 2) * 4;  // lg n <= 16 (OPEN_MAX_N)
+constexpr size_t OPEN_PIN_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS + OPEN_OUT_WORDS) + HACC_PIN_WORDS + 4;  // per slot; + the element one
 
 // jobs: the members that do not fail up front, in member order.  *ran = false: the device path does not apply (nothing done)
+// Coefficients of a member: the caller's host array (jb.coeffs), generated on the device (gen), or -- jb.hs set, for every member
+// alike -- acc::prover's h(X) accumulated on the device straight into the member's coefficient vector
 static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, bool gen, const int *slots_in, int S, bool *ran) {
     *ran = false;
     const size_t n = d + 1, lg = ilog2(n), A = jobs.size();
@@ -971,7 +977,9 @@ static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, b
     size_t ng = (A + G - 1) / G;
     if ((size_t)S > ng) S = (int)ng;
     const size_t ms = 7 * 4 * n;  // words of one member's vectors: c | z | s | s' | F_L | F_R | p_bar
-    const size_t per = G * ms + OPEN_AUX_WORDS;  // words of one slot's group
+    const bool accumulated = jobs[0].hs != nullptr;
+    const size_t hacc_words = accumulated ? hacc_stage_words(OPEN_MAX_GROUP, lg, HACC_TABLES) : 0;
+    const size_t per = G * ms + OPEN_AUX_WORDS + hacc_words;  // words of one slot's group
     size_t have = check_stage(ctx, (size_t)S, per * 8);
     if (have == 0) return HALO_OK;
     if ((size_t)S > have) S = (int)have;
@@ -1001,6 +1009,8 @@ static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, b
     auto h_consts = [&](int j) { return (OpenConst *)(h_tabs(j) + OPEN_MAX_GROUP * OPEN_TAB_WORDS); };
     auto h_outs = [&](int j) { return h_tabs(j) + OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS); };
     auto h_one = [&](int j) { return h_tabs(j) + OPEN_PIN_WORDS - 4; };
+    auto d_hacc = [&](int j) { return d_outs(j) + OPEN_MAX_GROUP * OPEN_OUT_WORDS; };
+    auto h_hacc = [&](int j) { return h_outs(j) + OPEN_MAX_GROUP * OPEN_OUT_WORDS; };
     auto out_of = [&](int j, size_t b) { return h_outs(j) + OPEN_OUT_WORDS * b; };
     auto s_cur = [&](int j) { return vec(j, fl[j].flip ? 3 : 2); };
     // the launches of one step of slot j's group on the slot's stream (the launch macro uses ctx->stream)
@@ -1068,7 +1078,17 @@ static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, b
             HALO_HIP(hipMemcpyAsync(d_tabs(j), h_tabs(j), OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS) * 8, hipMemcpyHostToDevice, st));
             int rc2 = HALO_OK;
             if (gen) rc2 = open_batch_rng(ctx, (int)f.cnt, d_consts(j), n, vec(j, 0), ms);  // p = PallasPoly::rand(d')
-            else
+            else if (accumulated) {  // p = h.get_poly() (acc.rs:85-94)
+                HAccMember hm[OPEN_MAX_GROUP];
+                for (size_t b = 0; b < f.cnt; ++b) {
+                    const AccHPolys &hs = *jobs[f.first + b].hs;
+                    hm[b].h0 = hs.h0;
+                    hm[b].count = hs.xis.size();
+                    hm[b].scales = hs.alphas.data() + 1;
+                    for (const std::vector<Fr> &x : hs.xis) hm[b].xis.push_back(x.data());
+                }
+                rc2 = h_accumulate_group(ctx, hm, f.cnt, lg, HACC_TABLES, h_hacc(j), d_hacc(j), vec(j, 0), ms);
+            } else
                 for (size_t b = 0; b < f.cnt; ++b)
                     HALO_HIP(hipMemcpyAsync(vec(j, 0) + b * ms, jobs[f.first + b].coeffs, n * 32, hipMemcpyHostToDevice, st));
             if (!rc2) rc2 = open_batch_eval(ctx, (int)f.cnt, vec(j, 0), ms, n, d_tabs(j), d_parts(j), d_outs(j));  // :135
@@ -1303,6 +1323,189 @@ static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const 
     }
     if (rng_state) *rng_state = rng.state;
     if (first >= 0) { set_error("member " + std::to_string(first) + ": " + errs[first]); return codes[first]; }
+    return HALO_OK;
+}
+
+// ------------------------------------------------------------------ acc::prover of k members at once
+// (halo_acc_prover_batch; acc.rs:190-220 per member, every member's blob, status and draws the loop's)
+//  1. the succinct half of every member, no randomness: all sum(counts) instances at once -- from kBatchVerifyMin instances on
+//     as halo_pcdl_succinct_check_batch runs them (transcripts on the host pool, the relations in one device launch), below on
+//     the pool.  A member is rejected exactly where halo_acc_prover rejects it ("d_i != d" first, then its succinct checks in
+//     instance order), and a rejected member draws nothing: the single call writes *rng_state only after common_subroutine.
+//  2. the survivors' draws in member order: h_0, omega, then (the stream is counter-based) the start of the open's q and w_bar.
+//  3. per member on the host pool: U_0 = h_0[0] G_0 + h_0[1] G_1, alpha and its powers, C = sum alpha^i U_i, z, C_bar = C +
+//     omega S, v = h(z).  These 3 + m scalar multiples per member (~27 us each on one thread, as the relation's 2 lg n + 1
+//     above) are spread over the pool: a second device launch with its round trip would cost more than it saves (the verifier
+//     batch folds such sums into a launch it needs anyway; here alpha hashes the drawn h_0, so they cannot ride the relations'
+//     launch).
+//  4. the hiding opens through open_batch_dev, their coefficients h(X) = h_0 + sum alpha^(i+1) h_i(X) accumulated on the device
+//     into the open's staging (h_accumulate_group), groups of up to 4 members over the idle slots.
+//  5. the blobs: C_bar | d | z | v | proof | h_0 | U_0 | omega.
+// *ran = false: the device form does not apply (size, staging) and nothing was written.
+struct ProverMember {
+    int rc = HALO_OK;
+    std::string err;
+    size_t first = 0, m = 0;  // its instances in the flat list
+    size_t r0 = 0;            // ... and the first of their check results
+    Fr w, z, v;
+    Point U0, C_bar;
+    AccHPolys hs;
+};
+static int acc_prover_batch_dev(halo_ctx *ctx, uint64_t state0, size_t d, const uint64_t *qs, const size_t *counts, size_t k, uint64_t *accs,
+                                const int *slots, int S, bool *ran, std::vector<int> &codes, std::vector<std::string> &errs, uint64_t *state_out) {
+    *ran = false;
+    const size_t n = d + 1, lg = ilog2(n), iw = instance_words(lg), aw = acc_words(lg);
+    constexpr uint64_t GAMMA = 0x9E3779B97F4A7C15ULL;
+    if (n < 2 || n > ctx->nofold_size || n > OPEN_MAX_N) return HALO_OK;
+    std::vector<ProverMember> mem(k);
+    size_t total = 0;
+    for (size_t j = 0; j < k; ++j) { mem[j].first = total; mem[j].m = counts[j]; total += counts[j]; }
+    // 1. the succinct half
+    bool all_reach = true;
+    for (size_t j = 0; j < k; ++j)
+        for (size_t i = 0; i < mem[j].m && !mem[j].rc; ++i) {
+            const uint64_t *q = qs + (mem[j].first + i) * iw;
+            if ((size_t)q[12] != d || q[22] != lg) { mem[j].rc = HALO_E_REJECT; mem[j].err = "d_i != d"; all_reach = false; }  // :169
+        }
+    std::vector<size_t> work;  // the instances whose checks run, and where their results go
+    for (size_t j = 0; j < k; ++j)
+        if (!mem[j].rc)
+            for (size_t i = 0; i < mem[j].m; ++i) work.push_back(mem[j].first + i);
+    std::vector<BatchCheck> res;
+    if (work.size() >= kBatchVerifyMin && ctx->batch_verify) {
+        std::vector<uint64_t> packed;  // (members that never reach their checks are left out: the rest, contiguous)
+        if (!all_reach) {
+            packed.resize(work.size() * iw);
+            for (size_t w = 0; w < work.size(); ++w) std::memcpy(&packed[w * iw], qs + work[w] * iw, iw * 8);
+        }
+        int rc = succinct_check_batch(ctx, d, all_reach ? qs : packed.data(), work.size(), res);
+        if (rc) return rc;
+    } else {
+        res.assign(work.size(), BatchCheck());
+        pool_run(work.size(), [&](size_t w) {
+            const uint64_t *q = qs + work[w] * iw;
+            res[w].rc = succinct_challenges(ctx, Point::load(q), d, Fr::load(q + 13), Fr::load(q + 17), q + 21, &res[w].st);
+            if (!res[w].rc) res[w].rc = succinct_relation(res[w].st, Fr::load(q + 13), Fr::load(q + 17), q + 21);
+            if (res[w].rc) res[w].err = halo_last_error();
+        });
+    }
+    {
+        size_t w = 0;
+        for (size_t j = 0; j < k; ++j) {
+            ProverMember &M = mem[j];
+            if (M.rc) continue;
+            M.r0 = w;
+            for (size_t i = 0; i < M.m; ++i, ++w) {
+                if (res[w].rc && !M.rc) { M.rc = res[w].rc; M.err = res[w].err; }  // :158-170 in instance order
+                if (!M.rc) M.hs.xis.push_back(res[w].st.xis);
+            }
+        }
+    }
+    // 2. the draws, in member order
+    host::Rng rng{state0};
+    std::vector<OpenJob> jobs;
+    jobs.reserve(k);
+    for (size_t j = 0; j < k; ++j) {
+        ProverMember &M = mem[j];
+        if (M.rc) continue;
+        M.hs.lg_n = lg;
+        M.hs.h0[0] = rng.scalar();  // :192
+        M.hs.h0[1] = rng.scalar();
+        M.w = rng.scalar();         // :198
+        OpenJob jb;
+        jb.idx = j;
+        jb.hiding = true;
+        jb.hs = &M.hs;
+        jb.deg = M.m ? d : (M.hs.h0[1].is_zero() ? 0 : 1);
+        if (jb.deg == 0) { M.rc = HALO_E_ASSERT; M.err = "open: hiding needs p.degree() >= 1"; continue; }  // pcdl_open_dev: before its draws
+        jb.w = M.w;
+        jb.s_q = rng.state;
+        rng.state += 4 * (uint64_t)jb.deg * GAMMA;
+        jb.w_bar = rng.scalar();
+        jb.proof = accs + j * aw + 21;
+        jobs.push_back(jb);
+    }
+    // 3. U_0, alpha, C, z, C_bar, v
+    if (!jobs.empty()) {
+        uint64_t g01[16];
+        int rc = halo_ctx_read_bases(ctx, 0, 2, g01);
+        if (rc) return rc;
+        const std::vector<Point> G01{Point::load_affine(g01), Point::load_affine(g01 + 8)};
+        pool_run(jobs.size(), [&](size_t a) {
+            OpenJob &jb = jobs[a];
+            ProverMember &M = mem[jb.idx];
+            M.U0 = host::small_msm(G01, std::vector<Fr>{M.hs.h0[0], M.hs.h0[1]});  // :195
+            std::vector<Point> Us{M.U0};
+            for (size_t i = 0; i < M.m; ++i) Us.push_back(res[M.r0 + i].st.U);
+            set_alphas(&M.hs);                                               // :173
+            const Point C = host::small_msm(Us, M.hs.alphas);                // :178
+            M.z = rho1_C_alpha(C, M.hs.alpha);                               // :181
+            M.C_bar = (C + public_s_table().mul(M.w)).normalized();          // :184
+            M.v = M.hs.eval(M.z);                                            // :205
+            jb.C = M.C_bar;
+            jb.z = M.z;
+        });
+        // 4. the opens (:209)
+        for (OpenJob &jb : jobs) {
+            std::memset(accs + jb.idx * aw, 0, 8 * aw);
+            jb.proof[1] = lg;
+        }
+        rc = open_batch_dev(ctx, d, jobs, false, slots, S, ran);
+        if (rc) return rc;
+        if (!*ran) return HALO_OK;
+    }
+    *ran = true;
+    // 5. the blobs and the outcomes
+    for (OpenJob &jb : jobs) {
+        ProverMember &M = mem[jb.idx];
+        if (jb.rc) { M.rc = jb.rc; M.err = jb.err; continue; }
+        uint64_t *acc = accs + jb.idx * aw, *piV = acc + iw;
+        M.C_bar.store(acc);
+        acc[12] = d;
+        M.z.store(acc + 13);
+        M.v.store(acc + 17);
+        M.hs.h0[0].store(piV);
+        M.hs.h0[1].store(piV + 4);
+        M.U0.store_normalized(piV + 8);
+        M.w.store(piV + 20);
+    }
+    for (size_t j = 0; j < k; ++j) { codes[j] = mem[j].rc; errs[j] = mem[j].err; }
+    *state_out = rng.state;
+    return HALO_OK;
+}
+
+// halo_acc_prover_batch after its argument checks: the device form, or, where it does not apply, the loop itself
+static int acc_prover_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *qs, const size_t *counts, size_t k, uint64_t *accs,
+                                  int *status) {
+    const size_t lg = ilog2(d + 1), iw = instance_words(lg), aw = acc_words(lg);
+    int slots[HALO_SLOTS], S = 0;
+    for (int s = 0; s < HALO_SLOTS; ++s)
+        if (!ctx->wss[s].in_flight && ctx->wss[s].lent_from < 0 && !ctx->fan[s].active) slots[S++] = s;
+    if (!S) { set_error("prover_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
+    std::vector<int> codes(k, HALO_OK);
+    std::vector<std::string> errs(k);
+    uint64_t state = rng_state ? *rng_state : 0;
+    bool ran = false;
+    int rc = acc_prover_batch_dev(ctx, state, d, qs, counts, k, accs, slots, S, &ran, codes, errs, &state);
+    if (rc) return rc;
+    if (!ran) {  // one member at a time through the single prover, from the same states
+        size_t first = 0;
+        for (size_t j = 0; j < k; first += counts[j], ++j) {
+            rc = halo_acc_prover(ctx, &state, d, qs + first * iw, counts[j], accs + j * aw);
+            if (rc == HALO_E_ASSERT || rc == HALO_E_REJECT) { codes[j] = rc; errs[j] = halo_last_error(); }
+            else if (rc) return rc;
+        }
+    }
+    int first_bad = -1;
+    for (size_t j = 0; j < k; ++j) {
+        if (codes[j]) {
+            std::memset(accs + j * aw, 0, 8 * aw);
+            if (first_bad < 0) first_bad = (int)j;
+        }
+        if (status) status[j] = codes[j];
+    }
+    if (rng_state) *rng_state = state;
+    if (first_bad >= 0) { set_error("member " + std::to_string(first_bad) + ": " + errs[first_bad]); return codes[first_bad]; }
     return HALO_OK;
 }
 
@@ -1651,6 +1854,23 @@ int halo_acc_prover(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t
     w.store(piV + 20);
     if (rng_state) *rng_state = rng.state;
     return rc;
+}
+
+// acc::prover of k members at once (see acc_prover_batch_dev).  The argument checks are the whole call's and come before any work.
+int halo_acc_prover_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *instances, const size_t *counts, size_t k, uint64_t *accs_out,
+                          int *status) {
+    HALO_CTX2(ctx);
+    if (k && (!accs_out || !counts)) { set_error("prover_batch: null pointer"); return HALO_E_ARG; }
+    size_t total = 0;
+    for (size_t j = 0; j < k; ++j) {
+        if (counts[j] > ((size_t)1 << 32) - total) { set_error("prover_batch: too many instances"); return HALO_E_ARG; }
+        total += counts[j];
+    }
+    if (total && !instances) { set_error("prover_batch: null pointer"); return HALO_E_ARG; }
+    if (!is_pow2(d + 1)) return fail_assert("prover: d + 1 is not a power of two");
+    if (d + 1 > ctx->n) return fail_assert("prover: d > D");
+    if (k == 0) return HALO_OK;
+    return acc_prover_batch_entry(ctx, rng_state, d, instances, counts, k, accs_out, status);
 }
 
 // acc.rs:223-243

@@ -321,6 +321,27 @@ int halo_acc_decider_batch(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t
  * multi-device context runs the batch on devices[0]. */
 int halo_acc_verifier_batch(halo_ctx *ctx, size_t d, const uint64_t *instances, const size_t *counts, size_t k,
                             const uint64_t *accs, int *status /*nullable*/);
+/* acc::prover (acc.rs:190-220) of k members at once.  Layout as halo_acc_verifier_batch: counts[j] Instances for member j (0
+ * allowed), member j's right after member j - 1's, at stride halo_instance_words(lg(d+1)); accs_out = k Accumulator blobs at
+ * stride halo_accumulator_words(lg(d+1)).
+ * - Same results as a loop: every succeeded member's blob, every status[j] and the final *rng_state equal k calls of
+ *   halo_acc_prover in member order with the same rng_state pointer (NULL: state 0), continuing after a member that fails.  A
+ *   member fails exactly where the single call fails (every d_i / proof length first, "d_i != d", then the succinct checks in
+ *   instance order); such a member draws nothing, as the single call writes *rng_state only after its instances were accepted,
+ *   and the next member starts from the same state.  The one difference from the loop: a failed member's blob is zero-filled.
+ *   Returns 0 if every member succeeded, else the first non-zero status in member order, halo_last_error() = "member j:
+ *   <the single call's message>".
+ * - Before any work (status, *rng_state and accs_out not written): a null ctx, k > 0 with null counts or accs_out, or a non-zero
+ *   total with null instances: HALO_E_ARG; d + 1 not a power of two or above the key: HALO_E_ASSERT with the single call's
+ *   messages.  k = 0: HALO_OK, nothing touched.  No idle slot: HALO_E_ARG.  A device failure returns its code.
+ * - Where the hiding open takes its no-fold form (2 <= d + 1 <= the no-fold size, 2^14 by default): the succinct half of all
+ *   instances at once (from 64 instances on in one device launch, as halo_pcdl_succinct_check_batch), the members' sums on a
+ *   host thread pool, then groups of up to 4 members through the launches of halo_pcdl_open_batch, their polynomials h(X) =
+ *   h_0 + sum alpha^(i+1) h_i(X) accumulated on the device straight into the open's state.  Elsewhere, and without the staging
+ *   memory (optional memory, halo_set_memory_budget), the members run one at a time as halo_acc_prover runs them, with the same
+ *   results.  A multi-device context runs the batch on devices[0]. */
+int halo_acc_prover_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *instances, const size_t *counts, size_t k,
+                          uint64_t *accs_out, int *status /*nullable*/);
 /* benches/acc.rs:15-29 random_instance: the workload generator of the reference's benchmark */
 int halo_random_instance(halo_ctx *ctx, uint64_t *rng_state, size_t d, uint64_t *instance_out);
 

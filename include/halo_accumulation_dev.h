@@ -22,9 +22,9 @@ extern "C" {
  * "shard_fail_rank" + "shard_fail_at" (the rank with that offset fails locally before collective number `at` of a sharded open:
  * 0 = the share of p(z), 1.. = the rounds, then the tail; at = -2: in a sharded check; at = -3: the rank with that `rank`
  * before the collective of halo_msm_sharded / _dev_sharded / _end_sharded), "batch_stage_fail" (value != 0: the staging of
- * halo_pcdl_check_batch / halo_acc_decider_batch / halo_pcdl_open_batch / halo_random_instance_batch is refused, as over the
+ * halo_pcdl_check_batch / halo_acc_decider_batch / halo_pcdl_open_batch / halo_random_instance_batch / halo_acc_prover_batch is refused, as over the
  * memory budget: one member at a time; halo_acc_verifier_batch: its sums on the host pool), "check_batch_group" (members per MSM launch of the check batch, 1..8; 0: the measured
- * default), "open_batch_group" (members per launch of the open batch, 1..4; 0: the measured default), "verifier_batch_min" (relations
+ * default), "open_batch_group" (members per launch of the open and prover batches, 1..4; 0: the measured default), "verifier_batch_min" (relations
  * from which halo_acc_verifier_batch runs its sums on the device, >= 1; 0: the measured default), "reset" (all off). */
 int halo_dev_hook(const char *name, long value);
 /* What the library read from the environment at its first use (csrc/tuning.hip), by field: "host_split_set", "host_pieces", "host_split0".."host_split3",
@@ -42,6 +42,14 @@ int halo_bench_fr_kernel(halo_ctx *ctx, int which, size_t n, int reps);
  * Montgomery words, out = m x 2^lg_n x 4 words; member b's block equals halo_h_coeffs(xis_b, lg_n).  2^lg_n <= the context's
  * size (64 at least). */
 int halo_dev_h_coeffs_batch(halo_ctx *ctx, const uint64_t *xis, size_t m, size_t lg_n, uint64_t *out);
+
+/* The prover batch's accumulated polynomials (k_h_tables with scales + k_h_accumulate_batch) on their own: member j of `members`
+ * has counts[j] polynomials h_i (0 allowed), given one after the other in xis ((lg_n + 1) x 4 Montgomery words each) and alphas
+ * (their scales, 4 words each), and h0s[8 j ..] = its two h_0 coefficients.  out = members x 2^lg_n x 4 words: member j's block is
+ * h_0 + sum_i alphas_i h_i(X).  max_tables: polynomials per pass (0: all in one pass; fewer than a member brings: the later
+ * passes add to what is there).  1 <= lg_n, 2^lg_n <= the context's size (64 at least). */
+int halo_dev_h_accumulate_batch(halo_ctx *ctx, const uint64_t *h0s, const uint64_t *xis, const uint64_t *alphas, const size_t *counts,
+                                size_t members, size_t lg_n, size_t max_tables, uint64_t *out);
 
 /* replay cached hipGraphs of the MSM launch sequence when the same shape repeats (default on) */
 int halo_set_graphs(halo_ctx *ctx, int on);  /* also: environment HALO_GRAPHS=0 at context creation; HALO_TRACE=1 logs every launch */

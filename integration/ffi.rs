@@ -53,6 +53,9 @@ extern "C" {
     pub fn halo_acc_decider_batch(ctx: *mut HaloCtx, d: usize, accs: *const u64, m: usize, status: *mut c_int) -> c_int;
     // acc::verifier of k accumulators at once (counts[j] instances for accs[j]; status may be null)
     pub fn halo_acc_verifier_batch(ctx: *mut HaloCtx, d: usize, instances: *const u64, counts: *const usize, k: usize, accs: *const u64, status: *mut c_int) -> c_int;
+    // acc::prover of k members at once (counts[j] instances for member j; rng_state and status may be null)
+    pub fn halo_acc_prover_batch(ctx: *mut HaloCtx, rng_state: *mut u64, d: usize, instances: *const u64, counts: *const usize, k: usize,
+                                 accs_out: *mut u64, status: *mut c_int) -> c_int;
     // pcdl::open / random_instance of m members at once (ws, status may be null)
     pub fn halo_pcdl_open_batch(ctx: *mut HaloCtx, rng_state: *mut u64, d: usize, coeffs: *const u64, m: usize, cs: *const u64, zs: *const u64,
                                 ws: *const u64, proofs_out: *mut u64, status: *mut c_int) -> c_int;
