@@ -138,6 +138,8 @@ _SIGS = {
     "halo_rng_scalars_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.c_void_p]),
 }
 
+u32p = C.POINTER(C.c_uint32)
+
 # libhalo_hip_dev.so (include/halo_accumulation_dev.h): experiment knobs, primitive test hooks, fault injectors.  Loaded only
 # when one of these is called -- tests and tools/; the product path (pcdl.py, acc.py, sharded.py, bench.py's timed legs) never does.
 _DEV_SIGS = {
@@ -161,6 +163,8 @@ _DEV_SIGS = {
     "halo_dev_h_coeffs_batch": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_size_t, u64p]),
     "halo_dev_h_accumulate_batch": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.c_size_t, u64p]),
     "halo_dev_small_msm_seg": (C.c_int, [C.c_void_p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, u64p]),
+    "halo_test_lazy_field_op": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t, u32p]),
+    "halo_test_lazy_point_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, u32p, u32p, C.c_size_t, u32p]),
 }
 
 
@@ -535,6 +539,23 @@ class Context:
         b = None if b is None else np.ascontiguousarray(b, dtype=np.uint64)
         out = np.zeros_like(a)
         check(self.lib.halo_test_point_op(self.h, op, ptr(a), ptr(b), a.shape[0], ptr(out)))
+        return out
+
+    # ---- raw-limb hooks (csrc/dev_lazy_ops.hpp): native operands whose limbs the caller chooses
+    def lazy_field_op(self, op, a):
+        """a: (n, 40) uint32, four operands of 9 limbs + pad -> (n, 10) uint32"""
+        a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, 40)
+        out = np.zeros((a.shape[0], 10), dtype=np.uint32)
+        check(self.lib.halo_test_lazy_field_op(self.h, op, a.ctypes.data_as(u32p), a.shape[0], out.ctypes.data_as(u32p)))
+        return out
+
+    def lazy_point_op(self, op, a, b, quad=False):
+        """a, b: (n, 40) uint32 native points -> (n, 40) uint32; quad: the quad-parallel form of curve_quad.hpp"""
+        a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, 40)
+        b = np.ascontiguousarray(b, dtype=np.uint32).reshape(-1, 40)
+        assert a.shape == b.shape
+        out = np.zeros_like(a)
+        check(self.lib.halo_test_lazy_point_op(self.h, op, int(quad), a.ctypes.data_as(u32p), b.ctypes.data_as(u32p), a.shape[0], out.ctypes.data_as(u32p)))
         return out
 
 

@@ -12,6 +12,7 @@
 
 #include "../../include/halo_accumulation_dev.h"
 #include "curve_quad.hpp"
+#include "dev_lazy_ops.hpp"
 #include "internal.hpp"
 
 namespace halo {
@@ -115,6 +116,47 @@ __global__ __launch_bounds__(256) void k_test_point_quad(int op, const uint64_t 
     if (op == 5) x = xyzz_dbl_quad(x, ql);
     else xyzz_add_quad(x, y, ql);
     if (live && ql == 0) xyzz_store_jac_words(out + 12 * (size_t)i, x);
+}
+
+// ---- raw-limb hooks (dev_lazy_ops.hpp): the caller chooses the representative of every operand, one case per lane
+// (*unknown is set where the table of dev_lazy_ops.hpp does not know the operation: the switch there is the only list)
+__global__ __launch_bounds__(256) void k_lazy_field(int op, const uint32_t *in, uint32_t n, uint32_t *out, uint32_t *unknown) {
+    uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (!lazy_field_op(op, in + (size_t)LAZY_FIELD_IN * i, out + (size_t)LAZY_SLOT * i)) *unknown = 1u;
+}
+__global__ __launch_bounds__(256) void k_lazy_point(int op, const uint32_t *a, const uint32_t *b, uint32_t n, uint32_t *out, uint32_t *unknown) {
+    uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    if (!lazy_point_op(op, a + (size_t)LAZY_POINT_WORDS * i, b + (size_t)LAZY_POINT_WORDS * i, out + (size_t)LAZY_POINT_WORDS * i)) *unknown = 1u;
+}
+// the quad-parallel forms of curve_quad.hpp over the same operands, one case per 4 lanes (neighbouring cases share a wave):
+// xyzz_add_quad, xyzz_dbl_quad, jac_madd_quad (beta^e = 1; an affine infinity is a dead addition) and jac_dbl_quad.  Every
+// lane of a quad holds the result; lane (case mod 4) stores it, so a broadcast that reached only lane 0 would show.
+__global__ __launch_bounds__(256) void k_lazy_point_quad(int op, const uint32_t *a, const uint32_t *b, uint32_t n, uint32_t *out) {
+    uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    uint32_t i = t >> 2;
+    int ql = (int)(t & 3);
+    bool live = i < n;
+    if (!live) i = n - 1;  // whole quads, whole waves: the DPP moves read every lane
+    const uint32_t *pa = a + (size_t)LAZY_POINT_WORDS * i, *pb = b + (size_t)LAZY_POINT_WORDS * i;
+    uint32_t *o = out + (size_t)LAZY_POINT_WORDS * i;
+    bool store = live && ql == (int)(i & 3);
+    if (op == LZP_XYZZ_ADD || op == LZP_XYZZ_DBL) {
+        XyzzN x = xyzz_load(pa);
+        if (op == LZP_XYZZ_ADD) xyzz_add_quad(x, xyzz_load(pb), ql);
+        else x = xyzz_dbl_quad(x, ql);
+        if (store) xyzz_store(o, x);
+    } else {
+        JacN p = lz_jac(pa);
+        if (op == LZP_JAC_MADD) {
+            AffN q = aff_load(pb);
+            p = jac_madd_quad(p, q.x, q.y, fq_widen<2>(fq_one()), !aff_is_inf(q), ql);
+        } else {
+            p = jac_dbl_quad(p, ql);
+        }
+        if (store) lz_put_jac(o, p);
+    }
 }
 
 int test_field_op(halo_ctx *ctx, int field, int op, const uint64_t *d_a, const uint64_t *d_b, size_t n, uint64_t *d_out) {
@@ -384,6 +426,57 @@ int halo_test_point_op(halo_ctx *ctx, int op, const uint64_t *a_jac, const uint6
     if (rc) return rc;
     for (size_t i = 0; i < n; ++i) host::Point::load(out_jac + 12 * i).store_normalized(out_jac + 12 * i);
     return HALO_OK;
+}
+
+// n cases of one operation of dev_lazy_ops.hpp over caller-chosen limbs: temporary device buffers of this call only, every
+// copy and the launch in order on the context's stream.  kind 0: field (no second operand), 1: point, 2: point, quad forms.
+static int lazy_run(halo_ctx *ctx, int kind, int op, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out) {
+    const size_t in_words = n * (kind == 0 ? (size_t)LAZY_FIELD_IN : (size_t)LAZY_POINT_WORDS);
+    const size_t out_words = n * (kind == 0 ? (size_t)LAZY_SLOT : (size_t)LAZY_POINT_WORDS);
+    const size_t b_words = b ? in_words : 0;
+    uint32_t *d = nullptr, unknown = 0;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d, (in_words + b_words + out_words + 4) * 4));
+    uint32_t *d_a = d, *d_b = d_a + in_words, *d_out = d_b + b_words, *d_unknown = d_out + out_words;  // (every part a multiple of 16 bytes)
+    hipError_t e = hipMemcpyAsync(d_a, a, in_words * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && b) e = hipMemcpyAsync(d_b, b, b_words * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_unknown, 0, 16, ctx->stream);
+    int rc = e == hipSuccess ? HALO_OK : hip_fail(e, "hipMemcpyAsync");
+    if (!rc) {
+        dim3 block(256), grid((unsigned)((n + 255) / 256)), qgrid((unsigned)((4 * n + 255) / 256));
+        if (kind == 0) HALO_LAUNCH(ctx, "k_lazy_field", k_lazy_field, grid, block, 0, op, d_a, (uint32_t)n, d_out, d_unknown);
+        else if (kind == 1) HALO_LAUNCH(ctx, "k_lazy_point", k_lazy_point, grid, block, 0, op, d_a, d_b, (uint32_t)n, d_out, d_unknown);
+        else HALO_LAUNCH(ctx, "k_lazy_point_quad", k_lazy_point_quad, qgrid, block, 0, op, d_a, d_b, (uint32_t)n, d_out);
+        if ((e = hipGetLastError()) != hipSuccess) rc = hip_fail(e, "launch");
+    }
+    if (!rc && (e = hipMemcpyAsync(out, d_out, out_words * 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+    if (!rc && (e = hipMemcpyAsync(&unknown, d_unknown, 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+    e = hipStreamSynchronize(ctx->stream);  // (also on failure: nothing of this call may be in flight when its buffers go)
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    (void)hipFree(d);
+    if (!rc && unknown) { set_error("test_lazy_op: unknown operation"); rc = HALO_E_ARG; }
+    return rc;
+}
+
+int halo_test_lazy_field_op(halo_ctx *ctx, int op, const uint32_t *in, size_t n, uint32_t *out) {
+    HALO_CTX(ctx);
+    if (n == 0) return HALO_OK;
+    if (!in || !out) { set_error("test_lazy_field_op: null pointer"); return HALO_E_ARG; }
+    if (n > ((size_t)1 << 22)) { set_error("test_lazy_field_op: at most 2^22 cases"); return HALO_E_ARG; }
+    return lazy_run(ctx, 0, op, in, nullptr, n, out);
+}
+
+int halo_test_lazy_point_op(halo_ctx *ctx, int op, int quad, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out) {
+    HALO_CTX(ctx);
+    if (n == 0) return HALO_OK;
+    if (!a || !b || !out) { set_error("test_lazy_point_op: null pointer"); return HALO_E_ARG; }
+    if (n > ((size_t)1 << 20)) { set_error("test_lazy_point_op: at most 2^20 cases"); return HALO_E_ARG; }
+    if (op < 0 || op >= LZP_COUNT) { set_error("test_lazy_point_op: unknown operation"); return HALO_E_ARG; }
+    if (quad && !(op == LZP_XYZZ_ADD || op == LZP_XYZZ_DBL || op == LZP_JAC_MADD || op == LZP_JAC_DBL)) {
+        set_error("test_lazy_point_op: the quad forms are xyzz_add, xyzz_dbl, jac_madd and jac_dbl");
+        return HALO_E_ARG;
+    }
+    return lazy_run(ctx, quad ? 2 : 1, op, a, b, n, out);
 }
 
 }  // extern "C"

@@ -30,7 +30,16 @@ struct FrCfg {  // ark_pallas::Fr (group.rs:9 PallasScalar)
     static constexpr uint32_t PM2[8] = {0xffffffffu, 0x8c46eb20u, 0x0994a8ddu, 0x224698fcu, 0u, 0u, 0u, 0x40000000u};
 };
 
+// Both macros may be defined before this header is included: tests/native/lazy_field_host.cpp compiles the lazy fields and
+// the group law for the CPU (HALO_DEV = inline, HALO_PIN_VGPR = nothing) to run them under ASan + UBSan.
+#ifndef HALO_DEV
 #define HALO_DEV __device__ __forceinline__
+#endif
+// An empty asm with a "+v" operand: the value is pinned in a vector register at this point of the program, which stops the
+// compiler from folding or reassociating across it (fq29.hpp says at each use what that buys).  No instruction is emitted.
+#ifndef HALO_PIN_VGPR
+#define HALO_PIN_VGPR(x) asm volatile("" : "+v"(x))
+#endif
 
 HALO_DEV Fe fe_zero() {
     Fe r;

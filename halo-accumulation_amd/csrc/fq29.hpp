@@ -9,8 +9,8 @@
 // products (each < 2^58) fit a 64-bit accumulator without any carry, so a column is a plain
 // chain of v_mad_u64_u32: ~230 instructions per product, and field additions are 9 plain adds.
 //
-// Lazy values.  Fq<K> holds a value < K*p (not reduced mod p) with limbs 0..7 < 2^29 and a
-// small top limb.  Because R' = 2^261 = 128 * 2^254, a product of operands < Ka*p and < Kb*p
+// Lazy values.  Fq<K> holds a value < K*p (not reduced mod p; <= K*p after fq_neg, see there) with limbs
+// 0..7 < 2^29 and a small top limb.  Because R' = 2^261 = 128 * 2^254, a product of operands < Ka*p and < Kb*p
 // comes out < (Ka*Kb/128 + 1) p, so with Ka*Kb <= 120 no conditional subtraction is ever needed
 // and the result is an Fq<2>.  K is a template parameter: every bound in the group law is
 // checked by the compiler (static_assert), not by hand.
@@ -100,7 +100,7 @@ HALO_DEV Fq<2> fq_mul(const Fq<Ka> &a, const Fq<Kb> &b) {
     static_assert(Ka * Kb <= 120, "Montgomery product bound: Ka*Kb/128 + 1 must stay < 2");
     uint64_t c[18];
     uint64_t k29 = M29;
-    asm volatile("" : "+v"(k29));  // a register pair, so it is the free addend of each column's first mad
+    HALO_PIN_VGPR(k29);  // a register pair, so it is the free addend of each column's first mad
 #pragma unroll
     for (int k = 0; k < 17; k++) {
         uint64_t acc = k < 9 ? k29 : 0;  // 2^29 - 1 in the columns the reduction consumes
@@ -110,14 +110,14 @@ HALO_DEV Fq<2> fq_mul(const Fq<Ka> &a, const Fq<Kb> &b) {
             int j = k - i;
             if (j >= 0 && j < 9) {
                 acc = (uint64_t)a.v[i] * b.v[j] + acc;
-                if (first) { asm volatile("" : "+v"(acc)); first = false; }  // keep k29 as this mad's addend (no reassociation)
+                if (first) { HALO_PIN_VGPR(acc); first = false; }  // keep k29 as this mad's addend (no reassociation)
             }
         }
         c[k] = acc;
     }
     c[17] = 0;
     uint32_t p8 = P29::L[8];
-    asm volatile("" : "+v"(p8));  // keep m * 2^22 on v_mad_u64_u32 (5.3 cycles) instead of a 64-bit shift + add (9.2)
+    HALO_PIN_VGPR(p8);  // keep m * 2^22 on v_mad_u64_u32 (5.3 cycles) instead of a 64-bit shift + add (9.2)
     // Step i: t = c[i] + carry, m = -t mod 2^29, carry' = (t + m) >> 29 = ceil(t / 2^29).  The low
     // columns were started at 2^29 - 1 (see above), so here t already holds t + 2^29 - 1: the carry is
     // a plain shift and m = ~t mod 2^29 -- no "c[i] += m" and no zero-extension of m.
@@ -152,7 +152,7 @@ HALO_DEV Fq<2> fq_sqr(const Fq<Ka> &a) {
     for (int i = 0; i < 9; i++) d[i] = a.v[i] << 1;
     uint64_t c[18];
     uint64_t k29 = M29;
-    asm volatile("" : "+v"(k29));
+    HALO_PIN_VGPR(k29);
 #pragma unroll
     for (int k = 0; k < 17; k++) {
         uint64_t acc = k < 9 ? k29 : 0;
@@ -162,18 +162,18 @@ HALO_DEV Fq<2> fq_sqr(const Fq<Ka> &a) {
             int j = k - i;
             if (j >= 0 && j < 9 && i < j) {
                 acc = (uint64_t)d[i] * a.v[j] + acc;
-                if (first) { asm volatile("" : "+v"(acc)); first = false; }
+                if (first) { HALO_PIN_VGPR(acc); first = false; }
             }
             if (j >= 0 && j < 9 && i == j) {
                 acc = (uint64_t)a.v[i] * a.v[i] + acc;
-                if (first) { asm volatile("" : "+v"(acc)); first = false; }
+                if (first) { HALO_PIN_VGPR(acc); first = false; }
             }
         }
         c[k] = acc;
     }
     c[17] = 0;
     uint32_t p8 = P29::L[8];
-    asm volatile("" : "+v"(p8));  // keep m * 2^22 on v_mad_u64_u32 (5.3 cycles) instead of a 64-bit shift + add (9.2)
+    HALO_PIN_VGPR(p8);  // keep m * 2^22 on v_mad_u64_u32 (5.3 cycles) instead of a 64-bit shift + add (9.2)
     // Step i: t = c[i] + carry, m = -t mod 2^29, carry' = (t + m) >> 29 = ceil(t / 2^29).  The low
     // columns were started at 2^29 - 1 (see above), so here t already holds t + 2^29 - 1: the carry is
     // a plain shift and m = ~t mod 2^29 -- no "c[i] += m" and no zero-extension of m.
@@ -208,7 +208,7 @@ HALO_DEV Fq<2> fq_mul_add_mul(const Fq<Ka> &a, const Fq<Kb> &b, const Fq<Kc> &c2
     static_assert(Ka * Kb + Kc * Kd <= 120, "fused product bound: (KaKb + KcKd)/128 + 1 must stay < 2");
     uint64_t c[18];
     uint64_t k29 = M29;
-    asm volatile("" : "+v"(k29));
+    HALO_PIN_VGPR(k29);
 #pragma unroll
     for (int k = 0; k < 17; k++) {
         uint64_t acc = k < 9 ? k29 : 0;
@@ -224,7 +224,7 @@ HALO_DEV Fq<2> fq_mul_add_mul(const Fq<Ka> &a, const Fq<Kb> &b, const Fq<Kc> &c2
     }
     c[17] = 0;
     uint32_t p8 = P29::L[8];
-    asm volatile("" : "+v"(p8));
+    HALO_PIN_VGPR(p8);
     uint64_t carry = 0;
 #pragma unroll
     for (int i = 0; i < 9; i++) {
@@ -296,7 +296,11 @@ HALO_DEV Fq<k * Ka> fq_muls(const Fq<Ka> &a) {
     r.v[8] = a.v[8] * (uint32_t)k + carry;
     return r;
 }
-// Kc*p - a
+// Kc*p - a.  The one operation whose result can EQUAL its bound: fq_neg<Kc>(0) is Kc*p itself, so a negated value is
+// <= Kc*p where every other Fq<K> is < K*p.  Its consumers are the fused products (fq_mul_add_mul: the other factor of the
+// negated operand is strictly below its bound, so a*b + c*d stays strictly below (Ka*Kb + Kc*Kd) p^2 and the static_assert
+// counts Kc as it stands) and the sign flip of a stored affine y (aff_cneg, aff_store).  Do not pass it to fq_is_zero_modp:
+// Kc*p has limb 0 = Kc, which the limb-0 shortcut takes for "not a multiple".  tests/test_host_sanitizers.py lists the uses.
 template <int Kc, int Ka>
 HALO_DEV Fq<Kc> fq_neg(const Fq<Ka> &a) {
     static_assert(Ka <= Kc, "negation constant too small");

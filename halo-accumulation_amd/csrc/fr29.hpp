@@ -33,7 +33,7 @@ struct Fs {
 // The low columns start at 2^29 - 1 so that the carry of step i is a plain shift (see fq29.hpp fq_mul).
 HALO_DEV void fs_reduce_columns(uint64_t (&c)[18], uint32_t (&out)[9]) {
     uint32_t p8 = R29::L[8];
-    asm volatile("" : "+v"(p8));  // m * 2^22 stays a v_mad_u64_u32
+    HALO_PIN_VGPR(p8);  // m * 2^22 stays a v_mad_u64_u32
     uint64_t carry = 0;
 #pragma unroll
     for (int i = 0; i < 9; i++) {
@@ -59,7 +59,7 @@ HALO_DEV Fs<2> fs_mul(const Fs<Ka> &a, const Fs<Kb> &b) {
     static_assert(Ka * Kb <= 120, "Montgomery product bound: Ka*Kb/128 + 1 must stay < 2");
     uint64_t c[18];
     uint64_t k29 = M29;
-    asm volatile("" : "+v"(k29));
+    HALO_PIN_VGPR(k29);
 #pragma unroll
     for (int k = 0; k < 17; k++) {
         uint64_t acc = k < 9 ? k29 : 0;
@@ -69,7 +69,7 @@ HALO_DEV Fs<2> fs_mul(const Fs<Ka> &a, const Fs<Kb> &b) {
             int j = k - i;
             if (j >= 0 && j < 9) {
                 acc = (uint64_t)a.v[i] * b.v[j] + acc;
-                if (first) { asm volatile("" : "+v"(acc)); first = false; }
+                if (first) { HALO_PIN_VGPR(acc); first = false; }
             }
         }
         c[k] = acc;
@@ -85,7 +85,7 @@ HALO_DEV Fs<2> fs_mul_add_mul(const Fs<Ka> &a, const Fs<Kb> &b, const Fs<Kc> &c2
     static_assert(Ka * Kb + Kc * Kd <= 120, "fused product bound");
     uint64_t c[18];
     uint64_t k29 = M29;
-    asm volatile("" : "+v"(k29));
+    HALO_PIN_VGPR(k29);
 #pragma unroll
     for (int k = 0; k < 17; k++) {
         uint64_t acc = k < 9 ? k29 : 0;
@@ -132,6 +132,11 @@ HALO_DEV Fs<Kn> fs_widen(const Fs<K> &a) {
     return r;
 }
 // value < K r (K <= 60) -> value < 2 r: subtract (q - 1) r with q = floor(v / 2^254)
+// The bound K is what the types PROVE, not where the arithmetic stops working: q is read from the value, and the carries of
+// fs_add (int32 limb sums: top limb below 2^31) and the columns of fs_mul hold for any value below about 500 r.  An
+// accumulation that forgot its fs_tighten would therefore compute the same results until a lane had summed some 250 products --
+// no test of the kernels at their sizes can see that.  What catches it is the compiler: the sum is an Fs<Ka + Kb>, not the
+// Fs<2> of the accumulator, and fs_add refuses Ka + Kb > 60.  Keep the accumulators typed, never copy limbs across bounds.
 template <int K>
 HALO_DEV Fs<2> fs_tighten(const Fs<K> &a) {
     static_assert(K <= 60, "tighten: bound too large");

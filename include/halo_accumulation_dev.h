@@ -108,6 +108,17 @@ int halo_test_field_op(halo_ctx *ctx, int field /*0 Fq, 1 Fr*/, int op /*0 mul,1
  * 4, 5, 6: the quad-parallel forms (curve_quad.cuh): a + b, 2a, a + b with every fourth b replaced by a */
 int halo_test_point_op(halo_ctx *ctx, int op, const uint64_t *a_jac, const uint64_t *b, size_t n, uint64_t *out_jac);
 
+/* ---- raw-limb hooks (csrc/dev_lazy_ops.hpp): one operation of the lazy radix-2^29 fields or of the group law per case, over
+ * NATIVE operands whose limbs the caller chooses -- any representative below the declared bound K*p, which the word forms
+ * above cannot produce.  The tables of operations and bounds are in csrc/dev_lazy_ops.hpp and tests/lazy_cases.py.
+ * Field: in = n x 40 words (four operands of 9 limbs + pad), out = n x 10 words (raw limbs; a predicate is 0 / 1 in word 0;
+ * an 8-word form uses words 0..7). */
+int halo_test_lazy_field_op(halo_ctx *ctx, int op, const uint32_t *in, size_t n, uint32_t *out);
+/* Point: a, b, out = n x 40 words each: XYZZ as x | y | zz | zzz, Jacobian as x | y | z, affine as x | y (10 words per
+ * coordinate).  quad != 0: the quad-parallel form of curve_quad.hpp (operations 0 xyzz_add, 2 xyzz_dbl, 3 jac_madd, 4 jac_dbl),
+ * one case per 4 lanes, neighbouring cases in one wave. */
+int halo_test_lazy_point_op(halo_ctx *ctx, int op, int quad, const uint32_t *a, const uint32_t *b, size_t n, uint32_t *out);
+
 #ifdef __cplusplus
 }
 #endif
