@@ -123,6 +123,9 @@ _SIGS = {
     "halo_instance_decode": (C.c_int, [C.c_char_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "halo_accumulator_encode": (C.c_int, [u64p, C.c_char_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "halo_accumulator_decode": (C.c_int, [C.c_char_p, C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "halo_proof_decode_batch": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_size_t), C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "halo_instance_decode_batch": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_size_t), C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "halo_accumulator_decode_batch": (C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(C.c_size_t), C.c_size_t, u64p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
     "halo_prof_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "halo_prof_reset": (C.c_int, [C.c_void_p]),
     "halo_prof_count": (C.c_int, [C.c_void_p]),
@@ -163,6 +166,8 @@ _DEV_SIGS = {
     "halo_dev_h_coeffs_batch": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_size_t, u64p]),
     "halo_dev_h_accumulate_batch": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.c_size_t, u64p]),
     "halo_dev_small_msm_seg": (C.c_int, [C.c_void_p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, u64p]),
+    "halo_dev_fq_sqrt": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, u32p]),
+    "halo_dev_sqrt_tables": (C.c_int, [u32p, C.c_size_t]),
     "halo_test_lazy_field_op": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t, u32p]),
     "halo_test_lazy_point_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, u32p, u32p, C.c_size_t, u32p]),
 }
@@ -760,6 +765,37 @@ def accumulator_encode(acc):
 def accumulator_decode(data):
     lib = load()
     return _decode(lib.halo_accumulator_decode, data, lib.halo_accumulator_words)
+
+
+def _decode_batch(name, datas, words_of_lg, ctx, stride_words):
+    """m byte strings -> (blobs (m, stride), lgs, statuses); a member that fails has its code in statuses and a zero row"""
+    lib = load()
+    datas = [bytes(d) for d in datas]
+    m = len(datas)
+    offs = (C.c_size_t * (m + 1))()
+    for i, d in enumerate(datas):
+        offs[i + 1] = offs[i] + len(d)
+    if stride_words is None:  # the largest lg any member's length allows (33 bytes per L and per R)
+        stride_words = words_of_lg(min(40, max([len(d) // 66 for d in datas], default=0)))
+    out = np.zeros((m, int(stride_words)), dtype=np.uint64)
+    lgs, st = (C.c_size_t * max(m, 1))(), (C.c_int * max(m, 1))()
+    rc = getattr(lib, name)(ctx.h if ctx is not None else None, b"".join(datas), offs, m, ptr(out), int(stride_words), lgs, st)
+    if rc != HALO_OK and not any(st[i] for i in range(m)):
+        check(rc)  # a whole-call error
+    return out, np.array(lgs[:m], dtype=np.int64), np.array(st[:m], dtype=np.int32)
+
+
+def proof_decode_batch(datas, ctx=None, stride_words=None):
+    """halo_proof_decode_batch: (blobs[m, stride], lgs, statuses); member failures are reported in statuses, not raised"""
+    return _decode_batch("halo_proof_decode_batch", datas, load().halo_proof_words, ctx, stride_words)
+
+
+def instance_decode_batch(datas, ctx=None, stride_words=None):
+    return _decode_batch("halo_instance_decode_batch", datas, load().halo_instance_words, ctx, stride_words)
+
+
+def accumulator_decode_batch(datas, ctx=None, stride_words=None):
+    return _decode_batch("halo_accumulator_decode_batch", datas, load().halo_accumulator_words, ctx, stride_words)
 
 
 def point_sum(pts_jac):

@@ -214,8 +214,9 @@ int halo_dev_hook(const char *name, long value) {
     else if (!std::strcmp(name, "check_batch_group")) h.check_group = (int)value;
     else if (!std::strcmp(name, "open_batch_group")) h.open_group = (int)value;
     else if (!std::strcmp(name, "verifier_batch_min")) h.verifier_min = (int)value;
+    else if (!std::strcmp(name, "decode_batch_min")) h.decode_min = value;
     else if (!std::strcmp(name, "reset")) h = DevHooks();
-    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, verifier_batch_min, reset)"); return HALO_E_ARG; }
+    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, verifier_batch_min, decode_batch_min, reset)"); return HALO_E_ARG; }
     return HALO_OK;
 }
 
@@ -312,6 +313,39 @@ int halo_dev_small_msm_seg(halo_ctx *ctx, const uint64_t *points, const uint64_t
     if (!rc && (e = hipMemcpy(out_jac, d_out, nsums * 96, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d);
     return rc;
+}
+
+// the decode batch's square root in Fq (k_fq_sqrt, the routine of k_point_decompress) on its own (tests/test_gpu_decode_batch.py
+// holds it against Python integers): temporary device buffers of this call only
+int halo_dev_fq_sqrt(halo_ctx *ctx, const uint64_t *a, size_t m, uint64_t *root_out, uint32_t *ok_out) {
+    HALO_CTX(ctx);
+    if (m == 0) return HALO_OK;
+    if (!a || !root_out || !ok_out) { set_error("fq_sqrt: null pointer"); return HALO_E_ARG; }
+    if (m > ((size_t)1 << 22)) { set_error("fq_sqrt: at most 2^22 elements"); return HALO_E_ARG; }
+    const uint32_t *tab = sqrt_tables_host();
+    if (!tab) { set_error("fq_sqrt: the torsion tables could not be built"); return HALO_E_DEVICE; }
+    uint64_t *d = nullptr;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d, m * 64 + SQRT_TAB_WORDS * 4 + m * 4));
+    uint64_t *d_a = d, *d_root = d + 4 * m;
+    uint32_t *d_tab = reinterpret_cast<uint32_t *>(d_root + 4 * m), *d_ok = d_tab + SQRT_TAB_WORDS;  // (the tables 16-byte aligned)
+    hipError_t e = hipMemcpyAsync(d_a, a, m * 32, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tab, tab, SQRT_TAB_WORDS * 4, hipMemcpyHostToDevice, ctx->stream);
+    int rc = e == hipSuccess ? fq_sqrt_dev(ctx, d_a, m, d_tab, d_root, d_ok) : hip_fail(e, "hipMemcpyAsync");
+    if (!rc && (e = hipMemcpyAsync(root_out, d_root, m * 32, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+    if (!rc && (e = hipMemcpyAsync(ok_out, d_ok, m * 4, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+    e = hipStreamSynchronize(ctx->stream);  // (also on failure: nothing of this call may be in flight when its buffers go)
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    (void)hipFree(d);
+    return rc;
+}
+
+// host only: the torsion tables of that square root as the kernels get them (tests/test_decompress_host.py)
+int halo_dev_sqrt_tables(uint32_t *out, size_t cap_words) {
+    const uint32_t *tab = sqrt_tables_host();
+    if (!out || cap_words < SQRT_TAB_WORDS || !tab) { set_error("sqrt_tables: null pointer, fewer than 8448 words, or no tables"); return HALO_E_ARG; }
+    std::memcpy(out, tab, SQRT_TAB_WORDS * 4);
+    return HALO_OK;
 }
 
 int halo_bench_fr_kernel(halo_ctx *ctx, int which, size_t n, int reps) {

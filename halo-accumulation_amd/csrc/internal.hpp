@@ -567,6 +567,17 @@ int open_batch_dots(halo_ctx *ctx, int G, const uint64_t *d_c, const uint64_t *d
 int open_batch_fold(halo_ctx *ctx, int G, uint64_t *d_c, uint64_t *d_z, const uint64_t *d_s_in, uint64_t *d_s_out, size_t ms, size_t m,
                     size_t s_len, const uint64_t *d_consts);
 
+// ---- decompress.hip: point decompression of the wire format on the device (wire.hip halo_*_decode_batch)
+constexpr size_t DECOMP_IN_WORDS = 6;    // a point's 33 wire bytes, zero-padded to 48
+constexpr size_t DECOMP_OUT_WORDS = 14;  // 12 Jacobian blob words, ok, pad
+constexpr size_t SQRT_TAB_WORDS = 4 * 256 * 8 + 256;  // 32-bit words of the square root's torsion tables
+const uint32_t *sqrt_tables_host();  // built on first use (null: the lookup limbs collide -- never for this field)
+int point_decompress_dev(halo_ctx *ctx, const uint64_t *d_in, size_t n, const uint32_t *d_tab, uint64_t *d_out);  // on ctx->stream
+int fq_sqrt_dev(halo_ctx *ctx, const uint64_t *d_a, size_t n, const uint32_t *d_tab, uint64_t *d_root, uint32_t *d_ok);
+// ---- pcdl_acc.hip: the context's staging for batched calls (optional memory), grown to `want` x per_bytes if the budget
+// allows; returns how many units of per_bytes it holds (0: none)
+size_t check_stage(halo_ctx *ctx, size_t want, size_t per_bytes);
+
 // ---- abi.hip (device-pointer forms used by pcdl_acc.hip)
 // H' = xi0 * H for this state (pcdl.rs:181): lets the rounds use the process-wide window table of H
 void ipa_set_hprime_scalar(halo_ipa *st, const host::Fr &xi0);

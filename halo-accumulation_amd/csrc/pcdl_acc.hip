@@ -419,7 +419,7 @@ static int check_group_size(const halo_ctx *ctx, size_t n) {
 // Member buffers of n coefficients + one set of tables each in the context's check staging: grown to `want` buffers if the
 // memory budget and the device allow (optional memory: halo_set_memory_budget), never shrunk.  Returns how many buffers it
 // holds (0: none -- the caller runs one member at a time in ctx->d_tmp_a; never an error).
-static size_t check_stage(halo_ctx *ctx, size_t want, size_t per_bytes) {
+size_t check_stage(halo_ctx *ctx, size_t want, size_t per_bytes) {
     if (dev_hooks().batch_stage_fail) return 0;  // (development library: the fallback path)
     const size_t bytes = want * per_bytes;
     if (ctx->check_stage_bytes < bytes && table_budget_reserve(ctx, bytes)) {

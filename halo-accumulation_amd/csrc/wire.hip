@@ -11,7 +11,10 @@
 // The reference derives no (de)serialisation for these three structs and no Rust toolchain exists here, so the layout is
 // "best known", exactly like the transcript encoding of host_math.hpp (parity unpinned).  Decoding validates
 // everything a checked arkworks deserialisation would: canonical field elements, flag bits, points on the curve.
-// Host-only code: no device is needed or touched.
+// The single-blob entry points are host-only code: no device is needed or touched.  The batched decoders (halo_*_decode_batch,
+// at the end) read every member's structure on the host and decompress the points of the whole batch at once -- on the device
+// (decompress.hip) when a context is given and the batch is large enough, else on the host pool.
+#include <algorithm>
 #include <cstring>
 
 #include "internal.hpp"
@@ -82,10 +85,19 @@ bool fq_sqrt(const Fq &a, Fq *root) {
     return true;
 }
 
+// a point whose decompression a batched decode has put off: its 33 bytes and where its 12 words go
+struct PendingPoint {
+    const uint8_t *src;
+    uint64_t *dst;
+};
+// the point of Reader::point on its own: false = rejected
+bool decompress_point(const uint8_t *src, uint64_t *jac_out);
+
 struct Reader {
     const uint8_t *in;
     size_t len, pos = 0;
     bool ok = true;
+    std::vector<PendingPoint> *defer = nullptr;  // batched decode: points are queued here, unexamined, and count as good
     bool take(void *p, size_t n) {
         if (!ok || pos + n > len) { ok = false; return false; }
         std::memcpy(p, in + pos, n);
@@ -101,29 +113,40 @@ struct Reader {
         c.to_mont().store(mont_out);
     }
     void point(uint64_t *jac_out) {
-        uint8_t b[33];
-        if (!take(b, 33)) return;
-        uint8_t flags = b[32] & 0xC0;
-        b[32] &= 0x3F;
-        if (flags == 0xC0) { ok = false; return; }
-        if (flags == 0x40) {
-            for (int i = 0; i < 33; ++i) if (b[i]) { ok = false; return; }
-            Point::infinity().store(jac_out);
+        if (defer) {
+            if (ok && pos + 33 <= len) { defer->push_back({in + pos, jac_out}); pos += 33; }
+            else ok = false;
             return;
         }
-        if (b[32]) { ok = false; return; }  // x >= 2^256
-        Fq xc;
-        std::memcpy(xc.l, b, 32);
-        if (Fq::geq(xc.l, host::FqP::M)) { ok = false; return; }
-        Fq x = xc.to_mont(), y;
-        if (!fq_sqrt(x.sqr() * x + Fq::from_u64(5), &y)) { ok = false; return; }  // not on the curve
-        Fq yc = y.from_mont(), nyc = (-y).from_mont();
-        bool y_larger = !Fq::geq(nyc.l, yc.l);
-        if (y_larger != (flags == 0x80)) y = -y;
-        if (y.is_zero() && flags == 0x80) { ok = false; return; }
-        Point::from_affine(x, y).store(jac_out);
+        uint8_t b[33];
+        if (!take(b, 33)) return;
+        if (!decompress_point(b, jac_out)) ok = false;
     }
 };
+bool decompress_point(const uint8_t *src, uint64_t *jac_out) {
+    uint8_t b[33];
+    std::memcpy(b, src, 33);
+    uint8_t flags = b[32] & 0xC0;
+    b[32] &= 0x3F;
+    if (flags == 0xC0) return false;
+    if (flags == 0x40) {
+        for (int i = 0; i < 33; ++i) if (b[i]) return false;
+        Point::infinity().store(jac_out);
+        return true;
+    }
+    if (b[32]) return false;  // x >= 2^256
+    Fq xc;
+    std::memcpy(xc.l, b, 32);
+    if (Fq::geq(xc.l, host::FqP::M)) return false;
+    Fq x = xc.to_mont(), y;
+    if (!fq_sqrt(x.sqr() * x + Fq::from_u64(5), &y)) return false;  // not on the curve
+    Fq yc = y.from_mont(), nyc = (-y).from_mont();
+    bool y_larger = !Fq::geq(nyc.l, yc.l);
+    if (y_larger != (flags == 0x80)) y = -y;
+    if (y.is_zero() && flags == 0x80) return false;
+    Point::from_affine(x, y).store(jac_out);
+    return true;
+}
 
 void write_proof(Writer &w, const uint64_t *pf) {
     size_t lg = (size_t)pf[1];
@@ -192,6 +215,156 @@ int finish_write(const Writer &w, size_t *len) {
 }
 int reject(const char *what) { set_error(std::string("decode: malformed ") + what); return HALO_E_REJECT; }
 
+// The three decoders after their null checks: status and message (set_error) of halo_*_decode; *lg_n on success.  With
+// r.defer set the points count as good and the caller judges them afterwards (decode_batch).
+enum WireKind { WIRE_PROOF, WIRE_INSTANCE, WIRE_ACCUMULATOR };
+const char *const kWireName[3] = {"EvalProof", "Instance", "Accumulator"};
+int decode_proof(Reader &r, uint64_t *proof_out, size_t cap_words, size_t *lg_n) {
+    size_t lg = read_proof(r, proof_out, cap_words);
+    if (lg == (size_t)-1 || !r.ok || r.pos != r.len) return reject("EvalProof");
+    *lg_n = lg;
+    return HALO_OK;
+}
+int decode_instance(Reader &r, uint64_t *inst_out, size_t cap_words, size_t *lg_n) {
+    size_t lg = read_instance(r, inst_out, cap_words);
+    if (lg == (size_t)-1 || !r.ok || r.pos != r.len) return reject("Instance");
+    *lg_n = lg;
+    return HALO_OK;
+}
+// Accumulator = Instance fields | pi_V { h: DensePolynomial (<= 2 coefficients, trailing zeros stripped), U, w }
+int decode_accumulator(Reader &r, uint64_t *acc_out, size_t cap_words, size_t *lg_n) {
+    size_t lg = read_instance(r, acc_out, cap_words);
+    if (lg == (size_t)-1 || !r.ok) return reject("Accumulator");
+    if (cap_words < instance_words(lg) + 24) { set_error("decode: output buffer too small"); return HALO_E_ARG; }
+    uint64_t *piV = acc_out + instance_words(lg);
+    std::memset(piV, 0, 24 * 8);
+    uint64_t hlen = r.u64le();
+    if (!r.ok || hlen > 2) return reject("Accumulator (h has at most two coefficients, acc.rs:192)");
+    for (uint64_t k = 0; k < hlen; ++k) r.scalar(piV + 4 * k);
+    if (r.ok && hlen && !(piV[4 * (hlen - 1)] | piV[4 * (hlen - 1) + 1] | piV[4 * (hlen - 1) + 2] | piV[4 * (hlen - 1) + 3]))
+        return reject("Accumulator (leading coefficient of h is zero)");
+    r.point(piV + 8);
+    r.scalar(piV + 20);
+    if (!r.ok || r.pos != r.len) return reject("Accumulator");
+    *lg_n = lg;
+    return HALO_OK;
+}
+
+// ---- halo_*_decode_batch
+// Member i = in[offs[i], offs[i + 1]) -> out + i * stride, every member's outcome the single call's with cap_words = stride:
+//  1. one pool pass over the members reads each one's structure (lengths, option tags, the lg cap, canonical scalars, the
+//     accumulator's h) with its points queued, not examined (Reader::defer);
+//  2. the queued points of the whole batch are decompressed: by k_point_decompress (decompress.hip) on a slot idle at entry,
+//     in chunks of what the context's staging holds, from kDecodeBatchMin finite points on; with no context, no idle slot,
+//     no staging or fewer points, by the host pool, point by point;
+//  3. a member one of whose queued points was rejected is "malformed <kind>" -- the single call reads in byte order and
+//     stops at the first failure, a member's points are queued only up to its first structural failure, and every failure
+//     a bad point can precede is reported in those words or after it (the accumulator's "output buffer too small" and its
+//     messages about h come after the Instance part; after U only the generic message is left).
+constexpr size_t kDecodeBatchMin = 512;          // finite points; measured: tools/time_decode_batch.py
+constexpr size_t kDecodeChunk = (size_t)1 << 16;  // points per launch the staging is asked for
+constexpr size_t kDecompBytes = (DECOMP_IN_WORDS + DECOMP_OUT_WORDS) * 8;
+
+struct DecodeMember {
+    int rc = HALO_OK;
+    std::string err;
+    size_t lg = 0, first = 0;
+    std::vector<PendingPoint> pts;
+};
+
+// ok[j] = point j accepted (its words written); returns non-zero only for a failing HIP call
+int decompress_on_device(halo_ctx *ctx, int slot, size_t chunk, const std::vector<PendingPoint> &pts, std::vector<uint8_t> &ok) {
+    const uint32_t *tab = sqrt_tables_host();
+    uint64_t *d_tab = ctx->d_check_stage, *d_in = d_tab + SQRT_TAB_WORDS / 2, *d_out = d_in + chunk * DECOMP_IN_WORDS;
+    hipStream_t saved = ctx->stream;
+    ctx->stream = ctx->streams[slot];  // (the launch macro uses ctx->stream: the slot's own)
+    std::vector<uint64_t> hin(chunk * DECOMP_IN_WORDS), hout(chunk * DECOMP_OUT_WORDS);
+    hipError_t e = hipMemcpyAsync(d_tab, tab, SQRT_TAB_WORDS * 4, hipMemcpyHostToDevice, ctx->stream);
+    int rc = e == hipSuccess ? HALO_OK : hip_fail(e, "hipMemcpyAsync");
+    for (size_t lo = 0; lo < pts.size() && !rc; lo += chunk) {
+        const size_t cnt = std::min(chunk, pts.size() - lo);
+        std::fill(hin.begin(), hin.begin() + cnt * DECOMP_IN_WORDS, 0);
+        for (size_t j = 0; j < cnt; ++j) std::memcpy(&hin[j * DECOMP_IN_WORDS], pts[lo + j].src, 33);
+        if ((e = hipMemcpyAsync(d_in, hin.data(), cnt * DECOMP_IN_WORDS * 8, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+        if (!rc) rc = point_decompress_dev(ctx, d_in, cnt, reinterpret_cast<const uint32_t *>(d_tab), d_out);
+        if (!rc && (e = hipMemcpyAsync(hout.data(), d_out, cnt * DECOMP_OUT_WORDS * 8, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+        e = hipStreamSynchronize(ctx->stream);  // (also on failure: the host buffers are reused and go with this call)
+        if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+        for (size_t j = 0; j < cnt && !rc; ++j) {
+            const uint64_t *o = &hout[j * DECOMP_OUT_WORDS];
+            ok[lo + j] = o[12] == 1;
+            if (ok[lo + j]) std::memcpy(pts[lo + j].dst, o, 96);
+        }
+    }
+    ctx->stream = saved;
+    bool busy = false;
+    for (int k = 0; k < HALO_SLOTS; ++k) busy = busy || ctx->wss[k].in_flight;
+    if (!rc && ctx->prof.on && !busy) ctx->prof.collect();
+    return rc;
+}
+
+int decode_batch(halo_ctx *ctx, WireKind kind, const uint8_t *in, const size_t *offs, size_t m, uint64_t *out, size_t stride, size_t *lg_out, int *status) {
+    if (m == 0) return HALO_OK;
+    if (!in || !offs || !out) { set_error("decode_batch: null pointer"); return HALO_E_ARG; }
+    for (size_t i = 0; i < m; ++i)
+        if (offs[i + 1] < offs[i]) { set_error("decode_batch: offsets must not decrease"); return HALO_E_ARG; }
+    if (ctx) {
+        hipError_t e = hipSetDevice(ctx->device);
+        if (e != hipSuccess) return hip_fail(e, "hipSetDevice");
+    }
+    // 1. the structure of every member
+    std::vector<DecodeMember> mem(m);
+    pool_run(m, [&](size_t i) {
+        DecodeMember &M = mem[i];
+        uint64_t *slot = out + i * stride;
+        std::memset(slot, 0, stride * 8);
+        Reader r{in + offs[i], offs[i + 1] - offs[i]};
+        r.defer = &M.pts;
+        M.rc = kind == WIRE_PROOF ? decode_proof(r, slot, stride, &M.lg) : kind == WIRE_INSTANCE ? decode_instance(r, slot, stride, &M.lg) : decode_accumulator(r, slot, stride, &M.lg);
+        if (M.rc) M.err = halo_last_error();
+    });
+    std::vector<PendingPoint> pts;
+    size_t finite = 0;
+    for (size_t i = 0; i < m; ++i) {
+        mem[i].first = pts.size();
+        for (const PendingPoint &p : mem[i].pts) { pts.push_back(p); finite += !(p.src[32] & 0x40); }
+    }
+    // 2. every point
+    std::vector<uint8_t> ok(pts.size(), 0);
+    int slot = -1;
+    size_t chunk = 0;
+    if (ctx && !pts.empty() && sqrt_tables_host()) {
+        for (int s = 0; s < HALO_SLOTS && slot < 0; ++s)
+            if (!ctx->wss[s].in_flight && ctx->wss[s].lent_from < 0 && !ctx->fan[s].active) slot = s;
+        const long forced = dev_hooks().decode_min;  // (development library: the threshold sweep of tools/time_decode_batch.py)
+        const size_t min_pts = forced >= 1 ? (size_t)forced : kDecodeBatchMin;
+        const size_t tab_units = (SQRT_TAB_WORDS * 4 + kDecompBytes - 1) / kDecompBytes;  // the tables in front, in units of a point's staging
+        if (slot >= 0 && finite >= min_pts) {
+            const size_t have = check_stage(ctx, std::min(pts.size(), kDecodeChunk) + tab_units, kDecompBytes);
+            if (have > tab_units) chunk = std::min(have - tab_units, kDecodeChunk);
+        }
+    }
+    if (chunk) {
+        int rc = decompress_on_device(ctx, slot, chunk, pts, ok);
+        if (rc) return rc;
+    } else {
+        pool_run(pts.size(), [&](size_t j) { ok[j] = decompress_point(pts[j].src, pts[j].dst); });
+    }
+    // 3. every member's status
+    int first = -1;
+    for (size_t i = 0; i < m; ++i) {
+        DecodeMember &M = mem[i];
+        for (size_t j = 0; j < M.pts.size(); ++j)
+            if (!ok[M.first + j]) { M.rc = HALO_E_REJECT; M.err = std::string("decode: malformed ") + kWireName[kind]; break; }
+        if (M.rc) std::memset(out + i * stride, 0, stride * 8);
+        if (lg_out) lg_out[i] = M.rc ? 0 : M.lg;
+        if (status) status[i] = M.rc;
+        if (M.rc && first < 0) first = (int)i;
+    }
+    if (first >= 0) { set_error("member " + std::to_string(first) + ": " + mem[first].err); return mem[first].rc; }
+    return HALO_OK;
+}
+
 }  // namespace
 }  // namespace halo
 
@@ -214,10 +387,7 @@ int halo_proof_encode(const uint64_t *proof, uint8_t *out, size_t cap, size_t *l
 int halo_proof_decode(const uint8_t *in, size_t len, uint64_t *proof_out, size_t cap_words, size_t *lg_n) {
     if (!in || !proof_out || !lg_n) { set_error("decode: null pointer"); return HALO_E_ARG; }
     Reader r{in, len};
-    size_t lg = read_proof(r, proof_out, cap_words);
-    if (lg == (size_t)-1 || !r.ok || r.pos != len) return reject("EvalProof");
-    *lg_n = lg;
-    return HALO_OK;
+    return decode_proof(r, proof_out, cap_words, lg_n);
 }
 int halo_instance_encode(const uint64_t *inst, uint8_t *out, size_t cap, size_t *len) {
     if (!inst || !out || !len) { set_error("encode: null pointer"); return HALO_E_ARG; }
@@ -229,10 +399,7 @@ int halo_instance_encode(const uint64_t *inst, uint8_t *out, size_t cap, size_t 
 int halo_instance_decode(const uint8_t *in, size_t len, uint64_t *inst_out, size_t cap_words, size_t *lg_n) {
     if (!in || !inst_out || !lg_n) { set_error("decode: null pointer"); return HALO_E_ARG; }
     Reader r{in, len};
-    size_t lg = read_instance(r, inst_out, cap_words);
-    if (lg == (size_t)-1 || !r.ok || r.pos != len) return reject("Instance");
-    *lg_n = lg;
-    return HALO_OK;
+    return decode_instance(r, inst_out, cap_words, lg_n);
 }
 // Accumulator = Instance fields | pi_V { h: DensePolynomial (<= 2 coefficients, trailing zeros stripped), U, w }
 int halo_accumulator_encode(const uint64_t *acc, uint8_t *out, size_t cap, size_t *len) {
@@ -253,21 +420,17 @@ int halo_accumulator_encode(const uint64_t *acc, uint8_t *out, size_t cap, size_
 int halo_accumulator_decode(const uint8_t *in, size_t len, uint64_t *acc_out, size_t cap_words, size_t *lg_n) {
     if (!in || !acc_out || !lg_n) { set_error("decode: null pointer"); return HALO_E_ARG; }
     Reader r{in, len};
-    size_t lg = read_instance(r, acc_out, cap_words);
-    if (lg == (size_t)-1 || !r.ok) return reject("Accumulator");
-    if (cap_words < instance_words(lg) + 24) { set_error("decode: output buffer too small"); return HALO_E_ARG; }
-    uint64_t *piV = acc_out + instance_words(lg);
-    std::memset(piV, 0, 24 * 8);
-    uint64_t hlen = r.u64le();
-    if (!r.ok || hlen > 2) return reject("Accumulator (h has at most two coefficients, acc.rs:192)");
-    for (uint64_t k = 0; k < hlen; ++k) r.scalar(piV + 4 * k);
-    if (r.ok && hlen && !(piV[4 * (hlen - 1)] | piV[4 * (hlen - 1) + 1] | piV[4 * (hlen - 1) + 2] | piV[4 * (hlen - 1) + 3]))
-        return reject("Accumulator (leading coefficient of h is zero)");
-    r.point(piV + 8);
-    r.scalar(piV + 20);
-    if (!r.ok || r.pos != len) return reject("Accumulator");
-    *lg_n = lg;
-    return HALO_OK;
+    return decode_accumulator(r, acc_out, cap_words, lg_n);
+}
+
+int halo_proof_decode_batch(halo_ctx *ctx, const uint8_t *in, const size_t *offs, size_t m, uint64_t *out, size_t stride_words, size_t *lg_out, int *status) {
+    return decode_batch(ctx, WIRE_PROOF, in, offs, m, out, stride_words, lg_out, status);
+}
+int halo_instance_decode_batch(halo_ctx *ctx, const uint8_t *in, const size_t *offs, size_t m, uint64_t *out, size_t stride_words, size_t *lg_out, int *status) {
+    return decode_batch(ctx, WIRE_INSTANCE, in, offs, m, out, stride_words, lg_out, status);
+}
+int halo_accumulator_decode_batch(halo_ctx *ctx, const uint8_t *in, const size_t *offs, size_t m, uint64_t *out, size_t stride_words, size_t *lg_out, int *status) {
+    return decode_batch(ctx, WIRE_ACCUMULATOR, in, offs, m, out, stride_words, lg_out, status);
 }
 
 }  // extern "C"

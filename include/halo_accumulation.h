@@ -371,7 +371,7 @@ int halo_pcdl_open_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uin
  * z, then its hiding open's).  The conventions of halo_pcdl_open_batch; d < 2: the single call's assert. */
 int halo_random_instance_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, size_t m, uint64_t *instances_out);
 
-/* ---- wire format (host only; no device needed) ----------------------------------------------
+/* ---- wire format (no device needed) ----------------------------------------------------------
  * EvalProof (pcdl.rs:22-30), Instance (acc.rs:21-28) and Accumulator (acc.rs:43-59) in the byte layout a derived
  * ark-serialize `CanonicalSerialize` (compressed) writes: fields in declaration order; Fr = 32 bytes LE canonical;
  * point = 33 bytes (x LE, byte 32: bit 7 = y is the larger of {y, -y}, bit 6 = infinity); usize = u64 LE; Vec = u64 LE
@@ -386,6 +386,26 @@ int halo_instance_encode(const uint64_t *instance, uint8_t *out, size_t cap, siz
 int halo_instance_decode(const uint8_t *in, size_t len, uint64_t *instance_out, size_t cap_words, size_t *lg_n);
 int halo_accumulator_encode(const uint64_t *acc, uint8_t *out, size_t cap, size_t *len);
 int halo_accumulator_decode(const uint8_t *in, size_t len, uint64_t *acc_out, size_t cap_words, size_t *lg_n);
+/* m blobs decoded in one call: member i is the bytes in[offs[i] .. offs[i + 1]) (offs: m + 1 non-decreasing entries) and its blob
+ * goes to out + i * stride_words.
+ * - Every member's outcome is the single call's with cap_words = stride_words: status[i] (nullable) its code; on success
+ *   lg_out[i] (nullable) and the blob's words are the single call's and the rest of the slot is zero; a failed member's whole
+ *   slot is zero-filled and its lg_out[i] is 0; the other members are unaffected.  Returns 0 if every member decoded, else
+ *   the first non-zero status in member order, halo_last_error() = "member i: <the single call's message>".
+ * - Before any work (status, lg_out and out untouched): m > 0 with a null in, offs or out, or offs decreasing: HALO_E_ARG.
+ *   m = 0: HALO_OK.
+ * - ctx may be null: the wire format stays usable without a device; the members then run on the host thread pool.  With a
+ *   context the structure of every member is read on the host and, from 512 finite points in the batch on, every point is
+ *   decompressed on the device (the square root in Fq that dominates a decode: one lane per point), on a slot that is idle
+ *   on entry -- a caller's MSM in flight is left alone; a multi-device context uses its first device.  The staging is
+ *   optional memory (halo_set_memory_budget); larger batches run in chunks of it.  With no idle slot, no staging or fewer
+ *   points the host pool runs instead, with the same results. */
+int halo_proof_decode_batch(halo_ctx *ctx /*nullable*/, const uint8_t *in, const size_t *offs, size_t m, uint64_t *out,
+                            size_t stride_words, size_t *lg_out /*nullable*/, int *status /*nullable*/);
+int halo_instance_decode_batch(halo_ctx *ctx /*nullable*/, const uint8_t *in, const size_t *offs, size_t m, uint64_t *out,
+                               size_t stride_words, size_t *lg_out /*nullable*/, int *status /*nullable*/);
+int halo_accumulator_decode_batch(halo_ctx *ctx /*nullable*/, const uint8_t *in, const size_t *offs, size_t m, uint64_t *out,
+                                  size_t stride_words, size_t *lg_out /*nullable*/, int *status /*nullable*/);
 
 /* ---- measurement and resource policy ------------------------------------------------------ */
 /* (Experiment knobs, the primitive test hooks, halo_bench_fr_kernel and the fault injectors are NOT part of this library:

@@ -25,7 +25,9 @@ extern "C" {
  * halo_pcdl_check_batch / halo_acc_decider_batch / halo_pcdl_open_batch / halo_random_instance_batch / halo_acc_prover_batch is refused, as over the
  * memory budget: one member at a time; halo_acc_verifier_batch: its sums on the host pool), "check_batch_group" (members per MSM launch of the check batch, 1..8; 0: the measured
  * default), "open_batch_group" (members per launch of the open and prover batches, 1..4; 0: the measured default), "verifier_batch_min" (relations
- * from which halo_acc_verifier_batch runs its sums on the device, >= 1; 0: the measured default), "reset" (all off). */
+ * from which halo_acc_verifier_batch runs its sums on the device, >= 1; 0: the measured default), "decode_batch_min" (finite points
+ * from which halo_*_decode_batch decompresses on the device, >= 1; 0: the measured default; "batch_stage_fail" refuses its staging
+ * too: the host pool), "reset" (all off). */
 int halo_dev_hook(const char *name, long value);
 /* What the library read from the environment at its first use (csrc/tuning.hip), by field: "host_split_set", "host_pieces", "host_split0".."host_split3",
  * "fold_table_after", "graph_cache", "pow_e", "spin_us", "graphs", "memory_budget" (MiB, -1 unset), "trace", "tagged"; -1 for an
@@ -94,6 +96,13 @@ int halo_set_task_len(halo_ctx *ctx, int len);
  * sum after sum; out_jac = nsums x 12 Jacobian words */
 int halo_dev_small_msm_seg(halo_ctx *ctx, const uint64_t *points, const uint64_t *scalars, const size_t *lens, size_t nsums,
                            uint64_t *out_jac);
+
+/* The decode batch's square root in Fq (the routine of k_point_decompress) on its own, one lane per element: a = m x 4
+ * Montgomery words; ok_out[i] = 1 and root_out[i]^2 = a[i] if a[i] is a square, else ok_out[i] = 0 */
+int halo_dev_fq_sqrt(halo_ctx *ctx, const uint64_t *a, size_t m, uint64_t *root_out, uint32_t *ok_out);
+/* host only: that square root's torsion tables as the kernels get them, 8448 32-bit words: S[i][d] = g^(-d 2^(8 i) / 2) for
+ * i < 4, d < 256 (S[0][d] = g^-(d >> 1); 8 Montgomery words each; g = 5^t, p - 1 = 2^32 t), then limb 0 of (g^(2^24))^d, d < 256 */
+int halo_dev_sqrt_tables(uint32_t *out, size_t cap_words);
 
 /* ---- primitive hooks used by the parity tests (elementwise over n) ----------------------- */
 /* host-only: base-2 expansion of the fold scalar over the Eisenstein units (host_math.hpp glv_digits):

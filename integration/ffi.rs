@@ -60,6 +60,13 @@ extern "C" {
     pub fn halo_pcdl_open_batch(ctx: *mut HaloCtx, rng_state: *mut u64, d: usize, coeffs: *const u64, m: usize, cs: *const u64, zs: *const u64,
                                 ws: *const u64, proofs_out: *mut u64, status: *mut c_int) -> c_int;
     pub fn halo_random_instance_batch(ctx: *mut HaloCtx, rng_state: *mut u64, d: usize, m: usize, instances_out: *mut u64) -> c_int;
+    // m wire blobs -> m library blobs at `stride_words` (ctx, lg_out, status may be null; member i = bytes offs[i]..offs[i + 1])
+    pub fn halo_proof_decode_batch(ctx: *mut HaloCtx, input: *const u8, offs: *const usize, m: usize, out: *mut u64, stride_words: usize,
+                                   lg_out: *mut usize, status: *mut c_int) -> c_int;
+    pub fn halo_instance_decode_batch(ctx: *mut HaloCtx, input: *const u8, offs: *const usize, m: usize, out: *mut u64, stride_words: usize,
+                                      lg_out: *mut usize, status: *mut c_int) -> c_int;
+    pub fn halo_accumulator_decode_batch(ctx: *mut HaloCtx, input: *const u8, offs: *const usize, m: usize, out: *mut u64, stride_words: usize,
+                                         lg_out: *mut usize, status: *mut c_int) -> c_int;
     pub fn halo_h_accumulate(ctx: *mut HaloCtx, h0: *const u64, xis: *const u64, alphas: *const u64, m: usize, lg_n: usize, out: *mut u64) -> c_int;
     pub fn halo_ipa_begin(ctx: *mut HaloCtx, n: usize, coeffs: *const u64, len: usize, z: *const u64, out: *mut *mut HaloIpa) -> c_int;
     pub fn halo_ipa_round_lr(st: *mut HaloIpa, h_prime: *const u64, l: *mut u64, r: *mut u64) -> c_int;
