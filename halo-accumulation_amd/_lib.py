@@ -167,6 +167,7 @@ _DEV_SIGS = {
     "halo_dev_h_accumulate_batch": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.c_size_t, u64p]),
     "halo_dev_small_msm_seg": (C.c_int, [C.c_void_p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, u64p]),
     "halo_dev_fq_sqrt": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, u32p]),
+    "halo_dev_fold_points": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_int, u64p, C.c_int, C.c_int, u64p]),
     "halo_dev_sqrt_tables": (C.c_int, [u32p, C.c_size_t]),
     "halo_test_lazy_field_op": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t, u32p]),
     "halo_test_lazy_point_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, u32p, u32p, C.c_size_t, u32p]),
@@ -547,6 +548,19 @@ class Context:
         return out
 
     # ---- raw-limb hooks (csrc/dev_lazy_ops.hpp): native operands whose limbs the caller chooses
+    def fold_points(self, key, levels, scalars, form=0, in_place=False, n=None):
+        """halo_dev_fold_points: one point fold over `key` (n x 8 words; None: the first n points of the context's own key) in the
+        kernel form `form` -> m x 8 affine words"""
+        if key is not None:
+            key = np.ascontiguousarray(key, dtype=np.uint64).reshape(-1, 8)
+            n = key.shape[0]
+        n = self.size if n is None else int(n)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        assert scalars.shape[0] == (3 if levels == 2 else 1)
+        out = np.zeros((max(n // (4 if levels == 2 else 2), 1), 8), dtype=np.uint64)
+        check(self.lib.halo_dev_fold_points(self.h, ptr(key), n, int(levels), ptr(scalars), int(form), int(bool(in_place)), ptr(out)))
+        return out
+
     def lazy_field_op(self, op, a):
         """a: (n, 40) uint32, four operands of 9 limbs + pad -> (n, 10) uint32"""
         a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, 40)

@@ -492,6 +492,66 @@ static int lazy_run(halo_ctx *ctx, int kind, int op, const uint32_t *a, const ui
     return rc;
 }
 
+// One point fold through the product's launcher over a key of the caller's choice, in a kernel form of the caller's choice
+// (include/halo_accumulation_dev.h).  Device buffers of this call only; every copy and launch in order on the context's stream.
+int halo_dev_fold_points(halo_ctx *ctx, const uint64_t *key_affine, size_t n, int levels, const uint64_t *scalars, int form, int in_place,
+                         uint64_t *out_affine) {
+    HALO_CTX(ctx);
+    if (levels != 1 && levels != 2) { set_error("dev_fold_points: levels must be 1 or 2"); return HALO_E_ARG; }
+    const size_t parts = 2 * (size_t)levels;
+    if (n == 0 || n % parts || n > ((size_t)1 << 24)) { set_error("dev_fold_points: n must be a positive multiple of 2 (levels 1) or 4 (levels 2), at most 2^24"); return HALO_E_ARG; }
+    if (!scalars || !out_affine) { set_error("dev_fold_points: null pointer"); return HALO_E_ARG; }
+    if (!key_affine && n > ctx->n) { set_error("dev_fold_points: n exceeds the context's key"); return HALO_E_ARG; }
+    if (form < 0 || form > 5 || (levels == 1 && form > 2)) { set_error("dev_fold_points: form is 0, 1 or 2 for levels 1; 0 .. 5 for levels 2"); return HALO_E_ARG; }
+    const size_t m = n / parts;
+    const bool table = form >= 4;
+    if (table && (key_affine || n != ctx->n || n < 64)) { set_error("dev_fold_points: the table forms fold the context's own key (key_affine = NULL, n = its size >= 64)"); return HALO_E_ARG; }
+    if (table && in_place) { set_error("dev_fold_points: the table kernel never runs in place"); return HALO_E_ARG; }
+    // the source: the uploaded key, or the context's own -- itself where nothing is written to it, else a copy
+    const bool own_src = !key_affine && levels == 2 && !in_place;
+    const size_t src_words = own_src ? 0 : n * (size_t)AFF_STRIDE, dst_words = (levels == 2 && !in_place) ? m * (size_t)AFF_STRIDE : 0;
+    const size_t in_words = key_affine ? n * 8 : 0, out_words = m * 8;
+    uint32_t *d = nullptr;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d, (src_words + dst_words) * 4 + (in_words + out_words) * 8));
+    uint32_t *d_src = d, *d_dst = d + src_words;  // (every part a multiple of 128 bytes or of 64)
+    uint64_t *d_in = reinterpret_cast<uint64_t *>(d_dst + dst_words), *d_out = d_in + in_words;
+    int rc = HALO_OK;
+    hipError_t e = hipSuccess;
+    if (key_affine) {
+        e = hipMemcpyAsync(d_in, key_affine, in_words * 8, hipMemcpyHostToDevice, ctx->stream);
+        rc = e == hipSuccess ? aff_words_to_native(ctx, d_in, n, d_src) : hip_fail(e, "hipMemcpyAsync");
+    } else if (!own_src) {
+        e = hipMemcpyAsync(d_src, ctx->d_bases, src_words * 4, hipMemcpyDeviceToDevice, ctx->stream);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+    }
+    const uint32_t *src = own_src ? ctx->d_bases : d_src;
+    uint32_t *dst = dst_words ? d_dst : d_src;
+    if (!rc && levels == 1) rc = ipa_fold_points(ctx, d_src, m, host::Fr::load(scalars), form);
+    if (!rc && levels == 2) {
+        const host::Fr s[3] = {host::Fr::load(scalars), host::Fr::load(scalars + 4), host::Fr::load(scalars + 8)};
+        const int mode = ctx->fold_table_mode;
+        if (table) {  // as halo_set_fold_table(ctx, 1): built at this fold if it is not there yet
+            ctx->fold_table_mode = 1;
+            ctx->foldtab_retry_at = 0;
+        }
+        rc = ipa_fold_points4(ctx, src, dst, m, s, form);
+        if (table) {
+            ctx->fold_table_mode = mode;
+            if (mode == 0) {  // a context that was told to hold no table holds none afterwards
+                (void)hipStreamSynchronize(ctx->stream);
+                foldtab_release(ctx);
+            }
+        }
+    }
+    if (!rc) rc = aff_native_to_words(ctx, dst, m, d_out);
+    if (!rc && (e = hipMemcpyAsync(out_affine, d_out, out_words * 8, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+    e = hipStreamSynchronize(ctx->stream);  // (also on failure: nothing of this call may be in flight when its buffers go)
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    (void)hipFree(d);
+    return rc;
+}
+
 int halo_test_lazy_field_op(halo_ctx *ctx, int op, const uint32_t *in, size_t n, uint32_t *out) {
     HALO_CTX(ctx);
     if (n == 0) return HALO_OK;

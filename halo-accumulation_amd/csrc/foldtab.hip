@@ -354,7 +354,8 @@ static int foldtab_build(halo_ctx *ctx, uint32_t *tab = nullptr, uint32_t *tmp =
 
 // Called by the IPA at the two-level fold from the context's own key (m = n / 4 outputs).  Returns 1 if the table kernel
 // ran, 0 if the caller should take the generic kernel, < 0 on a launch error.
-int fold_points4_tab(halo_ctx *ctx, const uint32_t *d_src, uint32_t *d_dst, size_t m, const host::Fr s[3]) {
+// form (development hook): 4 / 5 = one / two outputs per lane whatever m is; anything else: m decides.
+int fold_points4_tab(halo_ctx *ctx, const uint32_t *d_src, uint32_t *d_dst, size_t m, const host::Fr s[3], int form) {
     if (d_src != ctx->d_bases || 4 * m != ctx->n || m < 16 || d_dst == d_src || ctx->fold_table_mode == 0) return 0;
     if (!ctx->d_foldtab) (void)foldtab_adopt(ctx);
     if (!ctx->d_foldtab) {
@@ -436,7 +437,7 @@ int fold_points4_tab(halo_ctx *ctx, const uint32_t *d_src, uint32_t *d_dst, size
                                      ((uint32_t)(uint8_t)d[4 * q + 3] << 24);
         }
     }
-    size_t half = m >= 512 ? (m + 1) / 2 : m;
+    size_t half = (form >= 4 ? form == 5 : m >= 512) ? (m + 1) / 2 : m;
     size_t lo = ctx->n / 4, cnt = ctx->n - lo;
     HALO_LAUNCH(ctx, "k_fold_points4_tab", k_fold_tab4, dim3((unsigned)((half + 255) / 256)), dim3(256), 0, d_src, ctx->d_foldtab, d_dst, (uint32_t)m,
                 (uint32_t)half, (uint32_t)lo, (uint32_t)cnt, dg);

@@ -450,7 +450,7 @@ void table_budget_release(halo_ctx *ctx, size_t bytes);
 
 // ---- foldtab.hip: the first two-level fold of an open from a comb table over the context's key
 void foldtab_cancel_alloc(halo_ctx *ctx);  // joins the helper thread and frees what it obtained
-int fold_points4_tab(halo_ctx *ctx, const uint32_t *d_src, uint32_t *d_dst, size_t m, const host::Fr s[3]);  // 1 = done, 0 = not applicable
+int fold_points4_tab(halo_ctx *ctx, const uint32_t *d_src, uint32_t *d_dst, size_t m, const host::Fr s[3], int form = 0);  // 1 = done, 0 = not applicable
 void foldtab_release(halo_ctx *ctx);
 void fold_digits_host(const host::Fr &s, int8_t out[44]);
 
@@ -480,8 +480,9 @@ int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, uint3
 int smsm_prepare();
 
 // ---- ipa.hip
-int ipa_fold_points(halo_ctx *ctx, uint32_t *d_G, size_t m, const host::Fr &xi_mont);
-int ipa_fold_points4(halo_ctx *ctx, const uint32_t *d_src, uint32_t *d_dst, size_t m, const host::Fr s[3]);
+// (form: 0 in the product -- the sizes pick the kernel form; halo_dev_fold_points forces one, include/halo_accumulation_dev.h)
+int ipa_fold_points(halo_ctx *ctx, uint32_t *d_G, size_t m, const host::Fr &xi_mont, int form = 0);
+int ipa_fold_points4(halo_ctx *ctx, const uint32_t *d_src, uint32_t *d_dst, size_t m, const host::Fr s[3], int form = 0);
 int ipa_fold_scalars(halo_ctx *ctx, uint64_t *d_c, uint64_t *d_z, size_t m, const host::Fr &xi, const host::Fr &xi_inv);
 // out[0] = <xs0, ys0>, out[1] = <xs1, ys1> (either pair may be null to skip)
 int fr_dot2(halo_ctx *ctx, const uint64_t *xs0, const uint64_t *ys0, const uint64_t *xs1, const uint64_t *ys1, size_t m,

@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "curve_quad.hpp"
+#include "fold_lane.hpp"
 #include "fr29.hpp"
 #include "internal.hpp"
 
@@ -47,56 +48,7 @@ HALO_DEV Fe from_arg(const FeArg &a) {
 }
 
 // ------------------------------------------------------------------ K3: G'[j] = G[j] + xi * G[j+m]
-// xi is one scalar for the whole launch, expanded on the host as xi = sum_i d_i 2^i with digits from the six
-// Eisenstein units {+-1, +-lambda, +-lambda^2} (host_math.hpp glv_digits): a ~127-step double-and-add with
-// ~71 additions, each of a "free" point d_i * P = (beta^e x, +-y) -- two multiplications per input point.
-// Every branch below depends only on kernel arguments, so the 64 lanes of a wave never diverge.
-struct GlvArg {
-    uint32_t dig[14];  // ten 3-bit digit codes per word, least significant digit first (host_math.hpp glv_digits)
-    int ndigits;
-};
-HALO_DEV Fq<2> fq_const(const uint32_t (&c)[9]) {
-    Fq<2> r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.v[i] = c[i];
-    return r;
-}
-HALO_DEV Fq<2> pick3(int e, const Fq<2> &a, const Fq<2> &b, const Fq<2> &c) {
-    Fq<2> r;
-#pragma unroll
-    for (int i = 0; i < 9; i++) r.v[i] = e == 0 ? a.v[i] : (e == 1 ? b.v[i] : c.v[i]);
-    return r;
-}
-// G[j] + xi * G[j + m] as a Jacobian point
-HALO_DEV JacN fold_one(const uint32_t *__restrict__ G, uint32_t j, uint32_t m, const GlvArg &a) {
-    AffN hi = aff_load(G + AFF_STRIDE * (size_t)(j + m));
-    AffN lo = aff_load(G + AFF_STRIDE * (size_t)j);
-    if (aff_is_inf(hi)) return jac_from_aff(lo);  // G[j] + xi * infinity = G[j]
-    constexpr uint32_t BETA[9] = {0x1342a796, 0x3fdac51, 0x54dab11, 0x5b221a6, 0xccd27ac, 0x15cc87a4, 0x1b1533b6, 0x169e85e1, 0x3b0093};
-    constexpr uint32_t BETA2[9] = {0xcbd58eb, 0x1a2f8f16, 0xd140efa, 0x7bdfb9, 0x1333ecad, 0xa33785b, 0x4eacc49, 0x9617a1e, 0x4ff6c};
-    Fq<2> x0 = hi.x, x1 = fq_mul(hi.x, fq_const(BETA)), x2 = fq_mul(hi.x, fq_const(BETA2));
-    Fq<2> yp = hi.y, yn = fq_neg<2>(hi.y);
-    JacN acc = jac_inf();
-    int top = a.ndigits - 1;
-#pragma unroll 1
-    for (int word = top / 10; word >= 0; word--) {
-        uint32_t w = 0;
-#pragma unroll
-        for (int q = 0; q < 14; q++) w = (q == word) ? a.dig[q] : w;
-#pragma unroll 1
-        for (int k = (word == top / 10) ? (top % 10) : 9; k >= 0; k--) {
-            acc = jac_dbl(acc);
-            uint32_t code = (w >> (3 * k)) & 7u;
-            if (code) {  // wave-uniform: +-w^e * hi = (beta^e x, +-y)
-                AffN t;
-                t.x = pick3((int)((code - 1) % 3), x0, x1, x2);
-                t.y = code > 3 ? yn : yp;
-                acc = jac_madd(acc, t);
-            }
-        }
-    }
-    return jac_madd(acc, lo);
-}
+// fold_one (fold_lane.hpp) is one lane's G[j] + xi * G[j + m] as a Jacobian point.
 // Each lane folds two points (j and j + half) and brings both back to affine with ONE Fermat inversion
 // (of Z_a * Z_b): the inversion is ~15 % of a single fold.
 __global__ __launch_bounds__(256) void k_fold_points(uint32_t *__restrict__ G, uint32_t m, uint32_t half, GlvArg a) {
@@ -126,52 +78,7 @@ __global__ __launch_bounds__(256) void k_fold_points(uint32_t *__restrict__ G, u
 }
 
 // ------------------------------------------------------------------ K3': two halving rounds of G in one pass
-// After two rounds without touching G the folded key is G''[j] = G[j] + s1 G[j+m] + s2 G[j+2m] + s3 G[j+3m] with
-// (s1, s2, s3) = (xi_2, xi_1, xi_1 xi_2), m = a quarter of the key (pcdl.rs:218 applied twice).  The three scalar
-// multiplications share ONE doubling chain (Straus): ~128 doublings + 3 x ~71 additions per output instead of
-// 2 x (128 + 71) for each of the 1.5 outputs the two separate folds produce -- ~38 % fewer field products for the
-// same two rounds.  The rounds in between take L and R from MSMs over the unfolded key (the "no-fold" form below).
-struct GlvArg3 {
-    uint32_t dig[3][14];  // as GlvArg, one digit string per scalar
-    int ndigits;          // longest of the three
-};
-HALO_DEV JacN fold_one4(const uint32_t *G, uint32_t j, uint32_t m, const GlvArg3 &a) {
-    constexpr uint32_t BETA[9] = {0x1342a796, 0x3fdac51, 0x54dab11, 0x5b221a6, 0xccd27ac, 0x15cc87a4, 0x1b1533b6, 0x169e85e1, 0x3b0093};
-    constexpr uint32_t BETA2[9] = {0xcbd58eb, 0x1a2f8f16, 0xd140efa, 0x7bdfb9, 0x1333ecad, 0xa33785b, 0x4eacc49, 0x9617a1e, 0x4ff6c};
-    AffN p1 = aff_load(G + AFF_STRIDE * (size_t)(j + m)), p2 = aff_load(G + AFF_STRIDE * (size_t)(j + 2 * m)),
-         p3 = aff_load(G + AFF_STRIDE * (size_t)(j + 3 * m));
-    bool live1 = !aff_is_inf(p1), live2 = !aff_is_inf(p2), live3 = !aff_is_inf(p3);
-    // acc += unit(code) * p: code is wave-uniform; lambda^e * (x, y) = (beta^e x, y)
-    auto step = [&](JacN &acc, const AffN &p, bool live, uint32_t code) {
-        if (!code) return;
-        int e = (int)((code - 1) % 3);
-        AffN q;
-        q.x = p.x;
-        if (e) q.x = fq_mul(p.x, fq_const(e == 1 ? BETA : BETA2));
-        q.y = code > 3 ? fq_neg<2>(p.y) : p.y;
-        if (live) acc = jac_madd(acc, q);
-    };
-    JacN acc = jac_inf();
-    int top = a.ndigits - 1;
-#pragma unroll 1
-    for (int word = top / 10; word >= 0; word--) {
-        uint32_t w1 = 0, w2 = 0, w3 = 0;
-#pragma unroll
-        for (int q = 0; q < 14; q++) {
-            w1 = (q == word) ? a.dig[0][q] : w1;
-            w2 = (q == word) ? a.dig[1][q] : w2;
-            w3 = (q == word) ? a.dig[2][q] : w3;
-        }
-#pragma unroll 1
-        for (int k = (word == top / 10) ? (top % 10) : 9; k >= 0; k--) {
-            acc = jac_dbl(acc);
-            step(acc, p1, live1, (w1 >> (3 * k)) & 7u);
-            step(acc, p2, live2, (w2 >> (3 * k)) & 7u);
-            step(acc, p3, live3, (w3 >> (3 * k)) & 7u);
-        }
-    }
-    return jac_madd(acc, aff_load(G + AFF_STRIDE * (size_t)j));
-}
+// fold_one4 (fold_lane.hpp) is one lane's G[j] + s1 G[j+m] + s2 G[j+2m] + s3 G[j+3m].
 // G (read) and out (written) may be the same array: a lane reads the indices j + t m and writes index j only
 __global__ __launch_bounds__(256, 2) void k_fold_points4(const uint32_t *G, uint32_t *out, uint32_t m, uint32_t half, GlvArg3 a) {
     // the first result waits in LDS while the second ladder runs (three bases + the accumulator + a mixed addition's
@@ -917,7 +824,8 @@ __global__ __launch_bounds__(256) void k_nofold_s_update_batch(const uint64_t *_
 }
 
 // ================================================================== host launchers
-int ipa_fold_points(halo_ctx *ctx, uint32_t *d_G, size_t m, const host::Fr &xi_mont) {
+// form (development hook, halo_dev_fold_points): 0 = the size decides; 1 / 2 = one / two outputs per lane whatever m is
+int ipa_fold_points(halo_ctx *ctx, uint32_t *d_G, size_t m, const host::Fr &xi_mont, int form) {
     if (m == 0) return HALO_OK;
     host::GlvDigits dg = host::glv_digits(xi_mont);
     GlvArg a;
@@ -925,18 +833,21 @@ int ipa_fold_points(halo_ctx *ctx, uint32_t *d_G, size_t m, const host::Fr &xi_m
     for (int i = 0; i < dg.n; ++i) a.dig[i / 10] |= (uint32_t)dg.d[i] << (3 * (i % 10));
     a.ndigits = dg.n;
     // a lane folds the points j and j + half where that still leaves >= 4 waves per SIMD; below, one point per lane
-    size_t half = m >= ((size_t)1 << 18) ? (m + 1) / 2 : m;
+    size_t half = (form ? form == 2 : m >= ((size_t)1 << 18)) ? (m + 1) / 2 : m;
     HALO_LAUNCH(ctx, "k_fold_points", k_fold_points, dim3((unsigned)((half + 255) / 256)), dim3(256), 0, d_G, (uint32_t)m, (uint32_t)half, a);
     HALO_HIP(hipGetLastError());
     return HALO_OK;
 }
 // dst[j] <- src[j] + s[0] src[j+m] + s[1] src[j+2m] + s[2] src[j+3m], j < m (dst may be src)
-int ipa_fold_points4(halo_ctx *ctx, const uint32_t *d_src, uint32_t *d_dst, size_t m, const host::Fr s[3]) {
+// form (development hook): 0 = the sizes decide; 1 / 2 = k_fold_points4 with one / two outputs per lane; 3 = the quad kernel;
+// 4 / 5 = the table kernel with one / two outputs per lane, an error where it cannot run
+int ipa_fold_points4(halo_ctx *ctx, const uint32_t *d_src, uint32_t *d_dst, size_t m, const host::Fr s[3], int form) {
     if (m == 0) return HALO_OK;
-    {   // the fold from the context's own (constant) key: a comb table replaces the doubling chain (foldtab.hip)
-        int done = fold_points4_tab(ctx, d_src, d_dst, m, s);
+    if (form == 0 || form >= 4) {  // the fold from the context's own (constant) key: a comb table replaces the doubling chain (foldtab.hip)
+        int done = fold_points4_tab(ctx, d_src, d_dst, m, s, form);
         if (done < 0) return done;
         if (done) return HALO_OK;
+        if (form) { set_error("fold_points4: the table kernel cannot run here (not the context's own key, in place, or no table)"); return HALO_E_ARG; }
     }
     GlvArg3 a;
     a.ndigits = 0;
@@ -946,12 +857,12 @@ int ipa_fold_points4(halo_ctx *ctx, const uint32_t *d_src, uint32_t *d_dst, size
         for (int i = 0; i < dg.n; ++i) a.dig[t][i / 10] |= (uint32_t)dg.d[i] << (3 * (i % 10));
         if (dg.n > a.ndigits) a.ndigits = dg.n;
     }
-    if (m < ((size_t)1 << 16)) {  // a latency chain at this size: one output per quad (in place is fine: a quad reads j + t m, writes j)
+    if (form ? form == 3 : m < ((size_t)1 << 16)) {  // a latency chain at this size: one output per quad (in place is fine: a quad reads j + t m, writes j)
         HALO_LAUNCH(ctx, "k_fold_points4_quad", k_fold_points4_quad, dim3((unsigned)((4 * m + 255) / 256)), dim3(256), 0, d_src, d_dst, (uint32_t)m, a);
         HALO_HIP(hipGetLastError());
         return HALO_OK;
     }
-    size_t half = m >= ((size_t)1 << 17) ? (m + 1) / 2 : m;
+    size_t half = (form ? form == 2 : m >= ((size_t)1 << 17)) ? (m + 1) / 2 : m;
     HALO_LAUNCH(ctx, "k_fold_points4", k_fold_points4, dim3((unsigned)((half + 255) / 256)), dim3(256), 0, d_src, d_dst, (uint32_t)m, (uint32_t)half, a);
     HALO_HIP(hipGetLastError());
     return HALO_OK;

@@ -97,6 +97,22 @@ int halo_set_task_len(halo_ctx *ctx, int len);
 int halo_dev_small_msm_seg(halo_ctx *ctx, const uint64_t *points, const uint64_t *scalars, const size_t *lens, size_t nsums,
                            uint64_t *out_jac);
 
+/* One point fold of pcdl::open's halving loop on its own, through the product's launcher: out[j] = G[j] + xi G[j+m] (levels 1,
+ * m = n / 2) or G[j] + s1 G[j+m] + s2 G[j+2m] + s3 G[j+3m] (levels 2, m = n / 4; two rounds xi1, xi2 are (s1, s2, s3) =
+ * (xi2, xi1, xi1 xi2)).  key_affine = n x 8 words, (0, 0) = infinity -- any points, m may be odd -- or NULL: the first n points of
+ * the context's own key.  scalars: xi, or s1 | s2 | s3, Montgomery words.  The path is upload, k_aff_to_native, ipa_fold_points /
+ * ipa_fold_points4, k_native_to_aff, download; out_affine = m x 8 words.
+ * form picks the kernel form whatever m is: 0 = what the product chooses at this m; 1 = one output per lane; 2 = two outputs per
+ * lane (j and j + (m + 1) / 2, one shared inversion); 3 = one output per quad (levels 2); 4 / 5 = the comb-table kernel with one /
+ * two outputs per lane (levels 2, key_affine == NULL, n = the context's size >= 64; the table is built as halo_set_fold_table(ctx,
+ * 1) would at the next open, and released again if the context's mode is 0).
+ * in_place != 0 (levels 2): destination == source (a lane reads j + t m and writes j); the table kernel never allows it.  The
+ * one-level kernel always folds in place: in a copy of the key.  The context's own key is never written.
+ * HALO_E_ARG: n not a positive multiple of 2 levels (or above 2^24, or above the context's size with NULL), levels not 1 / 2, a
+ * form the levels do not have, a table form with a foreign key, another size or in_place. */
+int halo_dev_fold_points(halo_ctx *ctx, const uint64_t *key_affine, size_t n, int levels, const uint64_t *scalars, int form, int in_place,
+                         uint64_t *out_affine);
+
 /* The decode batch's square root in Fq (the routine of k_point_decompress) on its own, one lane per element: a = m x 4
  * Montgomery words; ok_out[i] = 1 and root_out[i]^2 = a[i] if a[i] is a square, else ok_out[i] = 0 */
 int halo_dev_fq_sqrt(halo_ctx *ctx, const uint64_t *a, size_t m, uint64_t *root_out, uint32_t *ok_out);

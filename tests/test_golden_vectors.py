@@ -109,6 +109,21 @@ def test_gpu_fold_vector(vec, gctx, switch):
         ipa = h._lib.Ipa(gctx, 8, mont(f["c"]), orc.fr_to_mont(int(f["z"], 16)))
         L, R = ipa.round_lr(H)
         assert orc.point_canonical(L) == P(f["L"]) and orc.point_canonical(R) == P(f["R"])
+        # the fold with the fixture's xi: G_out from the fold kernel over the same 8 points (halo_dev_fold_points), c_out and z_out
+        # from k_fold_scalars -- their dot product on this state, each pair (j, j + 4) on a 2-element state of its own
+        xi = orc.fr_to_mont(int(f["xi"], 16)); xi_inv = orc.z(4); assert orc.lib().orc_fr_inv(orc.ptr(xi), orc.ptr(xi_inv)) == 0
+        for form in (0, 1, 2):
+            G_out = gctx.fold_points(None, 1, xi, form=form, n=8)
+            assert [orc.affine_canonical(G_out[j]) for j in range(4)] == [P(p) for p in f["G_out"]]
+        ipa.round_fold(xi, xi_inv)
+        c_out, z_out = [int(h, 16) for h in f["c_out"]], [int(h, 16) for h in f["z_out"]]
+        assert orc.fr_from_mont(ipa.dot_cz()) == sum(a * b for a, b in zip(c_out, z_out)) % pm.R_ORDER
+        cs, zs = mont(f["c"]), orc.powers(orc.fr_to_mont(int(f["z"], 16)), 8)
+        for j in range(4):
+            pair = h._lib.Ipa(gctx, 2, cs[[j, j + 4]], None, z_vec=zs[[j, j + 4]])
+            pair.round_fold(xi, xi_inv)
+            _, c1, z1 = pair.finish_z()
+            assert (orc.fr_from_mont(c1), orc.fr_from_mont(z1)) == (c_out[j], z_out[j])
     finally:
         gctx.set_ipa_switch(1 << 14)
 

@@ -98,10 +98,13 @@ def test_u_check(hal, ctx, ipa_mode):
     assert [orc.fr_from_mont(c) for c in ctx.h_coeffs(xm)] == [1, 3, 2, 6, 1, 3, 2, 6]
 
 
-@pytest.fixture(params=[(0, 1, 0), (1 << 16, 2, -1), (16, 1, 0), (0, 2, 0), (16, 2, 0), (0, 2, 1), (16, 2, 1), (64, 2, 0, 1), (16, 2, 1, 1), (0, 2, 0, 1)],
-                ids=["always-fold", "default", "switch-at-16", "two-level-folds-to-the-end", "two-level-folds-switch-at-16",
-                     "fold-table-two-level-folds-to-the-end", "fold-table-switch-at-16", "folds-beside-the-rounds-switch-at-64",
-                     "fold-table-folds-beside-the-rounds-switch-at-16", "folds-beside-the-rounds-to-the-end"])
+IPA_MODES = [(0, 1, 0), (1 << 16, 2, -1), (16, 1, 0), (0, 2, 0), (16, 2, 0), (0, 2, 1), (16, 2, 1), (64, 2, 0, 1), (16, 2, 1, 1), (0, 2, 0, 1)]
+IPA_MODE_IDS = ["always-fold", "default", "switch-at-16", "two-level-folds-to-the-end", "two-level-folds-switch-at-16",
+                "fold-table-two-level-folds-to-the-end", "fold-table-switch-at-16", "folds-beside-the-rounds-switch-at-64",
+                "fold-table-folds-beside-the-rounds-switch-at-16", "folds-beside-the-rounds-to-the-end"]
+
+
+@pytest.fixture(params=IPA_MODES, ids=IPA_MODE_IDS)
 def ipa_mode(request, ctx):
     """Every IPA strategy must give the reference's results: folding G every round (k_fold_points), every other round
     (two halvings per pass, k_fold_points4, L/R from MSMs over the unfolded key in between), the first of those passes from
@@ -147,6 +150,86 @@ def test_ipa_rounds_vs_oracle(hal, ctx, pp, n, ipa_mode):
         m //= 2
     U, c = ipa.finish()
     assert canon(U) == canon(gj[0]) and c.tolist() == cs[0].tolist()
+
+
+# The same round-by-round comparison over a key of exceptional points and a chosen challenge schedule: the folded key cannot be
+# read, so a wrong output point of a fold kernel shows as a wrong L, R of a later round or a wrong U
+@pytest.fixture(scope="module")
+def xkey():
+    """1024 points in the classes of tests/fold_cases.py (infinities, equal, opposite and lambda-related points; G[j] = +-(the sum
+    the first two rounds add to it) for the challenges (r - 1, lambda))"""
+    import fold_cases as fc
+    key, key_jac, classes = fc.make_key(2, 256, fc.triple_of(("pair", fc.R - 1, fc.LAM)), 0)
+    assert set(classes) == set(fc.L2_CLASSES)
+    return key, key_jac
+
+
+@pytest.fixture(scope="module")
+def xctx(hal, xkey):
+    c = hal._lib.Context(bases=xkey[0])
+    yield c
+    c.close()
+
+
+_XKEY_TRANSCRIPTS = {}
+
+
+def _xkey_transcript(hal, xkey, which, edges):
+    """the oracle's rounds over the exceptional key, once per (coefficients, schedule): [(xi, xi_inv, L, R)], U, c"""
+    import fold_cases as fc
+    if (which, edges) not in _XKEY_TRANSCRIPTS:
+        n = 1024
+        _, H = hal._lib.public_points()
+        Hp = np.ascontiguousarray(H, dtype=np.uint64)
+        zx, seed = orc.rng_scalars(0x584B4559, 1)
+        cs = np.zeros((n, 4), dtype=np.uint64)
+        if which == "random":
+            cs[: n - 1], seed = orc.rng_scalars(seed, n - 1)
+        else:
+            cs[0 if which == "e_0" else n - 1] = orc.fr_to_mont(1)
+        coeffs = cs.copy()
+        gj, zs = xkey[1].copy(), orc.powers(zx[0], n)
+        rounds, m, k = [], n // 2, 0
+        while m >= 1:
+            Lw, Rw = orc.z(12), orc.z(12)
+            orc.lib().orc_ipa_round_lr(orc.ptr(gj), orc.ptr(cs), orc.ptr(zs), orc.C.c_size_t(m), orc.ptr(Hp), orc.ptr(Lw), orc.ptr(Rw))
+            if k < len(edges):
+                xi = orc.fr_to_mont(edges[k])
+            else:
+                xr, seed = orc.rng_scalars(seed, 1)
+                xi = xr[0].copy()
+            xi_inv = orc.z(4); assert orc.lib().orc_fr_inv(orc.ptr(xi), orc.ptr(xi_inv)) == 0
+            orc.lib().orc_ipa_round_fold(orc.ptr(gj), orc.ptr(cs), orc.ptr(zs), orc.C.c_size_t(m), orc.ptr(xi), orc.ptr(xi_inv))
+            rounds.append((xi, xi_inv, canon(Lw), canon(Rw)))
+            m //= 2; k += 1
+        _XKEY_TRANSCRIPTS[(which, edges)] = (coeffs, zx[0], Hp, rounds, canon(gj[0]), cs[0].tolist())
+    return _XKEY_TRANSCRIPTS[(which, edges)]
+
+
+@pytest.mark.parametrize("which", ["random", "e_0", "e_n-1"])
+@pytest.mark.parametrize("mode", IPA_MODES, ids=IPA_MODE_IDS)
+def test_ipa_rounds_over_an_exceptional_key_vs_oracle(hal, xctx, xkey, mode, which):
+    """L, R of every round, U and c at the end, under every IPA strategy, over the exceptional key with edge challenges in the
+    first two rounds (the xi1, xi2 of a two-level fold), random ones after.  The coefficient vectors e_0 and e_(n-1) leave c1 = 0
+    or c0 = 0 in the last round -- L or R at infinity -- so halo_ipa_finish takes its fallback, not U from the last round."""
+    import fold_cases as fc
+    xctx.set_ipa_switch(mode[0]); xctx.set_fold_levels(mode[1]); xctx.set_fold_table(mode[2]); xctx.set_fold_async(mode[3] if len(mode) > 3 else 0)
+    try:
+        for edges in ((fc.R - 1, fc.LAM), (1 << 10, 1)):
+            coeffs, z, Hp, rounds, U_want, c_want = _xkey_transcript(hal, xkey, which, edges)
+            ipa = hal._lib.Ipa(xctx, 1024, coeffs, z)
+            for k, (xi, xi_inv, L_want, R_want) in enumerate(rounds):
+                L, R = ipa.round_lr(Hp)
+                assert (canon(L), canon(R)) == (L_want, R_want), (edges, k)
+                ipa.round_fold(xi, xi_inv)
+            if which != "random":
+                assert rounds[-1][2] is None or rounds[-1][3] is None  # (L or R of the last round at infinity)
+            U, c = ipa.finish()
+            assert canon(U) == U_want and c.tolist() == c_want, edges
+            ipa.close()
+    finally:
+        xctx.set_fold_async(-1); xctx.set_ipa_switch(1 << 14); xctx.set_fold_levels(2)
+        xctx.set_fold_table(0); xctx.set_fold_table(-1)
 
 
 # ------------------------------------------------------------------ pcdl level

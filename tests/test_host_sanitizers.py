@@ -80,7 +80,7 @@ def test_negation_bound_is_counted_where_a_negated_operand_is_used():
     reviewed = {
         ("curve.hpp", "xyzz_madd", 8, "acc.y"): "fused", ("curve.hpp", "jac_madd", 8, "p.y"): "fused", ("curve.hpp", "xyzz_add", 2, "S1"): "fused",
         ("curve.hpp", "aff_cneg", 2, "p.y"): "sign of y", ("curve.hpp", "aff_store", 2, "a.y"): "sign of y",
-        ("ipa.hip", "fold_one", 2, "hi.y"): "sign of y", ("ipa.hip", "fold_one4", 2, "p.y"): "sign of y",
+        ("fold_lane.hpp", "fold_one", 2, "hi.y"): "sign of y", ("fold_lane.hpp", "fold_one4", 2, "p.y"): "sign of y",
         ("ipa.hip", "k_fold_points4_quad", 2, "p.y"): "sign of y",
     }
     sites = lz.neg_call_sites()
