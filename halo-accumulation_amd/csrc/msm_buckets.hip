@@ -146,12 +146,16 @@ __global__ __launch_bounds__(256) void k_msm_task_order(const uint32_t *__restri
     if (live) order[base[bin] + rank] = rec;
 }
 
+// One lane per record of `order`.  Records [0, ovf_records) are live up to *live (the general pipeline: every record, *live = the
+// number of tasks; the table pipeline: the overflow region in front of its static layout, *live = what the sort reserved);
+// the records behind are all there and a length of 0 marks an empty one (the table pipeline's slot of an empty bucket).
 __global__ __launch_bounds__(256) void k_msm_accumulate(const uint32_t *__restrict__ bases, const uint32_t *__restrict__ sorted,
-                                                        const uint32_t *__restrict__ meta, const uint4 *__restrict__ order,
-                                                        uint32_t *__restrict__ partial) {
+                                                        const uint32_t *__restrict__ live, uint32_t ovf_records,
+                                                        const uint4 *__restrict__ order, uint32_t *__restrict__ partial) {
     uint32_t tid = blockIdx.x * 256 + threadIdx.x;
-    if (tid >= meta[0]) return;
+    if (tid < ovf_records && tid >= *live) return;
     uint4 rec = order[tid];
+    if (rec.z == 0) return;
     uint32_t t = rec.x, st = rec.y, cnt = rec.z;
     XyzzN acc = xyzz_inf();
     // the next point's coordinates are fetched before the current mixed add is issued, and ITS index one add earlier

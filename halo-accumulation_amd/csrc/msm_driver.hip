@@ -59,7 +59,7 @@ static int workspace_alloc_buffers(MsmWorkspace &ws, const WorkspaceNeed &need) 
     HALO_HIP(hipMalloc(&ws.d_biglist, ws.cap_counts * 4));
     HALO_HIP(hipMalloc(&ws.d_meta, 1024));
     HALO_HIP(hipMalloc(&ws.d_task_g, ws.cap_tasks * 4));
-    HALO_HIP(hipMalloc(&ws.d_order, ws.cap_tasks * 16));  // uint4 per task (k_msm_task_order)
+    HALO_HIP(hipMalloc(&ws.d_order, ws.cap_tasks * 16));  // uint4 per record (k_msm_task_order; table pipeline: k_tmsm_fine_sort)
     HALO_HIP(hipMalloc(&ws.d_seg, ws.cap_windows * 64 * 2 * XYZZ_WORDS * 4));
     HALO_HIP(hipMalloc(&ws.d_winsum, ws.cap_windows * 12 * 8));
     // (the host reads both while the kernel that writes them is still running: fine-grained coherent, said explicitly)
@@ -85,10 +85,14 @@ int msm_workspace_alloc(halo_ctx *ctx, size_t n, int slot) {
     // (a key of the c = 20 table plan: room for the TWO bucket sets of a tagged launch from the start -- growing the workspace at
     // the first tagged launch cost the first open of a context a second of hipFree / hipMalloc)
     if (n >= ((size_t)1 << 20) && need.counts < ((size_t)1 << 20)) need.counts = (size_t)1 << 20;
-    {   // tasks: one per non-empty bucket plus entries / kmax (kmax = 16 only below 2^18 points, W <= 32 there)
+    {   // tasks: one per non-empty bucket plus entries / kmax (kmax = 16 only below 2^18 points, W <= 32 there).
+        // cap_tasks sizes the partials (d_buckets), d_task_g and the bucket kernel's records (d_order):
+        //   general pipeline: tasks <= buckets + entries / kmax, one record and one task_g word per task;
+        //   table pipeline: task ids as above; d_order holds an overflow region of entries / kmax + 1 records rounded up to
+        //     256, then one record per bucket of every set (sets * B, k_tmsm_fine_sort) -- hence + 256; d_task_g is not used.
         size_t small = need.sorted < ((size_t)1 << 23) ? need.sorted : ((size_t)1 << 23);
         size_t extra = need.sorted / KMAX > small / 16 ? need.sorted / KMAX : small / 16;
-        need.tasks = need.counts + extra + 1;
+        need.tasks = need.counts + extra + 256;
     }
     need.hist = (size_t)256 * 32768 + need.counts;  // W * nchunks <= 256 blocks of B <= 32768 counters
     need.windows = 64;
@@ -142,7 +146,7 @@ static bool batch_need(const halo_ctx *ctx, const MsmWorkspace &ws, size_t n, in
         if (total < sets << 16) total = sets << 16;
     }
     size_t hist = (Wt > 256 ? Wt : 256) * (size_t)p.B;
-    size_t tasks = total + sorted / msm_kmax(ctx, n) + 1;
+    size_t tasks = total + sorted / msm_kmax(ctx, n) + 256;  // (+ 256: the table pipeline rounds its overflow region, msm_workspace_alloc)
     bool grow = n > ws.cap_n || total > ws.cap_counts || sorted > ws.cap_sorted || hist > ws.cap_hist || Wt > ws.cap_windows ||
                 tasks > ws.cap_tasks;
     need.n = n > ws.cap_n ? n : ws.cap_n;
@@ -197,7 +201,7 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
         if (members.tagged) {  // two sets of 2^19 buckets: per-bucket arrays of 2^20, a task per non-empty bucket and per kmax entries beyond
             const TblPlan tp = ctx->tbl;
             size_t counts = 2 * (size_t)tp.B, kmax = ctx->task_len > 0 ? (size_t)ctx->task_len : KMAX;
-            size_t tasks = counts + (size_t)tp.W * n / kmax + 1;
+            size_t tasks = counts + (size_t)tp.W * n / kmax + 256;
             if (counts > ws.cap_counts || tasks > ws.cap_tasks) {
                 need.n = ws.cap_n; need.sorted = ws.cap_sorted; need.hist = ws.cap_hist; need.windows = ws.cap_windows;
                 need.counts = counts > ws.cap_counts ? counts : ws.cap_counts;
@@ -222,9 +226,14 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
         tuning().piece_alternate) {
         int cand = slot ^ 1;
         if (!ctx->wss[cand].in_flight) {
-            if (!ctx->wss[cand].d_counts || ctx->wss[cand].cap_n < ws.cap_n) {
-                if (ctx->wss[cand].d_counts) { alloc_epoch_bump(ctx); workspace_release(ctx->wss[cand]); }
-                if (msm_workspace_alloc(ctx, ws.cap_n, cand) == HALO_OK) partner = cand;
+            // the partner runs pieces of THIS launch: it needs this slot's capacities, which a forced task length may have grown
+            // beyond what a workspace for cap_n points gets (batch_need above: more tasks, more records in d_order)
+            MsmWorkspace &pw = ctx->wss[cand];
+            if (!pw.d_counts || pw.cap_n < ws.cap_n || pw.cap_tasks < ws.cap_tasks || pw.cap_counts < ws.cap_counts || pw.cap_sorted < ws.cap_sorted) {
+                WorkspaceNeed like{ws.cap_n, ws.cap_counts, ws.cap_sorted, ws.cap_tasks, ws.cap_hist, ws.cap_windows};
+                alloc_epoch_bump(ctx);
+                if (pw.d_counts) workspace_release(pw);
+                if (workspace_alloc(pw, like) == HALO_OK) partner = cand;
                 else (void)hipGetLastError();  // no room for a second workspace: the pieces run one after the other, same result
             } else partner = cand;
         }

@@ -37,6 +37,9 @@ constexpr size_t TBL_PIECE = 1310720;
 constexpr uint32_t TDIGIT_NONE = 0xFFFFFFFFu;
 constexpr int TBL_E = 4;  // points per lane of the kernels that share one inversion (k_table_step, k_batch_to_affine)
 constexpr uint32_t TBL_STAGE = 35840;  // entries staged in LDS: 140 KiB next to 20 KiB of counters
+constexpr uint32_t TBL_ORDER_RUN = 8;  // consecutive ranks of one range in a wave of the bucket kernel (k_tmsm_fine_sort); divides 64
+// words of a launch's small state (d_meta, 256 words, cleared by the recode kernels) beside the ones named in msm_buckets.hip
+constexpr uint32_t META_OVF = 141;        // table pipeline: records reserved in the overflow region of `order`
 
 struct MemberScalars { const uint64_t *p[MSM_MAX_BATCH]; };
 struct MemberOffsets { uint32_t v[MSM_MAX_BATCH]; };
@@ -61,8 +64,8 @@ __global__ __launch_bounds__(256) void k_msm_task_order(const uint32_t *__restri
                                                         const uint32_t *__restrict__ toff, const uint32_t *__restrict__ tblockoff,
                                                         uint32_t kmax, uint4 *__restrict__ order);
 __global__ __launch_bounds__(256) void k_msm_accumulate(const uint32_t *__restrict__ bases, const uint32_t *__restrict__ sorted,
-                                                        const uint32_t *__restrict__ meta, const uint4 *__restrict__ order,
-                                                        uint32_t *__restrict__ partial);
+                                                        const uint32_t *__restrict__ live, uint32_t ovf_records,
+                                                        const uint4 *__restrict__ order, uint32_t *__restrict__ partial);
 __global__ __launch_bounds__(64) void k_msm_combine(const uint32_t *__restrict__ ntask, const uint32_t *__restrict__ toff,
                                                     const uint32_t *__restrict__ tblockoff, const uint32_t *__restrict__ meta,
                                                     const uint32_t *__restrict__ biglist, uint32_t total, uint32_t small_blocks,

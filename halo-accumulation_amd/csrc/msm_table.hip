@@ -18,8 +18,8 @@ namespace halo {
 //   * the weighted bucket sum is taken once over 2^19 buckets -- as many as 16 windows x 2^15 today -- and the host no longer
 //     runs a 240-doubling Horner chain: it combines 16 (plain, weighted) pairs with ~50 additions.
 // The sort is the two-level one (coarse: 512 bucket ranges, runs advance sequentially; fine: one block per range, 1024 buckets,
-// staged in LDS); everything after it (tasks, k_msm_accumulate, combine, window sums) is the general pipeline's, which sees
-// 16 "virtual windows" of 2^15 buckets.
+// staged in LDS, which also writes the bucket kernel's task records); everything after it (k_msm_accumulate, combine, window
+// sums) is the general pipeline's, which sees 16 "virtual windows" of 2^15 buckets.
 //
 // Two plans (TblPlan, fixed when a context builds its table):
 //   key of >= 2^20 points: c = 20, 13 windows, 2^19 buckets, 512 coarse ranges of 1024 buckets, 16 virtual windows of 2^15;
@@ -282,16 +282,34 @@ __global__ __launch_bounds__(1024) void k_tmsm_coarse_scatter2(const uint32_t *_
 // Fine sort of run r: counts and absolute starts of its 1024 buckets, entries placed in [lo, hi) of `sorted` -- and the
 // task lists the general pipeline builds with four more kernels (k_scan_blocks/_top, k_msm_task_bins, k_msm_task_order):
 // a bucket of c entries is ceil(c / kmax) tasks with consecutive ids; the block reserves its ids with one atomic
-// (meta[0]), writes toff[g] = first id (absolute: the block offsets of the two-level scan format stay zero) and task_g, and
-// adds its tasks-per-length counts to meta[2 ..]: k_msm_task_order then lays the tasks out by decreasing length over the
-// WHOLE launch (longest first: with a per-block order the last waves of k_msm_accumulate were long ones, +35 % on it).
+// (meta[0]) and writes toff[g] = first id (absolute: the block offsets of the two-level scan format stay zero).
 // Multi-task buckets are listed for k_msm_combine (meta[1], meta[140]).
+//
+// The block also writes the bucket kernel's records (`order`, the format of k_msm_task_order) for its own buckets, into a
+// STATIC layout that needs no global length histogram -- and so no launch between the sort and the bucket kernel:
+//   * every bucket has one slot in [obase, obase + ranges * 2^fbits): its LAST task (the only one, for uniform scalars), or a
+//     record of length 0 for an empty bucket.  Inside the block a bucket gets rank rho by decreasing length of that task (a
+//     counting sort over the 65 lengths, lbin); the slot is rank-major over the whole launch: ranks [8 q, 8 q + 8) of every
+//     range come before ranks [8 q + 8, ..) of any range, and a wave of the bucket kernel holds TBL_ORDER_RUN = 8 consecutive
+//     ranks of 64 / 8 = 8 neighbouring ranges (tmsm_order_slot).  Ranges are statistically alike, so the lanes of a wave run
+//     chains of near-equal length and the longest waves of all ranges are dispatched first (a per-block order, each range's
+//     tasks contiguous, had the long waves last: +35 % on k_msm_accumulate);
+//   * the tasks in front of a bucket's last (buckets of more than kmax entries: skewed scalars, a short forced task length) are
+//     all of the full length kmax and go to the overflow region [0, obase), reserved per block with one atomic on
+//     meta[META_OVF]: they run first.
+// The records carry a task's first entry, so they are written after the placement.
+HALO_DEV uint32_t tmsm_order_slot(uint32_t rho, uint32_t r, uint32_t ranges) {
+    constexpr uint32_t G = 64u / TBL_ORDER_RUN;  // ranges side by side in a wave
+    return ((rho / TBL_ORDER_RUN) * (ranges / G) + r / G) * 64u + (r % G) * TBL_ORDER_RUN + rho % TBL_ORDER_RUN;
+}
 __global__ __launch_bounds__(1024) void k_tmsm_fine_sort(const uint32_t *__restrict__ presort, const uint16_t *__restrict__ presort_fine,
                                                          const uint32_t *__restrict__ cstart, uint32_t kmax, TblPlan tp, uint32_t *__restrict__ counts,
                                                          uint32_t *__restrict__ starts, uint32_t *__restrict__ ntask, uint32_t *__restrict__ toff,
-                                                         uint32_t *__restrict__ task_g, uint32_t *__restrict__ biglist,
-                                                         uint32_t *__restrict__ meta, uint32_t *__restrict__ sorted) {
-    __shared__ uint32_t hist[1024], scan[1024], tscan[1024], lbin[KMAX + 8], misc[2];
+                                                         uint32_t *__restrict__ biglist, uint32_t *__restrict__ meta, uint32_t *sorted,
+                                                         uint32_t obase, uint4 *__restrict__ order) {
+    // lbin: [0, 65) buckets per length of the last task (64 - length), then the counters of the block's lists (LB_*)
+    constexpr uint32_t LB_BIG = KMAX + 1, LB_SMALL = KMAX + 2, LB_BIG0 = KMAX + 3, LB_SMALL0 = KMAX + 4, LB_OVF0 = KMAX + 5;
+    __shared__ uint32_t hist[1024], scan[1024], tscan[1024], lbin[KMAX + 8], lbase[KMAX + 1], wlive[16], misc[2];
     uint32_t r = blockIdx.x, lo = cstart[r], hi = cstart[r + 1], tid = threadIdx.x;
 #ifdef TMSM_TIMING
     uint64_t tm[10]; int tmi = 0;
@@ -335,14 +353,22 @@ __global__ __launch_bounds__(1024) void k_tmsm_fine_sort(const uint32_t *__restr
     }
     __syncthreads();
     TMARK();
-    bool owner = tid < (1u << tp.fbits);  // one bucket per thread
+    const uint32_t nb = 1u << tp.fbits;
+    bool owner = tid < nb;  // one bucket per thread
     uint32_t mine = owner ? hist[tid] : 0u, nt = (mine + kmax - 1) / kmax;
     scan[tid] = mine;
     tscan[tid] = nt;
-    // lengths of this bucket's tasks: kmax for all but the last
-    if (nt) {
-        if (nt > 1) atomicAdd(&lbin[KMAX - kmax], nt - 1);
-        atomicAdd(&lbin[KMAX - (mine - (nt - 1) * kmax)], 1u);
+    // the bucket's last task: its length, and the bucket's rank among the block's buckets of that length
+    const uint32_t llen = nt ? mine - (nt - 1) * kmax : 0u;
+    uint32_t rho = owner ? atomicAdd(&lbin[KMAX - llen], 1u) : 0u;
+    // non-empty buckets in front of this one (ballots, wave totals through LDS): with the task scan, the tasks in front that
+    // go to the overflow region
+    uint32_t live_before;
+    {
+        unsigned long long bal = __ballot(nt != 0);
+        uint32_t lane = tid & 63u;
+        live_before = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wlive[tid >> 6] = (uint32_t)__popcll(bal);
     }
     __syncthreads();
     for (uint32_t o = 1; o < 1024; o <<= 1) {
@@ -353,37 +379,47 @@ __global__ __launch_bounds__(1024) void k_tmsm_fine_sort(const uint32_t *__restr
         __syncthreads();
     }
     TMARK();
-    if (tid == 1023) misc[0] = atomicAdd(&meta[0], tscan[1023]);  // this block's task ids: [base, base + total)
-    if (tid <= KMAX && lbin[tid]) atomicAdd(&meta[2 + tid], lbin[tid]);  // tasks per length, whole launch
+    for (uint32_t wv = 0; wv < (tid >> 6); wv++) live_before += wlive[wv];
+    if (tid == 1023) {
+        misc[0] = atomicAdd(&meta[0], tscan[1023]);  // this block's task ids: [base, base + total)
+        misc[1] = tscan[1023] - (live_before + (nt != 0));  // its overflow tasks
+        lbin[LB_OVF0] = misc[1] ? atomicAdd(&meta[META_OVF], misc[1]) : 0u;
+    }
+    if (tid <= KMAX) {
+        uint32_t start = 0;  // buckets with a longer last task
+        for (uint32_t k = 0; k < tid; k++) start += lbin[k];
+        lbase[tid] = start;
+    }
     __syncthreads();
     TMARK();
-    uint32_t begin = lo + scan[tid] - mine, tfirst = misc[0] + tscan[tid] - nt;
+    const uint32_t begin = lo + scan[tid] - mine, tfirst = misc[0] + tscan[tid] - nt, ofirst = tscan[tid] - nt - live_before;
+    rho += lbase[KMAX - llen];
+    __syncthreads();
     if (owner) {
         uint32_t g = (r << tp.fbits) + tid;
         counts[g] = mine;
         ntask[g] = nt;
         starts[g] = begin;  // absolute: the block offsets of the two-level scan format are zeroed by the recode kernel
         toff[g] = tfirst;   // likewise
-        for (uint32_t j = 0; j < nt; j++) {
-            uint32_t len = j + 1 < nt ? kmax : mine - (nt - 1) * kmax;
-            task_g[tfirst + j] = g | ((KMAX - len) << 24);
-        }
         hist[tid] = begin;
     }
+    // for the overflow records, written by the whole block after the placement: first overflow task and first task id per bucket
+    scan[tid] = owner ? ofirst : 0xffffffffu;
+    tscan[tid] = tfirst;
     // multi-task buckets for k_msm_combine: counted in LDS, one reservation per block and list (a global atomic per bucket
     // serialises on one address: 1 ms when a third of the buckets hold more than kmax entries)
     TMARK();
     uint32_t big_rank = 0, small_rank = 0;
-    if (owner && nt > 8) big_rank = atomicAdd(&lbin[KMAX + 1], 1u);
-    else if (owner && nt > 1) small_rank = atomicAdd(&lbin[KMAX + 2], 1u);
+    if (owner && nt > 8) big_rank = atomicAdd(&lbin[LB_BIG], 1u);
+    else if (owner && nt > 1) small_rank = atomicAdd(&lbin[LB_SMALL], 1u);
     __syncthreads();
     if (tid == 0) {
-        lbin[KMAX + 3] = lbin[KMAX + 1] ? atomicAdd(&meta[1], lbin[KMAX + 1]) : 0u;
-        lbin[KMAX + 4] = lbin[KMAX + 2] ? atomicAdd(&meta[140], lbin[KMAX + 2]) : 0u;
+        lbin[LB_BIG0] = lbin[LB_BIG] ? atomicAdd(&meta[1], lbin[LB_BIG]) : 0u;
+        lbin[LB_SMALL0] = lbin[LB_SMALL] ? atomicAdd(&meta[140], lbin[LB_SMALL]) : 0u;
     }
     __syncthreads();
-    if (owner && nt > 8) biglist[lbin[KMAX + 3] + big_rank] = (r << tp.fbits) + tid;
-    else if (owner && nt > 1) biglist[tp.B - 1 - (lbin[KMAX + 4] + small_rank)] = (r << tp.fbits) + tid;
+    if (owner && nt > 8) biglist[lbin[LB_BIG0] + big_rank] = (r << tp.fbits) + tid;
+    else if (owner && nt > 1) biglist[tp.B - 1 - (lbin[LB_SMALL0] + small_rank)] = (r << tp.fbits) + tid;
     extern __shared__ uint32_t stage[];  // TBL_STAGE entries
     TMARK();
     if (staged) {
@@ -393,32 +429,51 @@ __global__ __launch_bounds__(1024) void k_tmsm_fine_sort(const uint32_t *__restr
         __syncthreads();
         TMARK();
         for (uint32_t e = lo + tid; e < hi; e += 1024) sorted[e] = stage[e - lo];
-#ifdef TMSM_TIMING
-        TMARK();
-        if (tid == 0 && (blockIdx.x % 100 == 0 || tm[8] - tm[0] > 3000))
-            printf("fine block %u (%u entries): load %llu hist %llu scan %llu reserve %llu owner %llu biglist %llu place %llu write %llu (x10 ns)\n", blockIdx.x, hi - lo,
-                   (unsigned long long)(tm[1] - tm[0]), (unsigned long long)(tm[2] - tm[1]), (unsigned long long)(tm[3] - tm[2]), (unsigned long long)(tm[4] - tm[3]),
-                   (unsigned long long)(tm[5] - tm[4]), (unsigned long long)(tm[6] - tm[5]), (unsigned long long)(tm[7] - tm[6]), (unsigned long long)(tm[8] - tm[7]));
-#endif
-        return;
-    }
-    for (uint32_t e = lo + tid; e < hi; e += 4 * 1024) {  // an oversized run (skewed scalars): placed directly
-        uint32_t v[4], f[4], pos[4];
+    } else {
+        for (uint32_t e = lo + tid; e < hi; e += 4 * 1024) {  // an oversized run (skewed scalars): placed directly
+            uint32_t v[4], f[4], pos[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            bool in = e + k * 1024 < hi;
-            v[k] = in ? presort[e + k * 1024] : 0u;
-            f[k] = in ? presort_fine[e + k * 1024] : 0u;
+            for (int k = 0; k < 4; k++) {
+                bool in = e + k * 1024 < hi;
+                v[k] = in ? presort[e + k * 1024] : 0u;
+                f[k] = in ? presort_fine[e + k * 1024] : 0u;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) pos[k] = e + k * 1024 < hi ? atomicAdd(&hist[f[k]], 1u) : 0u;
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (e + k * 1024 < hi) sorted[pos[k]] = v[k];
         }
-#pragma unroll
-        for (int k = 0; k < 4; k++) pos[k] = e + k * 1024 < hi ? atomicAdd(&hist[f[k]], 1u) : 0u;
-#pragma unroll
-        for (int k = 0; k < 4; k++)
-            if (e + k * 1024 < hi) sorted[pos[k]] = v[k];
+        __threadfence();  // the records below read entries that other threads of the block have just placed
+        __syncthreads();
+    }
+    // a placed entry: from the stage, or from `sorted` past this CU's vector cache
+    auto entry = [&](uint32_t e) -> uint32_t { return staged ? stage[e - lo] : __hip_atomic_load(&sorted[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+    // the bucket's slot in the static region: its last task, or an empty record
+    if (owner) {
+        uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+        if (nt) {
+            uint32_t st = begin + (nt - 1) * kmax;
+            rec = make_uint4(tfirst + nt - 1, st, llen, entry(st));
+        }
+        order[obase + tmsm_order_slot(rho, r, gridDim.x)] = rec;
+    }
+    // the overflow region: task i of the block's overflow tasks belongs to the last bucket b with scan[b] <= i (hist[b] is
+    // the end of bucket b's entries by now: the start of bucket b + 1)
+    const uint32_t novf = misc[1], ovf0 = lbin[LB_OVF0];
+    for (uint32_t i = tid; i < novf; i += 1024) {
+        uint32_t b0 = 0, b1 = nb - 1;
+        while (b0 < b1) {
+            uint32_t mid = (b0 + b1 + 1) >> 1;
+            if (scan[mid] <= i) b0 = mid; else b1 = mid - 1;
+        }
+        uint32_t j = i - scan[b0], st = (b0 ? hist[b0 - 1] : lo) + j * kmax;
+        order[ovf0 + i] = make_uint4(tscan[b0] + j, st, kmax, entry(st));
     }
 #ifdef TMSM_TIMING
     TMARK();
-    if (tid == 0) printf("fine block %u UNSTAGED (%u entries): total %llu (x10 ns)\n", blockIdx.x, hi - lo, (unsigned long long)(tm[tmi - 1] - tm[0]));
+    if (tid == 0 && (blockIdx.x % 100 == 0 || tm[tmi - 1] - tm[0] > 3000))
+        printf("fine block %u (%u entries, %s): total %llu (x10 ns)\n", blockIdx.x, hi - lo, staged ? "staged" : "UNSTAGED", (unsigned long long)(tm[tmi - 1] - tm[0]));
 #endif
 }
 
@@ -566,6 +621,17 @@ static TblPlan table_launch_plan(const halo_ctx *ctx, int count) {
     if (count > 1 && tp.vw_bits < 15 && tp.B >= (1u << 15)) { tp.vw_bits = 15; tp.vw = tp.B >> 15; }
     return tp;
 }
+// task length of the bucket kernel for a table launch of `entries` digits: the chain bound per lane, the W n additions over the
+// chip's 2048 x 64 lanes in one round
+static uint32_t tmsm_kmax(const halo_ctx *ctx, size_t entries) {
+    if (ctx->task_len > 0) return (uint32_t)ctx->task_len;
+    if (entries <= (size_t)16 * 131072) return 16;
+    if (entries <= (size_t)32 * 131072) return 32;
+    return KMAX;
+}
+// records in front of the static layout of `order`: one per kmax entries at most (the bound of the tasks beyond one per
+// bucket), rounded so that the blocks of the bucket kernel line up with the static layout
+static size_t tmsm_ovf_records(size_t entries, uint32_t kmax) { return (entries / kmax + 1 + 255) / 256 * 256; }
 int tmsm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MsmBatch &members, bool mont, size_t n, int partner) {
     const TblPlan tp = table_launch_plan(ctx, members.count);
     size_t pieces = tp.c == 20 ? (n + TBL_PIECE - 1) / TBL_PIECE : 1;
@@ -583,7 +649,10 @@ int tmsm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bas
     int slot = (int)(&ws - ctx->wss);
     hipStream_t mine = ctx->stream;
     if (partner >= 0) {
-        if (2 * tp.vw * cpow > ctx->wss[partner].cap_windows || rc_points(rcs) * cpow > ctx->wss[partner].cap_windows) partner = -1;
+        const size_t entries = (size_t)tp.W * len * members.count;
+        if (2 * tp.vw * cpow > ctx->wss[partner].cap_windows || rc_points(rcs) * cpow > ctx->wss[partner].cap_windows ||
+            tmsm_ovf_records(entries, tmsm_kmax(ctx, entries)) + (size_t)tp.B * cpow > ctx->wss[partner].cap_tasks)
+            partner = -1;  // (the pieces then run one after the other on this slot: same result)
     }
     if (partner >= 0) {
         HALO_HIP(hipEventRecord(ctx->ev_piece[slot][0], mine));
@@ -637,11 +706,7 @@ static int tmsm_enqueue_piece(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d
     chunk_len = (chunk_len + 3) / 4 * 4;
     dim3 gridc((unsigned)(rows * nchunks)), b1024(1024), b256(256);
     uint32_t *chist = ws.d_hist, *cstart = ws.d_hist + (size_t)rows * nchunks * tp.ranges;  // <= 255 * 512 + 513 words <= cap_hist
-    // chain bound per lane of the bucket kernel: the W n additions over the chip's 2048 x 64 lanes, in one round
-    uint32_t kmax = KMAX;
-    if (ctx->task_len > 0) kmax = (uint32_t)ctx->task_len;
-    else if (entries <= (size_t)16 * 131072) kmax = 16;
-    else if (entries <= (size_t)32 * 131072) kmax = 32;
+    const uint32_t kmax = tmsm_kmax(ctx, entries);
     const bool wide = tp.ranges > TBL_MAX_RANGES;  // (two bucket sets of the c = 20 plan: 1024 coarse ranges)
     if (wide) HALO_LAUNCH(ctx, "k_tmsm_coarse_hist2", k_tmsm_coarse_hist2, gridc, b1024, 0, d_digits, (uint32_t)n, nchunks, chunk_len, tp, chist);
     else HALO_LAUNCH(ctx, "k_tmsm_coarse_hist", k_tmsm_coarse_hist, gridc, b1024, 0, d_digits, (uint32_t)n, nchunks, chunk_len, tp, chist);
@@ -652,16 +717,16 @@ static int tmsm_enqueue_piece(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d
                           (uint32_t)ctx->n, base_off, tp, ws.d_presort, ws.d_fine16);
     else HALO_LAUNCH(ctx, "k_tmsm_coarse_scatter", k_tmsm_coarse_scatter, gridc, b1024, 0, d_digits, (uint32_t)n, nchunks, chunk_len, chist, cstart,
                      (uint32_t)ctx->n, base_off, tp, ws.d_presort, ws.d_fine16);
+    // `order` (d_order): an overflow region of `ovf` records, then one record per bucket (k_tmsm_fine_sort).  No global task
+    // order, no task_g: the table pipeline has no launch between sort and bucket kernel.
+    const uint32_t total = tp.B;
+    const size_t ovf = tmsm_ovf_records(entries, kmax);
+    if (ovf + total > ws.cap_tasks) { set_error("msm: table plan exceeds workspace"); return HALO_E_ARG; }
     HALO_LAUNCH(ctx, "k_tmsm_fine_sort", k_tmsm_fine_sort, dim3(tp.ranges), b1024, TBL_STAGE * 4, ws.d_presort, ws.d_fine16, cstart, kmax, tp, ws.d_counts,
-                ws.d_starts, ws.d_ntask, ws.d_toff, ws.d_task_g, ws.d_biglist, ws.d_meta, ws.d_sorted);
-    uint32_t total = tp.B;
-    size_t max_tasks = (size_t)total + entries / kmax + 1;
-    if (max_tasks > ws.cap_tasks) max_tasks = ws.cap_tasks;
-    dim3 gridt((unsigned)((max_tasks + 255) / 256));
-    HALO_LAUNCH(ctx, "k_msm_task_order", k_msm_task_order, gridt, b256, 0, ws.d_task_g, ws.d_meta, ws.d_sorted, ws.d_starts, ws.d_blockoff, ws.d_counts,
-                ws.d_toff, ws.d_tblockoff, kmax, reinterpret_cast<uint4 *>(ws.d_order));
-    HALO_LAUNCH(ctx, "k_msm_accumulate", k_msm_accumulate, gridt, b256, 0, ctx->d_table, ws.d_sorted, ws.d_meta, reinterpret_cast<const uint4 *>(ws.d_order),
-                ws.d_buckets);
+                ws.d_starts, ws.d_ntask, ws.d_toff, ws.d_biglist, ws.d_meta, ws.d_sorted, (uint32_t)ovf, reinterpret_cast<uint4 *>(ws.d_order));
+    dim3 gridt((unsigned)((ovf + total) / 256));  // (a multiple of 256 records: no lane past the last one)
+    HALO_LAUNCH(ctx, "k_msm_accumulate", k_msm_accumulate, gridt, b256, 0, ctx->d_table, ws.d_sorted, ws.d_meta + META_OVF, (uint32_t)ovf,
+                reinterpret_cast<const uint4 *>(ws.d_order), ws.d_buckets);
     HALO_LAUNCH(ctx, "k_msm_combine", k_msm_combine, dim3(512 + 1024), dim3(64), 0, ws.d_ntask, ws.d_toff, ws.d_tblockoff, ws.d_meta, ws.d_biglist,
                 total, 512u, ws.d_buckets);
     // window sums: the buckets as tp.vw virtual windows of 2^vw_bits, 64 segments each (c = 20: 8 buckets per lane; c = 17: 1)
