@@ -295,6 +295,12 @@ int halo_ctx_devices(const halo_ctx *ctx) { return ctx ? (ctx->shards.empty() ? 
 int halo_ctx_clone(halo_ctx *src, halo_ctx **out) {
     if (!src || !out) { set_error("ctx_clone: null argument"); return HALO_E_ARG; }
     if (!src->shards.empty() || src->parent) { set_error("ctx_clone: multi-device contexts and their shards are not cloned"); return HALO_E_ARG; }
+    // A key with clones is a service that opens: while `src` is still the table's only user, an all-shifts MSM table that leaves the
+    // fold table no room goes down to its 13 rows (internal.hpp table_demote; declined while src has launches in flight)
+    if (fold_table_wanted(src) && !table_budget_room(src, foldtab_need_bytes(src->n)) && table_should_demote(src)) {
+        HALO_CTX(src);
+        (void)table_demote_now(src);
+    }
     halo_ctx *ctx = new (std::nothrow) halo_ctx();
     if (!ctx) { set_error("out of host memory"); return HALO_E_ARG; }
     ctx->share = src->share;
@@ -1385,7 +1391,7 @@ int halo_point_sum(const uint64_t *pts_jac, size_t k, uint64_t out[12]) {
 
 
 int halo_set_table_mode(halo_ctx *ctx, int mode) {
-    if (!ctx || mode < -1 || mode > 0) { set_error("table mode must be -1 (automatic) or 0 (never)"); return HALO_E_ARG; }
+    if (!ctx || mode < -1 || mode > 1) { set_error("table mode must be -1 (automatic), 0 (never) or 1 (automatic, fixed-window plan only)"); return HALO_E_ARG; }
     if (mode == 0 && ctx->d_table) {  // "no table memory": a table already built is released, not just left unused
         HALO_CTX(ctx);
         int rc = table_release(ctx);
@@ -1403,6 +1409,16 @@ int halo_set_fold_table(halo_ctx *ctx, int mode) {
         HALO_CTX(ctx);
         for (int k = 0; k < HALO_SLOTS; ++k) HALO_HIP(hipStreamSynchronize(ctx->streams[k]));
         foldtab_release(ctx);
+    }
+    if (mode == 0) {
+        ctx->table_demote = false;
+        std::lock_guard<std::mutex> lk(ctx->share->mu);
+        ctx->share->table_fixed_only = false;
+    }
+    if (mode == 1 && !ctx->d_foldtab && !table_budget_room(ctx, foldtab_need_bytes(ctx->n)) && table_should_demote(ctx)) {
+        // the caller asks for the fold table and the budget has room for it only without this context's all-shifts MSM table: that one goes
+        HALO_CTX(ctx);
+        (void)table_demote_now(ctx);
     }
     ctx->fold_table_mode = mode;
     ctx->foldtab_retry_at = 0;  // (a table that could not be had before is considered again)
@@ -1442,6 +1458,11 @@ bool table_budget_reserve(halo_ctx *ctx, size_t bytes) {
     ctx->share->budget_held += bytes;  // (on the books of the key: a clone may outlive the context that built a table)
     return true;
 }
+bool table_budget_room(halo_ctx *ctx, size_t bytes, size_t freed) {
+    std::lock_guard<std::mutex> lk(g_budget_mu);
+    DeviceBudget &b = budget_of(ctx->device);
+    return b.used - (freed < b.used ? freed : b.used) + bytes <= b.budget;
+}
 void table_budget_release(halo_ctx *ctx, size_t bytes) {
     std::lock_guard<std::mutex> lk(g_budget_mu);
     DeviceBudget &b = g_budget[ctx->device & 63];
@@ -1460,15 +1481,22 @@ int halo_set_memory_budget(halo_ctx *ctx, size_t bytes) {
     }
     // a table that was refused is considered again at the next opportunity
     ctx->foldtab_retry_at = 0; ctx->table_retry_at = 0;
+    ctx->table_demote = false;
+    { std::lock_guard<std::mutex> lk(ctx->share->mu); ctx->share->table_fixed_only = false; }
     for (halo_ctx *sh : ctx->shards) (void)halo_set_memory_budget(sh, bytes);  // (a shard on another device: that device's budget)
     return HALO_OK;
 }
 /* what: 0 = bytes of the MSM fixed-base table, 1 = bytes of the fold table, 2 = microseconds its build took, 3 = the budget for optional
  * table memory on this context's device, 4 = bytes of it in use (all contexts of the process), 5 / 6 = status of the fold table / the
- * MSM table: 0 nothing yet, 1 memory requested, 2 built, 3 over the budget, 4 allocation failed (tried again later), 5 off */
+ * MSM table: 0 nothing yet, 1 memory requested, 2 built, 3 over the budget, 4 allocation failed (tried again later), 5 off,
+ * 7 = microseconds the MSM table's build took, 8 = its rows (13 / 15: fixed windows, 255: every shift, the sliding-window plan),
+ * 9 = plan of the launch enqueued last: 0 no table pipeline, 1 its fixed windows, w + 1 sliding windows of at most w bits */
 size_t halo_ctx_info(const halo_ctx *ctx, int what) {
     if (!ctx) return 0;
-    if (what == 0) return ctx->d_table ? (size_t)ctx->tbl.W * ctx->n * 128 : 0;
+    if (what == 0) return ctx->d_table ? (size_t)ctx->tbl.rows * ctx->n * 128 : 0;
+    if (what == 7) return (size_t)(ctx->share ? ctx->share->table_build_ms * 1e3 : 0);
+    if (what == 8) return ctx->d_table ? (size_t)ctx->tbl.rows : 0;
+    if (what == 9) return (size_t)(ctx->last_table_plan + 1);
     if (what == 1) return ctx->foldtab_bytes;
     if (what == 2) return (size_t)(ctx->foldtab_build_ms * 1e3);
     if (what == 3 || what == 4) {

@@ -215,8 +215,9 @@ int halo_dev_hook(const char *name, long value) {
     else if (!std::strcmp(name, "open_batch_group")) h.open_group = (int)value;
     else if (!std::strcmp(name, "verifier_batch_min")) h.verifier_min = (int)value;
     else if (!std::strcmp(name, "decode_batch_min")) h.decode_min = value;
+    else if (!std::strcmp(name, "table_slide_min")) h.slide_min = value > 0 && value < 4096 ? 4096 : value;
     else if (!std::strcmp(name, "reset")) h = DevHooks();
-    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, verifier_batch_min, decode_batch_min, reset)"); return HALO_E_ARG; }
+    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, verifier_batch_min, decode_batch_min, table_slide_min, reset)"); return HALO_E_ARG; }
     return HALO_OK;
 }
 

@@ -276,7 +276,15 @@ static hipError_t foldtab_alloc(size_t n, uint32_t **tab, uint32_t **tmp) {
 // The memory of table + temporary is RESERVED against the device's budget for optional memory before anything is allocated
 // (internal.hpp table_budget_reserve: all contexts of the process on this device together stay within it, and never more than
 // half of what is free at that moment is taken) and given back on every path that does not end with a table.
-static bool foldtab_reserve(halo_ctx *ctx) { return table_budget_reserve(ctx, foldtab_table_bytes(ctx->n) + foldtab_tmp_bytes(ctx->n)); }
+static bool foldtab_reserve(halo_ctx *ctx) {
+    if (table_budget_reserve(ctx, foldtab_table_bytes(ctx->n) + foldtab_tmp_bytes(ctx->n))) return true;
+    // refused beside an all-shifts MSM table: that one is taken down to its 13 rows at the next idle moment (internal.hpp
+    // table_demote), and the fold table is asked for again at the next full-size open
+    // (only a table no clone shares, and only if that makes the room: otherwise the refusal takes its usual course)
+    if (table_should_demote(ctx)) ctx->table_demote = true;
+    return false;
+}
+size_t foldtab_need_bytes(size_t n) { return foldtab_table_bytes(n) + foldtab_tmp_bytes(n); }
 static void foldtab_unreserve(halo_ctx *ctx, bool keep_table) {
     table_budget_release(ctx, foldtab_tmp_bytes(ctx->n) + (keep_table ? 0 : foldtab_table_bytes(ctx->n)));
 }
@@ -284,6 +292,7 @@ static void foldtab_unreserve(halo_ctx *ctx, bool keep_table) {
 // go, budgets are raised (no latch) -- and said once on stderr; halo_ctx_info(ctx, 5) carries the status
 static void foldtab_later(halo_ctx *ctx, int status, const char *why) {
     ctx->foldtab_status = status;
+    if (status == 3 && ctx->table_demote) return;  // (room is being made: no back-off, nothing to say)
     ctx->foldtab_retry_at = ctx->foldtab_opens + ctx->foldtab_backoff;
     if (ctx->foldtab_backoff < 1024) ctx->foldtab_backoff *= 2;
     if (!ctx->foldtab_said)

@@ -76,6 +76,9 @@ struct MsmPlan {
     int table_sets = 1;      // bucket sets side by side in a batched table launch (members, rounded up to a power of two)
     bool table_rc = false;   // window sums by rows and columns of the bucket index (msm.hip k_msm_reduce_rc): (S, T) pairs per set
     int table_rc_lg_rows = 0, table_rc_lg_cols = 0;
+    // the sliding odd-digit plan over the all-shifts table (TblPlan::slide): bucket index = range * 2^lg_cols + fine holds the
+    // digits of magnitude 2 (fine * 2^lg_rows + range) + 1 -- other constants in msm_combine_member, same (S, T) pairs
+    int table_slide = 0;  // (its window width)
     // > 0: the launch's last kernel(s) write their sums straight into the slot's pinned buffer and each adds one to the slot's
     // pinned counter when its last block is through (MsmWorkspace::h_done; one per piece); msm_wait polls the counter.  0: a copy
     // and a stream wait.
@@ -87,6 +90,14 @@ struct TblPlan {
     int c, W, fbits, vw_bits;        // window bits, windows, fine-bucket bits of a coarse range, log2 buckets per virtual window
     uint32_t B, ranges, vw, spread;  // buckets (2^(c-1)), coarse ranges, virtual windows, modulus of the top-window spread (0: none)
     int fold_top;                    // scalars >= 2^254 are recoded as r - s with flipped signs (c = 17: the top window is full)
+    // The table of a c = 20 key may hold EVERY shift, rows 0 .. 254 (`rows` = 255: T[j][i] = 2^j G_i) instead of the W rows 2^(c w) G_i.
+    // slide > 0 (21): the launch recodes its scalars into sliding windows of at most `slide` bits that start at set bits only (odd
+    // digits, slide_lane.hpp), a digit names its own row, coarse range = bucket & (ranges - 1), fine key = bucket >> log2(ranges).
+    // slide = 0 on such a table: the fixed windows, window w on row row_step * w (row_step = c).
+    // Only slide = 21 is built: B = 2^19, the 19-bit bucket field of a digit word (TBL_ROW_SHIFT) and the 512 x 1024 shape of the
+    // window sums are those of 21-bit windows; a width of 20 (2^18 buckets) would have to derive all three from it.
+    // rbits = log2(ranges).
+    int rows, row_step, slide, rbits;
 };
 TblPlan table_plan(size_t key_n);
 // the members of a batched launch: same n, one scalar array and one base offset (in points) each
@@ -267,10 +278,12 @@ struct KeyShare {
     uint32_t *d_bases = nullptr;
     uint32_t *d_table = nullptr;
     halo::TblPlan tbl{};
+    double table_build_ms = 0;  // build of d_table (kernels, without the allocation)
     uint32_t *d_foldtab = nullptr;
     size_t foldtab_bytes = 0;
     double foldtab_build_ms = 0;
     bool table_busy = false, foldtab_busy = false;
+    bool table_fixed_only = false;  // the key's all-shifts MSM table made room for the fold table: table_build keeps to the fixed windows (until halo_set_fold_table(ctx, 0) or a new budget)
     long full_opens = 0;     // full-size opens over this key by any of its contexts while no fold table existed (the automatic mode builds from tuning().fold_table_after on)
     size_t budget_held = 0;  // bytes of optional memory reserved for this key (abi.hip table_budget_*)
 };
@@ -291,8 +304,8 @@ struct halo_ctx {
     int reduce_span = 0;                   // buckets per lane in k_msm_reduce1 (0 = automatic)
     int sort_two_level = -1;               // two-level sort: -1 automatic (n >= 2^17), 0 never, 1 whenever the shape allows
     int task_len = 0;                      // longest chain per lane in k_msm_accumulate (0 = automatic)
-    int table_mode = -1;                   // fixed-base tables for MSMs over the context's own bases: -1 automatic (n >= 2^20), 0 never
-    uint32_t *d_table = nullptr;           // W x n native affine points: T[w][i] = 2^(c w) G_i (built on first use)
+    int table_mode = -1;                   // fixed-base tables for MSMs over the context's own bases: -1 automatic (n >= 2^20), 0 never, 1 as -1 with the fixed-window plan forced (no all-shifts table is built; one that exists is read through its row stride)
+    uint32_t *d_table = nullptr;           // tbl.rows x n native affine points: T[w][i] = 2^(c w) G_i, or every shift T[j][i] = 2^j G_i (built on first use)
     halo::TblPlan tbl{};                   // the plan d_table was built for
     int small_path = -1;                   // smsm.hip pipeline: -1 automatic (n <= 2^16, one MSM per launch), 0 never
     bool use_graphs = true;                // replay cached hipGraphs for repeated MSM shapes
@@ -309,6 +322,14 @@ struct halo_ctx {
     int foldtab_retry_at = 0, foldtab_backoff = 8, foldtab_status = 0;
     long table_calls = 0, table_retry_at = 0, table_backoff = 64;
     int table_status = 0;
+    // The all-shifts MSM table (34 GB at 2^20 points) and the fold table (35 + 5 GB) do not both fit the default budget, and the
+    // fold table saves an opening workload more.  The decision is per KEY (msm_table.hip table_should_demote): a fold table that the
+    // budget refused beside an all-shifts table which only this context uses, and that would fit without it, asks for the MSM table
+    // to be taken down to its 13 rows (table_demote: done at the next MSM enqueued with every slot idle, or at once by
+    // halo_set_fold_table(ctx, 1) and by halo_ctx_clone, whose callers open); KeyShare::table_fixed_only then keeps table_build from
+    // asking for the large table again.  A table that clones share is never taken from them: the fold table is refused with its
+    // usual back-off and line on stderr -- and a key with clones builds the large table only if the budget holds both.
+    bool table_demote = false;
     bool table_said = false, foldtab_said = false;  // the one line on stderr has been printed
     // (the optional-memory bytes are on the books of the key: share->budget_held)
     // automatic mode: the table's 40 GB are requested on a helper thread at the first full-size open (hipMalloc of that size
@@ -340,6 +361,7 @@ struct halo_ctx {
     halo::HostWorker worker;      // host arithmetic overlapped with the caller's (see HostWorker; multi.hip also runs a shard's HIP calls on it)
     IpaBuffers ipa_bufs;          // reused by every halo_ipa of this context (one at a time; a second one allocates its own)
     uint64_t alloc_epoch = 0;     // bumped whenever this context allocates or frees device memory (see msm.hip, launch graphs)
+    int last_table_plan = -1;     // the launch enqueued last: -1 no table pipeline, 0 its fixed windows, else the sliding plan's window width (halo_ctx_info 9)
     int may_borrow = 0;           // > 0 inside a synchronous MSM call: a large MSM may run its odd pieces on the neighbouring slot (msm.hip)
     hipEvent_t ev_piece[HALO_SLOTS][2] = {};  // fork / join of those pieces (created on first use)
     // multi-device contexts (multi.hip): one shard context per device over its index block of the key; MSMs over the key fan out
@@ -446,6 +468,11 @@ int test_point_op(halo_ctx *ctx, int op, const uint64_t *d_a, const uint64_t *d_
 // process-wide: reserve() succeeds if what all contexts of this process hold on ctx's device plus `bytes` stays within the
 // device's budget (halo_set_memory_budget; default 1/6 of the device's memory) and at least 2 x bytes are free right now
 bool table_budget_reserve(halo_ctx *ctx, size_t bytes);
+bool table_budget_room(halo_ctx *ctx, size_t bytes, size_t freed = 0);  // would `bytes` more stay within the budget once `freed` bytes have gone back?  (reserves nothing)
+size_t foldtab_need_bytes(size_t n);                 // foldtab.hip: the fold table of an n-point key and its build's temporary
+bool table_should_demote(halo_ctx *ctx);             // msm_table.hip: this context alone holds an all-shifts table, and the key's fold table fits the budget only without it
+bool fold_table_wanted(const halo_ctx *ctx);         // msm_table.hip: the key may still ask for a fold table (mode 1, or the automatic mode at its sizes)
+int table_demote_now(halo_ctx *ctx);                 // msm_table.hip: that table goes (every slot idle, no other user); the next table MSM builds the fixed windows
 void table_budget_release(halo_ctx *ctx, size_t bytes);
 
 // ---- foldtab.hip: the first two-level fold of an open from a comb table over the context's key

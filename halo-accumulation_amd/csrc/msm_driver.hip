@@ -214,6 +214,10 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
         }
     }
     StreamGuard guard(ctx, ctx->streams[slot]);
+    if (ctx->table_demote) {  // a fold table is waiting for the room an all-shifts MSM table takes (internal.hpp)
+        int rc = table_demote_now(ctx);
+        if (rc) return rc;
+    }
     if (!ctx->d_table && table_eligible(ctx, d_bases, members, n)) {
         int rc = table_build(ctx);
         if (rc) return rc;
@@ -279,6 +283,7 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
         HALO_HIP(hipGraphLaunch(hit->exec, ctx->streams[slot]));
         hit->used = ++ws.graph_clock;
         ws.plan = hit->plan;
+        ctx->last_table_plan = ws.plan.table_vw > 0 ? ws.plan.table_slide : -1;
         ws.done_expect += (uint32_t)ws.plan.publishers;
         ws.in_flight = true;
         if (partner >= 0) { ws.borrowed = partner; ctx->wss[partner].in_flight = true; ctx->wss[partner].lent_from = slot; }
@@ -325,6 +330,7 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
         ws.done_expect = *(volatile uint32_t *)ws.h_done;
         return rc;
     }
+    ctx->last_table_plan = ws.plan.table_vw > 0 ? ws.plan.table_slide : -1;
     ws.done_expect += (uint32_t)ws.plan.publishers;
     ws.in_flight = true;
     if (partner >= 0) { ws.borrowed = partner; ctx->wss[partner].in_flight = true; ctx->wss[partner].lent_from = slot; }
@@ -417,6 +423,17 @@ void msm_combine_member(halo_ctx *ctx, int slot, int b, host::Point *out) {
             if (plain) *plain = run;
             return t + tot;
         };
+        if (p.table_slide) {
+            // sliding plan: bucket (row, col) = (range, fine) holds the digits 2 (col 2^lg_rows + row) + 1:
+            //   sum = 2^(lg_rows + 1) sum_col col C_col + 2 sum_row row R_row + sum B,  sum_col col C_col = [columns] - sum B
+            host::Point s_cols, s_all;
+            host::Point cw = weighted(0, cblocks, &s_cols) - s_cols;
+            host::Point rw = weighted(cblocks, rblocks, &s_all) - s_all;
+            for (int k = 0; k < p.table_rc_lg_rows + 1 && !cw.is_inf(); ++k) cw = cw.dbl();
+            if (!rw.is_inf()) rw = rw.dbl();
+            *out = cw + rw + s_all;
+            return;
+        }
         host::Point s_rows;
         host::Point cols = weighted(0, cblocks, nullptr);
         host::Point rows = weighted(cblocks, rblocks, &s_rows) - s_rows;

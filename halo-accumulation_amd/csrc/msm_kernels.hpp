@@ -35,6 +35,7 @@ constexpr uint32_t TBL_MAX_RANGES = 512;
 // 2^24) and k_msm_combine folded 2 .. 8 partials per bucket.  The pieces' window sums are added on the host.
 constexpr size_t TBL_PIECE = 1310720;
 constexpr uint32_t TDIGIT_NONE = 0xFFFFFFFFu;
+constexpr uint32_t TBL_ROW_SHIFT = 19;  // sliding plan: a digit word is bucket (19 bits) | table row << 19 (8 bits) | sign << 31
 constexpr int TBL_E = 4;  // points per lane of the kernels that share one inversion (k_table_step, k_batch_to_affine)
 constexpr uint32_t TBL_STAGE = 35840;  // entries staged in LDS: 140 KiB next to 20 KiB of counters
 constexpr uint32_t TBL_ORDER_RUN = 8;  // consecutive ranks of one range in a wave of the bucket kernel (k_tmsm_fine_sort); divides 64

@@ -5,6 +5,7 @@
 #include <thread>
 
 #include "msm_kernels.hpp"
+#include "slide_lane.hpp"
 
 namespace halo {
 
@@ -26,9 +27,20 @@ namespace halo {
 //   key of 2^17 .. 2^19 points (a rank's index shard of a 2^20-point MSM): c = 17, 15 windows (15 x 17 = 255 bits exactly),
 //     2^16 buckets, n / 2048 coarse ranges (so that a range's 15 n / ranges entries fit the fine sort's LDS stage), 16 virtual
 //     windows of 2^12 -- 15 n additions against 16 n, an eighth of the buckets of the general plan's 16 x 2^15.
+//
+// Third plan, the default of a c = 20 key whose ALL-SHIFTS table could be had (255 rows T[j][i] = 2^j G_i, 255 x 128 B per point:
+// optional memory like the 13 rows): sliding windows of at most 21 bits that start at set bits only (slide_lane.hpp).  Every digit
+// is odd, bucket m holds the digits +-(2 m + 1) -- the same 2^19 buckets --, a digit names its own table row, and a uniform scalar
+// has 12.0 digits instead of 13: 12/13 of the sort's entries and of the bucket kernel's additions.  The window widths vary (19 ..
+// 21 bits), so low buckets fill more than high ones: the coarse range is the bucket's LOW nine bits and the fine key its high ten
+// (every range gets the same mix); the bucket array keeps the index range * 1024 + fine and msm_combine_member weighs rows and
+// columns accordingly.  Rows 20 w of that table are the 13-row table: the fixed plan, the tagged launch and the pieces of an MSM
+// of more than TBL_PIECE points read it through row_step = 20.
+size_t table_slide_min() { return dev_hooks().slide_min > 0 ? (size_t)dev_hooks().slide_min : (size_t)1 << 20; }
 TblPlan table_plan(size_t key_n) {
     TblPlan t{};
-    if (key_n >= ((size_t)1 << 20)) {
+    t.row_step = 1; t.slide = 0;
+    if (key_n >= table_slide_min()) {
         t.c = 20; t.W = 13; t.B = 1u << 19; t.fbits = 10; t.vw_bits = 15; t.spread = 31; t.fold_top = 0;
     } else {
         t.c = 17; t.W = 15; t.B = 1u << 16; t.vw_bits = 12; t.spread = 0; t.fold_top = 1;
@@ -38,7 +50,23 @@ TblPlan table_plan(size_t key_n) {
         for (uint32_t r = ranges; r > 1; r >>= 1) t.fbits--;
     }
     t.ranges = t.B >> t.fbits;
+    t.rbits = 0;
+    while ((1u << t.rbits) < t.ranges) t.rbits++;
     t.vw = t.B >> t.vw_bits;
+    t.rows = t.W;
+    return t;
+}
+// the default plan of a key whose table holds every shift
+static TblPlan table_plan_slide(size_t key_n) {
+    TblPlan t = table_plan(key_n);
+    t.rows = SLIDE_BITS; t.slide = 21; t.spread = 0; t.row_step = t.c;
+    return t;
+}
+// ... and the fixed windows on the same table
+static TblPlan table_plan_fixed_on(const TblPlan &built, size_t key_n) {
+    TblPlan t = table_plan(key_n);
+    t.rows = built.rows;
+    t.row_step = built.rows == SLIDE_BITS ? t.c : 1;
     return t;
 }
 
@@ -64,6 +92,106 @@ __global__ __launch_bounds__(256) void k_table_step(const uint32_t *__restrict__
     });
 }
 
+// The all-shifts table: rows 1 .. rows - 1 from row 0, T[j] = 2 T[j - 1], one doubling and a return to affine per row.  A block owns
+// ALLS_E x 256 points through all the rows and shares ONE inversion per row among them (k_table_step shares one among 4 points:
+// at one doubling per row the inversion would be 97 % of the build).  The Z of the doubled point is 2 y, so a first pass over
+// the previous row needs the y's only: every lane multiplies up the Z's of its own points (prefix products, as
+// jac_batch_to_aff), the 256 lane products go through LDS -- sixteen lanes take prefix products over sixteen of them each, lane 0
+// over the sixteen group products, inverts once and walks back down --, and a second pass doubles each point and unwinds its 1 / Z
+// from the inverse of the lane's product.  A lane reads back only what it wrote itself.
+constexpr int ALLS_E = 16;  // points per lane
+constexpr int ALLS_G = 16;  // lane products per group, groups per block
+HALO_DEV Fq<2> lds_get(const uint32_t *p) { Fq<2> r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.v[i] = p[i];
+    return r; }
+HALO_DEV void lds_put(uint32_t *p, const Fq<2> &a) {
+#pragma unroll
+    for (int i = 0; i < 9; i++) p[i] = a.v[i]; }
+// Z of jac_dbl(jac_from_aff(a)) up to the representation: 2 y (1 for the point at infinity, whose y is 0: the curve has no point of order 2)
+HALO_DEV Fq<2> alls_z(const uint32_t *entry) {
+    Fq<2> y;
+#pragma unroll
+    for (int i = 0; i < 9; i++) y.v[i] = entry[10 + i];
+    if (fq_limbs_zero(y)) return fq_widen<2>(fq_one());
+    return fq_tighten(fq_muls<2>(y));
+}
+__global__ __launch_bounds__(256) void k_table_all_shifts(uint32_t *__restrict__ tbl, uint32_t n, int rows) {
+    __shared__ uint32_t prod[256 * 9], pre[256 * 9], gpre[ALLS_G * 9], inv[256 * 9];
+    const uint32_t tid = threadIdx.x, base = blockIdx.x * (256u * ALLS_E);
+#pragma unroll 1
+    for (int j = 1; j < rows; j++) {
+        const uint32_t *prev = tbl + AFF_STRIDE * ((size_t)(j - 1) * n);
+        uint32_t *next = tbl + AFF_STRIDE * ((size_t)j * n);
+        Fq<2> lp[ALLS_E];  // lp[e] = z_0 ... z_e
+        static_for<0, ALLS_E>([&](auto ic) {
+            constexpr int e = decltype(ic)::value;
+            uint32_t i = base + (uint32_t)e * 256u + tid;
+            Fq<2> z = i < n ? alls_z(prev + AFF_STRIDE * (size_t)i) : fq_widen<2>(fq_one());
+            if constexpr (e == 0) lp[0] = z;
+            else lp[e] = fq_mul(lp[e - 1], z);
+        });
+        lds_put(prod + 9 * tid, lp[ALLS_E - 1]);
+        __syncthreads();
+        if (tid < ALLS_G) {  // prefix products inside group tid
+            Fq<2> run = lds_get(prod + 9 * (tid * ALLS_G));
+            lds_put(pre + 9 * (tid * ALLS_G), run);
+#pragma unroll 1
+            for (int k = 1; k < ALLS_G; k++) {
+                run = fq_mul(run, lds_get(prod + 9 * (tid * ALLS_G + k)));
+                lds_put(pre + 9 * (tid * ALLS_G + k), run);
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {  // over the groups' products; gpre[g] ends as the inverse of group g's product
+            Fq<2> run = lds_get(pre + 9 * (ALLS_G - 1));
+            lds_put(gpre, run);
+#pragma unroll 1
+            for (int g = 1; g < ALLS_G; g++) {
+                run = fq_mul(run, lds_get(pre + 9 * (g * ALLS_G + ALLS_G - 1)));
+                lds_put(gpre + 9 * g, run);
+            }
+            Fq<2> iv = fq_inv(run);
+#pragma unroll 1
+            for (int g = ALLS_G - 1; g >= 1; g--) {
+                Fq<2> gi = fq_mul(iv, lds_get(gpre + 9 * (g - 1)));
+                iv = fq_mul(iv, lds_get(pre + 9 * (g * ALLS_G + ALLS_G - 1)));
+                lds_put(gpre + 9 * g, gi);
+            }
+            lds_put(gpre, iv);
+        }
+        __syncthreads();
+        if (tid < ALLS_G) {  // inverses of the lane products of group tid
+            Fq<2> iv = lds_get(gpre + 9 * tid);
+#pragma unroll 1
+            for (int k = ALLS_G - 1; k >= 1; k--) {
+                lds_put(inv + 9 * (tid * ALLS_G + k), fq_mul(iv, lds_get(pre + 9 * (tid * ALLS_G + k - 1))));
+                iv = fq_mul(iv, lds_get(prod + 9 * (tid * ALLS_G + k)));
+            }
+            lds_put(inv + 9 * (tid * ALLS_G), iv);
+        }
+        __syncthreads();
+        Fq<2> iv = lds_get(inv + 9 * tid);
+        static_for_down<ALLS_E - 1>([&](auto ic) {
+            constexpr int e = decltype(ic)::value;
+            uint32_t i = base + (uint32_t)e * 256u + tid;
+            if (i < n) {  // (a point past the end entered the product as 1)
+                JacN p = jac_dbl(jac_from_aff(aff_load(prev + AFF_STRIDE * (size_t)i)));
+                Fq<2> z = jac_is_inf(p) ? fq_widen<2>(fq_one()) : fq_tighten(p.z);
+                Fq<2> zi = iv;
+                if constexpr (e > 0) { zi = fq_mul(iv, lp[e - 1]); iv = fq_mul(iv, z); }
+                Fq<2> zi2 = fq_sqr(zi);
+                AffN a;
+                a.x = fq_mul(p.x, zi2);
+                a.y = fq_mul(p.y, fq_mul(zi2, zi));
+                if (jac_is_inf(p)) a = aff_inf();
+                aff_store(next + AFF_STRIDE * (size_t)i, a);
+            }
+        });
+        // (the next row's first barrier orders this row's reads of `inv` before its writes)
+    }
+}
+
 // signed 20-bit digits, u32 [w][i]: (|d| - 1) | sign << 31, TDIGIT_NONE for zero; block 0 clears the launch's small state
 // blockIdx.y = member of a batched launch (small-key plan): its digits go to rows [member W, (member + 1) W) and carry
 // member * B on top of the bucket number, so that every later kernel sees one MSM with count * B buckets.
@@ -72,6 +200,11 @@ __global__ __launch_bounds__(256) void k_table_step(const uint32_t *__restrict__
 __global__ __launch_bounds__(256) void k_tmsm_recode(TblScalars members, int mont, int tagged, uint32_t n, TblPlan tp, uint32_t *__restrict__ digits,
                                                      uint32_t *__restrict__ meta, uint32_t *__restrict__ zero_b, uint32_t *__restrict__ zero_t) {
     __shared__ uint32_t sw[256 * 9];
+    __shared__ uint8_t wtab[256];  // sliding plan: window width by bits left (slide_lane.hpp)
+    if (tp.slide) {
+        wtab[threadIdx.x] = (uint8_t)slide_width(threadIdx.x ? (int)threadIdx.x : 1, tp.slide);
+        __syncthreads();
+    }
     const uint64_t *__restrict__ scalars = members.p[blockIdx.y];
     if (blockIdx.x == 0 && blockIdx.y == 0) {
         meta[threadIdx.x] = 0;
@@ -85,6 +218,16 @@ __global__ __launch_bounds__(256) void k_tmsm_recode(TblScalars members, int mon
 #pragma unroll
     for (int k = 0; k < 8; k++) my[k] = s.v[k];
     my[8] = 0;
+    if (tp.slide) {
+        // sliding odd digits (slide_lane.hpp; one member, one bucket set): slot k holds bucket (|d| - 1) / 2 | row << 19 | sign << 31,
+        // the slots behind the last digit TDIGIT_NONE (row <= 254: no live slot reads as TDIGIT_NONE)
+        if (!mont) slide_canon(my);  // (out of Montgomery form a scalar is canonical already)
+        int cnt = slide_recode(my, tp.slide, wtab, [&](int k, uint32_t mag, uint32_t neg, uint32_t row) {
+            if (k < SLIDE_SLOTS) digits[(size_t)k * n + i] = ((mag - 1u) >> 1) | (row << TBL_ROW_SHIFT) | (neg << 31);
+        });
+        for (int k = cnt; k < SLIDE_SLOTS; k++) digits[(size_t)k * n + i] = TDIGIT_NONE;
+        return;
+    }
     uint32_t set = blockIdx.y;
     if (tagged) { set = my[7] >> 31; my[7] &= 0x7fffffffu; }
     uint32_t flip = 0;
@@ -130,6 +273,10 @@ __global__ __launch_bounds__(256) void k_tmsm_recode(TblScalars members, int mon
         digits[((size_t)blockIdx.y * tp.W + w) * n + i] = d.mag ? ((d.mag - 1 + set * tp.B) | ((d.neg ^ flip) << 31)) : TDIGIT_NONE;
     }
 }
+// coarse range and fine key of a digit word (B = buckets of the whole launch, a power of two): the high and the low bits of the
+// bucket -- or, under the sliding plan, the low and the high ones
+HALO_DEV uint32_t tbl_range(uint32_t v, const TblPlan &tp) { return tp.slide ? v & (tp.ranges - 1u) : (v & (tp.B - 1u)) >> tp.fbits; }
+HALO_DEV uint32_t tbl_fine(uint32_t v, const TblPlan &tp) { return tp.slide ? (v & (tp.B - 1u)) >> tp.rbits : v & ((1u << tp.fbits) - 1u); }
 // block (w, chunk): counts of the 512 coarse ranges, one private row per wave
 // (MAXR = 1024: the c = 20 plan with TWO bucket sets, a `tagged` launch -- the kernels with a 2 in their names)
 template <uint32_t MAXR>
@@ -147,7 +294,7 @@ HALO_DEV void tmsm_coarse_hist_body(const uint32_t *__restrict__ digits, uint32_
         uint32_t v[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
         for (int k = 0; k < 4; k++)
-            if (v[k] != TDIGIT_NONE) atomicAdd(&mine[(v[k] & (tp.B - 1u)) >> tp.fbits], 1u);
+            if (v[k] != TDIGIT_NONE) atomicAdd(&mine[tbl_range(v[k], tp)], 1u);
     }
     __syncthreads();
     if (threadIdx.x < tp.ranges) {
@@ -207,14 +354,15 @@ HALO_DEV void tmsm_coarse_scatter_body(const uint32_t *__restrict__ digits, uint
                                        const uint32_t *__restrict__ chist, const uint32_t *__restrict__ cstart, uint32_t table_n, uint32_t base_off,
                                        const TblPlan &tp, uint32_t *__restrict__ presort, uint16_t *__restrict__ presort_fine) {
     __shared__ uint32_t cur[MAXR], tcount[MAXR], toff[MAXR], wsum[MAXR / 64];
-    const uint32_t ranges = tp.ranges, fmask = (1u << tp.fbits) - 1u;
+    const uint32_t ranges = tp.ranges;
     __shared__ uint32_t t_idx[TBL_TILE], t_dest[TBL_TILE];
     __shared__ uint16_t t_fine[TBL_TILE];
     uint32_t row = blockIdx.x / nchunks, chunk = blockIdx.x % nchunks, tid = threadIdx.x;  // row = member * W + w
     if (tid < ranges) cur[tid] = cstart[tid] + chist[(size_t)blockIdx.x * ranges + tid];
     uint32_t lo = chunk * chunk_len, hi = lo + chunk_len < n ? lo + chunk_len : n;
     const uint32_t *dg = digits + (size_t)row * n;
-    uint32_t tbase = (row % (uint32_t)tp.W) * table_n + base_off;
+    // the table row of the entries: the window's (fixed plans), or the one each digit names (sliding plan: < 2^28 with the index)
+    const uint32_t tbase = (row % (uint32_t)tp.W) * (uint32_t)tp.row_step * table_n + base_off;
     for (uint32_t t0 = lo; t0 < hi; t0 += TBL_TILE) {
         if (tid < ranges) tcount[tid] = 0;
         __syncthreads();
@@ -227,7 +375,7 @@ HALO_DEV void tmsm_coarse_scatter_body(const uint32_t *__restrict__ digits, uint
             v[4 * h] = q.x; v[4 * h + 1] = q.y; v[4 * h + 2] = q.z; v[4 * h + 3] = q.w;
         }
 #pragma unroll
-        for (int k = 0; k < 8; k++) rank[k] = v[k] != TDIGIT_NONE ? atomicAdd(&tcount[(v[k] & (tp.B - 1u)) >> tp.fbits], 1u) : 0u;
+        for (int k = 0; k < 8; k++) rank[k] = v[k] != TDIGIT_NONE ? atomicAdd(&tcount[tbl_range(v[k], tp)], 1u) : 0u;
         __syncthreads();
         {   // inclusive scan of the tile's counts: shuffles within a wave, the <= 8 wave totals through LDS -- two barriers
             // (a Hillis-Steele pass over LDS took 18, per tile, for sixteen waves)
@@ -250,11 +398,12 @@ HALO_DEV void tmsm_coarse_scatter_body(const uint32_t *__restrict__ digits, uint
 #pragma unroll
         for (int k = 0; k < 8; k++)
             if (v[k] != TDIGIT_NONE) {
-                uint32_t r = (v[k] & (tp.B - 1u)) >> tp.fbits;
+                uint32_t r = tbl_range(v[k], tp);
                 uint32_t slot = toff[r] - tcount[r] + rank[k];
                 uint32_t i = t0 + 4 * tid + (uint32_t)(k >> 2) * 4096 + (uint32_t)(k & 3);
-                t_idx[slot] = (tbase + i) | (v[k] & 0x80000000u);
-                t_fine[slot] = (uint16_t)(v[k] & fmask);
+                uint32_t at = tp.slide ? ((v[k] >> TBL_ROW_SHIFT) & 0xffu) * table_n + base_off : tbase;
+                t_idx[slot] = (at + i) | (v[k] & 0x80000000u);
+                t_fine[slot] = (uint16_t)tbl_fine(v[k], tp);
                 t_dest[slot] = cur[r] + rank[k];
             }
         __syncthreads();
@@ -482,10 +631,12 @@ int msm_table_prepare() {
     return HALO_OK;
 }
 
-static int tmsm_enqueue_piece(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MsmBatch &members, size_t soff, bool mont, size_t n, int piece,
-                              uint64_t *h_dst);
-// T[w][i] = 2^(c w) G_i over the whole key, built window by window on the context's first table MSM (one-off: W - 1 passes
-// of c doublings and an inversion per point, ~10 ms at n = 2^20)
+static int tmsm_enqueue_piece(halo_ctx *ctx, MsmWorkspace &ws, const TblPlan &plan, const uint32_t *d_bases, const MsmBatch &members, size_t soff, bool mont,
+                              size_t n, int piece, uint64_t *h_dst);
+// The table over the whole key, built on the context's first table MSM (one-off).  A c = 20 key of one device asks for the
+// all-shifts table first (255 rows, k_table_all_shifts: 34 GB at n = 2^20) unless table mode 1 forces the fixed windows; if the
+// optional-memory budget or the allocation refuses that, it builds T[w][i] = 2^(c w) G_i window by window like every other key
+// (W - 1 passes of c doublings and an inversion per point, ~10 ms at n = 2^20) and runs the fixed plan -- never an error.
 int table_build(halo_ctx *ctx) {
     if (ctx->d_table) return HALO_OK;
     // a table that could not be had is tried again after table_backoff more eligible MSMs (64, 128, ... 4096), not never:
@@ -505,50 +656,70 @@ int table_build(halo_ctx *ctx) {
     }
     struct Busy { KeyShare *k; ~Busy() { std::lock_guard<std::mutex> lk(k->mu); k->table_busy = false; } } busy{ctx->share.get()};
     ++ctx->table_calls;
-    size_t n = ctx->n;
-    TblPlan tp = table_plan(n);
-    const size_t bytes = (size_t)tp.W * n * 128;
-    auto later = [ctx, bytes](int status, const char *why) {
-        ctx->table_status = status;
-        ctx->table_retry_at = ctx->table_calls + ctx->table_backoff;
-        if (ctx->table_backoff < 4096) ctx->table_backoff *= 2;
-        if (!ctx->table_said)
-            fprintf(stderr, "[halo] fixed-base table of %zu bytes not built (%s): the table-free pipeline runs, same results (halo_ctx_info 6; tried again later)\n", bytes, why);
-        ctx->table_said = true;
-    };
-    if (!table_budget_reserve(ctx, bytes)) { later(3, "over the budget for optional memory, halo_set_memory_budget"); return HALO_OK; }
-    alloc_epoch_bump(ctx);
-    // built into a local pointer and published (d_table + tbl together) only after the last step has succeeded: a
-    // half-built table is never visible to table_eligible / tmsm_enqueue_piece
-    uint32_t *tbl = nullptr;
-    hipError_t e = dev_hooks().table_fail ? hipErrorOutOfMemory : hipMalloc(&tbl, bytes);  // (development library's hook: the failure path)
-    if (e == hipSuccess) {
-        if (debug_trace()) fprintf(stderr, "[halo] table ctx=%p c=%d [%p, +%zu)\n", (void *)ctx, tp.c, (void *)tbl, bytes);
-        e = hipMemcpyAsync(tbl, ctx->d_bases, n * 128, hipMemcpyDeviceToDevice, ctx->stream);
-        for (int w = 1; w < tp.W && e == hipSuccess; ++w) {
-            HALO_LAUNCH(ctx, "k_table_step", k_table_step, dim3((unsigned)(((n + TBL_E - 1) / TBL_E + 255) / 256)), dim3(256), 0,
-                        tbl + (size_t)(w - 1) * n * AFF_STRIDE, (uint32_t)n, tp.c, tbl + (size_t)w * n * AFF_STRIDE);
-            e = hipGetLastError();
+    const size_t n = ctx->n;
+    const TblPlan fixed = table_plan(n);
+    // (entry references are row * n + index: below 2^28 for the all-shifts table, which leaves the digit word's row field its 8 bits)
+    bool key_fixed_only, key_shared;
+    { std::lock_guard<std::mutex> lk(ctx->share->mu); key_fixed_only = ctx->share->table_fixed_only; key_shared = ctx->share->users > 1; }
+    const bool all_shifts = fixed.c == 20 && ctx->table_mode != 1 && !key_fixed_only && !ctx->parent && ctx->shards.empty() && (size_t)SLIDE_BITS * n <= ((size_t)1 << 28);
+    // (a caller that has asked for the fold table and not got it yet keeps the room for it, and so does a key with clones, from
+    // whom the table could not be taken back: internal.hpp table_demote)
+    const bool fold_first = fold_table_wanted(ctx) && (ctx->fold_table_mode == 1 || key_shared);
+    const TblPlan plans[2] = {table_plan_slide(n), fixed};
+    int status = 0;
+    size_t bytes = 0;
+    std::string why;
+    for (int k = all_shifts ? 0 : 1; k < 2; ++k) {
+        const TblPlan &tp = plans[k];
+        bytes = (size_t)tp.rows * n * 128;
+        if (k == 0 && fold_first && !table_budget_room(ctx, bytes + foldtab_need_bytes(n))) continue;
+        if (!table_budget_reserve(ctx, bytes)) { status = 3; why = "over the budget for optional memory, halo_set_memory_budget"; continue; }
+        alloc_epoch_bump(ctx);
+        // built into a local pointer and published (d_table + tbl together) only after the last step has succeeded: a
+        // half-built table is never visible to table_eligible / tmsm_enqueue_piece
+        uint32_t *tbl = nullptr;
+        hipError_t e = dev_hooks().table_fail ? hipErrorOutOfMemory : hipMalloc(&tbl, bytes);  // (development library's hook: the failure path)
+        if (e == hipSuccess) {
+            if (debug_trace()) fprintf(stderr, "[halo] table ctx=%p c=%d rows=%d [%p, +%zu)\n", (void *)ctx, tp.c, tp.rows, (void *)tbl, bytes);
+            const auto t0 = std::chrono::steady_clock::now();
+            e = hipMemcpyAsync(tbl, ctx->d_bases, n * 128, hipMemcpyDeviceToDevice, ctx->stream);
+            if (tp.rows == SLIDE_BITS && e == hipSuccess) {
+                HALO_LAUNCH(ctx, "k_table_all_shifts", k_table_all_shifts, dim3((unsigned)((n + 256 * ALLS_E - 1) / (256 * ALLS_E))), dim3(256), 0, tbl, (uint32_t)n, tp.rows);
+                e = hipGetLastError();
+            }
+            for (int w = 1; tp.rows != SLIDE_BITS && w < tp.W && e == hipSuccess; ++w) {
+                HALO_LAUNCH(ctx, "k_table_step", k_table_step, dim3((unsigned)(((n + TBL_E - 1) / TBL_E + 255) / 256)), dim3(256), 0,
+                            tbl + (size_t)(w - 1) * n * AFF_STRIDE, (uint32_t)n, tp.c, tbl + (size_t)w * n * AFF_STRIDE);
+                e = hipGetLastError();
+            }
+            hipError_t e2 = hipStreamSynchronize(ctx->stream);
+            if (e == hipSuccess) e = e2;
+            if (e == hipSuccess) ctx->share->table_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         }
-        hipError_t e2 = hipStreamSynchronize(ctx->stream);
-        if (e == hipSuccess) e = e2;
-    }
-    if (e != hipSuccess) {
-        // No table, no problem: the general pipeline needs no table memory and gives the same point.
-        (void)hipGetLastError();
-        if (tbl) (void)hipFree(tbl);
-        table_budget_release(ctx, bytes);
-        later(4, hipGetErrorString(e));
+        if (e != hipSuccess) {
+            // No table, no problem: the general pipeline needs no table memory and gives the same point.
+            (void)hipGetLastError();
+            if (tbl) (void)hipFree(tbl);
+            table_budget_release(ctx, bytes);
+            status = 4; why = hipGetErrorString(e);
+            continue;
+        }
+        {
+            std::lock_guard<std::mutex> lk(ctx->share->mu);
+            ctx->share->tbl = tp;
+            ctx->share->d_table = tbl;
+        }
+        ctx->tbl = tp;
+        ctx->d_table = tbl;
+        ctx->table_status = 2;
         return HALO_OK;
     }
-    {
-        std::lock_guard<std::mutex> lk(ctx->share->mu);
-        ctx->share->tbl = tp;
-        ctx->share->d_table = tbl;
-    }
-    ctx->tbl = tp;
-    ctx->d_table = tbl;
-    ctx->table_status = 2;
+    ctx->table_status = status;
+    ctx->table_retry_at = ctx->table_calls + ctx->table_backoff;
+    if (ctx->table_backoff < 4096) ctx->table_backoff *= 2;
+    if (!ctx->table_said)
+        fprintf(stderr, "[halo] fixed-base table of %zu bytes not built (%s): the table-free pipeline runs, same results (halo_ctx_info 6; tried again later)\n", bytes, why.c_str());
+    ctx->table_said = true;
     return HALO_OK;
 }
 // A tagged launch (MsmBatch::tagged) has no table-free form: the caller asks first and keeps its two plain launches otherwise
@@ -571,6 +742,30 @@ int table_release(halo_ctx *ctx) {
     table_detach(ctx);
     return HALO_OK;
 }
+bool fold_table_wanted(const halo_ctx *ctx) {
+    if (ctx->d_foldtab || ctx->fold_table_mode == 0 || !ctx->shards.empty() || ctx->parent) return false;
+    return ctx->fold_table_mode == 1 || (tuning().fold_table_after > 0 && ctx->n >= ((size_t)1 << 18) && ctx->n <= ((size_t)1 << 21));
+}
+bool table_should_demote(halo_ctx *ctx) {
+    if (!ctx->d_table || ctx->tbl.rows <= ctx->tbl.W) return false;
+    {
+        std::lock_guard<std::mutex> lk(ctx->share->mu);
+        if (ctx->share->users != 1 || ctx->share->d_table != ctx->d_table) return false;
+    }
+    return table_budget_room(ctx, foldtab_need_bytes(ctx->n), (size_t)(ctx->tbl.rows - ctx->tbl.W) * ctx->n * 128);
+}
+int table_demote_now(halo_ctx *ctx) {
+    ctx->table_demote = false;
+    if (!table_should_demote(ctx)) return HALO_OK;
+    for (int k = 0; k < HALO_SLOTS; ++k)
+        if (ctx->wss[k].in_flight) return HALO_OK;  // (not now: asked for again by the next refusal)
+    int rc = table_release(ctx);  // (the only user: the memory and its reservation go back)
+    if (rc) return rc;
+    { std::lock_guard<std::mutex> lk(ctx->share->mu); ctx->share->table_fixed_only = true; }
+    ctx->table_retry_at = 0;
+    ctx->table_status = 0;
+    return HALO_OK;
+}
 // this context stops using the table; the memory goes back when no clone uses it either (each user's view is its own d_table:
 // a user that still holds one is counted by looking at the share's other users -- conservatively: freed by the last user of the key)
 void table_detach(halo_ctx *ctx) {
@@ -582,7 +777,7 @@ void table_detach(halo_ctx *ctx) {
     }
     if (free_it) {
         (void)hipFree(ctx->d_table);
-        table_budget_release(ctx, (size_t)ctx->tbl.W * ctx->n * 128);
+        table_budget_release(ctx, (size_t)ctx->tbl.rows * ctx->n * 128);
     }
     ctx->d_table = nullptr;
     ctx->tbl = TblPlan{};
@@ -600,8 +795,9 @@ bool table_eligible(const halo_ctx *ctx, const uint32_t *d_bases, const MsmBatch
         for (int b = 1; b < members.count; ++b)
             if (members.base_off[b] != members.base_off[0]) return false;
     }
-    size_t least = tp.c == 20 ? ((size_t)1 << 20) : ((size_t)1 << 17);
-    if (ctx->n < least || (n < least && !(members.sub && tp.c == 20 && n >= 4096)) || (tp.c != 20 && 2 * n < ctx->n) || n % 4 != 0 || (size_t)tp.W * ctx->n >= ((size_t)1 << 31)) return false;
+    size_t least = tp.c == 20 ? table_slide_min() : ((size_t)1 << 17);
+    const size_t rows = ctx->d_table ? (size_t)ctx->tbl.rows : (size_t)tp.W;
+    if (ctx->n < least || (n < least && !(members.sub && tp.c == 20 && n >= 4096)) || (tp.c != 20 && 2 * n < ctx->n) || n % 4 != 0 || rows * ctx->n >= ((size_t)1 << 31)) return false;
     return d_bases >= ctx->d_bases && d_bases + AFF_STRIDE * n <= ctx->d_bases + AFF_STRIDE * ctx->n;
 }
 // the shape of the row / column window sums (k_msm_reduce_rc) for a launch of `sets` bucket sets of B buckets each; per = 0: none
@@ -616,8 +812,12 @@ static RcShape table_rc_shape(int c, uint32_t B, uint32_t sets) {
 // A batch is about throughput: its window sums take 2^15-bucket virtual windows (8 buckets per lane) like the large plan --
 // with 2^12 (one bucket per lane: the short chain a single MSM wants) the wave-wide step of k_msm_reduce1 cost as many
 // instructions as the bucket kernel itself.
-static TblPlan table_launch_plan(const halo_ctx *ctx, int count) {
+// A context whose table holds every shift slides (ctx->tbl.slide) -- one MSM in one piece with the row / column window sums; the
+// tagged launch, the pieces of a larger MSM and table mode 1 take the fixed windows on rows 20 w of the same table.
+static TblPlan table_launch_plan(const halo_ctx *ctx, const MsmBatch &members, size_t n) {
+    const int count = members.count;
     TblPlan tp = ctx->tbl;
+    if (tp.rows == SLIDE_BITS && (members.tagged || count != 1 || n > TBL_PIECE || ctx->table_mode == 1 || !tuning().reduce_rc)) tp = table_plan_fixed_on(ctx->tbl, ctx->n);
     if (count > 1 && tp.vw_bits < 15 && tp.B >= (1u << 15)) { tp.vw_bits = 15; tp.vw = tp.B >> 15; }
     return tp;
 }
@@ -633,7 +833,7 @@ static uint32_t tmsm_kmax(const halo_ctx *ctx, size_t entries) {
 // bucket), rounded so that the blocks of the bucket kernel line up with the static layout
 static size_t tmsm_ovf_records(size_t entries, uint32_t kmax) { return (entries / kmax + 1 + 255) / 256 * 256; }
 int tmsm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MsmBatch &members, bool mont, size_t n, int partner) {
-    const TblPlan tp = table_launch_plan(ctx, members.count);
+    const TblPlan tp = table_launch_plan(ctx, members, n);
     size_t pieces = tp.c == 20 ? (n + TBL_PIECE - 1) / TBL_PIECE : 1;
     uint32_t cpow = 1;  // a batch (small-key plan, one piece) lays its members' bucket sets side by side: a power of two of them
     while ((int)cpow < msm_outputs(members)) cpow <<= 1;
@@ -662,7 +862,7 @@ int tmsm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bas
         size_t m = off + len <= n ? len : n - off;  // (n and len are multiples of 4)
         bool alt = partner >= 0 && (k & 1);
         StreamGuard on(ctx, alt ? ctx->streams[partner] : mine);
-        int rc = tmsm_enqueue_piece(ctx, alt ? ctx->wss[partner] : ws, d_bases + AFF_STRIDE * off, members, off, mont, m, (int)k, ws.h_winsum);
+        int rc = tmsm_enqueue_piece(ctx, alt ? ctx->wss[partner] : ws, tp, d_bases + AFF_STRIDE * off, members, off, mont, m, (int)k, ws.h_winsum);
         if (rc) return rc;
     }
     if (partner >= 0) {
@@ -676,13 +876,14 @@ int tmsm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bas
     p.table_rc = rcs.per != 0;
     p.table_rc_lg_rows = rcs.lg_rows;
     p.table_rc_lg_cols = rcs.lg_cols;
+    p.table_slide = tp.slide;
     ws.plan = p;
     return HALO_OK;
 }
 // one piece: window sums to slot `piece` of d_winsum / h_winsum (sets * vw weighted sums, then sets * vw plain sums)
-static int tmsm_enqueue_piece(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MsmBatch &members, size_t soff, bool mont, size_t n, int piece,
-                              uint64_t *h_dst) {
-    TblPlan tp = table_launch_plan(ctx, members.count);
+static int tmsm_enqueue_piece(halo_ctx *ctx, MsmWorkspace &ws, const TblPlan &plan, const uint32_t *d_bases, const MsmBatch &members, size_t soff, bool mont,
+                              size_t n, int piece, uint64_t *h_dst) {
+    TblPlan tp = plan;
     uint32_t cpow = 1;
     while ((int)cpow < msm_outputs(members)) cpow <<= 1;
     size_t entries = (size_t)tp.W * n * members.count;
@@ -701,6 +902,7 @@ static int tmsm_enqueue_piece(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d
     // from here on: ONE MSM of rows = count * W digit rows over sets * B buckets
     const uint32_t rows = (uint32_t)tp.W * (uint32_t)members.count;
     tp.B *= cpow; tp.ranges *= cpow; tp.vw *= cpow;
+    for (uint32_t k = cpow; k > 1; k >>= 1) tp.rbits++;
     uint32_t nchunks = 256u / rows;  // 19 (17) chunks per window: about one block per CU
     uint32_t chunk_len = (uint32_t)((n + nchunks - 1) / nchunks);
     chunk_len = (chunk_len + 3) / 4 * 4;

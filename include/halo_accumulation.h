@@ -449,7 +449,9 @@ int halo_set_memory_budget(halo_ctx *ctx, size_t bytes);
 /* what: 0 = bytes of the MSM fixed-base table, 1 = bytes of the fold table, 2 = microseconds the fold table took to build,
  * 3 = the budget for optional memory on this context's device, 4 = bytes of it in use (all contexts of this process on
  * that device), 5 = status of the fold table, 6 = status of the MSM table: 0 nothing yet, 1 memory requested, 2 built,
- * 3 over the budget, 4 allocation failed (tried again later), 5 switched off */
+ * 3 over the budget, 4 allocation failed (tried again later), 5 switched off; 7 = microseconds the MSM table took to build
+ * (without its allocation), 8 = rows of the MSM table (13 / 15: fixed windows; 255: every shift), 9 = plan of the launch
+ * enqueued last (0: no table pipeline, 1: its fixed windows, w + 1: sliding windows of at most w bits) */
 size_t halo_ctx_info(const halo_ctx *ctx, int what);
 /* MSM tuning: fixed-base tables.  -1 (default): an MSM of n >= 2^20 points over the context's own key uses the table
  * T[w][i] = 2^(20 w) G_i (13 x 128 bytes per point of the key, built on the first such MSM): 13 instead of 16 mixed
@@ -457,7 +459,19 @@ size_t halo_ctx_info(const halo_ctx *ctx, int what);
  * T[w][i] = 2^(17 w) G_i instead (15 x 128 bytes per point, 15 additions, 2^16 buckets) for MSMs over at least half of
  * its key.  0: never (no table memory).  Optional memory: subject to halo_set_memory_budget; a table that cannot be had
  * (budget, allocation) is not an error -- the table-free pipeline runs (halo_ctx_info(ctx, 6)) and the table is tried again
- * later.  Results are identical. */
+ * later.  Results are identical.
+ * A key of >= 2^20 points on one device first asks for the ALL-SHIFTS table T[j][i] = 2^j G_i, j = 0 .. 254 (255 x 128 bytes per
+ * point: 34 GB at 2^20; keys up to 2^20 points) and, with it, recodes the scalars into sliding windows of at most 21 bits that
+ * start at set bits only: 12.0 additions per point instead of 13 (one MSM per launch; the IPA's tagged launch and MSMs run in
+ * pieces read rows 20 w of the same table).  If the budget or the allocation refuses the 34 GB, the 13 rows are built as before.
+ * The fold table has the first claim on the budget (the default budget holds one of the two), decided per key: when it is
+ * refused beside an all-shifts table that only this context uses, and would fit without it, the MSM table is taken down to its
+ * 13 rows -- at once by halo_set_fold_table(ctx, 1) and by halo_ctx_clone (a key with clones is a service that opens), else at
+ * the next MSM enqueued with nothing in flight -- and the key keeps to 13 rows until halo_set_fold_table(ctx, 0) or a new budget.
+ * A key that has clones builds the all-shifts table only if the budget holds both tables; a table that clones already share is
+ * never taken from them (the fold table is then refused as over the budget, halo_ctx_info(ctx, 5) == 3).
+ * 1: as -1 with the fixed windows forced: no all-shifts table is built, and one that exists is read through its row stride
+ * (A/B runs, tests). */
 int halo_set_table_mode(halo_ctx *ctx, int mode);
 
 

@@ -25,7 +25,8 @@ extern "C" {
  * halo_pcdl_check_batch / halo_acc_decider_batch / halo_pcdl_open_batch / halo_random_instance_batch / halo_acc_prover_batch is refused, as over the
  * memory budget: one member at a time; halo_acc_verifier_batch: its sums on the host pool), "check_batch_group" (members per MSM launch of the check batch, 1..8; 0: the measured
  * default), "open_batch_group" (members per launch of the open and prover batches, 1..4; 0: the measured default), "verifier_batch_min" (relations
- * from which halo_acc_verifier_batch runs its sums on the device, >= 1; 0: the measured default), "decode_batch_min" (finite points
+ * from which halo_acc_verifier_batch runs its sums on the device, >= 1; 0: the measured default), "table_slide_min" (keys from this many points, >= 4096, take the c = 20 table plans and
+ * the all-shifts table with its sliding-window recode; 0: 2^20), "decode_batch_min" (finite points
  * from which halo_*_decode_batch decompresses on the device, >= 1; 0: the measured default; "batch_stage_fail" refuses its staging
  * too: the host pool), "reset" (all off). */
 int halo_dev_hook(const char *name, long value);
