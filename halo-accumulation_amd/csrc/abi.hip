@@ -6,7 +6,7 @@
 #include <new>
 #include <utility>
 
-#include "internal.hpp"
+#include "pcdl_internal.hpp"  // (is_pow2, the transcript's hashes)
 
 namespace halo {
 
@@ -83,10 +83,6 @@ static int ctx_alloc_common(halo_ctx *ctx, int device, size_t n) {
     host::g_inv_fermat = tuning().host_inv_fermat;
     return msm_workspace_alloc(ctx, n, 0);
 }
-
-static bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
-
-// guard used by every entry point
 
 int upload_words(halo_ctx *ctx, uint64_t *dst, const uint64_t *src, size_t words) {
     if (words == 0) return HALO_OK;
@@ -882,11 +878,8 @@ static int ipa_round_lr_points(halo_ipa *st, host::Fr dots[2], host::Point *Lp_o
     const int dots_env = tuning().dots_first;  // development switch
     const bool dots_first = dots_env >= 0 ? dots_env != 0 : (st->nofold ? st->M : m) > ((size_t)1 << 16);
     auto launch_dots = [&]() -> int {
-        hipStream_t saved = ctx->stream;
-        ctx->stream = ctx->streams[2];
-        int rcl = fr_dot2_launch(ctx, st->d_c + 4 * m, st->d_z, st->d_c, st->d_z + 4 * m, m);
-        ctx->stream = saved;
-        return rcl;
+        StreamGuard on_third(ctx, ctx->streams[2]);
+        return fr_dot2_launch(ctx, st->d_c + 4 * m, st->d_z, st->d_c, st->d_z + 4 * m, m);
     };
     if (dots_first) { int rcl = launch_dots(); if (rcl) return rcl; }
     // the last round of a no-fold phase: its two coefficients travel to the host with the round's results (halo_ipa_finish
@@ -1042,10 +1035,8 @@ static int ipa_round_fold_impl(halo_ipa *st, const uint64_t xi[4], const uint64_
             HALO_HIP(hipEventRecord(st->ev, ctx->streams[0]));
             HALO_HIP(hipStreamWaitEvent(ctx->streams[3], st->ev, 0));
             {
-                hipStream_t saved = ctx->stream;
-                ctx->stream = ctx->streams[3];
+                StreamGuard on_fourth(ctx, ctx->streams[3]);
                 rc = ipa_fold_points4(ctx, st->G_src, dst, m, &st->s_host[1]);
-                ctx->stream = saved;
             }
             if (rc) return rc;
             HALO_HIP(hipEventRecord(st->ev_fold, ctx->streams[3]));
@@ -1244,9 +1235,7 @@ int halo_open_start(const uint64_t C[12], const uint64_t z[4], const uint64_t *v
     if (!C || !z || !v_parts || !v_out || !xi0 || !Hp_out || P == 0) { set_error("open_start: bad argument"); return HALO_E_ARG; }
     host::Fr v = host::Fr::zero();
     for (size_t i = 0; i < P; ++i) v = v + host::Fr::load(v_parts + 4 * i);  // p(z) = sum of the shards' <c, z>
-    host::Transcript t;
-    t.point(host::Point::load(C)); t.scalar(host::Fr::load(z)); t.scalar(v);
-    host::Fr x0 = t.finish(0);  // pcdl.rs:180
+    host::Fr x0 = rho0_C_z_v(host::Point::load(C), host::Fr::load(z), v);  // pcdl.rs:180
     uint64_t S[12], H[12];
     halo_public_points(S, H);
     host::Point::load(H).mul(x0).store_normalized(Hp_out);  // pcdl.rs:181
@@ -1270,16 +1259,14 @@ int halo_open_hiding_combine(const uint64_t C[12], const uint64_t z[4], const ui
         v = v + host::Fr::load(v_parts + 4 * i);
         Cb = Cb + host::Point::load(Cbar_parts + 12 * i);
     }
-    host::Rng rng{*rng_state + 4 * (uint64_t)deg * 0x9E3779B97F4A7C15ULL};  // past the deg coefficients of q (pcdl.rs:141)
+    host::Rng rng = host::Rng{*rng_state}.skip_scalars(deg);                // past the deg coefficients of q (pcdl.rs:141)
     host::Fr w_bar = rng.scalar();                                          // pcdl.rs:147
     *rng_state = rng.state;
     uint64_t Sw[12], Hw[12];
     halo_public_points(Sw, Hw);
     host::Point S = host::Point::load(Sw), Cp = host::Point::load(C);
     Cb = (S.mul(w_bar) + Cb).normalized();                                  // pcdl.rs:150 via pedersen.rs:15-17
-    host::Transcript t;
-    t.point(Cp); t.scalar(host::Fr::load(z)); t.scalar(v); t.point(Cb);
-    host::Fr a = t.finish(0);                                               // pcdl.rs:153
+    host::Fr a = rho0_C_z_v_Cbar(Cp, host::Fr::load(z), v, Cb);             // pcdl.rs:153
     host::Fr wp = w_bar * a + host::Fr::load(w);                            // pcdl.rs:159
     (Cp + Cb.mul(a) - S.mul(wp)).store_normalized(C_prime);                 // pcdl.rs:162
     Cb.store(Cbar);
@@ -1306,9 +1293,7 @@ int halo_open_combine(const uint64_t *parts, size_t P, const uint64_t Hp[12], co
     }
     Lp = (Lp + hp_tab.mul(dl)).normalized();  // pcdl.rs:204
     Rp = (Rp + hp_tab.mul(dr)).normalized();  // pcdl.rs:208
-    host::Transcript t;
-    t.scalar(host::Fr::load(xi_prev)); t.point(Lp); t.point(Rp);
-    host::Fr x = t.finish(0);  // pcdl.rs:212
+    host::Fr x = rho0_xi_L_R(host::Fr::load(xi_prev), Lp, Rp);  // pcdl.rs:212
     if (x.is_zero()) { set_error("open: challenge is zero (inverse().unwrap())"); return HALO_E_ASSERT; }
     Lp.store(L); Rp.store(R);
     x.store(xi);
@@ -1353,9 +1338,7 @@ int halo_open_tail(const uint64_t *recs, size_t P, const uint64_t Hp[12], const 
         for (size_t j = 0; j < m; ++j) { L = L + term[j]; R = R + term[m + j]; }
         L = (L + term[2 * m]).normalized();
         R = (R + term[2 * m + 1]).normalized();
-        host::Transcript t;
-        t.scalar(xi); t.point(L); t.point(R);
-        host::Fr x = t.finish(0);  // :212
+        host::Fr x = rho0_xi_L_R(xi, L, R);  // :212
         if (x.is_zero()) { set_error("open: challenge is zero (inverse().unwrap())"); return HALO_E_ASSERT; }
         host::Fr xinv = x.inv();
         L.store(Ls + 12 * round);
@@ -1378,7 +1361,7 @@ int halo_rng_scalars_dev(halo_ctx *ctx, uint64_t *rng_state, size_t n, void *d_o
     int rc = rng_scalars_dev(ctx, *rng_state, n, static_cast<uint64_t *>(d_out));
     if (rc) return rc;
     HALO_HIP(hipStreamSynchronize(ctx->stream));
-    *rng_state += 4 * (uint64_t)n * 0x9E3779B97F4A7C15ULL;  // n scalars = 4n draws of the SplitMix64 stream
+    *rng_state = host::Rng{*rng_state}.skip_scalars(n).state;  // n scalars = 4n draws of the SplitMix64 stream
     return HALO_OK;
 }
 int halo_point_sum(const uint64_t *pts_jac, size_t k, uint64_t out[12]) {

@@ -729,9 +729,10 @@ inline Fr urs_scalar(u64 index) {
 
 // SplitMix64 stream shared with the tests' input generator
 struct Rng {
+    static constexpr u64 GAMMA = 0x9E3779B97F4A7C15ULL;
     u64 state;
     u64 next() {
-        state += 0x9E3779B97F4A7C15ULL;
+        state += GAMMA;
         u64 z = state;
         z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
         z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
@@ -743,7 +744,25 @@ struct Rng {
         while (Fr::geq(v.l, FrP::M)) Fr::sub_limbs(v.l, v.l, FrP::M);
         return v.to_mont();
     }
+    // past k scalars (4 draws each) that someone else draws -- a kernel, from the same state: the stream is a counter
+    Rng &skip_scalars(u64 k) { state += 4 * k * GAMMA; return *this; }
 };
+
+// h(z) for the challenges xis[0 .. lg] as pcdl.rs:79-91 evaluates it: (1 + xi_lg z) prod_{0 < k < lg} (1 + xi_(lg-k) z^(2^k)).
+// (xis[0] takes no part from lg = 1 on; at lg = 0 the head factor is all there is -- the reference's value, kept.)
+inline Fr h_eval(const Fr *xis, size_t lg, const Fr &z) {
+    Fr hz = Fr::one() + xis[lg] * z, zi = z;
+    for (size_t k = 1; k < lg; ++k) { zi = zi.sqr(); hz = hz * (Fr::one() + xis[lg - k] * zi); }
+    return hz;
+}
+
+// out[i] = 1 / in[i] for n non-zero elements with ONE inversion (Montgomery's trick); out must not alias in
+inline void batch_inverse(const Fr *in, size_t n, Fr *out) {
+    std::vector<Fr> pref(n + 1, Fr::one());
+    for (size_t i = 0; i < n; ++i) pref[i + 1] = pref[i] * in[i];
+    Fr run = n ? pref[n].inv() : Fr::one();
+    for (size_t i = n; i-- > 0;) { out[i] = run * pref[i]; run = run * in[i]; }
+}
 
 }  // namespace host
 }  // namespace halo

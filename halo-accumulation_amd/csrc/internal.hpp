@@ -349,7 +349,7 @@ struct halo_ctx {
     size_t slot_scalars_bytes[HALO_SLOTS] = {};
     uint64_t *d_verify = nullptr;  // staging of the batched verifier (points, scalars, challenges, results), grown on demand
     size_t verify_words = 0;
-    // staging of halo_pcdl_check_batch / halo_acc_decider_batch (pcdl_acc.hip): h coefficients and tables of the members in flight.
+    // staging of halo_pcdl_check_batch / halo_acc_decider_batch (pcdl_batch.hip): h coefficients and tables of the members in flight.
     // Optional memory (on the budget of halo_set_memory_budget; released at destroy), only grown, so its address stays put
     uint64_t *d_check_stage = nullptr;
     size_t check_stage_bytes = 0;
@@ -423,6 +423,37 @@ struct BorrowScope {
     explicit BorrowScope(halo_ctx *ctx) : c(ctx) { c->may_borrow++; }
     ~BorrowScope() { c->may_borrow--; }
 };
+// the launch macro uses ctx->stream: a slot's own stream for the launches of a scope
+struct StreamGuard {
+    halo_ctx *ctx;
+    hipStream_t saved;
+    StreamGuard(halo_ctx *c, hipStream_t s) : ctx(c), saved(c->stream) { c->stream = s; }
+    ~StreamGuard() { ctx->stream = saved; }
+};
+// The slots a batched call may use: no MSM of the caller's in flight, not lent to a neighbour's large MSM, no fan-out over the
+// shards.  out[0 .. count), in slot order.
+inline int idle_slots(const halo_ctx *ctx, int out[HALO_SLOTS]) {
+    int S = 0;
+    for (int k = 0; k < HALO_SLOTS; ++k)
+        if (!ctx->wss[k].in_flight && ctx->wss[k].lent_from < 0 && !ctx->fan[k].active) out[S++] = k;
+    return S;
+}
+// The outcomes of a batched call in member order: status[i] (nullable) = code_of(i), on_fail(i) for every failing member (its
+// output zeroed, or nothing).  Returns the first failing member's code with the message "<noun> <i>: <err_of(i)>", else 0.
+template <class CodeOf, class ErrOf, class OnFail>
+int report_members(const char *noun, size_t m, CodeOf code_of, ErrOf err_of, int *status, OnFail on_fail) {
+    size_t first = m;
+    for (size_t i = 0; i < m; ++i) {
+        const int rc = code_of(i);
+        if (status) status[i] = rc;
+        if (!rc) continue;
+        on_fail(i);
+        if (first == m) first = i;
+    }
+    if (first == m) return HALO_OK;
+    set_error(std::string(noun) + " " + std::to_string(first) + ": " + err_of(first));
+    return code_of(first);
+}
 // a context's count of its own device (de)allocations
 inline void alloc_epoch_bump(halo_ctx *ctx) { ctx->alloc_epoch++; }
 int msm_workspace_alloc(halo_ctx *ctx, size_t n, int slot);
@@ -560,7 +591,7 @@ int nofold_expand(halo_ctx *ctx, const uint64_t *d_c, const uint64_t *d_s, size_
 int nofold_expand_tagged(halo_ctx *ctx, const uint64_t *d_c, const uint64_t *d_s, size_t m, size_t M, uint64_t *d_F);  // one array for a tagged launch
 int nofold_s_update(halo_ctx *ctx, const uint64_t *d_s_in, size_t len, const host::Fr &xi, uint64_t *d_s_out);
 
-// ---- ipa.hip: the member-batched kernels of halo_pcdl_open_batch (pcdl_acc.hip).  G <= OPEN_MAX_GROUP members per launch,
+// ---- ipa.hip: the member-batched kernels of halo_pcdl_open_batch (pcdl_batch.hip).  G <= OPEN_MAX_GROUP members per launch,
 // blockIdx.y = member.  Member b's vectors sit at b * ms words from the base pointers; its window table, constants, partial sums
 // and results at b * OPEN_*_WORDS in the group's own regions.
 constexpr int OPEN_MAX_GROUP = 4;
@@ -602,11 +633,11 @@ constexpr size_t SQRT_TAB_WORDS = 4 * 256 * 8 + 256;  // 32-bit words of the squ
 const uint32_t *sqrt_tables_host();  // built on first use (null: the lookup limbs collide -- never for this field)
 int point_decompress_dev(halo_ctx *ctx, const uint64_t *d_in, size_t n, const uint32_t *d_tab, uint64_t *d_out);  // on ctx->stream
 int fq_sqrt_dev(halo_ctx *ctx, const uint64_t *d_a, size_t n, const uint32_t *d_tab, uint64_t *d_root, uint32_t *d_ok);
-// ---- pcdl_acc.hip: the context's staging for batched calls (optional memory), grown to `want` x per_bytes if the budget
+// ---- pcdl_batch.hip: the context's staging for batched calls (optional memory), grown to `want` x per_bytes if the budget
 // allows; returns how many units of per_bytes it holds (0: none)
 size_t check_stage(halo_ctx *ctx, size_t want, size_t per_bytes);
 
-// ---- abi.hip (device-pointer forms used by pcdl_acc.hip)
+// ---- abi.hip (device-pointer forms used by pcdl_acc.hip and pcdl_batch.hip)
 // H' = xi0 * H for this state (pcdl.rs:181): lets the rounds use the process-wide window table of H
 void ipa_set_hprime_scalar(halo_ipa *st, const host::Fr &xi0);
 // process-wide window table of the public point H (consts.rs:45-65), built on first use

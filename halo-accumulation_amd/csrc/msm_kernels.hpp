@@ -79,12 +79,6 @@ __global__ __launch_bounds__(64) void k_msm_reduce_rc(const uint32_t *__restrict
                                                       RcShape sh, uint32_t *__restrict__ ent);
 
 // ---- host functions that cross unit boundaries
-struct StreamGuard {  // the launch macro uses ctx->stream
-    halo_ctx *ctx;
-    hipStream_t saved;
-    StreamGuard(halo_ctx *c, hipStream_t s) : ctx(c), saved(c->stream) { c->stream = s; }
-    ~StreamGuard() { ctx->stream = saved; }
-};
 uint32_t msm_kmax(const halo_ctx *ctx, size_t n);                       // msm_driver.hip: task length of the bucket kernel for an MSM of n points
 int launch_c(const halo_ctx *ctx, const MsmBatch &members);            // msm_driver.hip: window bits of a launch
 int msm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MsmBatch &members, bool mont, size_t n, int partner);  // msm_general.hip

@@ -1,0 +1,1016 @@
+// The batched calls of the pcdl / acc level: m or k of the single calls of pcdl_acc.hip in one, every member's output, status,
+// message and draws those of the loop over the single call.  Four pipelines -- the check / decider batch, the verifier batch, the
+// open / random-instance batch, the prover batch -- and their entry points.  What they share with the single calls is declared
+// in pcdl_internal.hpp; the slots, streams and outcome reports they share with each other (and with wire.hip's decode batch) in
+// internal.hpp: idle_slots, StreamGuard, report_members.
+#include "pcdl_internal.hpp"
+
+namespace halo {
+
+using host::Fr;
+using host::Point;
+
+// ------------------------------------------------------------------ the staging every batched call shares
+// Member buffers of n coefficients + one set of tables each in the context's check staging: grown to `want` buffers if the
+// memory budget and the device allow (optional memory: halo_set_memory_budget), never shrunk.  Returns how many buffers it
+// holds (0: none -- the caller runs one member at a time in ctx->d_tmp_a; never an error).
+size_t check_stage(halo_ctx *ctx, size_t want, size_t per_bytes) {
+    if (dev_hooks().batch_stage_fail) return 0;  // (development library: the fallback path)
+    const size_t bytes = want * per_bytes;
+    if (ctx->check_stage_bytes < bytes && table_budget_reserve(ctx, bytes)) {
+        uint64_t *p = nullptr;
+        if (hipMalloc(&p, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            p = nullptr;
+            table_budget_release(ctx, bytes);
+        } else {
+            alloc_epoch_bump(ctx);  // (cached launch graphs name the old buffer)
+            if (ctx->d_check_stage) {
+                for (int k = 0; k < HALO_SLOTS; ++k)
+                    if (!ctx->wss[k].in_flight) (void)hipStreamSynchronize(ctx->streams[k]);
+                (void)hipFree(ctx->d_check_stage);
+                table_budget_release(ctx, ctx->check_stage_bytes);
+            }
+            ctx->d_check_stage = p;
+            ctx->check_stage_bytes = bytes;
+        }
+    }
+    return ctx->check_stage_bytes / per_bytes;
+}
+
+namespace {  // (everything below is local to this file; the entry points at the end are the way in)
+
+// Members per batched launch: the forced size (the development library's sweeps) if it lies in 1 .. max, else max; then as many
+// as the small pipeline's bucket limit allows with `arrays` scalar arrays per member (windows x arrays x buckets <= 2^22)
+static int group_size(const halo_ctx *ctx, size_t n, int forced, int max, int arrays) {
+    int g = forced >= 1 && forced <= max ? forced : max;
+    MsmPlan p = msm_plan(n, ctx->window_bits);
+    while (g > 1 && (size_t)p.W * (size_t)(arrays * g) * p.B > ((size_t)1 << 22)) --g;
+    return g;
+}
+
+// ------------------------------------------------------------------ pcdl::check of m instances at once
+// The succinct half of every member as halo_pcdl_succinct_check_batch runs it (the relations on the device from kBatchVerifyMin
+// members on, on the host pool below); then the accepted members in groups of up to MSM_MAX_BATCH: their h coefficients expanded
+// on the device (k_h_tables + k_h_coeffs_batch: two launches per group) into the group's staging, and the group's n-point MSMs
+// as ONE batched launch sequence over the key.  Groups rotate over the slots that were idle at entry; when a slot comes round
+// again its group is collected and every member's point compared with its U (pcdl.rs:338-339) on the host while the other slots'
+// groups run.  Every member gets its own exact MSM.  A multi-device context runs the groups on its own device (devices[0], which
+// holds the whole key), as halo_pcdl_check does: no fan-out, the same points.
+//
+// Members per launch (check_group_size): the small pipeline (smsm.hip, n <= 2^16) takes batches of 8 within its bucket limit
+// (windows x batch x buckets <= 2^22); a key of 2^20 points or more runs its MSMs of >= 2^20 points through the fixed-base table,
+// which takes single members only, so there each member is a group of its own.  Measured: DESIGN.md "Batched checks".
+static int check_group_size(const halo_ctx *ctx, size_t n) {
+    const int forced = dev_hooks().check_group;  // (development library: the sweep of tools/time_decider_batch.py)
+    if (forced <= 0 && n >= ((size_t)1 << 20) && ctx->n >= ((size_t)1 << 20) && ctx->table_mode != 0) return 1;
+    return group_size(ctx, n, forced, MSM_MAX_BATCH, 1);
+}
+// blobs: m Instances (or Accumulators, whose Instance prefix is checked) at `stride` words, all of degree bound d (checked by
+// the caller); status[i] (nullable) = what halo_pcdl_check returns for member i alone
+static int pcdl_check_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t stride, size_t m, int *status) {
+    const size_t n = d + 1, lg = ilog2(n);
+    int slots[HALO_SLOTS], S = idle_slots(ctx, slots);
+    if (!S) { set_error("check_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
+    // 1. the succinct half (pcdl.rs:333)
+    std::vector<BatchCheck> res;
+    int rc = succinct_half(ctx, d, [&](size_t i) { return qs + i * stride; }, m, res);
+    if (rc) return rc;
+    std::vector<size_t> ok;  // the accepted members, in order
+    for (size_t i = 0; i < m; ++i)
+        if (!res[i].rc) ok.push_back(i);
+    const size_t A = ok.size();
+    if (A) {
+        if (lg > 24) { set_error("h_coeffs: lg_n > 24 unsupported"); return HALO_E_ARG; }
+        // 2. their challenges in device memory, in that order (one copy)
+        const size_t xw = (lg + 1) * 4;
+        std::vector<uint64_t> xis(A * xw);
+        for (size_t a = 0; a < A; ++a)
+            for (size_t k = 0; k <= lg; ++k) res[ok[a]].st.xis[k].store(&xis[a * xw + 4 * k]);
+        rc = verify_staging(ctx, xis.size());
+        if (rc) return rc;
+        HALO_HIP(hipMemcpy(ctx->d_verify, xis.data(), xis.size() * 8, hipMemcpyHostToDevice));
+        // 3. groups of G members over S slots, G x S member buffers in the staging (fewer if it cannot grow; none: d_tmp_a)
+        size_t G = (size_t)check_group_size(ctx, n);
+        if (G > A) G = A;
+        size_t ng = (A + G - 1) / G;
+        if ((size_t)S > ng) S = (int)ng;
+        const size_t per = n * 4 + H_TABLES_WORDS;  // words of one member buffer
+        size_t have = check_stage(ctx, G * (size_t)S, per * 8);
+        const bool scratch = have == 0;
+        if (scratch) { G = 1; S = 1; }
+        else if (have < G * (size_t)S) {
+            if (G > have) G = have;
+            if ((size_t)S > have / G) S = (int)(have / G);
+        }
+        ng = (A + G - 1) / G;
+        auto coeffs_of = [&](size_t j) { return scratch ? ctx->d_tmp_a : ctx->d_check_stage + j * G * n * 4; };
+        auto tables_of = [&](size_t j) { return scratch ? ctx->d_tmp_c + 8 * 1024 + 1024 : ctx->d_check_stage + (size_t)S * G * n * 4 + j * G * H_TABLES_WORDS; };
+        std::vector<long> flight(S, -1);  // the group in flight on slots[j]
+        auto collect = [&](size_t j) -> int {
+            long g = flight[j];
+            if (g < 0) return HALO_OK;
+            flight[j] = -1;
+            size_t first = (size_t)g * G, cnt = A - first < G ? A - first : G;
+            Point pts[MSM_MAX_BATCH];
+            int rc2 = msm_finish_batch(ctx, slots[j], pts, (int)cnt);
+            if (rc2) return rc2;
+            for (size_t b = 0; b < cnt; ++b) {
+                BatchCheck &r = res[ok[first + b]];
+                if (r.st.U != pts[b]) { r.rc = HALO_E_REJECT; r.err = "U != CM.Commit(ck, h_vec)"; }  // :339
+            }
+            return HALO_OK;
+        };
+        auto abandon = [&]() {  // (a device error: nothing of this call stays in flight)
+            std::string err = halo_last_error();
+            for (int j = 0; j < S; ++j)
+                if (flight[j] >= 0) {
+                    Point pts[MSM_MAX_BATCH];
+                    size_t first = (size_t)flight[j] * G;
+                    (void)msm_finish_batch(ctx, slots[j], pts, (int)(A - first < G ? A - first : G));
+                    flight[j] = -1;
+                }
+            set_error(err);
+        };
+        for (size_t g = 0; g < ng; ++g) {
+            const size_t j = g % (size_t)S, first = g * G, cnt = A - first < G ? A - first : G;
+            rc = collect(j);
+            if (!rc) {
+                StreamGuard on_slot(ctx, ctx->streams[slots[j]]);
+                rc = h_coeffs_batch_dev(ctx, ctx->d_verify + first * xw, cnt, lg, tables_of(j), coeffs_of(j), n * 4);  // h.get_poly().coeffs
+            }
+            if (!rc) {
+                MsmBatch mb;
+                mb.count = (int)cnt;
+                for (size_t b = 0; b < cnt; ++b) mb.scalars[b] = coeffs_of(j) + b * n * 4;
+                rc = msm_enqueue_batch(ctx, slots[j], ctx->d_bases, mb, true, n);  // :338, asynchronous
+            }
+            if (rc) { abandon(); return rc; }
+            flight[j] = (long)g;
+        }
+        for (size_t g = ng > (size_t)S ? ng - (size_t)S : 0; g < ng; ++g) {
+            rc = collect(g % (size_t)S);
+            if (rc) { abandon(); return rc; }
+        }
+    }
+    return report_members("instance", m, [&](size_t i) { return res[i].rc; }, [&](size_t i) { return res[i].err; }, status, [](size_t) {});
+}
+// the argument checks of both entry points (halo_pcdl_succinct_check_batch's), then the batch; acc: Accumulator blobs
+static int check_batch_entry(halo_ctx *ctx, size_t d, const uint64_t *blobs, size_t m, int *status, bool acc) {
+    if (m && !blobs) { set_error("check_batch: null pointer"); return HALO_E_ARG; }
+    if (!is_pow2(d + 1)) return fail_reject("d+1 is not a power of 2!");
+    size_t lg = ilog2(d + 1), stride = acc ? acc_words(lg) : instance_words(lg);
+    for (size_t i = 0; i < m; ++i)
+        if ((size_t)(blobs + i * stride)[12] != d || (blobs + i * stride)[22] != lg) return fail_reject("d_i != d");
+    if (m == 0) return HALO_OK;
+    return pcdl_check_batch_host(ctx, d, blobs, stride, m, status);
+}
+
+// ------------------------------------------------------------------ acc::verifier of k accumulators at once
+// (halo_acc_verifier_batch; acc.rs:223-243 per member, each member's outcome the single call's)
+//  1. the transcripts: one pool pass over the instances of every member that reaches its succinct checks -- C', the
+//     challenges (succinct_challenges) and h_i(z_i), i.e. the relation's terms (relation_terms); then one pass over the members:
+//     alpha = rho_1(hs) (:173), its powers, and the terms of h_0[0] G_0 + h_0[1] G_1 (:152-155) and C = sum_i alpha^i U_i (:178).
+//  2. every sum of the batch at once: ONE k_small_msm_seg launch on a slot idle at entry, from kVerifierBatchMin relations on;
+//     below that, without an idle slot or without staging (optional memory: check_stage), the host pool, sum by sum.
+//  3. one pass over the members: z' = rho_1(C, alpha) (:181), C_bar' = C + w S (:184), h(z), and the status in the single
+//     call's order (fields, U_0, d_i, the succinct checks in instance order, C_bar', z', d', h(z)).
+constexpr size_t kVerifierBatchMin = 64;  // relations; measured: tools/time_verifier_batch.py
+constexpr size_t kSegMaxTerms = 64;      // terms per sum of k_small_msm_seg (a longer C is summed in parts)
+
+struct VerifierMember {
+    int rc = HALO_OK;
+    std::string err;
+    size_t first = 0, m = 0;  // its instances in the flat list
+    bool sums = false;        // reaches the U_0 check (fields valid, deg h_0 <= d)
+    bool reach = false;       // ... and its succinct checks (every d_i == d)
+    bool all_ok = false;      // ... and every transcript held: C is summed
+    size_t s_u0 = 0, s_c = 0, n_c = 0;  // its sums: h_0 against U_0, the n_c parts of C
+    AccHPolys hs;
+};
+// Every sum of a batch, term by term: sum s holds terms off[s] .. off[s + 1], a term is a point (arkworks affine, (0, 0) =
+// infinity) and a canonical scalar -- the format of k_small_msm_seg
+struct SumList {
+    std::vector<uint32_t> off{0};
+    std::vector<uint64_t> pts, sc;
+    size_t add(size_t terms) { off.push_back(off.back() + (uint32_t)terms); return off.size() - 2; }
+    size_t count() const { return off.size() - 1; }
+    size_t terms() const { return off.back(); }
+    void put_point(size_t t, const Point &p) {
+        host::Affine a = p.to_affine();
+        if (!a.inf) { a.x.store(&pts[8 * t]); a.y.store(&pts[8 * t + 4]); }
+    }
+};
+
+// 0. what the single call checks before any arithmetic, and the sums' layout.  rel_sum: the relation sum of each instance;
+// work: the instances whose transcripts run
+static void verifier_layout(size_t d, const uint64_t *qs, const uint64_t *accs, std::vector<VerifierMember> &mem, SumList &L,
+                            std::vector<size_t> &rel_sum, std::vector<size_t> &work) {
+    const size_t lg = ilog2(d + 1), iw = instance_words(lg), aw = acc_words(lg), K = 2 * lg + 2;
+    const size_t u0_terms = d ? 2 : 1;  // (d = 0: h_0 is a constant, or the assert below)
+    for (size_t j = 0; j < mem.size(); ++j) {
+        VerifierMember &M = mem[j];
+        const uint64_t *acc = accs + j * aw, *piV = acc + iw;
+        M.hs.h0[0] = Fr::load(piV);
+        M.hs.h0[1] = Fr::load(piV + 4);
+        M.hs.lg_n = lg;
+        if (!Point::load(piV + 8).on_curve() || !Point::load(acc).on_curve() || !scalar_ok(M.hs.h0[0]) || !scalar_ok(M.hs.h0[1]) ||
+            !scalar_ok(Fr::load(piV + 20)) || !scalar_ok(Fr::load(acc + 13)) || !scalar_ok(Fr::load(acc + 17))) {
+            M.rc = HALO_E_REJECT;
+            M.err = "accumulator holds an invalid point or scalar";
+            continue;
+        }
+        if (host_poly_degree(piV, 2) > d) { M.rc = HALO_E_ASSERT; M.err = "commit: p.degree() > d"; continue; }  // pcdl_commit_host
+        M.sums = true;
+        M.s_u0 = L.add(u0_terms);
+        M.reach = true;
+        for (size_t i = 0; i < M.m && M.reach; ++i) {
+            const uint64_t *q = qs + (M.first + i) * iw;
+            if ((size_t)q[12] != d || q[22] != lg) M.reach = false;  // :169
+        }
+        if (!M.reach) continue;
+        for (size_t i = 0; i < M.m; ++i) {
+            rel_sum[M.first + i] = L.add(K);
+            work.push_back(M.first + i);
+        }
+        M.n_c = (M.m + 1 + kSegMaxTerms - 1) / kSegMaxTerms;
+        M.s_c = L.count();
+        for (size_t c = 0; c < M.n_c; ++c) L.add(c + 1 < M.n_c ? kSegMaxTerms : M.m + 1 - c * kSegMaxTerms);
+    }
+}
+// 2. every sum in ONE k_small_msm_seg launch on ctx->stream, through the context's staging (bytes): points nterms x 64 |
+// scalars nterms x 32 | results nsums x 96 | off (nsums + 1) x 4 | desc waves x 256
+static int sums_on_device(halo_ctx *ctx, const SumList &L, const std::vector<uint32_t> &desc, size_t waves, std::vector<Point> &sums) {
+    const size_t nsums = L.count(), nterms = L.terms();
+    uint64_t *d_pts = ctx->d_check_stage, *d_sc = d_pts + nterms * 8, *d_out = d_sc + nterms * 4;
+    uint32_t *d_off = reinterpret_cast<uint32_t *>(d_out + nsums * 12), *d_desc = d_off + nsums + 1;
+    auto copy = [&](void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+        hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, ctx->stream);
+        return e == hipSuccess ? HALO_OK : hip_fail(e, "hipMemcpyAsync");
+    };
+    int rc = copy(d_pts, L.pts.data(), nterms * 64, hipMemcpyHostToDevice);
+    if (!rc) rc = copy(d_sc, L.sc.data(), nterms * 32, hipMemcpyHostToDevice);
+    if (!rc) rc = copy(d_off, L.off.data(), (nsums + 1) * 4, hipMemcpyHostToDevice);
+    if (!rc) rc = copy(d_desc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice);
+    if (!rc) rc = small_msm_seg(ctx, d_pts, d_sc, d_off, d_desc, waves, d_out);
+    std::vector<uint64_t> out(nsums * 12);
+    if (!rc) rc = copy(out.data(), d_out, nsums * 96, hipMemcpyDeviceToHost);
+    if (rc) return rc;
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "hipStreamSynchronize");
+    for (size_t s = 0; s < nsums; ++s) sums[s] = Point::load(&out[12 * s]);
+    return HALO_OK;
+}
+
+static int acc_verifier_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, const size_t *counts, size_t k, const uint64_t *accs, int *status) {
+    const size_t lg = ilog2(d + 1), iw = instance_words(lg), aw = acc_words(lg), K = 2 * lg + 2;
+    if (K > kSegMaxTerms) { set_error("verifier_batch: lg n too large"); return HALO_E_ARG; }
+    std::vector<VerifierMember> mem(k);
+    size_t total = 0;
+    for (size_t j = 0; j < k; ++j) { mem[j].first = total; mem[j].m = counts[j]; total += counts[j]; }
+    SumList L;
+    std::vector<size_t> rel_sum(total, 0), work;
+    verifier_layout(d, qs, accs, mem, L, rel_sum, work);
+    const size_t nsums = L.count(), nterms = L.terms();
+    if (nterms >= ((size_t)1 << 31) || nsums >= ((size_t)1 << 28)) { set_error("verifier_batch: too many terms"); return HALO_E_ARG; }
+    L.pts.assign(nterms * 8, 0);
+    L.sc.assign(nterms * 4, 0);
+    // 1. the transcripts and the relations' terms
+    std::vector<BatchCheck> res(total);
+    pool_run(work.size(), [&](size_t w) {
+        const size_t i = work[w];
+        const uint64_t *q = qs + i * iw;
+        BatchCheck &r = res[i];
+        const Fr z = Fr::load(q + 13);
+        r.rc = succinct_challenges(ctx, Point::load(q), d, z, Fr::load(q + 17), q + 21, &r.st, false);
+        if (r.rc) { r.err = halo_last_error(); return; }
+        const size_t o = L.off[rel_sum[i]];
+        relation_terms(r.st, q, host::h_eval(r.st.xis.data(), lg, z), &L.pts[8 * o], &L.sc[4 * o]);  // h(z) as k_h_eval_z computes it
+    });
+    uint64_t g01[16] = {};  // G_0, G_1
+    const size_t u0_terms = d ? 2 : 1;
+    auto member_terms = [&](size_t j) {  // alpha, its powers, the terms of the U_0 check and of C
+        VerifierMember &M = mem[j];
+        const uint64_t *piV = accs + j * aw + iw;
+        const size_t u = L.off[M.s_u0];
+        for (size_t t = 0; t < u0_terms; ++t) {
+            std::memcpy(&L.pts[8 * (u + t)], g01 + 8 * t, 64);
+            M.hs.h0[t].from_mont().store(&L.sc[4 * (u + t)]);
+        }
+        if (!M.reach) return;
+        for (size_t i = 0; i < M.m; ++i)
+            if (res[M.first + i].rc) return;
+        M.all_ok = true;
+        for (size_t i = 0; i < M.m; ++i) M.hs.xis.push_back(res[M.first + i].st.xis);
+        set_alphas(&M.hs);
+        const size_t c0 = L.off[M.s_c];  // the parts of C are consecutive: term t of C is term c0 + t
+        for (size_t t = 0; t <= M.m; ++t) {
+            L.put_point(c0 + t, t ? res[M.first + t - 1].st.U : Point::load(piV + 8));
+            M.hs.alphas[t].from_mont().store(&L.sc[4 * (c0 + t)]);
+        }
+    };
+    // 2. every sum: on the device in one launch on a slot idle at entry, or on the host pool
+    std::vector<Point> sums(nsums, Point::infinity());
+    int idle[HALO_SLOTS];
+    const int slot = idle_slots(ctx, idle) ? idle[0] : -1;
+    std::vector<uint32_t> desc;
+    const size_t waves = small_msm_seg_plan(L.off.data(), nsums, desc);
+    const int forced = dev_hooks().verifier_min;  // (development library: the threshold sweep of tools/time_verifier_batch.py)
+    const size_t min_rel = forced >= 1 ? (size_t)forced : kVerifierBatchMin;
+    const bool device = slot >= 0 && ctx->batch_verify && work.size() >= min_rel && check_stage(ctx, 1, nterms * 96 + nsums * 96 + (nsums + 1) * 4 + desc.size() * 4) >= 1;
+    int rc;
+    {
+        // (the launch macro and the read of G_0, G_1 use ctx->stream: the slot's own on the device path, else as it was)
+        StreamGuard on_slot(ctx, device ? ctx->streams[slot] : ctx->stream);
+        rc = nsums ? halo_ctx_read_bases(ctx, 0, u0_terms, g01) : HALO_OK;
+        if (!rc) pool_run(k, [&](size_t j) { if (mem[j].sums) member_terms(j); });
+        if (!rc && device) rc = sums_on_device(ctx, L, desc, waves, sums);
+        else if (!rc)  // ... or on the host pool, sum by sum
+            pool_run(nsums, [&](size_t s) {
+                const size_t lo = L.off[s], len = L.off[s + 1] - lo;
+                std::vector<Point> p(len);
+                std::vector<Fr> kk(len);
+                for (size_t t = 0; t < len; ++t) { p[t] = Point::load_affine(&L.pts[8 * (lo + t)]); kk[t] = Fr::load(&L.sc[4 * (lo + t)]).to_mont(); }
+                sums[s] = host::small_msm(p, kk);
+            });
+    }
+    if (rc) return rc;
+    // 3. the tail and every member's status in the single call's order
+    pool_run(k, [&](size_t j) {
+        VerifierMember &M = mem[j];
+        if (M.rc) return;
+        const uint64_t *acc = accs + j * aw, *piV = acc + iw;
+        if (sums[M.s_u0] != Point::load(piV + 8)) { M.rc = HALO_E_REJECT; M.err = "U_0 != PCDL.Commit(h_0)"; return; }
+        if (!M.reach) { M.rc = HALO_E_REJECT; M.err = "d_i != d"; return; }  // :169
+        for (size_t i = 0; i < M.m; ++i) {  // :158-170 in instance order
+            const BatchCheck &r = res[M.first + i];
+            if (r.rc) { M.rc = r.rc; M.err = r.err; return; }
+            if (sums[rel_sum[M.first + i]] != -r.st.C_prime) { M.rc = HALO_E_REJECT; M.err = "C_(log_n) != CM.Commit_Sigma(c || v')"; return; }  // :307-310
+        }
+        Point C = Point::infinity();
+        for (size_t c = 0; c < M.n_c; ++c) C = C + sums[M.s_c + c];
+        const Fr z_p = rho1_C_alpha(C, M.hs.alpha);                         // :181
+        const Point C_bar_p = C + public_s_table().mul(Fr::load(piV + 20));  // :184
+        const Fr z = Fr::load(acc + 13), v = Fr::load(acc + 17);
+        if (C_bar_p != Point::load(acc)) { M.rc = HALO_E_REJECT; M.err = "C_bar' != C_bar"; }
+        else if (z_p != z) { M.rc = HALO_E_REJECT; M.err = "z' != z"; }
+        else if ((size_t)acc[12] != d) { M.rc = HALO_E_REJECT; M.err = "d' != d"; }
+        else if (M.hs.eval(z) != v) { M.rc = HALO_E_REJECT; M.err = "h(z) != v"; }
+    });
+    return report_members("member", k, [&](size_t j) { return mem[j].rc; }, [&](size_t j) { return mem[j].err; }, status, [](size_t) {});
+}
+
+// ------------------------------------------------------------------ pcdl::open of m polynomials at once
+// The randomness of every member is known before any device work: the counter-based stream's draws depend only on the members'
+// degrees (a hiding open draws deg scalars for q, then w_bar; random_instance draws d', w, the d' + 1 coefficients, z, then the
+// open's draws).  So the host computes every member's start state first, and the members run side by side.
+//
+// Device path (2 <= n <= the context's no-fold size, at most OPEN_MAX_N): the open in its no-fold form (abi.hip ipa_round_lr_points:
+// the key is never folded, every round's L and R are two MSMs over the same n points with expanded scalars) for a GROUP of up to
+// OPEN_MAX_GROUP members at a time.  Each step of a group is one set of member-batched launches (ipa.hip *_batch, blockIdx.y =
+// member) and ONE batched MSM launch sequence over the key (L and R of every member: up to 8 scalar arrays; the C_bar commits of the
+// hiding branch, and random_instance's commits, likewise).  Groups rotate over the slots that were idle on entry: while this
+// thread waits for one group's step and runs its host half -- window combines, H' terms, Fiat-Shamir hashes, xi^-1, on the host
+// pool for the group's members -- the other slots' groups run on the device.  Every group runs through all its rounds before
+// its slot takes the next one, so the staging holds G x S members.  Host arithmetic is the single open's, term for term
+// (pcdl_open_dev, halo_ipa_finish's last-round U), so every proof word is the one halo_pcdl_open writes.
+struct OpenJob {
+    size_t idx = 0, deg = 0;
+    uint64_t s_start = 0;                // rng state before the member's first draw (the single call's *rng_state)
+    uint64_t s_p = 0, s_q = 0;           // rng state before p's coefficients (random_instance) / before q's (hiding)
+    const uint64_t *coeffs = nullptr;    // the caller's n coefficients (null: p generated or accumulated on the device)
+    const AccHPolys *hs = nullptr;       // acc::prover's h_0, challenges and alpha powers: p = h.get_poly() accumulated on the device
+    bool hiding = false;
+    Point C, last_L, last_R;
+    Fr z, v, w, w_bar, xi0, xi, c0, c1, last_xi, last_xi_inv;
+    uint64_t *proof = nullptr;
+    int rc = HALO_OK;
+    std::string err;
+};
+// members per launch: 4 (8 scalar arrays per round) within the small pipeline's bucket limit; "open_batch_group" forces 1..4
+static size_t open_group_size(const halo_ctx *ctx, size_t n) {
+    // (development library: the sweep of tools/time_open_batch.py)
+    return (size_t)group_size(ctx, n, dev_hooks().open_group, OPEN_MAX_GROUP, 2);
+}
+constexpr size_t OPEN_AUX_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS + OPEN_PART_WORDS + OPEN_OUT_WORDS);
+// (the prover batch's third coefficient source: up to HACC_TABLES polynomials h_i per pass of a group, see h_accumulate_group)
+constexpr size_t HACC_TABLES = 32;
+constexpr size_t HACC_PIN_WORDS = OPEN_MAX_GROUP * HACC_REC_WORDS + HACC_TABLES * (16 + 2) * 4;  // lg n <= 16 (OPEN_MAX_N)
+constexpr size_t OPEN_PIN_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS + OPEN_OUT_WORDS) + HACC_PIN_WORDS + 4;  // per slot; + the element one
+
+// Slot j's regions of the staging.  Device (`per` words a slot): the group's member vectors (G x ms: c | z | s | s' | F_L | F_R |
+// p_bar of n scalars each), then its window tables | constants | partial sums | results | the prover batch's tables.  Pinned
+// (OPEN_PIN_WORDS a slot): the tables | constants (one upload) | results (one download) | the prover batch's records | the
+// element one.  Cached launch graphs and the kernels of ipa.hip (OPEN_*_WORDS) know this layout.
+struct OpenStage {
+    uint64_t *d_base = nullptr, *h_base = nullptr;
+    size_t per = 0, n = 0, ms = 0, G = 0;
+    uint64_t *vec(int j, int k) const { return d_base + (size_t)j * per + 4 * n * (size_t)k; }  // member 0's vector k; member b at + b * ms
+    uint64_t *d_tabs(int j) const { return d_base + (size_t)j * per + G * ms; }
+    uint64_t *d_consts(int j) const { return d_tabs(j) + OPEN_MAX_GROUP * OPEN_TAB_WORDS; }
+    uint64_t *d_parts(int j) const { return d_consts(j) + OPEN_MAX_GROUP * OPEN_CONST_WORDS; }
+    uint64_t *d_outs(int j) const { return d_parts(j) + OPEN_MAX_GROUP * OPEN_PART_WORDS; }
+    uint64_t *d_hacc(int j) const { return d_outs(j) + OPEN_MAX_GROUP * OPEN_OUT_WORDS; }
+    uint64_t *h_tabs(int j) const { return h_base + (size_t)j * OPEN_PIN_WORDS; }
+    OpenConst *h_consts(int j) const { return (OpenConst *)(h_tabs(j) + OPEN_MAX_GROUP * OPEN_TAB_WORDS); }
+    uint64_t *h_outs(int j) const { return h_tabs(j) + OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS); }
+    uint64_t *h_hacc(int j) const { return h_outs(j) + OPEN_MAX_GROUP * OPEN_OUT_WORDS; }
+    uint64_t *h_one(int j) const { return h_tabs(j) + OPEN_PIN_WORDS - 4; }
+    uint64_t *out_of(int j, size_t b) const { return h_outs(j) + OPEN_OUT_WORDS * b; }
+};
+
+// The groups of one batched open over S slots.  A group's steps: 0 the coefficients, p(z), the powers of z, p_bar and the commits;
+// 1 .. lg the rounds; lg + 1 the U of the members whose last round does not hold it.  Each step is enqueued on the slot's stream
+// (start, enqueue_round, the tail of after_round) and, when the slot comes round again, collected and taken through its host
+// half (advance).
+struct OpenGroups {
+    halo_ctx *ctx;
+    std::vector<OpenJob> &jobs;
+    const int *slots;  // the slots idle at entry; S of them are used
+    int S;
+    size_t n, lg, G, ms;
+    bool gen, hiding, accumulated, u_from_last_round;
+    OpenStage st;
+    struct Flight { long g = -1; size_t first = 0, cnt = 0, step = 0; int msm = 0; bool flip = false; std::vector<size_t> need_u; };
+    std::vector<Flight> fl;
+
+    hipStream_t stream(int j) const { return ctx->streams[slots[j]]; }
+    uint64_t *s_cur(int j) const { return st.vec(j, fl[j].flip ? 3 : 2); }
+    int download_outs(int j) {
+        HALO_HIP(hipMemcpyAsync(st.h_outs(j), st.d_outs(j), fl[j].cnt * OPEN_OUT_WORDS * 8, hipMemcpyDeviceToHost, stream(j)));
+        return HALO_OK;
+    }
+    int upload_consts(int j) {
+        HALO_HIP(hipMemcpyAsync(st.d_consts(j), st.h_consts(j), fl[j].cnt * OPEN_CONST_WORDS * 8, hipMemcpyHostToDevice, stream(j)));
+        return HALO_OK;
+    }
+    int enqueue_msm(int j, const MsmBatch &mb) {  // the step's MSMs over the key as one batched launch sequence
+        int rc = msm_enqueue_batch(ctx, slots[j], ctx->d_bases, mb, true, n);
+        if (!rc) fl[j].msm = mb.count;
+        return rc;
+    }
+
+    // step 0: coefficients (copied, generated, or accumulated), p(z), the powers of z, p_bar; the commits as one batched MSM
+    int start(int j, size_t g) {
+        Flight &f = fl[j];
+        f = Flight();
+        f.g = (long)g;
+        f.first = g * G;
+        f.cnt = jobs.size() - f.first < G ? jobs.size() - f.first : G;
+        for (size_t b = 0; b < f.cnt; ++b) {
+            const OpenJob &jb = jobs[f.first + b];
+            OpenConst &k = st.h_consts(j)[b];
+            std::memset(&k, 0, sizeof k);
+            int rc = open_batch_table(jb.z, n, st.h_tabs(j) + OPEN_TAB_WORDS * b, &k);
+            if (rc) return rc;
+            k.s_q = jb.s_q;
+            k.s_p = jb.s_p;
+            k.deg = (uint32_t)jb.deg;
+            k.len = (uint32_t)(jb.deg + 1);
+        }
+        {
+            StreamGuard on_slot(ctx, stream(j));  // (the launch macro uses ctx->stream)
+            HALO_HIP(hipMemcpyAsync(st.d_tabs(j), st.h_tabs(j), OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS) * 8, hipMemcpyHostToDevice, stream(j)));
+            int rc = HALO_OK;
+            if (gen) rc = open_batch_rng(ctx, (int)f.cnt, st.d_consts(j), n, st.vec(j, 0), ms);  // p = PallasPoly::rand(d')
+            else if (accumulated) {  // p = h.get_poly() (acc.rs:85-94)
+                HAccMember hm[OPEN_MAX_GROUP];
+                for (size_t b = 0; b < f.cnt; ++b) {
+                    const AccHPolys &hs = *jobs[f.first + b].hs;
+                    hm[b].h0 = hs.h0;
+                    hm[b].count = hs.xis.size();
+                    hm[b].scales = hs.alphas.data() + 1;
+                    for (const std::vector<Fr> &x : hs.xis) hm[b].xis.push_back(x.data());
+                }
+                rc = h_accumulate_group(ctx, hm, f.cnt, lg, HACC_TABLES, st.h_hacc(j), st.d_hacc(j), st.vec(j, 0), ms);
+            } else
+                for (size_t b = 0; b < f.cnt; ++b)
+                    HALO_HIP(hipMemcpyAsync(st.vec(j, 0) + b * ms, jobs[f.first + b].coeffs, n * 32, hipMemcpyHostToDevice, stream(j)));
+            if (!rc) rc = open_batch_eval(ctx, (int)f.cnt, st.vec(j, 0), ms, n, st.d_tabs(j), st.d_parts(j), st.d_outs(j));  // :135
+            if (!rc) rc = open_batch_powers(ctx, (int)f.cnt, st.d_tabs(j), st.d_consts(j), n, st.vec(j, 1), ms);
+            if (!rc && hiding) rc = open_batch_pbar(ctx, (int)f.cnt, st.d_consts(j), n, st.vec(j, 6), ms);  // :140-142
+            for (size_t b = 0; b < f.cnt && !rc; ++b)  // s = (1)
+                HALO_HIP(hipMemcpyAsync(st.vec(j, 2) + b * ms, st.h_one(j), 32, hipMemcpyHostToDevice, stream(j)));
+            if (!rc) rc = download_outs(j);
+            if (rc) return rc;
+        }
+        MsmBatch mb;  // random_instance's C of every member, then C_bar of every member (:150)
+        mb.count = 0;
+        if (gen)
+            for (size_t b = 0; b < f.cnt; ++b) mb.scalars[mb.count++] = st.vec(j, 0) + b * ms;
+        if (hiding)
+            for (size_t b = 0; b < f.cnt; ++b) mb.scalars[mb.count++] = st.vec(j, 6) + b * ms;
+        return mb.count ? enqueue_msm(j, mb) : HALO_OK;
+    }
+    // round r of slot j's group: F_L, F_R from c and s, the dot products, L and R of every member as one batched MSM
+    int enqueue_round(int j, size_t r) {
+        Flight &f = fl[j];
+        const size_t mcur = n >> r;
+        int rc;
+        {
+            StreamGuard on_slot(ctx, stream(j));
+            rc = open_batch_expand(ctx, (int)f.cnt, st.vec(j, 0), s_cur(j), ms, mcur, n, st.vec(j, 4), st.vec(j, 5));
+            if (!rc) rc = open_batch_dots(ctx, (int)f.cnt, st.vec(j, 0), st.vec(j, 1), ms, mcur / 2, st.d_parts(j), st.d_outs(j));
+            if (!rc && mcur == 2)  // the last round: c0, c1 travel with its results (halo_ipa_finish's U from this round's MSMs)
+                for (size_t b = 0; b < f.cnt; ++b)
+                    HALO_HIP(hipMemcpyAsync(st.d_outs(j) + OPEN_OUT_WORDS * b + 12, st.vec(j, 0) + b * ms, 64, hipMemcpyDeviceToDevice, stream(j)));
+            if (!rc) rc = download_outs(j);
+        }
+        if (!rc) {
+            MsmBatch mb;  // L, R of member 0, L, R of member 1, ..
+            mb.count = 2 * (int)f.cnt;
+            for (int k = 0; k < mb.count; ++k) mb.scalars[k] = st.vec(j, 4 + (k & 1)) + (size_t)(k >> 1) * ms;
+            rc = enqueue_msm(j, mb);
+        }
+        f.step = 1 + r;
+        return rc;
+    }
+    // slot j's step is done: its results through the host half, then the next step (or the group is through)
+    int advance(int j, bool *through) {
+        Flight &f = fl[j];
+        *through = false;
+        Point pts[MSM_MAX_BATCH];
+        if (f.msm) {
+            int rc = msm_finish_batch(ctx, slots[j], pts, f.msm);
+            f.msm = 0;
+            if (rc) return rc;
+        }
+        HALO_HIP(hipStreamSynchronize(stream(j)));
+        if (f.step == 0) return after_commits(j, pts);
+        if (f.step <= lg) return after_round(j, pts, through);
+        after_u(j, pts);
+        *through = true;
+        return HALO_OK;
+    }
+    // after step 0: v, C (random_instance), the hiding branch's C_bar, alpha, w' and C', xi_0; p' = p + alpha p_bar; round 0
+    int after_commits(int j, const Point *pts) {
+        Flight &f = fl[j];
+        pool_run(f.cnt, [&](size_t b) {
+            OpenJob &jb = jobs[f.first + b];
+            jb.v = Fr::load(st.out_of(j, b));
+            if (gen) jb.C = (public_s_table().mul(jb.w) + pts[b]).normalized();
+            Point C_prime = jb.C;
+            if (hiding) {
+                Point C_bar = public_s_table().mul(jb.w_bar) + pts[(gen ? f.cnt : 0) + b];
+                Fr a = rho0_C_z_v_Cbar(jb.C, jb.z, jb.v, C_bar);  // :153
+                Fr w_prime = jb.w_bar * a + jb.w;                  // :159
+                C_prime = jb.C + C_bar.mul(a) - public_s_table().mul(w_prime);  // :162
+                jb.proof[0] = 1;
+                C_bar.store_normalized(pf_Cbar(jb.proof, lg));
+                w_prime.store(pf_wp(jb.proof, lg));
+                open_const_alpha(&st.h_consts(j)[b], a);
+            } else {
+                Point::infinity().store(pf_Cbar(jb.proof, lg));
+            }
+            jb.xi0 = jb.xi = rho0_C_z_v(C_prime, jb.z, jb.v);  // :180
+        });
+        if (hiding) {
+            StreamGuard on_slot(ctx, stream(j));
+            int rc = upload_consts(j);
+            if (!rc) rc = open_batch_axpy(ctx, (int)f.cnt, st.vec(j, 0), st.vec(j, 6), ms, n, st.d_consts(j));  // :156
+            if (rc) return rc;
+        }
+        return enqueue_round(j, 0);
+    }
+    // after round r = step - 1 (:203-224): L, R with their H' terms, the next challenge and its inverse; the fold; the next round,
+    // or, after the last one, U and c
+    int after_round(int j, const Point *pts, bool *through) {
+        Flight &f = fl[j];
+        const size_t r = f.step - 1;
+        const bool last = r + 1 == lg;
+        pool_run(f.cnt, [&](size_t b) {
+            OpenJob &jb = jobs[f.first + b];
+            const uint64_t *o = st.out_of(j, b);
+            Fr dl = Fr::load(o + 4), dr = Fr::load(o + 8);
+            if (last) { jb.last_L = pts[2 * b]; jb.last_R = pts[2 * b + 1]; jb.c0 = Fr::load(o + 12); jb.c1 = Fr::load(o + 16); }
+            uint64_t *Lw = pf_L(jb.proof, r), *Rw = pf_R(jb.proof, lg, r);
+            (pts[2 * b] + public_h_table().mul(dl * jb.xi0)).normalized().store(Lw);
+            (pts[2 * b + 1] + public_h_table().mul(dr * jb.xi0)).normalized().store(Rw);
+            Fr xi_next = rho0_xi_L_R(jb.xi, Point::load(Lw), Point::load(Rw));  // :212
+            if (xi_next.is_zero() && !jb.rc) { jb.rc = HALO_E_ASSERT; jb.err = "open: challenge is zero (inverse().unwrap())"; }
+            Fr xi_inv = xi_next.inv();  // :213
+            jb.xi = xi_next;
+            if (last) { jb.last_xi = xi_next; jb.last_xi_inv = xi_inv; }
+            open_const_xi(&st.h_consts(j)[b], xi_next, xi_inv);
+        });
+        {
+            StreamGuard on_slot(ctx, stream(j));  // :216-224
+            int rc = upload_consts(j);
+            const uint64_t *s_in = s_cur(j);
+            f.flip = !f.flip;
+            if (!rc) rc = open_batch_fold(ctx, (int)f.cnt, st.vec(j, 0), st.vec(j, 1), s_in, s_cur(j), ms, n >> (r + 1), (size_t)1 << r, st.d_consts(j));
+            if (rc) return rc;
+        }
+        return last ? finish_u(j, through) : enqueue_round(j, r + 1);
+    }
+    // :230-231 as halo_ipa_finish: U from the last round's MSMs where both coefficients are non-zero, else U = <s, G> (one more step)
+    int finish_u(int j, bool *through) {
+        Flight &f = fl[j];
+        auto from_last_round = [&](const OpenJob &jb) { return u_from_last_round && !jb.c0.is_zero() && !jb.c1.is_zero(); };
+        pool_run(f.cnt, [&](size_t b) {
+            OpenJob &jb = jobs[f.first + b];
+            if (!from_last_round(jb)) return;
+            Fr inv01 = (jb.c0 * jb.c1).inv();
+            Fr a = inv01 * jb.c0, bb = inv01 * jb.c1 * jb.last_xi;  // 1 / c1, xi / c0
+            (jb.last_L.mul(a) + jb.last_R.mul(bb)).store_normalized(pf_U(jb.proof, lg));
+            (jb.c0 + jb.last_xi_inv * jb.c1).store(pf_c(jb.proof, lg));
+        });
+        f.need_u.clear();
+        for (size_t b = 0; b < f.cnt; ++b)
+            if (!from_last_round(jobs[f.first + b])) f.need_u.push_back(b);
+        if (f.need_u.empty()) { *through = true; return HALO_OK; }
+        int rc = HALO_OK;
+        {
+            StreamGuard on_slot(ctx, stream(j));
+            for (size_t k = 0; k < f.need_u.size(); ++k)
+                HALO_HIP(hipMemcpyAsync(st.d_outs(j) + OPEN_OUT_WORDS * f.need_u[k] + 20, st.vec(j, 0) + f.need_u[k] * ms, 32, hipMemcpyDeviceToDevice, stream(j)));
+            rc = download_outs(j);
+        }
+        if (!rc) {
+            MsmBatch mb;
+            mb.count = (int)f.need_u.size();
+            for (int k = 0; k < mb.count; ++k) mb.scalars[k] = s_cur(j) + f.need_u[(size_t)k] * ms;
+            rc = enqueue_msm(j, mb);
+        }
+        f.step = lg + 1;
+        return rc;
+    }
+    // after step lg + 1: U = <s, G> and c = c[0] (halo_ipa_finish)
+    void after_u(int j, const Point *pts) {
+        Flight &f = fl[j];
+        for (size_t k = 0; k < f.need_u.size(); ++k) {
+            OpenJob &jb = jobs[f.first + f.need_u[k]];
+            pts[k].store_normalized(pf_U(jb.proof, lg));
+            std::memcpy(pf_c(jb.proof, lg), st.out_of(j, f.need_u[k]) + 20, 32);
+        }
+    }
+    void abandon() {  // (a device error: nothing of this call stays in flight)
+        std::string err = halo_last_error();
+        for (int j = 0; j < S; ++j) {
+            if (fl[j].msm) {
+                Point pts[MSM_MAX_BATCH];
+                (void)msm_finish_batch(ctx, slots[j], pts, fl[j].msm);
+                fl[j].msm = 0;
+            }
+            (void)hipStreamSynchronize(stream(j));
+        }
+        set_error(err);
+    }
+    // every group through all its steps: a slot takes the next group when its own is through
+    int run() {
+        const size_t ng = (jobs.size() + G - 1) / G;
+        fl.assign(S, Flight());
+        size_t next = 0;
+        int rc = HALO_OK, active = 0;
+        for (int j = 0; j < S && next < ng && !rc; ++j, ++active) rc = start(j, next++);
+        while (!rc && active) {
+            for (int j = 0; j < S && !rc; ++j) {
+                if (fl[j].g < 0) continue;
+                bool through = false;
+                rc = advance(j, &through);
+                if (rc || !through) continue;
+                fl[j].g = -1;
+                --active;
+                if (next < ng) { rc = start(j, next++); ++active; }
+            }
+        }
+        if (rc) abandon();
+        return rc;
+    }
+};
+
+// jobs: the members that do not fail up front, in member order.  *ran = false: the device path does not apply (nothing done)
+// Coefficients of a member: the caller's host array (jb.coeffs), generated on the device (gen), or -- jb.hs set, for every member
+// alike -- acc::prover's h(X) accumulated on the device straight into the member's coefficient vector
+static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, bool gen, const int *slots_in, int S, bool *ran) {
+    *ran = false;
+    const size_t n = d + 1, lg = ilog2(n), A = jobs.size();
+    if (A == 0 || n < 2 || n > ctx->nofold_size || n > OPEN_MAX_N) return HALO_OK;
+    size_t G = open_group_size(ctx, n);
+    if (G > A) G = A;
+    const size_t ng = (A + G - 1) / G;
+    if ((size_t)S > ng) S = (int)ng;
+    const size_t ms = 7 * 4 * n;  // words of one member's vectors: c | z | s | s' | F_L | F_R | p_bar
+    const bool accumulated = jobs[0].hs != nullptr;
+    const size_t hacc_words = accumulated ? hacc_stage_words(OPEN_MAX_GROUP, lg, HACC_TABLES) : 0;
+    const size_t per = G * ms + OPEN_AUX_WORDS + hacc_words;  // words of one slot's group
+    size_t have = check_stage(ctx, (size_t)S, per * 8);
+    if (have == 0) return HALO_OK;
+    if ((size_t)S > have) S = (int)have;
+    if (!ctx->h_open_pinned) {
+        if (hipHostMalloc(&ctx->h_open_pinned, HALO_SLOTS * OPEN_PIN_WORDS * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->h_open_pinned = nullptr;
+            return HALO_OK;
+        }
+        for (int k = 0; k < HALO_SLOTS; ++k) Fr::one().store(ctx->h_open_pinned + k * OPEN_PIN_WORDS + OPEN_PIN_WORDS - 4);
+    }
+    *ran = true;
+    const OpenStage st{ctx->d_check_stage, ctx->h_open_pinned, per, n, ms, G};
+    // (hiding: the same for every member of a batch)
+    OpenGroups groups{ctx, jobs, slots_in, S, n, lg, G, ms, gen, jobs[0].hiding, accumulated, tuning().u_from_last_round, st, {}};
+    return groups.run();
+}
+
+// halo_pcdl_open_batch (coeffs != null) and halo_random_instance_batch (coeffs == null: `out` holds Instance blobs) after their
+// argument checks: the members' draws, then the device path or, where it does not apply, the members one at a time
+static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *Cs, const uint64_t *zs,
+                            const uint64_t *ws, uint64_t *out, int *status) {
+    const size_t n = d + 1, lg = ilog2(n);
+    const bool gen = coeffs == nullptr, hiding = gen || ws != nullptr;
+    const size_t stride = gen ? instance_words(lg) : proof_words(lg);
+    int slots[HALO_SLOTS], S = idle_slots(ctx, slots);
+    if (!S) { set_error("open_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
+    // 1. every member's draws, in member order (the loop's order)
+    host::Rng rng{rng_state ? *rng_state : 0};
+    std::vector<OpenJob> jobs;
+    std::vector<int> codes(m, HALO_OK);
+    std::vector<std::string> errs(m);
+    jobs.reserve(m);
+    for (size_t i = 0; i < m; ++i) {
+        OpenJob jb;
+        jb.idx = i;
+        jb.hiding = hiding;
+        jb.proof = out + i * stride + (gen ? 21 : 0);
+        jb.s_start = rng.state;
+        if (gen) {
+            size_t lo = d / 2;
+            jb.deg = lo + (size_t)(rng.next() % (uint64_t)(d - lo));
+            if (jb.deg == 0) jb.deg = 1;
+            jb.w = rng.scalar();
+            jb.s_p = rng.state;
+            rng.skip_scalars(jb.deg + 1);
+            jb.z = rng.scalar();
+        } else {
+            jb.coeffs = coeffs + i * n * 4;
+            jb.deg = host_poly_degree(jb.coeffs, n);
+            jb.C = Point::load(Cs + 12 * i);
+            jb.z = Fr::load(zs + 4 * i);
+            if (ws) jb.w = Fr::load(ws + 4 * i);
+            if (hiding && jb.deg == 0) { codes[i] = HALO_E_ASSERT; errs[i] = "open: hiding needs p.degree() >= 1"; continue; }  // (before any draw)
+        }
+        if (hiding) {
+            jb.s_q = rng.state;
+            rng.skip_scalars(jb.deg);
+            jb.w_bar = rng.scalar();
+        }
+        jobs.push_back(jb);
+    }
+    // 2. the device path; where it does not apply, the loop itself (the single calls' bodies, from the same states)
+    for (OpenJob &jb : jobs) {
+        std::memset(jb.proof, 0, 8 * proof_words(lg));
+        jb.proof[1] = lg;
+    }
+    bool ran = false;
+    int rc = open_batch_dev(ctx, d, jobs, gen, slots, S, &ran);  // (no jobs: nothing runs)
+    if (rc) return rc;
+    if (!ran) {
+        for (OpenJob &jb : jobs) {
+            uint64_t st = jb.s_start;
+            if (gen) rc = random_instance_one(ctx, &st, d, out + jb.idx * stride);
+            else rc = pcdl_open_host(ctx, &st, jb.coeffs, jb.deg, Cs + 12 * jb.idx, d, zs + 4 * jb.idx, ws ? ws + 4 * jb.idx : nullptr, jb.proof);
+            if (rc == HALO_E_ASSERT) { jb.rc = rc; jb.err = halo_last_error(); }
+            else if (rc) return rc;
+        }
+    }
+    // 3. outcomes in member order
+    for (OpenJob &jb : jobs) {
+        codes[jb.idx] = jb.rc;
+        errs[jb.idx] = jb.err;
+        // the Instance around the proof (random_instance_one writes its own)
+        if (gen && !jb.rc && ran) store_instance_head(out + jb.idx * stride, jb.C, d, jb.z, jb.v);
+    }
+    if (rng_state) *rng_state = rng.state;
+    return report_members("member", m, [&](size_t i) { return codes[i]; }, [&](size_t i) { return errs[i]; }, status,
+                          [&](size_t i) { std::memset(out + i * stride, 0, 8 * stride); });
+}
+
+// ------------------------------------------------------------------ acc::prover of k members at once
+// (halo_acc_prover_batch; acc.rs:190-220 per member, every member's blob, status and draws the loop's)
+//  1. the succinct half of every member, no randomness: all sum(counts) instances at once -- from kBatchVerifyMin instances on
+//     as halo_pcdl_succinct_check_batch runs them (transcripts on the host pool, the relations in one device launch), below on
+//     the pool.  A member is rejected exactly where halo_acc_prover rejects it ("d_i != d" first, then its succinct checks in
+//     instance order), and a rejected member draws nothing: the single call writes *rng_state only after common_subroutine.
+//  2. the survivors' draws in member order: h_0, omega, then (the stream is counter-based) the start of the open's q and w_bar.
+//  3. per member on the host pool: U_0 = h_0[0] G_0 + h_0[1] G_1, alpha and its powers, C = sum alpha^i U_i, z, C_bar = C +
+//     omega S, v = h(z).  These 3 + m scalar multiples per member (~27 us each on one thread, as the relation's 2 lg n + 1
+//     above) are spread over the pool: a second device launch with its round trip would cost more than it saves (the verifier
+//     batch folds such sums into a launch it needs anyway; here alpha hashes the drawn h_0, so they cannot ride the relations'
+//     launch).
+//  4. the hiding opens through open_batch_dev, their coefficients h(X) = h_0 + sum alpha^(i+1) h_i(X) accumulated on the device
+//     into the open's staging (h_accumulate_group), groups of up to 4 members over the idle slots.
+//  5. the blobs: C_bar | d | z | v | proof | h_0 | U_0 | omega.
+// *ran = false: the device form does not apply (size, staging) and nothing was written.
+struct ProverMember {
+    int rc = HALO_OK;
+    std::string err;
+    size_t first = 0, m = 0;  // its instances in the flat list
+    size_t r0 = 0;            // ... and the first of their check results
+    Fr w, z, v;
+    Point U0, C_bar;
+    AccHPolys hs;
+};
+static int acc_prover_batch_dev(halo_ctx *ctx, uint64_t state0, size_t d, const uint64_t *qs, const size_t *counts, size_t k, uint64_t *accs,
+                                const int *slots, int S, bool *ran, std::vector<int> &codes, std::vector<std::string> &errs, uint64_t *state_out) {
+    *ran = false;
+    const size_t n = d + 1, lg = ilog2(n), iw = instance_words(lg), aw = acc_words(lg);
+    if (n < 2 || n > ctx->nofold_size || n > OPEN_MAX_N) return HALO_OK;
+    std::vector<ProverMember> mem(k);
+    size_t total = 0;
+    for (size_t j = 0; j < k; ++j) { mem[j].first = total; mem[j].m = counts[j]; total += counts[j]; }
+    // 1. the succinct half
+    for (size_t j = 0; j < k; ++j)
+        for (size_t i = 0; i < mem[j].m && !mem[j].rc; ++i) {
+            const uint64_t *q = qs + (mem[j].first + i) * iw;
+            if ((size_t)q[12] != d || q[22] != lg) { mem[j].rc = HALO_E_REJECT; mem[j].err = "d_i != d"; }  // :169
+        }
+    std::vector<size_t> work;  // the instances whose checks run (a member that never reaches its checks is left out)
+    for (size_t j = 0; j < k; ++j)
+        if (!mem[j].rc)
+            for (size_t i = 0; i < mem[j].m; ++i) work.push_back(mem[j].first + i);
+    std::vector<BatchCheck> res;
+    int rc = succinct_half(ctx, d, [&](size_t w) { return qs + work[w] * iw; }, work.size(), res);
+    if (rc) return rc;
+    for (size_t j = 0, w = 0; j < k; ++j) {
+        ProverMember &M = mem[j];
+        if (M.rc) continue;
+        M.r0 = w;
+        for (size_t i = 0; i < M.m; ++i, ++w) {
+            if (res[w].rc && !M.rc) { M.rc = res[w].rc; M.err = res[w].err; }  // :158-170 in instance order
+            if (!M.rc) M.hs.xis.push_back(res[w].st.xis);
+        }
+    }
+    // 2. the draws, in member order
+    host::Rng rng{state0};
+    std::vector<OpenJob> jobs;
+    jobs.reserve(k);
+    for (size_t j = 0; j < k; ++j) {
+        ProverMember &M = mem[j];
+        if (M.rc) continue;
+        M.hs.lg_n = lg;
+        M.hs.h0[0] = rng.scalar();  // :192
+        M.hs.h0[1] = rng.scalar();
+        M.w = rng.scalar();         // :198
+        OpenJob jb;
+        jb.idx = j;
+        jb.hiding = true;
+        jb.hs = &M.hs;
+        jb.deg = M.m ? d : (M.hs.h0[1].is_zero() ? 0 : 1);
+        if (jb.deg == 0) { M.rc = HALO_E_ASSERT; M.err = "open: hiding needs p.degree() >= 1"; continue; }  // pcdl_open_dev: before its draws
+        jb.w = M.w;
+        jb.s_q = rng.state;
+        rng.skip_scalars(jb.deg);
+        jb.w_bar = rng.scalar();
+        jb.proof = accs + j * aw + 21;
+        jobs.push_back(jb);
+    }
+    // 3. U_0, alpha, C, z, C_bar, v
+    if (!jobs.empty()) {
+        uint64_t g01[16];
+        rc = halo_ctx_read_bases(ctx, 0, 2, g01);
+        if (rc) return rc;
+        const std::vector<Point> G01{Point::load_affine(g01), Point::load_affine(g01 + 8)};
+        pool_run(jobs.size(), [&](size_t a) {
+            OpenJob &jb = jobs[a];
+            ProverMember &M = mem[jb.idx];
+            M.U0 = host::small_msm(G01, std::vector<Fr>{M.hs.h0[0], M.hs.h0[1]});  // :195
+            std::vector<Point> Us{M.U0};
+            for (size_t i = 0; i < M.m; ++i) Us.push_back(res[M.r0 + i].st.U);
+            set_alphas(&M.hs);                                               // :173
+            const Point C = host::small_msm(Us, M.hs.alphas);                // :178
+            M.z = rho1_C_alpha(C, M.hs.alpha);                               // :181
+            M.C_bar = (C + public_s_table().mul(M.w)).normalized();          // :184
+            M.v = M.hs.eval(M.z);                                            // :205
+            jb.C = M.C_bar;
+            jb.z = M.z;
+        });
+        // 4. the opens (:209)
+        for (OpenJob &jb : jobs) {
+            std::memset(accs + jb.idx * aw, 0, 8 * aw);
+            jb.proof[1] = lg;
+        }
+        rc = open_batch_dev(ctx, d, jobs, false, slots, S, ran);
+        if (rc) return rc;
+        if (!*ran) return HALO_OK;
+    }
+    *ran = true;
+    // 5. the blobs and the outcomes
+    for (OpenJob &jb : jobs) {
+        ProverMember &M = mem[jb.idx];
+        if (jb.rc) { M.rc = jb.rc; M.err = jb.err; continue; }
+        uint64_t *acc = accs + jb.idx * aw, *piV = acc + iw;
+        store_instance_head(acc, M.C_bar, d, M.z, M.v);
+        M.hs.h0[0].store(piV);
+        M.hs.h0[1].store(piV + 4);
+        M.U0.store_normalized(piV + 8);
+        M.w.store(piV + 20);
+    }
+    for (size_t j = 0; j < k; ++j) { codes[j] = mem[j].rc; errs[j] = mem[j].err; }
+    *state_out = rng.state;
+    return HALO_OK;
+}
+
+// halo_acc_prover_batch after its argument checks: the device form, or, where it does not apply, the loop itself
+static int acc_prover_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *qs, const size_t *counts, size_t k, uint64_t *accs,
+                                  int *status) {
+    const size_t lg = ilog2(d + 1), iw = instance_words(lg), aw = acc_words(lg);
+    int slots[HALO_SLOTS], S = idle_slots(ctx, slots);
+    if (!S) { set_error("prover_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
+    std::vector<int> codes(k, HALO_OK);
+    std::vector<std::string> errs(k);
+    uint64_t state = rng_state ? *rng_state : 0;
+    bool ran = false;
+    int rc = acc_prover_batch_dev(ctx, state, d, qs, counts, k, accs, slots, S, &ran, codes, errs, &state);
+    if (rc) return rc;
+    if (!ran) {  // one member at a time through the single prover, from the same states
+        size_t first = 0;
+        for (size_t j = 0; j < k; first += counts[j], ++j) {
+            rc = halo_acc_prover(ctx, &state, d, qs + first * iw, counts[j], accs + j * aw);
+            if (rc == HALO_E_ASSERT || rc == HALO_E_REJECT) { codes[j] = rc; errs[j] = halo_last_error(); }
+            else if (rc) return rc;
+        }
+    }
+    if (rng_state) *rng_state = state;
+    return report_members("member", k, [&](size_t j) { return codes[j]; }, [&](size_t j) { return errs[j]; }, status,
+                          [&](size_t j) { std::memset(accs + j * aw, 0, 8 * aw); });
+}
+
+// the lists of the prover and verifier batches: k members, counts[j] instances each, one flat list of instances
+int member_lists_ok(const char *who, const void *accs, const size_t *counts, size_t k, const void *instances) {
+    auto bad = [&](const char *what) { set_error(std::string(who) + what); return HALO_E_ARG; };
+    if (k && (!accs || !counts)) return bad(": null pointer");
+    size_t total = 0;
+    for (size_t j = 0; j < k; ++j) {
+        if (counts[j] > ((size_t)1 << 32) - total) return bad(": too many instances");
+        total += counts[j];
+    }
+    return total && !instances ? bad(": null pointer") : HALO_OK;
+}
+
+}  // namespace
+}  // namespace halo
+
+using namespace halo;
+
+extern "C" {
+
+// pcdl::check of m instances at once (see pcdl_check_batch_host)
+int halo_pcdl_check_batch(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, int *status) {
+    HALO_CTX(ctx);
+    return check_batch_entry(ctx, d, instances, m, status, false);
+}
+
+// acc::prover of k members at once (see acc_prover_batch_dev).  The argument checks are the whole call's and come before any work.
+int halo_acc_prover_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *instances, const size_t *counts, size_t k, uint64_t *accs_out,
+                          int *status) {
+    HALO_CTX(ctx);
+    int rc = member_lists_ok("prover_batch", accs_out, counts, k, instances);
+    if (rc) return rc;
+    if (!is_pow2(d + 1)) return fail_assert("prover: d + 1 is not a power of two");
+    if (d + 1 > ctx->n) return fail_assert("prover: d > D");
+    if (k == 0) return HALO_OK;
+    return acc_prover_batch_entry(ctx, rng_state, d, instances, counts, k, accs_out, status);
+}
+
+// acc::verifier of k accumulators at once (benches/acc.rs:64-74's loop in one call; see acc_verifier_batch_host).  The argument
+// checks are the whole call's and come before any work: d + 1 above the key is the assert the single call meets in
+// pcdl_commit_host.  A multi-device context runs the batch on its own device (devices[0]) like the other batches.
+int halo_acc_verifier_batch(halo_ctx *ctx, size_t d, const uint64_t *instances, const size_t *counts, size_t k, const uint64_t *accs, int *status) {
+    HALO_CTX(ctx);
+    int rc = member_lists_ok("verifier_batch", accs, counts, k, instances);
+    if (rc) return rc;
+    if (!is_pow2(d + 1)) return fail_reject("d+1 is not a power of 2!");
+    if (d + 1 > ctx->n) return fail_assert("commit: d > D");
+    if (k == 0) return HALO_OK;
+    return acc_verifier_batch_host(ctx, d, instances, counts, k, accs, status);
+}
+
+// acc::decider of m accumulators at once (benches/acc.rs:100-106 in one call): the check batch over their Instance prefixes
+int halo_acc_decider_batch(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, int *status) {
+    HALO_CTX(ctx);
+    return check_batch_entry(ctx, d, accs, m, status, true);
+}
+
+// pcdl::open of m polynomials at once (see open_batch_dev)
+int halo_pcdl_open_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *Cs, const uint64_t *zs,
+                         const uint64_t *ws, uint64_t *proofs_out, int *status) {
+    HALO_CTX(ctx);
+    if (m == 0) return HALO_OK;
+    if (!coeffs || !Cs || !zs || !proofs_out) { set_error("open_batch: null pointer"); return HALO_E_ARG; }
+    const size_t n = d + 1;
+    if (!is_pow2(n)) return fail_assert("open: d + 1 is not a power of two");  // pcdl.rs:130 (p.degree() <= d: the arrays hold d + 1)
+    if (n > ctx->n) return fail_assert("open: d > D");                         // pcdl.rs:132
+    return open_batch_entry(ctx, rng_state, d, coeffs, m, Cs, zs, ws, proofs_out, status);
+}
+
+// benches/acc.rs:15-29 random_instance, m times (see open_batch_dev)
+int halo_random_instance_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, size_t m, uint64_t *instances_out) {
+    HALO_CTX(ctx);
+    if (m == 0) return HALO_OK;
+    if (!instances_out) { set_error("random_instance_batch: null pointer"); return HALO_E_ARG; }
+    if (!is_pow2(d + 1) || d < 2) return fail_assert("random_instance: bad d");
+    if (d + 1 > ctx->n) return fail_assert("random_instance: d > D");
+    return open_batch_entry(ctx, rng_state, d, nullptr, m, nullptr, nullptr, nullptr, instances_out, nullptr);
+}
+
+}  // extern "C"

@@ -1,0 +1,104 @@
+// Shared by the pcdl / acc level of the library: pcdl_acc.hip (the single calls, the sharded open and check), pcdl_batch.hip (the
+// batched calls) and, for the blob layout alone, wire.hip and abi.hip.
+#pragma once
+#include "internal.hpp"
+
+namespace halo {
+
+// ---- flat layouts (include/halo_accumulation.h, "pcdl / acc level")
+inline size_t proof_words(size_t lg) { return 2 + 24 * lg + 32; }
+inline size_t instance_words(size_t lg) { return 21 + proof_words(lg); }
+inline size_t acc_words(size_t lg) { return instance_words(lg) + 24; }
+inline uint64_t *pf_L(uint64_t *pf, size_t i) { return pf + 2 + 12 * i; }
+inline uint64_t *pf_R(uint64_t *pf, size_t lg, size_t i) { return pf + 2 + 12 * lg + 12 * i; }
+inline uint64_t *pf_U(uint64_t *pf, size_t lg) { return pf + 2 + 24 * lg; }
+inline uint64_t *pf_c(uint64_t *pf, size_t lg) { return pf + 2 + 24 * lg + 12; }
+inline uint64_t *pf_Cbar(uint64_t *pf, size_t lg) { return pf + 2 + 24 * lg + 16; }
+inline uint64_t *pf_wp(uint64_t *pf, size_t lg) { return pf + 2 + 24 * lg + 28; }
+
+// an Instance's fields in front of its proof: C | d | z | v
+inline void store_instance_head(uint64_t *inst, const host::Point &C, size_t d, const host::Fr &z, const host::Fr &v) {
+    C.store(inst);
+    inst[12] = d;
+    z.store(inst + 13);
+    v.store(inst + 17);
+}
+
+inline bool is_pow2(size_t n) { return n && !(n & (n - 1)); }
+inline size_t ilog2(size_t n) { size_t l = 0; while (n > 1) { n >>= 1; ++l; } return l; }
+inline int fail_assert(const char *m) { set_error(m); return HALO_E_ASSERT; }
+inline int fail_reject(const char *m) { set_error(m); return HALO_E_REJECT; }
+inline bool scalar_ok(const host::Fr &s) { return !host::Fr::geq(s.l, host::FrP::M); }
+
+// DensePolynomial::degree: the index of the last non-zero coefficient (0 for the zero polynomial).  Scanned from the END: a
+// dense polynomial answers at its first look (the forward scan this replaces read all 32 MiB of a 2^20-coefficient polynomial
+// on the host, ~1 ms of every halo_pcdl_open / halo_pcdl_commit with host coefficients).
+inline size_t host_poly_degree(const uint64_t *coeffs, size_t len) {
+    for (size_t i = len; i-- > 0;)
+        if (coeffs[4 * i] | coeffs[4 * i + 1] | coeffs[4 * i + 2] | coeffs[4 * i + 3]) return i;
+    return 0;
+}
+
+// ---- the transcript's hashes (rho_0!, rho_1!)
+inline host::Fr rho0_C_z_v(const host::Point &C, const host::Fr &z, const host::Fr &v) {
+    host::Transcript t; t.point(C); t.scalar(z); t.scalar(v); return t.finish(0);
+}
+inline host::Fr rho0_C_z_v_Cbar(const host::Point &C, const host::Fr &z, const host::Fr &v, const host::Point &Cb) {
+    host::Transcript t; t.point(C); t.scalar(z); t.scalar(v); t.point(Cb); return t.finish(0);
+}
+inline host::Fr rho0_xi_L_R(const host::Fr &xi, const host::Point &L, const host::Point &R) {
+    host::Transcript t; t.scalar(xi); t.point(L); t.point(R); return t.finish(0);
+}
+// acc.rs:181  z = rho_1(C, alpha)
+inline host::Fr rho1_C_alpha(const host::Point &C, const host::Fr &alpha) {
+    host::Transcript t; t.point(C); t.scalar(alpha); return t.finish(1);
+}
+
+// ---- pcdl_acc.hip: pcdl::succinct_check in two halves (see succinct_challenges there)
+struct SuccinctState {
+    size_t lg_n = 0;
+    host::Point C_prime, Hp, U;
+    std::vector<host::Fr> xis;
+};
+// one instance's outcome as its single call reports it: code, message, accepted transcript
+struct BatchCheck { int rc = HALO_OK; std::string err; SuccinctState st; };
+// key_n: the size of the key the check is against (ctx->n; a rank's cyclic shard stands for stride * ctx->n points)
+int succinct_challenges(halo_ctx *ctx, const host::Point &C, size_t d, const host::Fr &z, const host::Fr &v, const uint64_t *proof, SuccinctState *st,
+                        bool need_hp = true, size_t key_n = 0);
+int succinct_relation(const SuccinctState &st, const host::Fr &z, const host::Fr &v, const uint64_t *proof);
+// The 2 lg n + 2 terms of one instance's relation (q: its blob, hz = h(z) of its challenges, st: its accepted transcript) whose
+// sum is -C' exactly when pcdl.rs:288-310 accepts: points arkworks affine ((0, 0) = infinity), scalars canonical
+void relation_terms(const SuccinctState &st, const uint64_t *q, const host::Fr &hz, uint64_t *pts, uint64_t *sc);
+// The succinct half of m Instance blobs of degree bound d (checked by the caller), blob_at(i) = instance i's words: res[i] = what
+// halo_pcdl_succinct_check reports for it alone.  succinct_check_batch: the relations in two device launches.  succinct_half: the
+// one rule of every batched call -- that from kBatchVerifyMin instances on if ctx->batch_verify, else the host pool.  Both
+// return a device / argument error only.
+using BlobAt = std::function<const uint64_t *(size_t)>;
+constexpr size_t kBatchVerifyMin = 64;  // below this the host pool is faster than a 256-step device ladder (~2 ms)
+int succinct_check_batch(halo_ctx *ctx, size_t d, const BlobAt &blob_at, size_t m, std::vector<BatchCheck> &res);
+int succinct_half(halo_ctx *ctx, size_t d, const BlobAt &blob_at, size_t m, std::vector<BatchCheck> &res);
+int verify_staging(halo_ctx *ctx, size_t words);  // ctx->d_verify holds at least `words`
+
+// ---- pcdl_acc.hip: acc.rs
+struct AccHPolys {  // acc.rs:61-66
+    host::Fr h0[2];
+    std::vector<std::vector<host::Fr>> xis;
+    host::Fr alpha;
+    std::vector<host::Fr> alphas;  // alpha^0 .. alpha^m
+    size_t lg_n = 0;
+
+    host::Fr eval(const host::Fr &z) const {  // acc.rs:97-106
+        host::Fr v = h0[0] + h0[1] * z;
+        for (size_t i = 0; i < xis.size(); ++i) v = v + host::h_eval(xis[i].data(), lg_n, z) * alphas[i + 1];
+        return v;
+    }
+};
+// acc.rs:173  alpha = rho_1(hs): h_0 Some(poly), hs Vec<HPoly>, alpha None, alphas empty; then alpha^0 .. alpha^m
+void set_alphas(AccHPolys *hs);
+
+// ---- pcdl_acc.hip: the bodies of halo_pcdl_open (deg = host_poly_degree(coeffs) <= d) and halo_random_instance after their argument checks
+int pcdl_open_host(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *coeffs, size_t deg, const uint64_t C[12], size_t d, const uint64_t z[4],
+                   const uint64_t *w, uint64_t *proof_out);
+int random_instance_one(halo_ctx *ctx, uint64_t *rng_state, size_t d, uint64_t *inst);
+
+}  // namespace halo

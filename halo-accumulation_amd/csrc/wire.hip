@@ -17,7 +17,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "internal.hpp"
+#include "pcdl_internal.hpp"  // (the blob layout: proof_words, instance_words)
 
 namespace halo {
 namespace {
@@ -25,9 +25,6 @@ namespace {
 using host::Fq;
 using host::Fr;
 using host::Point;
-
-size_t proof_words(size_t lg) { return 2 + 24 * lg + 32; }
-size_t instance_words(size_t lg) { return 21 + proof_words(lg); }
 
 struct Writer {
     uint8_t *out;
@@ -276,27 +273,28 @@ struct DecodeMember {
 int decompress_on_device(halo_ctx *ctx, int slot, size_t chunk, const std::vector<PendingPoint> &pts, std::vector<uint8_t> &ok) {
     const uint32_t *tab = sqrt_tables_host();
     uint64_t *d_tab = ctx->d_check_stage, *d_in = d_tab + SQRT_TAB_WORDS / 2, *d_out = d_in + chunk * DECOMP_IN_WORDS;
-    hipStream_t saved = ctx->stream;
-    ctx->stream = ctx->streams[slot];  // (the launch macro uses ctx->stream: the slot's own)
-    std::vector<uint64_t> hin(chunk * DECOMP_IN_WORDS), hout(chunk * DECOMP_OUT_WORDS);
-    hipError_t e = hipMemcpyAsync(d_tab, tab, SQRT_TAB_WORDS * 4, hipMemcpyHostToDevice, ctx->stream);
-    int rc = e == hipSuccess ? HALO_OK : hip_fail(e, "hipMemcpyAsync");
-    for (size_t lo = 0; lo < pts.size() && !rc; lo += chunk) {
-        const size_t cnt = std::min(chunk, pts.size() - lo);
-        std::fill(hin.begin(), hin.begin() + cnt * DECOMP_IN_WORDS, 0);
-        for (size_t j = 0; j < cnt; ++j) std::memcpy(&hin[j * DECOMP_IN_WORDS], pts[lo + j].src, 33);
-        if ((e = hipMemcpyAsync(d_in, hin.data(), cnt * DECOMP_IN_WORDS * 8, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
-        if (!rc) rc = point_decompress_dev(ctx, d_in, cnt, reinterpret_cast<const uint32_t *>(d_tab), d_out);
-        if (!rc && (e = hipMemcpyAsync(hout.data(), d_out, cnt * DECOMP_OUT_WORDS * 8, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
-        e = hipStreamSynchronize(ctx->stream);  // (also on failure: the host buffers are reused and go with this call)
-        if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
-        for (size_t j = 0; j < cnt && !rc; ++j) {
-            const uint64_t *o = &hout[j * DECOMP_OUT_WORDS];
-            ok[lo + j] = o[12] == 1;
-            if (ok[lo + j]) std::memcpy(pts[lo + j].dst, o, 96);
+    int rc;
+    {
+        StreamGuard on_slot(ctx, ctx->streams[slot]);  // (the launch macro uses ctx->stream: the slot's own)
+        std::vector<uint64_t> hin(chunk * DECOMP_IN_WORDS), hout(chunk * DECOMP_OUT_WORDS);
+        hipError_t e = hipMemcpyAsync(d_tab, tab, SQRT_TAB_WORDS * 4, hipMemcpyHostToDevice, ctx->stream);
+        rc = e == hipSuccess ? HALO_OK : hip_fail(e, "hipMemcpyAsync");
+        for (size_t lo = 0; lo < pts.size() && !rc; lo += chunk) {
+            const size_t cnt = std::min(chunk, pts.size() - lo);
+            std::fill(hin.begin(), hin.begin() + cnt * DECOMP_IN_WORDS, 0);
+            for (size_t j = 0; j < cnt; ++j) std::memcpy(&hin[j * DECOMP_IN_WORDS], pts[lo + j].src, 33);
+            if ((e = hipMemcpyAsync(d_in, hin.data(), cnt * DECOMP_IN_WORDS * 8, hipMemcpyHostToDevice, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+            if (!rc) rc = point_decompress_dev(ctx, d_in, cnt, reinterpret_cast<const uint32_t *>(d_tab), d_out);
+            if (!rc && (e = hipMemcpyAsync(hout.data(), d_out, cnt * DECOMP_OUT_WORDS * 8, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+            e = hipStreamSynchronize(ctx->stream);  // (also on failure: the host buffers are reused and go with this call)
+            if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+            for (size_t j = 0; j < cnt && !rc; ++j) {
+                const uint64_t *o = &hout[j * DECOMP_OUT_WORDS];
+                ok[lo + j] = o[12] == 1;
+                if (ok[lo + j]) std::memcpy(pts[lo + j].dst, o, 96);
+            }
         }
     }
-    ctx->stream = saved;
     bool busy = false;
     for (int k = 0; k < HALO_SLOTS; ++k) busy = busy || ctx->wss[k].in_flight;
     if (!rc && ctx->prof.on && !busy) ctx->prof.collect();
@@ -334,8 +332,8 @@ int decode_batch(halo_ctx *ctx, WireKind kind, const uint8_t *in, const size_t *
     int slot = -1;
     size_t chunk = 0;
     if (ctx && !pts.empty() && sqrt_tables_host()) {
-        for (int s = 0; s < HALO_SLOTS && slot < 0; ++s)
-            if (!ctx->wss[s].in_flight && ctx->wss[s].lent_from < 0 && !ctx->fan[s].active) slot = s;
+        int idle[HALO_SLOTS];
+        if (idle_slots(ctx, idle)) slot = idle[0];
         const long forced = dev_hooks().decode_min;  // (development library: the threshold sweep of tools/time_decode_batch.py)
         const size_t min_pts = forced >= 1 ? (size_t)forced : kDecodeBatchMin;
         const size_t tab_units = (SQRT_TAB_WORDS * 4 + kDecompBytes - 1) / kDecompBytes;  // the tables in front, in units of a point's staging
@@ -351,18 +349,14 @@ int decode_batch(halo_ctx *ctx, WireKind kind, const uint8_t *in, const size_t *
         pool_run(pts.size(), [&](size_t j) { ok[j] = decompress_point(pts[j].src, pts[j].dst); });
     }
     // 3. every member's status
-    int first = -1;
     for (size_t i = 0; i < m; ++i) {
         DecodeMember &M = mem[i];
         for (size_t j = 0; j < M.pts.size(); ++j)
             if (!ok[M.first + j]) { M.rc = HALO_E_REJECT; M.err = std::string("decode: malformed ") + kWireName[kind]; break; }
-        if (M.rc) std::memset(out + i * stride, 0, stride * 8);
         if (lg_out) lg_out[i] = M.rc ? 0 : M.lg;
-        if (status) status[i] = M.rc;
-        if (M.rc && first < 0) first = (int)i;
     }
-    if (first >= 0) { set_error("member " + std::to_string(first) + ": " + mem[first].err); return mem[first].rc; }
-    return HALO_OK;
+    return report_members("member", m, [&](size_t i) { return mem[i].rc; }, [&](size_t i) { return mem[i].err; }, status,
+                          [&](size_t i) { std::memset(out + i * stride, 0, stride * 8); });
 }
 
 }  // namespace

@@ -1,8 +1,9 @@
 // Exercises the host-side arithmetic of the library (csrc/host_math.hpp: fields, group law, fixed-base table, GLV digit
-// expansion, SHA3-based key scalars) under AddressSanitizer + UBSan; built and run by tests/test_host_sanitizers.py.
+// expansion, SHA3-based key scalars, the stream skip, h(z), the batched inversion) under AddressSanitizer + UBSan; built and run by tests/test_host_sanitizers.py.
 #include <cstdio>
 #include <cstring>
 #include <random>
+#include <vector>
 #include "host_math.hpp"
 using namespace halo::host;
 int main() {
@@ -44,6 +45,39 @@ int main() {
         Fr p2 = Fr::one();
         for (int s = 0; s < 260; ++s) { p2 = p2 + p2; bad += !(p2.inv() == p2.inv_fermat()) + !((-p2).inv() == (-p2).inv_fermat()); }
         if (!Fr::zero().inv().is_zero() || bad) { printf("inverse mismatch: %ld\n", bad); return 1; }
+    }
+    // Rng::skip_scalars(k), then scalar(), is the (k + 1)-th scalar of the stream
+    for (u64 k : {0, 1, 5, 1000}) {
+        Rng a{0x48414C4F00000001ULL}, b{0x48414C4F00000001ULL};
+        a.skip_scalars(k);
+        Fr want;
+        for (u64 i = 0; i <= k; ++i) want = b.scalar();
+        if (!(a.scalar() == want) || a.state != b.state) { printf("skip_scalars mismatch at k = %llu\n", (unsigned long long)k); return 1; }
+    }
+    // h_eval against the product written out, factor by factor with z^(2^k) from the generic power: the head factor
+    // 1 + xi_lg z, then 1 + xi_(lg-k) z^(2^k) for 0 < k < lg (pcdl.rs:79-91; the head stands alone at lg = 0 and lg = 1, where the
+    // bounds 1 .. lg - 1 of the loop are empty), at a random z and at z = 0
+    for (size_t lg : {0, 1, 2, 5, 20}) {
+        std::vector<Fr> xis(lg + 1);
+        for (size_t i = 0; i <= lg; ++i) xis[i] = urs_scalar(5000 + 100 * lg + i);
+        for (const Fr &z : {urs_scalar(7000 + lg), Fr::zero()}) {
+            Fr want = Fr::one() + xis[lg] * z;
+            for (size_t k = 1; k < lg; ++k) {
+                const uint64_t e[4] = {(u64)1 << k, 0, 0, 0};
+                want = want * (Fr::one() + xis[lg - k] * z.pow(e));  // z^(2^k) by the generic power
+            }
+            if (!(h_eval(xis.data(), lg, z) == want)) { printf("h_eval mismatch at lg = %zu\n", lg); return 1; }
+            if (z.is_zero() && !(want == Fr::one())) { printf("h(0) != 1 at lg = %zu\n", lg); return 1; }
+        }
+    }
+    // batch_inverse times its inputs is one
+    for (size_t len : {0, 1, 2, 20}) {
+        std::vector<Fr> in(len), out(len + 1, Fr::from_u64(77));
+        for (size_t i = 0; i < len; ++i) in[i] = urs_scalar(9000 + i);
+        batch_inverse(in.data(), len, out.data());
+        for (size_t i = 0; i < len; ++i)
+            if (!(in[i] * out[i] == Fr::one())) { printf("batch_inverse mismatch at %zu of %zu\n", i, len); return 1; }
+        if (!(out[len] == Fr::from_u64(77))) { printf("batch_inverse wrote past its output\n"); return 1; }
     }
     uint64_t w[12]; acc.store_normalized(w);
     printf("ok %016llx\n", (unsigned long long)w[0]);
