@@ -169,6 +169,7 @@ _DEV_SIGS = {
     "halo_dev_fq_sqrt": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, u32p]),
     "halo_dev_fold_points": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_int, u64p, C.c_int, C.c_int, u64p]),
     "halo_dev_sqrt_tables": (C.c_int, [u32p, C.c_size_t]),
+    "halo_dev_table_read": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, u64p]),
     "halo_test_lazy_field_op": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t, u32p]),
     "halo_test_lazy_point_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, u32p, u32p, C.c_size_t, u32p]),
 }
@@ -559,6 +560,13 @@ class Context:
         assert scalars.shape[0] == (3 if levels == 2 else 1)
         out = np.zeros((max(n // (4 if levels == 2 else 2), 1), 8), dtype=np.uint64)
         check(self.lib.halo_dev_fold_points(self.h, ptr(key), n, int(levels), ptr(scalars), int(form), int(bool(in_place)), ptr(out)))
+        return out
+
+    def table_read(self, row, off=0, n=None):
+        """halo_dev_table_read: entries [off, off + n) of row `row` of the MSM table -> n x 8 affine words, as read_bases gives the key"""
+        n = self.size - off if n is None else n
+        out = np.zeros((n, 8), dtype=np.uint64)
+        check(self.lib.halo_dev_table_read(self.h, int(row), int(off), int(n), ptr(out)))
         return out
 
     def lazy_field_op(self, op, a):

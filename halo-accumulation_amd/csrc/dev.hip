@@ -553,6 +553,30 @@ int halo_dev_fold_points(halo_ctx *ctx, const uint64_t *key_affine, size_t n, in
     return rc;
 }
 
+// Entries [off, off + count) of row `row` of the context's MSM table as arkworks affine words (include/halo_accumulation_dev.h): the
+// conversion is halo_ctx_read_bases' (k_native_to_aff), the device buffer is this call's only.  Nothing may be in flight: a launch
+// enqueued with every slot idle may release or rebuild the table (table_demote), and its slot's stream is not the one waited for here.
+int halo_dev_table_read(halo_ctx *ctx, size_t row, size_t off, size_t count, uint64_t *out_affine) {
+    HALO_CTX(ctx);
+    if (!ctx->d_table) { set_error("dev_table_read: the context has no MSM table (built by its first table MSM)"); return HALO_E_ARG; }
+    if (row >= (size_t)ctx->tbl.rows) { set_error("dev_table_read: row exceeds the table's rows (halo_ctx_info 8)"); return HALO_E_ARG; }
+    if (off > ctx->n || count > ctx->n - off) { set_error("dev_table_read: range exceeds the context's key"); return HALO_E_ARG; }
+    for (int k = 0; k < HALO_SLOTS; ++k)
+        if (ctx->wss[k].in_flight || ctx->wss[k].lent_from >= 0 || ctx->fan[k].active) { set_error("dev_table_read: an MSM is in flight on this context"); return HALO_E_ARG; }
+    if (count == 0) return HALO_OK;
+    if (!out_affine) { set_error("dev_table_read: null pointer"); return HALO_E_ARG; }
+    uint64_t *d_out = nullptr;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d_out, count * 64));
+    int rc = aff_native_to_words(ctx, ctx->d_table + (size_t)AFF_STRIDE * (row * ctx->n + off), count, d_out);
+    hipError_t e = hipSuccess;
+    if (!rc && (e = hipMemcpyAsync(out_affine, d_out, count * 64, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+    e = hipStreamSynchronize(ctx->stream);  // (also on failure: nothing of this call may be in flight when its buffer goes)
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    (void)hipFree(d_out);
+    return rc;
+}
+
 int halo_test_lazy_field_op(halo_ctx *ctx, int op, const uint32_t *in, size_t n, uint32_t *out) {
     HALO_CTX(ctx);
     if (n == 0) return HALO_OK;

@@ -114,6 +114,13 @@ int halo_dev_small_msm_seg(halo_ctx *ctx, const uint64_t *points, const uint64_t
 int halo_dev_fold_points(halo_ctx *ctx, const uint64_t *key_affine, size_t n, int levels, const uint64_t *scalars, int form, int in_place,
                          uint64_t *out_affine);
 
+/* Entries [off, off + count) of row `row` of the context's MSM table (csrc/msm_table.hip: T[w][i] = 2^(c w) G_i for the 13 and 15
+ * rows, T[j][i] = 2^j G_i for the 255) as arkworks affine words, count x 8, Montgomery form, (0, 0) = infinity: what
+ * halo_ctx_read_bases gives for the key, through the same conversion.  It reads and waits for the context's stream; it builds
+ * nothing.  HALO_E_ARG: the context has no table (its first table MSM builds it), row >= halo_ctx_info(ctx, 8), a range that
+ * leaves the key, an MSM in flight on any slot. */
+int halo_dev_table_read(halo_ctx *ctx, size_t row, size_t off, size_t count, uint64_t *out_affine);
+
 /* The decode batch's square root in Fq (the routine of k_point_decompress) on its own, one lane per element: a = m x 4
  * Montgomery words; ok_out[i] = 1 and root_out[i]^2 = a[i] if a[i] is a square, else ok_out[i] = 0 */
 int halo_dev_fq_sqrt(halo_ctx *ctx, const uint64_t *a, size_t m, uint64_t *root_out, uint32_t *ok_out);

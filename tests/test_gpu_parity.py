@@ -930,3 +930,35 @@ def test_api_misuse_is_reported_not_crashed(hal, ctx16k):
         hal.Ipa(ctx16k, 6, sc[:4], sc[0])               # not a power of two (pcdl.rs:130)
     with pytest.raises(AssertionError):
         hal.Ipa(ctx16k, 1 << 15, sc[:4], sc[0])         # larger than the key (pcdl.rs:132)
+
+
+def test_table_read_misuse_is_reported(hal):
+    """halo_dev_table_read (development library): no table, a row or a range that is not there, an MSM in flight -- each refused
+    with its message; what it does return for row 0 is the key"""
+    import torch
+    hal.dev_hook("table_slide_min", 4096)
+    n = 4096
+    c = hal.Context(urs_n=n)
+    try:
+        with pytest.raises(hal.HaloError, match="no MSM table"):
+            c.table_read(0)
+        d = torch.empty(n * 4, dtype=torch.int64, device="cuda")
+        c.rng_scalars_dev(0x7461626C, n, d.data_ptr())
+        c.set_table_mode(1)
+        c.msm_dev(d.data_ptr(), n)
+        assert c.info(8) == 13
+        assert c.table_read(0).tolist() == c.read_bases().tolist()
+        assert c.table_read(12, off=n - 6).shape == (6, 8) and c.table_read(12, off=n, n=0).shape == (0, 8)
+        with pytest.raises(hal.HaloError, match="row exceeds"):
+            c.table_read(13)
+        for off, m in ((n - 6, 7), (n + 1, 0), (2**64 - 32, 64)):
+            with pytest.raises(hal.HaloError, match="range exceeds"):
+                c.table_read(1, off=off, n=m)
+        c.msm_dev_begin(2, d.data_ptr(), n)
+        with pytest.raises(hal.HaloError, match="in flight"):
+            c.table_read(1)
+        c.msm_dev_end(2)
+        assert c.table_read(1, n=4).any()
+    finally:
+        c.close()
+
