@@ -166,6 +166,8 @@ _DEV_SIGS = {
     "halo_dev_h_coeffs_batch": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_size_t, u64p]),
     "halo_dev_h_accumulate_batch": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.c_size_t, u64p]),
     "halo_dev_small_msm_seg": (C.c_int, [C.c_void_p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, u64p]),
+    "halo_dev_batch_small_msm": (C.c_int, [C.c_void_p, u64p, u64p, C.c_size_t, C.c_size_t, u64p]),
+    "halo_dev_batch_to_affine": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p]),
     "halo_dev_fq_sqrt": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, u32p]),
     "halo_dev_fold_points": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_int, u64p, C.c_int, C.c_int, u64p]),
     "halo_dev_sqrt_tables": (C.c_int, [u32p, C.c_size_t]),
@@ -567,6 +569,34 @@ class Context:
         n = self.size - off if n is None else n
         out = np.zeros((n, 8), dtype=np.uint64)
         check(self.lib.halo_dev_table_read(self.h, int(row), int(off), int(n), ptr(out)))
+        return out
+
+    def batch_to_affine(self, pts_jac):
+        """halo_dev_batch_to_affine: m x 12 Jacobian words through the product's batch_to_affine -> m x 8 affine words"""
+        pts_jac = np.ascontiguousarray(pts_jac, dtype=np.uint64).reshape(-1, 12)
+        out = np.zeros((pts_jac.shape[0], 8), dtype=np.uint64)
+        check(self.lib.halo_dev_batch_to_affine(self.h, ptr(pts_jac), pts_jac.shape[0], ptr(out)))
+        return out
+
+    def batch_small_msm(self, points, scalars, K):
+        """halo_dev_batch_small_msm: m sums of K terms (m K x 8 affine words, m K x 4 canonical scalar words) in one
+        k_batch_small_msm launch -> m x 12 Jacobian words"""
+        points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        assert points.shape[0] == scalars.shape[0] and points.shape[0] % K == 0
+        m = points.shape[0] // K
+        out = np.zeros((m, 12), dtype=np.uint64)
+        check(self.lib.halo_dev_batch_small_msm(self.h, ptr(points), ptr(scalars), m, int(K), ptr(out)))
+        return out
+
+    def small_msm_seg(self, points, scalars, lens):
+        """halo_dev_small_msm_seg: sums of lens[s] terms each, the terms sum after sum, in one k_small_msm_seg launch -> len(lens) x 12"""
+        points = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 8)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        assert points.shape[0] == scalars.shape[0] == sum(lens)
+        out = np.zeros((len(lens), 12), dtype=np.uint64)
+        cl = (C.c_size_t * len(lens))(*[int(x) for x in lens])
+        check(self.lib.halo_dev_small_msm_seg(self.h, ptr(points), ptr(scalars), cl, len(lens), ptr(out)))
         return out
 
     def lazy_field_op(self, op, a):

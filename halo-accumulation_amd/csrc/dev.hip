@@ -316,6 +316,51 @@ int halo_dev_small_msm_seg(halo_ctx *ctx, const uint64_t *points, const uint64_t
     return rc;
 }
 
+// the relation kernel of the device-side succinct checks on its own (tests/test_gpu_point_paths.py holds it against the oracle):
+// one k_batch_small_msm launch through the product's batch_small_msm, m sums of K terms each, temporary device buffers of this
+// call only
+int halo_dev_batch_small_msm(halo_ctx *ctx, const uint64_t *points, const uint64_t *scalars, size_t m, size_t K, uint64_t *out_jac) {
+    HALO_CTX(ctx);
+    if (m == 0) return HALO_OK;
+    if (!points || !scalars || !out_jac) { set_error("batch_small_msm: null pointer"); return HALO_E_ARG; }
+    if (m > 65535) { set_error("batch_small_msm: at most 65535 sums"); return HALO_E_ARG; }
+    if (K == 0 || K > 64) return batch_small_msm(ctx, nullptr, nullptr, m, K, nullptr);  // (the product's refusal, before any launch)
+    const size_t nterms = m * K;
+    uint64_t *d = nullptr;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d, nterms * 96 + m * 96));
+    uint64_t *d_pts = d, *d_sc = d_pts + nterms * 8, *d_out = d_sc + nterms * 4;
+    hipError_t e = hipMemcpy(d_pts, points, nterms * 64, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_sc, scalars, nterms * 32, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? batch_small_msm(ctx, d_pts, d_sc, m, K, d_out) : hip_fail(e, "hipMemcpy");
+    if (!rc && (e = hipStreamSynchronize(ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    if (!rc && (e = hipMemcpy(out_jac, d_out, m * 96, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d);
+    return rc;
+}
+
+// halo_msm_points' normalisation on its own (tests/test_gpu_point_paths.py holds every output against Python integers): upload,
+// the product's batch_to_affine (k_batch_to_affine), k_native_to_aff, download; temporary device buffers of this call only
+int halo_dev_batch_to_affine(halo_ctx *ctx, const uint64_t *pts_jac, size_t m, uint64_t *out_affine) {
+    HALO_CTX(ctx);
+    if (m == 0) return HALO_OK;
+    if (!pts_jac || !out_affine) { set_error("dev_batch_to_affine: null pointer"); return HALO_E_ARG; }
+    if (m > ((size_t)1 << 22)) { set_error("dev_batch_to_affine: at most 2^22 points"); return HALO_E_ARG; }
+    uint64_t *d = nullptr;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d, m * (96 + 64) + m * (size_t)AFF_STRIDE * 4));
+    uint64_t *d_jac = d, *d_out = d_jac + m * 12;
+    uint32_t *d_native = reinterpret_cast<uint32_t *>(d_out + m * 8);  // (every part a multiple of 32 bytes)
+    hipError_t e = hipMemcpyAsync(d_jac, pts_jac, m * 96, hipMemcpyHostToDevice, ctx->stream);
+    int rc = e == hipSuccess ? batch_to_affine(ctx, d_jac, m, d_native) : hip_fail(e, "hipMemcpyAsync");
+    if (!rc) rc = aff_native_to_words(ctx, d_native, m, d_out);
+    if (!rc && (e = hipMemcpyAsync(out_affine, d_out, m * 64, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+    e = hipStreamSynchronize(ctx->stream);  // (also on failure: nothing of this call may be in flight when its buffers go)
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    (void)hipFree(d);
+    return rc;
+}
+
 // the decode batch's square root in Fq (k_fq_sqrt, the routine of k_point_decompress) on its own (tests/test_gpu_decode_batch.py
 // holds it against Python integers): temporary device buffers of this call only
 int halo_dev_fq_sqrt(halo_ctx *ctx, const uint64_t *a, size_t m, uint64_t *root_out, uint32_t *ok_out) {

@@ -11,6 +11,7 @@
 #include "fold_lane.hpp"
 #include "fr29.hpp"
 #include "internal.hpp"
+#include "small_msm_lane.hpp"
 
 namespace halo {
 
@@ -511,30 +512,6 @@ __global__ __launch_bounds__(256) void k_h_eval_z(const uint64_t *__restrict__ x
 }
 
 // ------------------------------------------------------------------ batched verifier relation
-// k P for one lane's term: the 256-step ladder (double, add, keep the sum if the bit is set -- no divergence although the
-// scalars differ); k canonical (not Montgomery), a dead lane keeps infinity
-HALO_DEV JacN small_msm_ladder(const AffN &p, const Fe &k, bool live) {
-    JacN acc = jac_inf();
-#pragma unroll 1
-    for (int limb = 7; limb >= 0; limb--) {
-        uint32_t word = 0;
-#pragma unroll
-        for (int q = 0; q < 8; q++) word = (q == limb) ? k.v[q] : word;
-#pragma unroll 1
-        for (int bit = 31; bit >= 0; bit--) {
-            acc = jac_dbl(acc);
-            JacN s = jac_madd(acc, p);
-            bool take = live && ((word >> bit) & 1u);
-#pragma unroll
-            for (int i = 0; i < 9; i++) {
-                acc.x.v[i] = take ? s.x.v[i] : acc.x.v[i];
-                acc.y.v[i] = take ? s.y.v[i] : acc.y.v[i];
-                acc.z.v[i] = take ? s.z.v[i] : acc.z.v[i];
-            }
-        }
-    }
-    return acc;
-}
 // m independent sums of K <= 64 scalar multiples each (the 2 lg n + 2 terms of one pcdl::succinct_check, pcdl.rs:288-310):
 // one wave per sum, one lane per term.  Every lane runs the ladder, then the wave folds its lanes with a shuffle tree.
 // points: m x K x 8 words (arkworks affine, (0, 0) = infinity); scalars: m x K x 4 words, CANONICAL (not Montgomery).

@@ -98,6 +98,17 @@ int halo_set_task_len(halo_ctx *ctx, int len);
 int halo_dev_small_msm_seg(halo_ctx *ctx, const uint64_t *points, const uint64_t *scalars, const size_t *lens, size_t nsums,
                            uint64_t *out_jac);
 
+/* The relation kernel of the device-side succinct checks (k_batch_small_msm) on its own, in one launch through the product's
+ * batch_small_msm: m sums of K terms each, one wave per sum; points = m x K x 8 words (arkworks affine, (0, 0) = infinity),
+ * scalars = m x K x 4 canonical words, out_jac = m x 12 Jacobian words.  m = 0 is HALO_OK.  HALO_E_ARG: a null pointer, m above
+ * 65535, K outside 1..64 (the product's message). */
+int halo_dev_batch_small_msm(halo_ctx *ctx, const uint64_t *points, const uint64_t *scalars, size_t m, size_t K, uint64_t *out_jac);
+
+/* halo_msm_points' normalisation on its own: upload, the product's batch_to_affine (k_batch_to_affine: four points per lane, one
+ * shared inversion), k_native_to_aff, download.  pts_jac = m x 12 arkworks Jacobian words (any Z; Z = 0 is infinity whatever X
+ * and Y hold), out_affine = m x 8 affine words, (0, 0) = infinity.  m = 0 is HALO_OK.  HALO_E_ARG: a null pointer, m above 2^22. */
+int halo_dev_batch_to_affine(halo_ctx *ctx, const uint64_t *pts_jac, size_t m, uint64_t *out_affine);
+
 /* One point fold of pcdl::open's halving loop on its own, through the product's launcher: out[j] = G[j] + xi G[j+m] (levels 1,
  * m = n / 2) or G[j] + s1 G[j+m] + s2 G[j+2m] + s3 G[j+3m] (levels 2, m = n / 4; two rounds xi1, xi2 are (s1, s2, s3) =
  * (xi2, xi1, xi1 xi2)).  key_affine = n x 8 words, (0, 0) = infinity -- any points, m may be odd -- or NULL: the first n points of

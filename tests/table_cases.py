@@ -65,10 +65,12 @@ def raw_coordinates(rows):
 
 
 # ---------------------------------------------------------------------------------------------------- the key
-def exceptional_key(base_affine, layout="all_shifts"):
+def exceptional_key(base_affine, layout="all_shifts", pairs=(1000, 1500)):
     """n x 8 affine words of an ordinary key (distinct finite points) -> (key, classes): the same key with exceptional points
     planted, classes[i] = the name of what sits at index i ("plain" everywhere else).  layout "all_shifts": the positions of
-    k_table_all_shifts (i = 4096 block + 256 e + tid); "step": the same classes on the stripes of k_table_step (i = t + e stride)."""
+    k_table_all_shifts (i = 4096 block + 256 e + tid); "step": the same classes on the stripes of k_table_step (i = t + e stride).
+    pairs: the two originals whose copy and negation sit one stride further on, in the same lane (a key below 1500 + stride points
+    names smaller ones)."""
     key = np.array(base_affine, dtype=np.uint64).reshape(-1, 8)
     n = key.shape[0]
     assert key.any(axis=1).all() and len({r.tobytes() for r in key}) == n, "the base key is distinct finite points"
@@ -113,7 +115,7 @@ def exceptional_key(base_affine, layout="all_shifts"):
     assert COPIES % 64 and NEGATIONS % 64
     classes[ORIGINAL] = "original of the runs"
     # two pairs that share a lane
-    for a, sign in ((1000, 1), (1500, -1)):
+    for a, sign in ((pairs[0], 1), (pairs[1], -1)):
         plant(a + stride, "%sG[%d], same lane" % ("-" if sign < 0 else "", a), key[a] if sign > 0 else negated(key[a]))
         assert classes[a] == "plain"
         classes[a] = "original of a pair"
