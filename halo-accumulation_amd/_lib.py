@@ -163,6 +163,8 @@ _DEV_SIGS = {
     "halo_test_fold_digits": (C.c_int, [u64p, C.POINTER(C.c_int8)]),
     "halo_test_field_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, u64p, u64p, C.c_size_t, u64p]),
     "halo_test_point_op": (C.c_int, [C.c_void_p, C.c_int, u64p, u64p, C.c_size_t, u64p]),
+    "halo_dev_fr_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_size_t, C.POINTER(C.c_long)]),
+    "halo_dev_dot2_cross": (C.c_int, [C.c_void_p, u64p, u64p, C.c_size_t, u64p]),
     "halo_dev_h_coeffs_batch": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_size_t, u64p]),
     "halo_dev_h_accumulate_batch": (C.c_int, [C.c_void_p, u64p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.c_size_t, u64p]),
     "halo_dev_small_msm_seg": (C.c_int, [C.c_void_p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, u64p]),
@@ -235,6 +237,18 @@ class _Lib:
 def dev_hook(name: str, value: int) -> None:
     """fault injectors / forced test paths of the development library (csrc/tuning.hpp DevHooks); "reset" switches all off"""
     check(load().halo_dev_hook(name.encode(), int(value)))
+
+
+FR_PLAN_KERNELS = {"powers": 0, "poly_eval": 1, "dot": 2, "h_coeffs": 3, "poly_eval_batch": 4}
+
+
+def fr_plan(which: str, n: int, ctx=None) -> dict:
+    """The launch plan of one Fr kernel family at size n as its launcher computes it now (development hooks, environment, defaults;
+    csrc/fr_plan.hpp): {"E", "nwin", "blocks", "trips"}.  which: powers / poly_eval / dot / h_coeffs (n = 2^lg_n) /
+    poly_eval_batch (the p(z) of halo_pcdl_open_batch: at most 256 blocks per member).  Host only."""
+    out = (C.c_long * 4)()
+    check(load().halo_dev_fr_plan(None if ctx is None else ctx.h, FR_PLAN_KERNELS[which], int(n), out))
+    return dict(zip(("E", "nwin", "blocks", "trips"), [int(v) for v in out]))
 
 
 def ptr(a):
@@ -588,6 +602,15 @@ class Context:
         out = np.zeros((m, 12), dtype=np.uint64)
         check(self.lib.halo_dev_batch_small_msm(self.h, ptr(points), ptr(scalars), m, int(K), ptr(out)))
         return out
+
+    def dot2_cross(self, c, z):
+        """the two dot products of an IPA round over c, z of 2 m elements, any m (halo_dev_dot2_cross): <c_hi, z_lo>, <c_lo, z_hi>"""
+        c = np.ascontiguousarray(c, dtype=np.uint64).reshape(-1, 4)
+        z = np.ascontiguousarray(z, dtype=np.uint64).reshape(-1, 4)
+        assert len(c) == len(z) and len(c) % 2 == 0
+        out = np.zeros((2, 4), dtype=np.uint64)
+        check(self.lib.halo_dev_dot2_cross(self.h, ptr(c), ptr(z), len(c) // 2, ptr(out)))
+        return out[0], out[1]
 
     def small_msm_seg(self, points, scalars, lens):
         """halo_dev_small_msm_seg: sums of lens[s] terms each, the terms sum after sum, in one k_small_msm_seg launch -> len(lens) x 12"""

@@ -13,6 +13,7 @@
 #include "../../include/halo_accumulation_dev.h"
 #include "curve_quad.hpp"
 #include "dev_lazy_ops.hpp"
+#include "fr_plan.hpp"
 #include "internal.hpp"
 
 namespace halo {
@@ -195,6 +196,7 @@ long halo_dev_tuning(const char *name) {
     if (!std::strcmp(name, "fold_table_after")) return t.fold_table_after;
     if (!std::strcmp(name, "graph_cache")) return t.graph_cache;
     if (!std::strcmp(name, "pow_e")) return t.pow_e;
+    if (!std::strcmp(name, "dot_blocks")) return t.dot_blocks;
     if (!std::strcmp(name, "spin_us")) return t.spin_us;
     if (!std::strcmp(name, "graphs")) return t.graphs;
     if (!std::strcmp(name, "memory_budget")) return t.memory_budget_set ? (long)(t.memory_budget >> 20) : -1;  // MiB
@@ -216,8 +218,49 @@ int halo_dev_hook(const char *name, long value) {
     else if (!std::strcmp(name, "verifier_batch_min")) h.verifier_min = (int)value;
     else if (!std::strcmp(name, "decode_batch_min")) h.decode_min = value;
     else if (!std::strcmp(name, "table_slide_min")) h.slide_min = value > 0 && value < 4096 ? 4096 : value;
+    else if (!std::strcmp(name, "pow_e")) {
+        // (the rule of HALO_POW_E: k_h_coeffs' mid * high factor is wave-uniform only over a power-of-two chain)
+        if (value < 4 || value > 64 || (value & (value - 1)) != 0) { set_error("dev_hook: pow_e must be a power of two in [4, 64]"); return HALO_E_ARG; }
+        h.pow_e = (int)value;
+    } else if (!std::strcmp(name, "dot_blocks")) {
+        if (value < 1 || value > (long)FR_GRID_CAP) { set_error("dev_hook: dot_blocks must be in [1, " + std::to_string(FR_GRID_CAP) + "]"); return HALO_E_ARG; }
+        h.dot_blocks = (int)value;
+    } else if (!std::strcmp(name, "poly_blocks")) {
+        if (value < 1 || value > (long)FR_GRID_CAP) { set_error("dev_hook: poly_blocks must be in [1, " + std::to_string(FR_GRID_CAP) + "]"); return HALO_E_ARG; }
+        h.poly_blocks = (int)value;
+    }
     else if (!std::strcmp(name, "reset")) h = DevHooks();
-    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, verifier_batch_min, decode_batch_min, table_slide_min, reset)"); return HALO_E_ARG; }
+    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, verifier_batch_min, decode_batch_min, table_slide_min, pow_e, dot_blocks, poly_blocks, reset)"); return HALO_E_ARG; }
+    return HALO_OK;
+}
+
+// host only: the launch plan of one Fr kernel family at size n as its launcher computes it NOW (hooks, environment, defaults):
+// the plan_* functions of fr_plan.hpp, which are the ones the launchers of ipa.hip call.  which = 1 is the single open's p(z)
+// (fr_poly_eval: up to FR_GRID_CAP blocks), 4 the batched open's (open_batch_table / open_batch_eval: a member's OPEN_PART_WORDS / 4)
+int halo_dev_fr_plan(halo_ctx *ctx, int which, size_t n, long out[4]) {
+    (void)ctx;  // (no plan depends on the context today)
+    if (!out) { set_error("dev_fr_plan: null pointer"); return HALO_E_ARG; }
+    FrPlan p;
+    if (!fr_plan(which, n, &p)) { set_error("dev_fr_plan: which is 0 powers, 1 poly_eval, 2 dot, 3 h_coeffs, 4 poly_eval of the batched open"); return HALO_E_ARG; }
+    out[0] = p.E; out[1] = p.nwin; out[2] = (long)p.blocks; out[3] = (long)p.trips;
+    return HALO_OK;
+}
+
+// the two dot products of an IPA round (k_dot2_partial with both pairs, fr_dot2) on their own, over vectors of any half length m:
+// out = <c_hi, z_lo> | <c_lo, z_hi> for c, z of 2 m elements (tests/test_gpu_fr_plans.py: the rounds themselves only reach powers of two)
+int halo_dev_dot2_cross(halo_ctx *ctx, const uint64_t *c, const uint64_t *z, size_t m, uint64_t out[8]) {
+    HALO_CTX(ctx);
+    if (!out || (m && (!c || !z))) { set_error("dev_dot2_cross: null pointer"); return HALO_E_ARG; }
+    if (2 * m > (ctx->n < 64 ? 64 : ctx->n)) { set_error("dev_dot2_cross: 2 m exceeds context size"); return HALO_E_ARG; }
+    if (m == 0) { std::memset(out, 0, 64); return HALO_OK; }
+    int rc = upload_words(ctx, ctx->d_tmp_a, c, m * 8);
+    if (!rc) rc = upload_words(ctx, ctx->d_tmp_b, z, m * 8);
+    if (rc) return rc;
+    host::Fr r[2];
+    rc = fr_dot2(ctx, ctx->d_tmp_a + 4 * m, ctx->d_tmp_b, ctx->d_tmp_a, ctx->d_tmp_b + 4 * m, m, r);
+    if (rc) return rc;
+    r[0].store(out);
+    r[1].store(out + 4);
     return HALO_OK;
 }
 

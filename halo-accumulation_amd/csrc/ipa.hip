@@ -10,6 +10,7 @@
 #include "curve_quad.hpp"
 #include "fold_lane.hpp"
 #include "fr29.hpp"
+#include "fr_plan.hpp"
 #include "internal.hpp"
 #include "small_msm_lane.hpp"
 
@@ -293,19 +294,7 @@ HALO_DEV Fs<4> window_power(const uint64_t *__restrict__ tab, uint32_t e, int nw
         if (k < nwin) acc = fs_widen<4>(fs_mul(acc, fs_from_fe(w[k])));  // (nwin is a kernel argument: wave-uniform)
     return acc;
 }
-// elements per lane: a longer chain spreads the seed (nwin - 1 products) over more elements, a shorter one puts more
-// waves on the chip; measured at n = 2^20 (tools/fr_kernels.py with HALO_POW_E = 2 .. 32): k_powers 8, k_poly_eval_partial
-// 16, k_h_coeffs 4 (its "seed" is one product per four elements whatever the length)
-constexpr int POLY_EVAL_E = 16;  // coefficients per lane of k_poly_eval_partial
-static int pow_chain_len(size_t n, int best) {
-    // development override: a power of two in [4, 64] or it is ignored -- k_h_coeffs relies on a chain length that is a power of
-    // two (its mid * high factor is wave-uniform and changes every fourth step): another value would give wrong coefficients
-    const int forced = tuning().pow_e;  // (validated there)
-    if (forced > 0) return forced;
-    int e = best;
-    while (e > 4 && n / (64 * (size_t)e) < 1024) e >>= 1;  // small inputs: at least a wave per SIMD
-    return e;
-}
+// (elements per lane of these kernels, window count and grids: fr_plan.hpp)
 
 // ------------------------------------------------------------------ K6: out[i] = z^i
 // One product per 32 bytes written: VALU-bound (fr29.hpp: 5.3 TB/s if nothing else ran).  Lane l of a wave writes the
@@ -859,19 +848,11 @@ static unsigned reduce_blocks(size_t work_items) {
     return (unsigned)nb;
 }
 
-// two elements per lane and trip, at most 512 blocks (two waves per SIMD): the lanes of a large dot product run several trips
-static unsigned dot_blocks(size_t m) {
-    const size_t cap_env = tuning().dot_blocks > 0 ? (size_t)tuning().dot_blocks : 0;  // development override
-    size_t nb = ((m + 1) / 2 + 255) / 256, cap = cap_env ? cap_env : 512;
-    if (nb > cap) nb = cap;
-    if (nb == 0) nb = 1;
-    return (unsigned)nb;
-}
 // the two halves of fr_dot2: launch (kernels + the copy of the two sums to pinned memory, on ctx->stream) and collect (wait)
 int fr_dot2_launch(halo_ctx *ctx, const uint64_t *xs0, const uint64_t *ys0, const uint64_t *xs1, const uint64_t *ys1, size_t m) {
     if (m == 0) return HALO_OK;
     if (!xs0) { set_error("dot2: the first pair of vectors is required"); return HALO_E_ARG; }
-    unsigned nb = dot_blocks(m);
+    unsigned nb = plan_dot(m).blocks;  // (<= FR_GRID_CAP)
     uint64_t *partial = ctx->d_tmp_c;  // >= 1024 * 8 words
     if (xs1) HALO_LAUNCH(ctx, "k_dot2_partial", k_dot2_partial<true>, dim3(nb), dim3(256), 0, xs0, ys0, xs1, ys1, (uint32_t)m, partial);
     else HALO_LAUNCH(ctx, "k_dot2_partial", k_dot2_partial<false>, dim3(nb), dim3(256), 0, xs0, ys0, xs1, ys1, (uint32_t)m, partial);
@@ -898,11 +879,6 @@ int fr_dot2(halo_ctx *ctx, const uint64_t *xs0, const uint64_t *ys0, const uint6
 
 // Window table of z (see window_power): 16 A-form entries, then nwin x 16 N-form entries, staged through pinned memory.
 // ~32 nwin host products (a few microseconds).
-static int bits_for(size_t n) {
-    int b = 0;
-    while (((size_t)1 << b) < n) b++;
-    return b < 1 ? 1 : b;
-}
 // zpows > 0: N(z^(64 k)), k < zpows, behind the window table (k_poly_eval_partial's per-element multipliers)
 // fills h (16 (1 + nwin) + zpows entries of 4 words); -1 if that is more than 256 entries
 static long fill_window_table(const host::Fr &z, int nwin, uint64_t *h, host::Fr *z64, int zpows) {
@@ -937,20 +913,14 @@ static int upload_window_table(halo_ctx *ctx, const host::Fr &z, int nwin, uint6
     HALO_HIP(hipStreamSynchronize(ctx->stream));  // the staging memory is reused by the next call
     return HALO_OK;
 }
-static unsigned wave_blocks(size_t n, int E) {  // blocks of 4 waves, a wave per 64 * E elements
-    size_t waves = (n + 64 * (size_t)E - 1) / (64 * (size_t)E);
-    return (unsigned)((waves + 3) / 4);
-}
-
 int fr_powers(halo_ctx *ctx, const host::Fr &z, size_t n, uint64_t *d_out) {
     if (n == 0) return HALO_OK;
     uint64_t *d_tab = ctx->d_tmp_c + 8 * 1024 + 64;
-    int nwin = (bits_for(n) + 3) / 4;
+    const FrPlan p = plan_powers(n);
     host::Fr z64;
-    int rc = upload_window_table(ctx, z, nwin, d_tab, &z64);
+    int rc = upload_window_table(ctx, z, p.nwin, d_tab, &z64);
     if (rc) return rc;
-    int E = pow_chain_len(n, 8);
-    HALO_LAUNCH(ctx, "k_powers", k_powers, dim3(wave_blocks(n, E)), dim3(256), 0, d_tab, nwin, E, (uint32_t)n, to_nform(z64), d_out);
+    HALO_LAUNCH(ctx, "k_powers", k_powers, dim3(p.blocks), dim3(256), 0, d_tab, p.nwin, p.E, (uint32_t)n, to_nform(z64), d_out);
     HALO_HIP(hipGetLastError());
     return HALO_OK;
 }
@@ -959,13 +929,12 @@ int fr_poly_eval(halo_ctx *ctx, const uint64_t *d_coeffs, size_t len, const host
     *out = host::Fr::zero();
     if (len == 0) return HALO_OK;
     uint64_t *d_tab = ctx->d_tmp_c + 8 * 1024 + 64;
-    int nwin = (bits_for(len) + 3) / 4;
+    const FrPlan p = plan_poly_eval(len);
+    const int nwin = p.nwin, E = p.E;
     host::Fr z64;
-    int E = pow_chain_len(len, POLY_EVAL_E);
     int rc = upload_window_table(ctx, z, nwin, d_tab, &z64, E);
     if (rc) return rc;
-    unsigned nb = wave_blocks(len, E);
-    if (nb > 1024) nb = 1024;
+    const unsigned nb = p.blocks;  // (<= FR_GRID_CAP: the waves stride over what the grid does not cover)
     uint64_t *partial = ctx->d_tmp_c;
     HALO_LAUNCH(ctx, "k_poly_eval_partial", k_poly_eval_partial, dim3(nb), dim3(256), 0, d_coeffs, (uint32_t)len, d_tab, nwin, E,
                 d_tab + 4 * (size_t)(16 * (1 + nwin)), partial);
@@ -1001,8 +970,8 @@ int h_coeffs_dev(halo_ctx *ctx, const host::Fr *xis, size_t lg_n, const host::Fr
     HALO_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, ctx->stream));
     HALO_HIP(hipStreamSynchronize(ctx->stream));  // `tab` is pageable and dies at return
     size_t n = (size_t)1 << lg_n;
-    int E = pow_chain_len(n, 4);
-    HALO_LAUNCH(ctx, "k_h_coeffs", k_h_coeffs, dim3(wave_blocks(n, E)), dim3(256), 0, d_tab, (uint32_t)n, E, accumulate ? 1 : 0, d_out);
+    const FrPlan p = plan_h_coeffs(n);
+    HALO_LAUNCH(ctx, "k_h_coeffs", k_h_coeffs, dim3(p.blocks), dim3(256), 0, d_tab, (uint32_t)n, p.E, accumulate ? 1 : 0, d_out);
     HALO_HIP(hipGetLastError());
     return HALO_OK;
 }
@@ -1015,31 +984,29 @@ int bench_fr_kernel(halo_ctx *ctx, int which, size_t n, int reps) {
     uint64_t *a = ctx->d_tmp_a, *b = ctx->d_tmp_b, *c = ctx->d_tmp_b + 4 * n, *d = ctx->d_tmp_b + 8 * n;  // n x 4 words each (d_tmp_b: 16 n words)
     host::Fr z = host::Fr::from_u64(0x1234567) * host::Fr::from_u64(0x89abcdef), z64;
     uint64_t *d_tab = ctx->d_tmp_c + 8 * 1024 + 64, *partial = ctx->d_tmp_c;
-    int nwin = (bits_for(n) + 3) / 4;
+    int nwin = window_count(n);
     int rc = rng_scalars_dev(ctx, 0xF00D, n, b);
     if (!rc) rc = rng_scalars_dev(ctx, 0xBEEF, n, c);
     if (!rc) rc = rng_scalars_dev(ctx, 0xCAFE, n, d);
-    if (!rc) rc = upload_window_table(ctx, z, nwin, d_tab, &z64, which == 1 ? pow_chain_len(n, POLY_EVAL_E) : 0);
+    if (!rc) rc = upload_window_table(ctx, z, nwin, d_tab, &z64, which == 1 ? plan_poly_eval(n).E : 0);
     if (rc) return rc;
     size_t m = n / 2 ? n / 2 : 1;
     for (int r = 0; r < reps; ++r) {
         switch (which) {
-            case 0: { int E = pow_chain_len(n, 8); HALO_LAUNCH(ctx, "k_powers", k_powers, dim3(wave_blocks(n, E)), dim3(256), 0, d_tab, nwin, E, (uint32_t)n, to_nform(z64), a); break; }
+            case 0: { const FrPlan p = plan_powers(n); HALO_LAUNCH(ctx, "k_powers", k_powers, dim3(p.blocks), dim3(256), 0, d_tab, nwin, p.E, (uint32_t)n, to_nform(z64), a); break; }
             case 1: {
-                int E = pow_chain_len(n, POLY_EVAL_E);
-                unsigned nb = wave_blocks(n, E);
-                if (nb > 1024) nb = 1024;
-                HALO_LAUNCH(ctx, "k_poly_eval_partial", k_poly_eval_partial, dim3(nb), dim3(256), 0, b, (uint32_t)n, d_tab, nwin, E,
+                const FrPlan p = plan_poly_eval(n);
+                HALO_LAUNCH(ctx, "k_poly_eval_partial", k_poly_eval_partial, dim3(p.blocks), dim3(256), 0, b, (uint32_t)n, d_tab, nwin, p.E,
                             d_tab + 4 * (size_t)(16 * (1 + nwin)), partial);
                 break;
             }
-            case 2: HALO_LAUNCH(ctx, "k_dot2_partial", k_dot2_partial<false>, dim3(dot_blocks(n)), dim3(256), 0, b, c, (const uint64_t *)nullptr,
+            case 2: HALO_LAUNCH(ctx, "k_dot2_partial", k_dot2_partial<false>, dim3(plan_dot(n).blocks), dim3(256), 0, b, c, (const uint64_t *)nullptr,
                                 (const uint64_t *)nullptr, (uint32_t)n, partial); break;
-            case 3: HALO_LAUNCH(ctx, "k_dot2_partial", k_dot2_partial<true>, dim3(dot_blocks(m)), dim3(256), 0, b + 4 * m, c, b, c + 4 * m, (uint32_t)m, partial); break;
+            case 3: HALO_LAUNCH(ctx, "k_dot2_partial", k_dot2_partial<true>, dim3(plan_dot(m).blocks), dim3(256), 0, b + 4 * m, c, b, c + 4 * m, (uint32_t)m, partial); break;
             case 4: {
-                int E = pow_chain_len(n, 4);
+                const FrPlan p = plan_h_coeffs(n);
                 // (the table region holds the window table: valid field elements, which is all the kernel needs)
-                HALO_LAUNCH(ctx, "k_h_coeffs", k_h_coeffs, dim3(wave_blocks(n, E)), dim3(256), 0, ctx->d_tmp_c + 8 * 1024 + 1024, (uint32_t)n, E, 0, a);
+                HALO_LAUNCH(ctx, "k_h_coeffs", k_h_coeffs, dim3(p.blocks), dim3(256), 0, ctx->d_tmp_c + 8 * 1024 + 1024, (uint32_t)n, p.E, 0, a);
                 break;
             }
             case 5: HALO_LAUNCH(ctx, "k_fold_scalars", k_fold_scalars, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, b, c, (uint32_t)m, to_nform(z), to_nform(z64)); break;
@@ -1061,9 +1028,9 @@ int h_coeffs_batch_dev(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg
     if (m == 0) return HALO_OK;
     if (m > 65535) { set_error("h_coeffs_batch: at most 65535 members per launch"); return HALO_E_ARG; }
     size_t n = (size_t)1 << lg_n;
-    int E = pow_chain_len(n, 4);
+    const FrPlan p = plan_h_coeffs(n);
     HALO_LAUNCH(ctx, "k_h_tables", k_h_tables, dim3((unsigned)m), dim3(256), 0, d_xis, (int)lg_n, 0, d_tabs);
-    HALO_LAUNCH(ctx, "k_h_coeffs_batch", k_h_coeffs_batch, dim3(wave_blocks(n, E), (unsigned)m), dim3(256), 0, d_tabs, (uint32_t)n, E, d_out,
+    HALO_LAUNCH(ctx, "k_h_coeffs_batch", k_h_coeffs_batch, dim3(p.blocks, (unsigned)m), dim3(256), 0, d_tabs, (uint32_t)n, p.E, d_out,
                 (uint64_t)out_stride);
     HALO_HIP(hipGetLastError());
     return HALO_OK;
@@ -1081,7 +1048,7 @@ int h_accumulate_group(halo_ctx *ctx, const HAccMember *mem, size_t G, size_t lg
     if (G == 0) return HALO_OK;
     if (G > 65535 || cap == 0) { set_error("h_accumulate: 1..65535 members, at least one table"); return HALO_E_ARG; }
     const size_t n = (size_t)1 << lg_n, head = G * HACC_REC_WORDS, tw = (lg_n + 2) * 4;
-    const int E = pow_chain_len(n, 4);
+    const FrPlan p = plan_h_coeffs(n);
     uint64_t *d_tabs = d_stage + head + cap * tw;
     std::vector<size_t> done(G, 0);
     for (bool first_pass = true;; first_pass = false) {
@@ -1108,7 +1075,7 @@ int h_accumulate_group(halo_ctx *ctx, const HAccMember *mem, size_t G, size_t lg
         }
         HALO_HIP(hipMemcpyAsync(d_stage, h_stage, (head + T * tw) * 8, hipMemcpyHostToDevice, ctx->stream));
         if (T) HALO_LAUNCH(ctx, "k_h_tables", k_h_tables, dim3((unsigned)T), dim3(256), 0, d_stage + head, (int)lg_n, 1, d_tabs);
-        HALO_LAUNCH(ctx, "k_h_accumulate_batch", k_h_accumulate_batch, dim3(wave_blocks(n, E), (unsigned)G), dim3(256), 0, d_tabs, d_stage, (uint32_t)n, E,
+        HALO_LAUNCH(ctx, "k_h_accumulate_batch", k_h_accumulate_batch, dim3(p.blocks, (unsigned)G), dim3(256), 0, d_tabs, d_stage, (uint32_t)n, p.E,
                     d_out, (uint64_t)out_stride);
         HALO_HIP(hipGetLastError());
         if (!more) return HALO_OK;
@@ -1227,9 +1194,10 @@ int pbar_stream_dev(halo_ctx *ctx, uint64_t state0, size_t deg, const host::Fr &
 // One window table per member serves both of its uses: powers of z over n (window part) and p(z) over n coefficients (the
 // zpow entries behind it); fr_powers / fr_poly_eval build the same entries.
 int open_batch_table(const host::Fr &z, size_t n, uint64_t *h_tab, OpenConst *k) {
-    const int nwin = (bits_for(n) + 3) / 4;
+    const FrPlan p = plan_poly_eval_batch(n);  // (open_batch_eval's: the table carries its E multipliers)
+    const int nwin = p.nwin;
     host::Fr z64;
-    if (fill_window_table(z, nwin, h_tab, &z64, pow_chain_len(n, POLY_EVAL_E)) < 0) { set_error("window table: too many entries"); return HALO_E_ARG; }
+    if (fill_window_table(z, nwin, h_tab, &z64, p.E) < 0) { set_error("window table: too many entries"); return HALO_E_ARG; }
     FsArg a = to_nform(z64);
     FeArg b = to_arg(z);
     for (int i = 0; i < 9; ++i) k->z64_n[i] = a.v[i];
@@ -1247,9 +1215,11 @@ void open_const_alpha(OpenConst *k, const host::Fr &alpha) {
     for (int i = 0; i < 9; ++i) k->alpha_n[i] = a.v[i];
 }
 int open_batch_eval(halo_ctx *ctx, int G, const uint64_t *d_coeffs, size_t ms, size_t n, const uint64_t *d_tabs, uint64_t *d_parts, uint64_t *d_outs) {
-    const int nwin = (bits_for(n) + 3) / 4, E = pow_chain_len(n, POLY_EVAL_E);
-    unsigned nb = wave_blocks(n, E);
-    if (nb > OPEN_PART_WORDS / 4) { set_error("open_batch: polynomial too long for the batched evaluation"); return HALO_E_ARG; }
+    // at most OPEN_PART_WORDS / 4 partial records per member: the waves of a longer polynomial stride over the rest (the sums are
+    // exact: any grid gives the same field element)
+    const FrPlan p = plan_poly_eval_batch(n);
+    const int nwin = p.nwin, E = p.E;
+    const unsigned nb = p.blocks;
     HALO_LAUNCH(ctx, "k_poly_eval_partial_batch", k_poly_eval_partial_batch, dim3(nb, (unsigned)G), dim3(256), 0, d_coeffs, (uint64_t)ms, (uint32_t)n,
                 d_tabs, nwin, E, d_parts);
     HALO_LAUNCH(ctx, "k_sum_partials_batch", k_sum_partials_batch, dim3(1, (unsigned)G), dim3(256), 0, d_parts, nb, 1u, 0, d_outs);
@@ -1257,8 +1227,8 @@ int open_batch_eval(halo_ctx *ctx, int G, const uint64_t *d_coeffs, size_t ms, s
     return HALO_OK;
 }
 int open_batch_powers(halo_ctx *ctx, int G, const uint64_t *d_tabs, const uint64_t *d_consts, size_t n, uint64_t *d_z, size_t ms) {
-    const int nwin = (bits_for(n) + 3) / 4, E = pow_chain_len(n, 8);
-    HALO_LAUNCH(ctx, "k_powers_batch", k_powers_batch, dim3(wave_blocks(n, E), (unsigned)G), dim3(256), 0, d_tabs, d_consts, nwin, E, (uint32_t)n, d_z,
+    const FrPlan p = plan_powers(n);
+    HALO_LAUNCH(ctx, "k_powers_batch", k_powers_batch, dim3(p.blocks, (unsigned)G), dim3(256), 0, d_tabs, d_consts, p.nwin, p.E, (uint32_t)n, d_z,
                 (uint64_t)ms);
     HALO_HIP(hipGetLastError());
     return HALO_OK;
@@ -1287,7 +1257,7 @@ int open_batch_expand(halo_ctx *ctx, int G, const uint64_t *d_c, const uint64_t 
     return HALO_OK;
 }
 int open_batch_dots(halo_ctx *ctx, int G, const uint64_t *d_c, const uint64_t *d_z, size_t ms, size_t m, uint64_t *d_parts, uint64_t *d_outs) {
-    unsigned nb = dot_blocks(m);
+    unsigned nb = plan_dot(m).blocks;
     if (nb > OPEN_PART_WORDS / 8) nb = OPEN_PART_WORDS / 8;  // (the sums are exact: any grid gives the same field elements)
     HALO_LAUNCH(ctx, "k_dot2_partial_batch", k_dot2_partial_batch, dim3(nb, (unsigned)G), dim3(256), 0, d_c, d_z, (uint64_t)ms, (uint32_t)m, d_parts);
     HALO_LAUNCH(ctx, "k_sum_partials_batch", k_sum_partials_batch, dim3(1, (unsigned)G), dim3(256), 0, d_parts, nb, 2u, 1, d_outs + 4);

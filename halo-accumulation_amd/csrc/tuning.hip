@@ -56,6 +56,12 @@ Tuning read_env() {
         t.pow_e = 0;
     }
     t.dot_blocks = env_int("HALO_DOT_BLOCKS", 0);
+    if (t.dot_blocks < 0 || t.dot_blocks > FR_GRID_CAP) {
+        // k_dot2_partial writes a record per block below the result slot at 8 * FR_GRID_CAP words: a larger grid would write over it
+        const int clamped = t.dot_blocks < 0 ? 1 : FR_GRID_CAP;
+        fprintf(stderr, "[halo] HALO_DOT_BLOCKS=%d clamped to %d: the block cap must be in [1, %d]\n", t.dot_blocks, clamped, FR_GRID_CAP);
+        t.dot_blocks = clamped;
+    }
     t.smsm_kmax = env_int("HALO_SMSM_KMAX", 0);
     t.late_kmax = env_int("HALO_LATE_KMAX", 0);
     t.piece_alternate = !env_off("HALO_PIECE_ALTERNATE");

@@ -10,6 +10,10 @@
 
 namespace halo {
 
+// most blocks of k_poly_eval_partial and k_dot2_partial (fr_plan.hpp): their partial records end below the result slot at 8 * 1024
+// words; the range of HALO_DOT_BLOCKS and of the hooks "dot_blocks" / "poly_blocks"
+constexpr int FR_GRID_CAP = 1024;
+
 struct Tuning {
     // ---- operator-facing
     bool trace = false;            // HALO_TRACE=1          log allocations (address ranges), graph captures and replays to stderr
@@ -28,7 +32,7 @@ struct Tuning {
     bool ipa_c_hint = true;        // HALO_IPA_C_HINT=0     no 11-bit windows for the half-zero scalars of the 2^16-point rounds
     bool u_from_last_round = true; // HALO_U_FROM_LAST_ROUND=0  U from one more MSM instead of the last round's sums
     int pow_e = 0;                 // HALO_POW_E=4..64      chain length of k_powers / k_h_coeffs (power of two)
-    int dot_blocks = 0;            // HALO_DOT_BLOCKS       block cap of k_dot2_partial (default 512)
+    int dot_blocks = 0;            // HALO_DOT_BLOCKS=1..1024  block cap of k_dot2_partial (default 512; clamped: its partial records end at 8 * 1024 words)
     int smsm_kmax = 0;             // HALO_SMSM_KMAX        task length of the small pipeline
     int late_kmax = 0;             // HALO_LATE_KMAX        ... of MSMs of <= 2^14 points (default 8)
     bool piece_alternate = true;   // HALO_PIECE_ALTERNATE=0  pieces of a large synchronous MSM one after the other on one stream
@@ -57,6 +61,10 @@ struct DevHooks {
     int verifier_min = 0;      // "verifier_batch_min" relations from which halo_acc_verifier_batch launches (>= 1; 0: the measured default)
     long slide_min = 0;        // "table_slide_min"    keys from this many points take the c = 20 table plans and the all-shifts table (>= 4096; 0: 2^20)
     long decode_min = 0;       // "decode_batch_min"   finite points from which halo_*_decode_batch decompresses on the device (>= 1; 0: the measured default)
+    // the launch plan of the Fr kernels (fr_plan.hpp), each before the environment's value and the measured default; 0: not set
+    int pow_e = 0;             // "pow_e"        chain length of k_powers / k_poly_eval_partial / k_h_coeffs / k_h_accumulate_batch (a power of two in [4, 64])
+    int dot_blocks = 0;        // "dot_blocks"   block cap of k_dot2_partial (1..1024)
+    int poly_blocks = 0;       // "poly_blocks"  block cap of k_poly_eval_partial (1..1024; the batched open: at most OPEN_PART_WORDS / 4 of them)
 };
 DevHooks &dev_hooks();
 

@@ -28,10 +28,31 @@ extern "C" {
  * from which halo_acc_verifier_batch runs its sums on the device, >= 1; 0: the measured default), "table_slide_min" (keys from this many points, >= 4096, take the c = 20 table plans and
  * the all-shifts table with its sliding-window recode; 0: 2^20), "decode_batch_min" (finite points
  * from which halo_*_decode_batch decompresses on the device, >= 1; 0: the measured default; "batch_stage_fail" refuses its staging
- * too: the host pool), "reset" (all off). */
+ * too: the host pool), "reset" (all off).
+ * The launch plan of the Fr kernels (csrc/fr_plan.hpp), each taken before the environment's value and the measured default, every
+ * plan giving the same field elements: "pow_e" (elements per lane of k_powers, k_poly_eval_partial, k_h_coeffs and
+ * k_h_accumulate_batch and of their batch forms: a power of two in [4, 64], the rule of HALO_POW_E), "dot_blocks" (block cap of
+ * k_dot2_partial, 1..1024: its partial records end below the result slot at 8 * 1024 words; the batched open clamps to its own
+ * room), "poly_blocks" (block cap of k_poly_eval_partial, 1..1024; the batched open takes at most 256 of them: with fewer blocks
+ * than waves of 64 E coefficients the waves stride over the polynomial).  A value outside its range is HALO_E_ARG with the rule in
+ * halo_last_error and leaves the hook as it was; "reset" clears them. */
 int halo_dev_hook(const char *name, long value);
+/* Host only: the plan one Fr launcher computes at size n NOW (hooks, environment, defaults), from the very functions the launcher
+ * calls: out = { E, nwin, blocks, trips }.  which = 0 halo_powers (k_powers; E elements per lane, nwin 4-bit windows of the
+ * exponent, trips 1), 1 halo_poly_eval (k_poly_eval_partial; trips = passes of a wave through its grid-stride loop), 2
+ * halo_scalar_dot and the rounds' dot products over n elements per vector (k_dot2_partial; E = 2 elements per lane and trip, nwin 0,
+ * trips = the most passes of a lane), 3 halo_h_coeffs / halo_h_accumulate and their batch forms over n = 2^lg_n coefficients
+ * (nwin = the 256-entry tables low, mid, high with more than one entry, trips 1), 4 the p(z) of halo_pcdl_open_batch
+ * (k_poly_eval_partial_batch and its window table: as 1, but at most 256 blocks per member, the room of its partial records; 1
+ * is the plan of halo_poly_eval and of a single open, up to 1024 blocks).  ctx may be NULL: no plan depends on the context.
+ * HALO_E_ARG: another `which`, a null `out`. */
+int halo_dev_fr_plan(halo_ctx *ctx, int which, size_t n, long out[4]);
+/* The two dot products of an IPA round on their own (k_dot2_partial over both pairs of vectors, one launch): c, z = 2 m x 4
+ * Montgomery words, out = <c[m..2m), z[0..m)> | <c[0..m), z[m..2m)>.  Any m with 2 m <= the context's size (64 at least) -- the
+ * rounds themselves only ever reach powers of two; m = 0 gives zeros. */
+int halo_dev_dot2_cross(halo_ctx *ctx, const uint64_t *c, const uint64_t *z, size_t m, uint64_t out[8]);
 /* What the library read from the environment at its first use (csrc/tuning.hip), by field: "host_split_set", "host_pieces", "host_split0".."host_split3",
- * "fold_table_after", "graph_cache", "pow_e", "spin_us", "graphs", "memory_budget" (MiB, -1 unset), "trace", "tagged"; -1 for an
+ * "fold_table_after", "graph_cache", "pow_e", "dot_blocks", "spin_us", "graphs", "memory_budget" (MiB, -1 unset), "trace", "tagged"; -1 for an
  * unknown name.  Host only. */
 long halo_dev_tuning(const char *name);
 
