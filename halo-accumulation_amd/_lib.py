@@ -114,6 +114,10 @@ _SIGS = {
     "halo_random_instance": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, u64p]),
     "halo_pcdl_open_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, u64p, C.c_size_t, u64p, u64p, u64p, u64p, C.POINTER(C.c_int)]),
     "halo_random_instance_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.c_size_t, u64p]),
+    "halo_pcdl_commit_batch": (C.c_int, [C.c_void_p, C.c_size_t, u64p, C.c_size_t, u64p, u64p]),
+    "halo_pcdl_commit_dev_batch": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, u64p, u64p, C.POINTER(C.c_int)]),
+    "halo_instance_from_poly": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), u64p, C.c_size_t, C.c_size_t, u64p, u64p, u64p]),
+    "halo_instance_from_poly_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, u64p, C.c_size_t, u64p, u64p, u64p, C.POINTER(C.c_int)]),
     "halo_proof_encoded_size": (C.c_size_t, [C.c_size_t, C.c_int]),
     "halo_instance_encoded_size": (C.c_size_t, [C.c_size_t, C.c_int]),
     "halo_accumulator_encoded_size": (C.c_size_t, [C.c_size_t]),

@@ -5,7 +5,7 @@ import numpy as np
 
 from halo_accumulation_amd import _lib
 from halo_accumulation_amd._lib import check, ptr
-from halo_accumulation_amd.pcdl import _check_batch, lg_of
+from halo_accumulation_amd.pcdl import _a, _check_batch, _pack_polys, _pack_rows, lg_of
 
 
 def _cat(qs):
@@ -33,6 +33,38 @@ def random_instance_batch(ctx, rng, d, m):
     out = np.zeros((max(m, 1), ctx.lib.halo_instance_words(lg_of(d))), dtype=np.uint64)
     check(ctx.lib.halo_random_instance_batch(ctx.h, C.byref(st), d, m, ptr(out)))
     rng[0] = st.value
+    return [out[i].copy() for i in range(m)]
+
+
+def instance_from_poly(ctx, rng, p, d, z, w=None):
+    """benches/acc.rs:15-29 for the caller's polynomial (halo_instance_from_poly): commit, evaluate at z, open, pack -> Instance"""
+    p = _a(p).reshape(-1, 4)
+    st = C.c_uint64(rng[0])
+    inst = np.zeros(ctx.lib.halo_instance_words(max(lg_of(d), 0)), dtype=np.uint64)
+    check(ctx.lib.halo_instance_from_poly(ctx.h, C.byref(st), ptr(p), p.shape[0], d, ptr(_a(z)), ptr(_a(w)), ptr(inst)))
+    rng[0] = st.value
+    return inst
+
+
+def instance_from_poly_batch(ctx, rng, ps, d, zs, ws=None):
+    """... of m polynomials of degree bound d at once (halo_instance_from_poly_batch) -> the Instances m instance_from_poly calls
+    return in turn, rng[0] updated as they would update it.  A failing member raises as pcdl.open_batch does, with the status
+    list as the exception's second argument."""
+    m = len(ps)
+    zs = _pack_rows(zs, m, 4, "instance_from_poly_batch", "zs")
+    if zs is None:
+        raise ValueError("instance_from_poly_batch: zs is required")
+    ws = _pack_rows(ws, m, 4, "instance_from_poly_batch", "ws")
+    coeffs = _pack_polys(ps, d, "commit")
+    st = C.c_uint64(rng[0])
+    out = np.zeros((max(m, 1), ctx.lib.halo_instance_words(max(lg_of(d), 0))), dtype=np.uint64)
+    status = (C.c_int * max(m, 1))()
+    rc = ctx.lib.halo_instance_from_poly_batch(ctx.h, C.byref(st), d, ptr(coeffs), m, ptr(zs), ptr(ws), ptr(out), status)
+    if rc in (_lib.HALO_OK, _lib.HALO_E_ASSERT):
+        rng[0] = st.value
+    if rc == _lib.HALO_E_ASSERT:
+        raise AssertionError(ctx.lib.halo_last_error().decode(), [status[i] for i in range(m)], [out[i].copy() for i in range(m)])
+    check(rc)
     return [out[i].copy() for i in range(m)]
 
 

@@ -202,6 +202,7 @@ long halo_dev_tuning(const char *name) {
     if (!std::strcmp(name, "memory_budget")) return t.memory_budget_set ? (long)(t.memory_budget >> 20) : -1;  // MiB
     if (!std::strcmp(name, "trace")) return t.trace ? 1 : 0;
     if (!std::strcmp(name, "tagged")) return t.tagged ? 1 : 0;
+    if (!std::strcmp(name, "commit_batch_group")) return dev_hooks().commit_group;  // (the hook as it stands: a CPU test sees "reset" clear it)
     return -1;
 }
 
@@ -215,6 +216,7 @@ int halo_dev_hook(const char *name, long value) {
     else if (!std::strcmp(name, "batch_stage_fail")) h.batch_stage_fail = (int)value;
     else if (!std::strcmp(name, "check_batch_group")) h.check_group = (int)value;
     else if (!std::strcmp(name, "open_batch_group")) h.open_group = (int)value;
+    else if (!std::strcmp(name, "commit_batch_group")) h.commit_group = (int)value;
     else if (!std::strcmp(name, "verifier_batch_min")) h.verifier_min = (int)value;
     else if (!std::strcmp(name, "decode_batch_min")) h.decode_min = value;
     else if (!std::strcmp(name, "table_slide_min")) h.slide_min = value > 0 && value < 4096 ? 4096 : value;
@@ -230,7 +232,7 @@ int halo_dev_hook(const char *name, long value) {
         h.poly_blocks = (int)value;
     }
     else if (!std::strcmp(name, "reset")) h = DevHooks();
-    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, verifier_batch_min, decode_batch_min, table_slide_min, pow_e, dot_blocks, poly_blocks, reset)"); return HALO_E_ARG; }
+    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, commit_batch_group, verifier_batch_min, decode_batch_min, table_slide_min, pow_e, dot_blocks, poly_blocks, reset)"); return HALO_E_ARG; }
     return HALO_OK;
 }
 

@@ -625,6 +625,15 @@ int open_batch_dots(halo_ctx *ctx, int G, const uint64_t *d_c, const uint64_t *d
 // s_out[2t + u] = s_in[t] xi^u (t < s_len), then c' = c_l + xi^-1 c_r, z' = z_l + xi z_r over m
 int open_batch_fold(halo_ctx *ctx, int G, uint64_t *d_c, uint64_t *d_z, const uint64_t *d_s_in, uint64_t *d_s_out, size_t ms, size_t m,
                     size_t s_len, const uint64_t *d_consts);
+// ---- ipa.hip: the member-batched padding of halo_pcdl_commit_dev_batch (pcdl_batch.hip).  Entry k of the table: src[k], len[k]
+// Montgomery scalars in device memory (32-byte aligned), copied to d_out + row[k] * ms words and zero-padded to n scalars.  The
+// table travels as a kernel argument; count <= MSM_MAX_BATCH entries, one launch on ctx->stream.
+struct PadMembers {
+    const uint64_t *src[MSM_MAX_BATCH];
+    uint32_t len[MSM_MAX_BATCH];
+    uint32_t row[MSM_MAX_BATCH];
+};
+int pad_members_batch(halo_ctx *ctx, const PadMembers &t, int count, size_t n, uint64_t *d_out, size_t ms);
 
 // ---- decompress.hip: point decompression of the wire format on the device (wire.hip halo_*_decode_batch)
 constexpr size_t DECOMP_IN_WORDS = 6;    // a point's 33 wire bytes, zero-padded to 48

@@ -788,6 +788,17 @@ __global__ __launch_bounds__(256) void k_nofold_s_update_batch(const uint64_t *_
     if (i & 1) v = fe_mul<FrCfg>(v, fe_from_m8(open_const(consts).xi_m));
     fe_store(s_out + o + 4 * (size_t)i, v);
 }
+// The short members of one commit group zero-padded to n scalars in ONE launch (halo_pcdl_commit_dev_batch): blockIdx.y = entry
+// of the table that arrives with the launch -- source, length and row of the group's staging -- and a lane moves 16 bytes, half
+// a scalar: the source's below 2 len, zero from there to 2 n.  The sources are only read.
+__global__ __launch_bounds__(256) void k_pad_members_batch(PadMembers t, uint32_t n, uint64_t *__restrict__ out, uint64_t ms) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 2 * n) return;
+    const uint4 *src = reinterpret_cast<const uint4 *>(t.src[blockIdx.y]);
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (i < 2 * t.len[blockIdx.y]) v = src[i];
+    reinterpret_cast<uint4 *>(out + ms * t.row[blockIdx.y])[i] = v;
+}
 
 // ================================================================== host launchers
 // form (development hook, halo_dev_fold_points): 0 = the size decides; 1 / 2 = one / two outputs per lane whatever m is
@@ -1264,6 +1275,16 @@ int open_batch_dots(halo_ctx *ctx, int G, const uint64_t *d_c, const uint64_t *d
     HALO_HIP(hipGetLastError());
     return HALO_OK;
 }
+int pad_members_batch(halo_ctx *ctx, const PadMembers &t, int count, size_t n, uint64_t *d_out, size_t ms) {
+    if (count < 1 || count > MSM_MAX_BATCH || n == 0 || n > ((size_t)1 << 30)) { set_error("pad_members: bad shape"); return HALO_E_ARG; }
+    for (int k = 0; k < count; ++k)
+        if (t.len[k] > n || t.row[k] >= (uint32_t)MSM_MAX_BATCH || (t.len[k] && !t.src[k])) { set_error("pad_members: bad member"); return HALO_E_ARG; }
+    HALO_LAUNCH(ctx, "k_pad_members_batch", k_pad_members_batch, dim3((unsigned)((2 * n + 255) / 256), (unsigned)count), dim3(256), 0, t, (uint32_t)n,
+                d_out, (uint64_t)ms);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
 int open_batch_fold(halo_ctx *ctx, int G, uint64_t *d_c, uint64_t *d_z, const uint64_t *d_s_in, uint64_t *d_s_out, size_t ms, size_t m, size_t s_len,
                     const uint64_t *d_consts) {
     HALO_LAUNCH(ctx, "k_nofold_s_update_batch", k_nofold_s_update_batch, dim3((unsigned)((2 * s_len + 255) / 256), (unsigned)G), dim3(256), 0, d_s_in,

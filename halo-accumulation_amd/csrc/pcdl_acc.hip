@@ -56,7 +56,7 @@ static int commit_short_host(halo_ctx *ctx, const uint64_t *coeffs, size_t len, 
 }
 
 // pcdl.rs:99-110
-static int pcdl_commit_host(halo_ctx *ctx, const uint64_t *coeffs, size_t len, size_t d, const Fr *w, Point *out) {
+int pcdl_commit_host(halo_ctx *ctx, const uint64_t *coeffs, size_t len, size_t d, const Fr *w, Point *out) {
     size_t n = d + 1;
     if (!is_pow2(n)) return fail_assert("commit: d + 1 is not a power of two");
     size_t deg = host_poly_degree(coeffs, len);
@@ -73,14 +73,17 @@ static int pcdl_commit_host(halo_ctx *ctx, const uint64_t *coeffs, size_t len, s
     return HALO_OK;
 }
 
-// pcdl.rs:120-242 on a device-resident polynomial (d_poly: n coefficients, zero padded, clobbered)
+// pcdl.rs:120-242 on a device-resident polynomial (d_poly: n coefficients, zero padded, clobbered); v_known: p(z) where the
+// caller has it already (fr_poly_eval over the same buffer)
 static int pcdl_open_dev(halo_ctx *ctx, host::Rng *rng, size_t deg, const Point &C, size_t d, const Fr &z, const Fr *w,
-                         uint64_t *proof) {
+                         uint64_t *proof, const Fr *v_known = nullptr) {
     size_t n = d + 1, lg_n = ilog2(n);
     std::memset(proof, 0, 8 * proof_words(lg_n));
     proof[1] = lg_n;
     Fr v;
-    int rc = fr_poly_eval(ctx, ctx->d_poly, deg + 1, z, &v);  // :135
+    int rc = HALO_OK;
+    if (v_known) v = *v_known;
+    else rc = fr_poly_eval(ctx, ctx->d_poly, deg + 1, z, &v);  // :135
     if (rc) return rc;
     Point C_prime = C;
     if (w) {
@@ -474,6 +477,34 @@ int random_instance_one(halo_ctx *ctx, uint64_t *rng_state, size_t d, uint64_t *
     return rc;
 }
 
+// the body of halo_instance_from_poly after its argument checks (deg = host_poly_degree(coeffs, len) <= d): benches/acc.rs:15-29 for
+// the caller's polynomial from ONE upload -- the commit, p(z) and the open all read the padded copy in ctx->d_poly
+int instance_from_poly_one(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *coeffs, size_t len, size_t deg, size_t d, const uint64_t z[4],
+                           const uint64_t *w, uint64_t *inst) {
+    const size_t n = d + 1, lg = ilog2(n), used = deg + 1 < len ? deg + 1 : len;
+    int rc = ensure_poly_buffers(ctx);
+    if (rc) return rc;
+    HALO_HIP(hipMemsetAsync(ctx->d_poly, 0, n * 32, ctx->stream));
+    rc = upload_words(ctx, ctx->d_poly, coeffs, used * 4);
+    if (rc) return rc;
+    const Fr zf = Fr::load(z), wf = w ? Fr::load(w) : Fr::zero();
+    Point C;  // pcdl::commit, with pcdl_commit_host's shortcut for a short polynomial
+    if (used == 0) C = w ? public_s_table().mul(wf) : Point::infinity();
+    else if (used <= 16) rc = commit_short_host(ctx, coeffs, used, w ? &wf : nullptr, &C);
+    else rc = pedersen_commit_dev(ctx, w ? &wf : nullptr, ctx->d_poly, n, &C);
+    if (rc) return rc;
+    C = C.normalized();
+    Fr v;
+    rc = fr_poly_eval(ctx, ctx->d_poly, deg + 1, zf, &v);  // p.evaluate(&z)
+    if (rc) return rc;
+    std::memset(inst, 0, 8 * instance_words(lg));
+    store_instance_head(inst, C, d, zf, v);
+    host::Rng rng{rng_state ? *rng_state : 0};
+    rc = pcdl_open_dev(ctx, &rng, deg, C, d, zf, w ? &wf : nullptr, inst + 21, &v);
+    if (rng_state) *rng_state = rng.state;
+    return rc;
+}
+
 }  // namespace halo
 
 using namespace halo;
@@ -530,6 +561,21 @@ int halo_pcdl_open(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *coeffs, s
     if (deg > d) return fail_assert("open: p.degree() > d");                   // pcdl.rs:131
     if (n > ctx->n) return fail_assert("open: d > D");                         // pcdl.rs:132
     return pcdl_open_host(ctx, rng_state, coeffs, deg, C, d, z, w, proof_out);
+}
+
+// benches/acc.rs:15-29 for a polynomial the caller holds: commit, evaluate, open and pack from one upload (instance_from_poly_one).
+// The argument checks are those a caller of halo_pcdl_commit, halo_poly_eval and halo_pcdl_open meets, in that order: the commit's
+// come first and cover the other two's.
+int halo_instance_from_poly(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *coeffs, size_t len, size_t d, const uint64_t z[4], const uint64_t *w,
+                            uint64_t *instance_out) {
+    HALO_CTX(ctx);
+    if (!instance_out || !z || (len && !coeffs)) { set_error("instance_from_poly: null pointer"); return HALO_E_ARG; }
+    size_t n = d + 1;
+    if (!is_pow2(n)) return fail_assert("commit: d + 1 is not a power of two");
+    size_t deg = host_poly_degree(coeffs, len);
+    if (deg > d) return fail_assert("commit: p.degree() > d");
+    if (n > ctx->n) return fail_assert("commit: d > D");
+    return instance_from_poly_one(ctx, rng_state, coeffs, len, deg, d, z, w, instance_out);
 }
 
 // pcdl::open for a polynomial that already lives in device memory (the coefficients are copied, not clobbered)

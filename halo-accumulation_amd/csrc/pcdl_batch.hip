@@ -49,6 +49,47 @@ static int group_size(const halo_ctx *ctx, size_t n, int forced, int max, int ar
     return g;
 }
 
+// The rotation the check and commit batches share: A members in groups of G over S slots.  enqueue(j, first, cnt) puts the batched
+// MSM of members first .. first + cnt in flight on slots[j]; when the slot comes round again, and at the end, the group is
+// collected (msm_finish_batch) and done(first, cnt, pts) takes its points.  A failure leaves nothing of the call in flight.
+template <class Enqueue, class Done>
+static int rotate_groups(halo_ctx *ctx, const int *slots, int S, size_t A, size_t G, Enqueue enqueue, Done done) {
+    const size_t ng = (A + G - 1) / G;
+    auto cnt_of = [&](size_t g) { return A - g * G < G ? A - g * G : G; };
+    std::vector<long> flight(S, -1);  // the group in flight on slots[j]
+    auto collect = [&](size_t j) -> int {
+        const long g = flight[j];
+        if (g < 0) return HALO_OK;
+        flight[j] = -1;
+        Point pts[MSM_MAX_BATCH];
+        int rc = msm_finish_batch(ctx, slots[j], pts, (int)cnt_of((size_t)g));
+        if (!rc) done((size_t)g * G, cnt_of((size_t)g), pts);
+        return rc;
+    };
+    auto abandon = [&]() {  // (a device error: nothing of this call stays in flight)
+        std::string err = halo_last_error();
+        for (int j = 0; j < S; ++j)
+            if (flight[j] >= 0) {
+                Point pts[MSM_MAX_BATCH];
+                (void)msm_finish_batch(ctx, slots[j], pts, (int)cnt_of((size_t)flight[j]));
+                flight[j] = -1;
+            }
+        set_error(err);
+    };
+    for (size_t g = 0; g < ng; ++g) {
+        const size_t j = g % (size_t)S;
+        int rc = collect(j);
+        if (!rc) rc = enqueue(j, g * G, cnt_of(g));
+        if (rc) { abandon(); return rc; }
+        flight[j] = (long)g;
+    }
+    for (size_t g = ng > (size_t)S ? ng - (size_t)S : 0; g < ng; ++g) {
+        int rc = collect(g % (size_t)S);
+        if (rc) { abandon(); return rc; }
+    }
+    return HALO_OK;
+}
+
 // ------------------------------------------------------------------ pcdl::check of m instances at once
 // The succinct half of every member as halo_pcdl_succinct_check_batch runs it (the relations on the device from kBatchVerifyMin
 // members on, on the host pool below); then the accepted members in groups of up to MSM_MAX_BATCH: their h coefficients expanded
@@ -106,52 +147,27 @@ static int pcdl_check_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, si
         ng = (A + G - 1) / G;
         auto coeffs_of = [&](size_t j) { return scratch ? ctx->d_tmp_a : ctx->d_check_stage + j * G * n * 4; };
         auto tables_of = [&](size_t j) { return scratch ? ctx->d_tmp_c + 8 * 1024 + 1024 : ctx->d_check_stage + (size_t)S * G * n * 4 + j * G * H_TABLES_WORDS; };
-        std::vector<long> flight(S, -1);  // the group in flight on slots[j]
-        auto collect = [&](size_t j) -> int {
-            long g = flight[j];
-            if (g < 0) return HALO_OK;
-            flight[j] = -1;
-            size_t first = (size_t)g * G, cnt = A - first < G ? A - first : G;
-            Point pts[MSM_MAX_BATCH];
-            int rc2 = msm_finish_batch(ctx, slots[j], pts, (int)cnt);
-            if (rc2) return rc2;
-            for (size_t b = 0; b < cnt; ++b) {
-                BatchCheck &r = res[ok[first + b]];
-                if (r.st.U != pts[b]) { r.rc = HALO_E_REJECT; r.err = "U != CM.Commit(ck, h_vec)"; }  // :339
-            }
-            return HALO_OK;
-        };
-        auto abandon = [&]() {  // (a device error: nothing of this call stays in flight)
-            std::string err = halo_last_error();
-            for (int j = 0; j < S; ++j)
-                if (flight[j] >= 0) {
-                    Point pts[MSM_MAX_BATCH];
-                    size_t first = (size_t)flight[j] * G;
-                    (void)msm_finish_batch(ctx, slots[j], pts, (int)(A - first < G ? A - first : G));
-                    flight[j] = -1;
+        rc = rotate_groups(
+            ctx, slots, S, A, G,
+            [&](size_t j, size_t first, size_t cnt) -> int {
+                int rc2;
+                {
+                    StreamGuard on_slot(ctx, ctx->streams[slots[j]]);
+                    rc2 = h_coeffs_batch_dev(ctx, ctx->d_verify + first * xw, cnt, lg, tables_of(j), coeffs_of(j), n * 4);  // h.get_poly().coeffs
                 }
-            set_error(err);
-        };
-        for (size_t g = 0; g < ng; ++g) {
-            const size_t j = g % (size_t)S, first = g * G, cnt = A - first < G ? A - first : G;
-            rc = collect(j);
-            if (!rc) {
-                StreamGuard on_slot(ctx, ctx->streams[slots[j]]);
-                rc = h_coeffs_batch_dev(ctx, ctx->d_verify + first * xw, cnt, lg, tables_of(j), coeffs_of(j), n * 4);  // h.get_poly().coeffs
-            }
-            if (!rc) {
+                if (rc2) return rc2;
                 MsmBatch mb;
                 mb.count = (int)cnt;
                 for (size_t b = 0; b < cnt; ++b) mb.scalars[b] = coeffs_of(j) + b * n * 4;
-                rc = msm_enqueue_batch(ctx, slots[j], ctx->d_bases, mb, true, n);  // :338, asynchronous
-            }
-            if (rc) { abandon(); return rc; }
-            flight[j] = (long)g;
-        }
-        for (size_t g = ng > (size_t)S ? ng - (size_t)S : 0; g < ng; ++g) {
-            rc = collect(g % (size_t)S);
-            if (rc) { abandon(); return rc; }
-        }
+                return msm_enqueue_batch(ctx, slots[j], ctx->d_bases, mb, true, n);  // :338, asynchronous
+            },
+            [&](size_t first, size_t cnt, const Point *pts) {
+                for (size_t b = 0; b < cnt; ++b) {
+                    BatchCheck &r = res[ok[first + b]];
+                    if (r.st.U != pts[b]) { r.rc = HALO_E_REJECT; r.err = "U != CM.Commit(ck, h_vec)"; }  // :339
+                }
+            });
+        if (rc) return rc;
     }
     return report_members("instance", m, [&](size_t i) { return res[i].rc; }, [&](size_t i) { return res[i].err; }, status, [](size_t) {});
 }
@@ -164,6 +180,102 @@ static int check_batch_entry(halo_ctx *ctx, size_t d, const uint64_t *blobs, siz
         if ((size_t)(blobs + i * stride)[12] != d || (blobs + i * stride)[22] != lg) return fail_reject("d_i != d");
     if (m == 0) return HALO_OK;
     return pcdl_check_batch_host(ctx, d, blobs, stride, m, status);
+}
+
+// ------------------------------------------------------------------ pcdl::commit of m polynomials at once
+// (halo_pcdl_commit_batch: host polynomials, m x n scalars zero-padded; halo_pcdl_commit_dev_batch: device pointers and lengths.)
+// Groups of up to MSM_MAX_BATCH members, each ONE batched MSM launch sequence over the key, rotate over the slots idle on entry
+// exactly as the check batch's do.  A group's scalars reach its slot's region of the staging on the slot's own stream: the host
+// form copies the group's padded rows in one hipMemcpyAsync (the rows are contiguous in the caller's array), so the copy of
+// group g + 1 runs under the kernels of group g on another slot; the device form passes a full-length member to the launch in
+// place and pads the shorter ones with one k_pad_members_batch launch.  When a slot comes round again its group is collected and
+// the w_i S terms are added on the host.  Without the staging the members run one at a time through the single calls' bodies.
+// Members per launch: the rule of check_group_size ("commit_batch_group" forces one) -- single members where the fixed-base
+// table takes the MSM, there the gain is the copy hidden under the previous member's kernels.  ONE host polynomial at such a size
+// goes through the single call's body instead: it copies in stretches under its own kernels (msm_host_run), which one copy in
+// front of one launch sequence cannot match (1.70 against 1.81 ms at 2^20, the runs' ranges apart; from two members on the pipeline wins,
+// 3.32 against 2.83 ms).  Measured: DESIGN.md 4.9.
+static bool commit_table_single(const halo_ctx *ctx, size_t n) {  // (a forced group size: the pipeline, whatever the size)
+    return dev_hooks().commit_group <= 0 && n >= ((size_t)1 << 20) && ctx->n >= ((size_t)1 << 20) && ctx->table_mode != 0;
+}
+static int commit_group_size(const halo_ctx *ctx, size_t n) {
+    if (commit_table_single(ctx, n)) return 1;
+    return group_size(ctx, n, dev_hooks().commit_group, MSM_MAX_BATCH, 1);  // (development library: the sweep of tools/time_commit_batch.py)
+}
+// live: the members that run, in order (all of them in the host form); coeffs: the host form's array, else d_coeffs / lens.
+// Without the optional staging a group is ONE member and its row the slot's own scalar buffer (slot_scalars: what halo_msm_begin
+// copies into), so the members still run on the idle slots only, one at a time per slot, with the same points.
+static int commit_batch_run(halo_ctx *ctx, size_t d, const uint64_t *coeffs, const void *const *d_coeffs, const size_t *lens,
+                            const std::vector<size_t> &live, const uint64_t *ws, uint64_t *out, const int *slots, int S) {
+    const size_t n = d + 1, A = live.size();
+    if (A == 0) return HALO_OK;
+    auto finish = [&](size_t i, const Point &msm) {
+        (ws ? public_s_table().mul(Fr::load(ws + 4 * i)) + msm : msm).store_normalized(out + 12 * i);
+    };
+    // (the single call spreads its copy over slots 0 and 1: both idle, as a caller of halo_pcdl_commit must have them)
+    if (coeffs && A == 1 && commit_table_single(ctx, n) && S >= 2 && slots[0] == 0 && slots[1] == 1) {
+        const size_t i = live[0];
+        const Fr wf = ws ? Fr::load(ws + 4 * i) : Fr::zero();
+        Point r;
+        int rc = pcdl_commit_host(ctx, coeffs + i * n * 4, n, d, ws ? &wf : nullptr, &r);
+        if (!rc) r.store_normalized(out + 12 * i);
+        return rc;
+    }
+    size_t G = (size_t)commit_group_size(ctx, n);
+    if (G > A) G = A;
+    if ((size_t)S > (A + G - 1) / G) S = (int)((A + G - 1) / G);
+    bool pads = coeffs != nullptr;  // does any member need a row?  (device members of full length are read in place)
+    for (size_t a = 0; a < A && !pads; ++a) pads = lens[live[a]] != n;
+    const size_t have = pads ? check_stage(ctx, G * (size_t)S, n * 32) : G * (size_t)S;
+    uint64_t *own[HALO_SLOTS] = {};  // no staging: the slots' own scalar buffers, one member each
+    if (have == 0) {
+        G = 1;
+        if ((size_t)S > A) S = (int)A;
+        for (int j = 0; j < S; ++j)
+            if (!(own[j] = slot_scalars(ctx, slots[j], 1, 0))) return HALO_E_DEVICE;
+    } else if (have < G * (size_t)S) {
+        if (G > have) G = have;
+        if ((size_t)S > have / G) S = (int)(have / G);
+    }
+    auto row_of = [&](size_t j, size_t b) { return have ? ctx->d_check_stage + (j * G + b) * n * 4 : own[j]; };
+    return rotate_groups(
+        ctx, slots, S, A, G,
+        [&](size_t j, size_t first, size_t cnt) -> int {
+            MsmBatch mb;
+            mb.count = (int)cnt;
+            int rc = HALO_OK;
+            {
+                StreamGuard on_slot(ctx, ctx->streams[slots[j]]);
+                if (coeffs) {  // (live = every member: the group's rows are one stretch of the caller's array)
+                    HALO_HIP(hipMemcpyAsync(row_of(j, 0), coeffs + live[first] * n * 4, cnt * n * 32, hipMemcpyHostToDevice, ctx->stream));
+                    for (size_t b = 0; b < cnt; ++b) mb.scalars[b] = row_of(j, b);
+                } else {
+                    PadMembers t{};
+                    int short_members = 0;
+                    for (size_t b = 0; b < cnt; ++b) {
+                        const size_t i = live[first + b];
+                        if (lens[i] == n) { mb.scalars[b] = static_cast<const uint64_t *>(d_coeffs[i]); continue; }  // in place
+                        t.src[short_members] = static_cast<const uint64_t *>(d_coeffs[i]);
+                        t.len[short_members] = (uint32_t)lens[i];
+                        t.row[short_members++] = (uint32_t)b;
+                        mb.scalars[b] = row_of(j, b);
+                    }
+                    if (short_members) rc = pad_members_batch(ctx, t, short_members, n, row_of(j, 0), n * 4);
+                }
+            }
+            return rc ? rc : msm_enqueue_batch(ctx, slots[j], ctx->d_bases, mb, true, n);  // asynchronous
+        },
+        [&](size_t first, size_t cnt, const Point *pts) {
+            for (size_t b = 0; b < cnt; ++b) finish(live[first + b], pts[b]);
+        });
+}
+// the whole-call checks of both commit batches (pcdl_commit_host's asserts, before any work)
+static int commit_batch_checks(halo_ctx *ctx, size_t d, int *slots, int *S) {
+    if (!is_pow2(d + 1)) return fail_assert("commit: d + 1 is not a power of two");
+    if (d + 1 > ctx->n) return fail_assert("commit: d > D");
+    *S = idle_slots(ctx, slots);
+    if (!*S) { set_error("commit_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
+    return HALO_OK;
 }
 
 // ------------------------------------------------------------------ acc::verifier of k accumulators at once
@@ -429,7 +541,7 @@ struct OpenGroups {
     const int *slots;  // the slots idle at entry; S of them are used
     int S;
     size_t n, lg, G, ms;
-    bool gen, hiding, accumulated, u_from_last_round;
+    bool draw, commit, hiding, accumulated, u_from_last_round;  // draw: p from the stream; commit: C = commit(p) rides in step 0's MSM
     OpenStage st;
     struct Flight { long g = -1; size_t first = 0, cnt = 0, step = 0; int msm = 0; bool flip = false; std::vector<size_t> need_u; };
     std::vector<Flight> fl;
@@ -472,7 +584,7 @@ struct OpenGroups {
             StreamGuard on_slot(ctx, stream(j));  // (the launch macro uses ctx->stream)
             HALO_HIP(hipMemcpyAsync(st.d_tabs(j), st.h_tabs(j), OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS) * 8, hipMemcpyHostToDevice, stream(j)));
             int rc = HALO_OK;
-            if (gen) rc = open_batch_rng(ctx, (int)f.cnt, st.d_consts(j), n, st.vec(j, 0), ms);  // p = PallasPoly::rand(d')
+            if (draw) rc = open_batch_rng(ctx, (int)f.cnt, st.d_consts(j), n, st.vec(j, 0), ms);  // p = PallasPoly::rand(d')
             else if (accumulated) {  // p = h.get_poly() (acc.rs:85-94)
                 HAccMember hm[OPEN_MAX_GROUP];
                 for (size_t b = 0; b < f.cnt; ++b) {
@@ -494,9 +606,9 @@ struct OpenGroups {
             if (!rc) rc = download_outs(j);
             if (rc) return rc;
         }
-        MsmBatch mb;  // random_instance's C of every member, then C_bar of every member (:150)
+        MsmBatch mb;  // the C of every member (random_instance, instance_from_poly), then C_bar of every member (:150)
         mb.count = 0;
-        if (gen)
+        if (commit)
             for (size_t b = 0; b < f.cnt; ++b) mb.scalars[mb.count++] = st.vec(j, 0) + b * ms;
         if (hiding)
             for (size_t b = 0; b < f.cnt; ++b) mb.scalars[mb.count++] = st.vec(j, 6) + b * ms;
@@ -548,10 +660,10 @@ struct OpenGroups {
         pool_run(f.cnt, [&](size_t b) {
             OpenJob &jb = jobs[f.first + b];
             jb.v = Fr::load(st.out_of(j, b));
-            if (gen) jb.C = (public_s_table().mul(jb.w) + pts[b]).normalized();
+            if (commit) jb.C = (hiding ? public_s_table().mul(jb.w) + pts[b] : pts[b]).normalized();
             Point C_prime = jb.C;
             if (hiding) {
-                Point C_bar = public_s_table().mul(jb.w_bar) + pts[(gen ? f.cnt : 0) + b];
+                Point C_bar = public_s_table().mul(jb.w_bar) + pts[(commit ? f.cnt : 0) + b];
                 Fr a = rho0_C_z_v_Cbar(jb.C, jb.z, jb.v, C_bar);  // :153
                 Fr w_prime = jb.w_bar * a + jb.w;                  // :159
                 C_prime = jb.C + C_bar.mul(a) - public_s_table().mul(w_prime);  // :162
@@ -680,9 +792,10 @@ struct OpenGroups {
 };
 
 // jobs: the members that do not fail up front, in member order.  *ran = false: the device path does not apply (nothing done)
-// Coefficients of a member: the caller's host array (jb.coeffs), generated on the device (gen), or -- jb.hs set, for every member
-// alike -- acc::prover's h(X) accumulated on the device straight into the member's coefficient vector
-static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, bool gen, const int *slots_in, int S, bool *ran) {
+// Coefficients of a member: the caller's host array (jb.coeffs), generated on the device (draw), or -- jb.hs set, for every member
+// alike -- acc::prover's h(X) accumulated on the device straight into the member's coefficient vector.  commit: jb.C is not given
+// but computed, the members' commits riding in step 0's batched MSM
+static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, bool draw, bool commit, const int *slots_in, int S, bool *ran) {
     *ran = false;
     const size_t n = d + 1, lg = ilog2(n), A = jobs.size();
     if (A == 0 || n < 2 || n > ctx->nofold_size || n > OPEN_MAX_N) return HALO_OK;
@@ -708,17 +821,18 @@ static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, b
     *ran = true;
     const OpenStage st{ctx->d_check_stage, ctx->h_open_pinned, per, n, ms, G};
     // (hiding: the same for every member of a batch)
-    OpenGroups groups{ctx, jobs, slots_in, S, n, lg, G, ms, gen, jobs[0].hiding, accumulated, tuning().u_from_last_round, st, {}};
+    OpenGroups groups{ctx, jobs, slots_in, S, n, lg, G, ms, draw, commit, jobs[0].hiding, accumulated, tuning().u_from_last_round, st, {}};
     return groups.run();
 }
 
-// halo_pcdl_open_batch (coeffs != null) and halo_random_instance_batch (coeffs == null: `out` holds Instance blobs) after their
-// argument checks: the members' draws, then the device path or, where it does not apply, the members one at a time
+// halo_pcdl_open_batch (coeffs and Cs given), halo_instance_from_poly_batch (coeffs without Cs: the commits are computed and `out`
+// holds Instance blobs) and halo_random_instance_batch (neither: the polynomials are drawn as well) after their argument checks:
+// the members' draws, then the device path or, where it does not apply, the members one at a time
 static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *Cs, const uint64_t *zs,
                             const uint64_t *ws, uint64_t *out, int *status) {
     const size_t n = d + 1, lg = ilog2(n);
-    const bool gen = coeffs == nullptr, hiding = gen || ws != nullptr;
-    const size_t stride = gen ? instance_words(lg) : proof_words(lg);
+    const bool gen = coeffs == nullptr, commit = Cs == nullptr, hiding = gen || ws != nullptr;
+    const size_t stride = commit ? instance_words(lg) : proof_words(lg);
     int slots[HALO_SLOTS], S = idle_slots(ctx, slots);
     if (!S) { set_error("open_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
     // 1. every member's draws, in member order (the loop's order)
@@ -731,7 +845,7 @@ static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const 
         OpenJob jb;
         jb.idx = i;
         jb.hiding = hiding;
-        jb.proof = out + i * stride + (gen ? 21 : 0);
+        jb.proof = out + i * stride + (commit ? 21 : 0);
         jb.s_start = rng.state;
         if (gen) {
             size_t lo = d / 2;
@@ -744,7 +858,7 @@ static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const 
         } else {
             jb.coeffs = coeffs + i * n * 4;
             jb.deg = host_poly_degree(jb.coeffs, n);
-            jb.C = Point::load(Cs + 12 * i);
+            if (Cs) jb.C = Point::load(Cs + 12 * i);
             jb.z = Fr::load(zs + 4 * i);
             if (ws) jb.w = Fr::load(ws + 4 * i);
             if (hiding && jb.deg == 0) { codes[i] = HALO_E_ASSERT; errs[i] = "open: hiding needs p.degree() >= 1"; continue; }  // (before any draw)
@@ -761,13 +875,18 @@ static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const 
         std::memset(jb.proof, 0, 8 * proof_words(lg));
         jb.proof[1] = lg;
     }
+    // (ONE polynomial of the caller's: the single call's body is faster than a group of one -- 2.94 against 3.47 ms at 2^10, 5.10
+    // against 5.93 at 2^14; "open_batch_group" forces the group)
+    // (the single call's body runs on slots 0 and 1: only with both idle)
+    const bool alone = commit && !gen && jobs.size() == 1 && dev_hooks().open_group <= 0 && S >= 2 && slots[0] == 0 && slots[1] == 1;
     bool ran = false;
-    int rc = open_batch_dev(ctx, d, jobs, gen, slots, S, &ran);  // (no jobs: nothing runs)
+    int rc = alone ? HALO_OK : open_batch_dev(ctx, d, jobs, gen, commit, slots, S, &ran);  // (no jobs: nothing runs)
     if (rc) return rc;
     if (!ran) {
         for (OpenJob &jb : jobs) {
             uint64_t st = jb.s_start;
             if (gen) rc = random_instance_one(ctx, &st, d, out + jb.idx * stride);
+            else if (commit) rc = instance_from_poly_one(ctx, &st, jb.coeffs, n, jb.deg, d, zs + 4 * jb.idx, ws ? ws + 4 * jb.idx : nullptr, out + jb.idx * stride);
             else rc = pcdl_open_host(ctx, &st, jb.coeffs, jb.deg, Cs + 12 * jb.idx, d, zs + 4 * jb.idx, ws ? ws + 4 * jb.idx : nullptr, jb.proof);
             if (rc == HALO_E_ASSERT) { jb.rc = rc; jb.err = halo_last_error(); }
             else if (rc) return rc;
@@ -777,8 +896,8 @@ static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const 
     for (OpenJob &jb : jobs) {
         codes[jb.idx] = jb.rc;
         errs[jb.idx] = jb.err;
-        // the Instance around the proof (random_instance_one writes its own)
-        if (gen && !jb.rc && ran) store_instance_head(out + jb.idx * stride, jb.C, d, jb.z, jb.v);
+        // the Instance around the proof (random_instance_one and instance_from_poly_one write their own)
+        if (commit && !jb.rc && ran) store_instance_head(out + jb.idx * stride, jb.C, d, jb.z, jb.v);
     }
     if (rng_state) *rng_state = rng.state;
     return report_members("member", m, [&](size_t i) { return codes[i]; }, [&](size_t i) { return errs[i]; }, status,
@@ -889,7 +1008,7 @@ static int acc_prover_batch_dev(halo_ctx *ctx, uint64_t state0, size_t d, const 
             std::memset(accs + jb.idx * aw, 0, 8 * aw);
             jb.proof[1] = lg;
         }
-        rc = open_batch_dev(ctx, d, jobs, false, slots, S, ran);
+        rc = open_batch_dev(ctx, d, jobs, false, false, slots, S, ran);
         if (rc) return rc;
         if (!*ran) return HALO_OK;
     }
@@ -1001,6 +1120,50 @@ int halo_pcdl_open_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uin
     if (!is_pow2(n)) return fail_assert("open: d + 1 is not a power of two");  // pcdl.rs:130 (p.degree() <= d: the arrays hold d + 1)
     if (n > ctx->n) return fail_assert("open: d > D");                         // pcdl.rs:132
     return open_batch_entry(ctx, rng_state, d, coeffs, m, Cs, zs, ws, proofs_out, status);
+}
+
+// pcdl::commit of m host polynomials at once (see commit_batch_run)
+int halo_pcdl_commit_batch(halo_ctx *ctx, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *ws, uint64_t *out_jac) {
+    HALO_CTX(ctx);
+    if (m && (!coeffs || !out_jac)) { set_error("commit_batch: null pointer"); return HALO_E_ARG; }
+    int slots[HALO_SLOTS], S = 0;
+    int rc = commit_batch_checks(ctx, d, slots, &S);
+    if (rc || m == 0) return rc;
+    std::vector<size_t> live(m);
+    for (size_t i = 0; i < m; ++i) live[i] = i;
+    return commit_batch_run(ctx, d, coeffs, nullptr, nullptr, live, ws, out_jac, slots, S);
+}
+
+// ... and of m device-resident ones: a member longer than d + 1 fails alone, as halo_pcdl_commit_dev fails
+int halo_pcdl_commit_dev_batch(halo_ctx *ctx, size_t d, const void *const *d_coeffs, const size_t *lens, size_t m, const uint64_t *ws, uint64_t *out_jac,
+                               int *status) {
+    HALO_CTX(ctx);
+    if (m && (!d_coeffs || !lens || !out_jac)) { set_error("commit_dev_batch: null pointer"); return HALO_E_ARG; }
+    for (size_t i = 0; i < m; ++i)
+        if ((lens[i] && !d_coeffs[i]) || ((uintptr_t)d_coeffs[i] & 31)) { set_error("commit_dev_batch: null or misaligned pointer"); return HALO_E_ARG; }
+    int slots[HALO_SLOTS], S = 0;
+    int rc = commit_batch_checks(ctx, d, slots, &S);
+    if (rc || m == 0) return rc;
+    std::vector<size_t> live;
+    for (size_t i = 0; i < m; ++i)
+        if (lens[i] <= d + 1) live.push_back(i);
+    rc = commit_batch_run(ctx, d, nullptr, d_coeffs, lens, live, ws, out_jac, slots, S);
+    if (rc) return rc;
+    return report_members("member", m, [&](size_t i) { return lens[i] > d + 1 ? HALO_E_ASSERT : HALO_OK; },
+                          [&](size_t) { return std::string("commit: p.degree() > d"); }, status,
+                          [&](size_t i) { std::memset(out_jac + 12 * i, 0, 96); });
+}
+
+// benches/acc.rs:15-29 for m polynomials the caller holds: commit, evaluate, open and pack (open_batch_entry's third source)
+int halo_instance_from_poly_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *zs, const uint64_t *ws,
+                                  uint64_t *instances_out, int *status) {
+    HALO_CTX(ctx);
+    if (m == 0) return HALO_OK;
+    if (!coeffs || !zs || !instances_out) { set_error("instance_from_poly_batch: null pointer"); return HALO_E_ARG; }
+    const size_t n = d + 1;
+    if (!is_pow2(n)) return fail_assert("commit: d + 1 is not a power of two");  // (the first of the loop's three calls)
+    if (n > ctx->n) return fail_assert("commit: d > D");
+    return open_batch_entry(ctx, rng_state, d, coeffs, m, nullptr, zs, ws, instances_out, status);
 }
 
 // benches/acc.rs:15-29 random_instance, m times (see open_batch_dev)

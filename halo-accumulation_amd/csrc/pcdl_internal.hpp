@@ -100,5 +100,9 @@ void set_alphas(AccHPolys *hs);
 int pcdl_open_host(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *coeffs, size_t deg, const uint64_t C[12], size_t d, const uint64_t z[4],
                    const uint64_t *w, uint64_t *proof_out);
 int random_instance_one(halo_ctx *ctx, uint64_t *rng_state, size_t d, uint64_t *inst);
+// ... of halo_pcdl_commit (its own checks inside) and of halo_instance_from_poly (len coefficients of degree deg <= d)
+int pcdl_commit_host(halo_ctx *ctx, const uint64_t *coeffs, size_t len, size_t d, const host::Fr *w, host::Point *out);
+int instance_from_poly_one(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *coeffs, size_t len, size_t deg, size_t d, const uint64_t z[4],
+                           const uint64_t *w, uint64_t *inst);
 
 }  // namespace halo

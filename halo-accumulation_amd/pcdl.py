@@ -63,6 +63,61 @@ def open_batch(ctx, rng, ps, Cs, d, zs, ws=None):
     return [out[i].copy() for i in range(m)]
 
 
+def _pack_polys(ps, d, who):
+    """m coefficient arrays -> (max(m, 1), d + 1, 4), zero-padded (the layout of halo_pcdl_open_batch)"""
+    coeffs = np.zeros((max(len(ps), 1), d + 1, 4), dtype=np.uint64)
+    for i, p in enumerate(ps):
+        p = _a(p).reshape(-1, 4)
+        nz = np.nonzero(p.any(axis=1))[0]
+        k = int(nz[-1]) + 1 if len(nz) else 0
+        if k > d + 1:
+            raise AssertionError(who + ": p.degree() > d")
+        coeffs[i, :k] = p[:k]
+    return coeffs
+
+
+def _pack_rows(rows, m, width, who, what):
+    """m rows of `width` words (None stays None); a list of another length is the caller's mistake, found before the library runs"""
+    if rows is None:
+        return None
+    if len(rows) != m:
+        raise ValueError("%s: %d %s for %d polynomials" % (who, len(rows), what, m))
+    out = np.zeros((max(m, 1), width), dtype=np.uint64)
+    for i, r in enumerate(rows):
+        out[i] = _a(r).reshape(width)
+    return out
+
+
+def commit_batch(ctx, ps, d, ws=None):
+    """pcdl::commit of m polynomials of degree bound d at once (halo_pcdl_commit_batch) -> (m, 12): the points m pcdl.commit
+    calls return.  ws: one w per polynomial, or None (no member hides)."""
+    m = len(ps)
+    ws = _pack_rows(ws, m, 4, "commit_batch", "ws")
+    coeffs = _pack_polys(ps, d, "commit")
+    out = np.zeros((max(m, 1), 12), dtype=np.uint64)
+    check(ctx.lib.halo_pcdl_commit_batch(ctx.h, d, ptr(coeffs), m, ptr(ws), ptr(out)))
+    return out[:m].copy()
+
+
+def commit_dev_batch(ctx, dptrs, lens, d, ws=None):
+    """pcdl::commit of m device-resident polynomials at once (halo_pcdl_commit_dev_batch): dptrs[i] = device address of lens[i]
+    coefficients -> (m, 12).  A member longer than d + 1 raises as pcdl.commit_dev does, with the status list as the
+    exception's second argument and the points (that member's zero-filled) as its third."""
+    m = len(dptrs)
+    if len(lens) != m:
+        raise ValueError("commit_dev_batch: %d lengths for %d pointers" % (len(lens), m))
+    ws = _pack_rows(ws, m, 4, "commit_dev_batch", "ws")
+    ptrs = (C.c_void_p * max(m, 1))(*[C.c_void_p(int(p)) for p in dptrs])
+    ln = (C.c_size_t * max(m, 1))(*[int(k) for k in lens])
+    out = np.zeros((max(m, 1), 12), dtype=np.uint64)
+    status = (C.c_int * max(m, 1))()
+    rc = ctx.lib.halo_pcdl_commit_dev_batch(ctx.h, d, ptrs, ln, m, ptr(ws), ptr(out), status)
+    if rc == _lib.HALO_E_ASSERT:
+        raise AssertionError(ctx.lib.halo_last_error().decode(), [status[i] for i in range(m)], out[:m].copy())
+    check(rc)
+    return out[:m].copy()
+
+
 def commit_dev(ctx, dptr, length, d, w=None):
     """pcdl::commit for `length` coefficients resident in device memory"""
     out = np.zeros(12, dtype=np.uint64)

@@ -371,6 +371,52 @@ int halo_pcdl_open_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uin
  * z, then its hiding open's).  The conventions of halo_pcdl_open_batch; d < 2: the single call's assert. */
 int halo_random_instance_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, size_t m, uint64_t *instances_out);
 
+/* pcdl::commit (pcdl.rs:99-110) of m polynomials of degree bound d at once.  coeffs = m x (d + 1) x 4 words in the layout of
+ * halo_pcdl_open_batch (member i at i * (d + 1) * 4, zero-padded: the same buffer serves the commit and the open), ws = m x 4 or
+ * NULL (no member hides), out_jac = m x 12, normalised: member i is what halo_pcdl_commit(ctx, coeffs_i, d + 1, d, w_i, ..) writes
+ * (the zero polynomial: (1, 1, 0), or w S).  The layout bounds every degree, so no member fails alone and there is no status.
+ * - Before any work, nothing written: a null ctx, or a null coeffs or out_jac with m > 0: HALO_E_ARG; d + 1 not a power of two
+ *   or above the key: HALO_E_ASSERT with halo_pcdl_commit's messages; no idle slot: HALO_E_ARG; m = 0: HALO_OK.
+ * - Groups of up to 8 members (within the small pipeline's bucket limit; one member where the fixed-base table takes the MSM: a key
+ *   and d + 1 of at least 2^20) run as ONE batched MSM launch sequence each and rotate over the slots idle on entry (a caller's
+ *   MSM in flight on another slot is left alone).  A group's padded rows are copied on its slot's own stream, so the copy of the
+ *   next group runs under this group's kernels; the w_i S terms are added on the host when the group is collected.  (m = 1 at
+ *   such a table size, with slots 0 and 1 idle, runs as halo_pcdl_commit itself: its split copy is faster than one copy in
+ *   front of one launch.)
+ * - The staging is optional memory (halo_set_memory_budget): without it the members run one at a time per idle slot, through
+ *   the slots' own scalar buffers, same points.  A multi-device context runs the batch on devices[0]. */
+int halo_pcdl_commit_batch(halo_ctx *ctx, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *ws /*nullable*/, uint64_t *out_jac);
+/* The same for device-resident polynomials: d_coeffs[i] = a 32-byte aligned device pointer to lens[i] Montgomery scalars
+ * (lens[i] = 0 with a null pointer is allowed), read, not modified; the caller's writes to them are complete on entry, as for
+ * halo_pcdl_commit_dev, whose result member i equals.  No host-to-device traffic: a member of d + 1 scalars is passed to the
+ * launch in place, the shorter ones of a group are zero-padded into the staging by one kernel launch.  A member with
+ * lens[i] > d + 1 fails alone as the single call does (HALO_E_ASSERT, "commit: p.degree() > d"): its 12 words are zero-filled and
+ * status[i] (nullable) gets the code; returns the first non-zero status, halo_last_error() = "member i: <message>".  Whole-call
+ * errors as above, and HALO_E_ARG for a null lens or d_coeffs with m > 0, a null pointer with a non-zero length or a misaligned
+ * one. */
+int halo_pcdl_commit_dev_batch(halo_ctx *ctx, size_t d, const void *const *d_coeffs, const size_t *lens, size_t m,
+                               const uint64_t *ws /*nullable*/, uint64_t *out_jac, int *status /*nullable*/);
+/* benches/acc.rs:15-29 for a polynomial the caller holds: C = commit(p, d, w), v = p(z), pi = open(rng, p, C, d, z, w),
+ * Instance::new -- halo_pcdl_commit, halo_poly_eval over the p.degree() + 1 coefficients and halo_pcdl_open in one call, with the
+ * blob and the final *rng_state of that sequence.  The polynomial is uploaded once and all three read that copy.  Errors: a null
+ * ctx, coeffs (with len > 0), z or instance_out: HALO_E_ARG; then the asserts of halo_pcdl_commit in its order ("commit: d + 1 is
+ * not a power of two", "commit: p.degree() > d", "commit: d > D"), which cover the other two calls'; then halo_pcdl_open's own
+ * ("open: hiding needs p.degree() >= 1": no randomness consumed). */
+int halo_instance_from_poly(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *coeffs, size_t len, size_t d, const uint64_t z[4],
+                            const uint64_t *w /*nullable*/, uint64_t *instance_out);
+/* ... of m polynomials at once, in the layout of halo_pcdl_open_batch without Cs: instances_out = m Instance blobs at stride
+ * halo_instance_words(lg(d+1)).  Every word of member i and the final *rng_state equal the loop over halo_instance_from_poly in
+ * member order (draws per member are the open's only: a hiding member draws deg scalars for q, then w_bar).  A hiding member with a
+ * constant polynomial fails as halo_pcdl_open does: no randomness consumed, blob zero-filled, status[i] = HALO_E_ASSERT, the others
+ * unaffected.  The conventions of halo_pcdl_open_batch, with the commit's messages for d + 1 not a power of two or above the key.
+ * Where that call batches (2 <= d + 1 <= the no-fold size, staging available) the members' commits join the first batched MSM
+ * of their group; elsewhere, and for m = 1 with slots 0 and 1 idle (measured faster alone), the members run one at a time
+ * through halo_instance_from_poly's body.  That body, like halo_pcdl_open's in halo_pcdl_open_batch, runs on slot 0 and may
+ * borrow slot 1: above the no-fold size and without the staging, a caller's MSM in flight on one of these two makes the call
+ * return HALO_E_ARG ("slot already has an MSM in flight") at the first member that needs the slot. */
+int halo_instance_from_poly_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *zs,
+                                  const uint64_t *ws /*nullable*/, uint64_t *instances_out, int *status /*nullable*/);
+
 /* ---- wire format (no device needed) ----------------------------------------------------------
  * EvalProof (pcdl.rs:22-30), Instance (acc.rs:21-28) and Accumulator (acc.rs:43-59) in the byte layout a derived
  * ark-serialize `CanonicalSerialize` (compressed) writes: fields in declaration order; Fr = 32 bytes LE canonical;

@@ -22,9 +22,12 @@ extern "C" {
  * "shard_fail_rank" + "shard_fail_at" (the rank with that offset fails locally before collective number `at` of a sharded open:
  * 0 = the share of p(z), 1.. = the rounds, then the tail; at = -2: in a sharded check; at = -3: the rank with that `rank`
  * before the collective of halo_msm_sharded / _dev_sharded / _end_sharded), "batch_stage_fail" (value != 0: the staging of
- * halo_pcdl_check_batch / halo_acc_decider_batch / halo_pcdl_open_batch / halo_random_instance_batch / halo_acc_prover_batch is refused, as over the
+ * halo_pcdl_check_batch / halo_acc_decider_batch / halo_pcdl_open_batch / halo_random_instance_batch / halo_acc_prover_batch /
+ * halo_pcdl_commit_batch / halo_pcdl_commit_dev_batch / halo_instance_from_poly_batch is refused, as over the
  * memory budget: one member at a time; halo_acc_verifier_batch: its sums on the host pool), "check_batch_group" (members per MSM launch of the check batch, 1..8; 0: the measured
- * default), "open_batch_group" (members per launch of the open and prover batches, 1..4; 0: the measured default), "verifier_batch_min" (relations
+ * default), "open_batch_group" (members per launch of the open and prover batches and of halo_instance_from_poly_batch, 1..4; 0: the
+ * measured default), "commit_batch_group" (members per MSM launch of halo_pcdl_commit_batch / halo_pcdl_commit_dev_batch, 1..8; 0: the
+ * rule of the check batch), "verifier_batch_min" (relations
  * from which halo_acc_verifier_batch runs its sums on the device, >= 1; 0: the measured default), "table_slide_min" (keys from this many points, >= 4096, take the c = 20 table plans and
  * the all-shifts table with its sliding-window recode; 0: 2^20), "decode_batch_min" (finite points
  * from which halo_*_decode_batch decompresses on the device, >= 1; 0: the measured default; "batch_stage_fail" refuses its staging
@@ -53,7 +56,7 @@ int halo_dev_fr_plan(halo_ctx *ctx, int which, size_t n, long out[4]);
 int halo_dev_dot2_cross(halo_ctx *ctx, const uint64_t *c, const uint64_t *z, size_t m, uint64_t out[8]);
 /* What the library read from the environment at its first use (csrc/tuning.hip), by field: "host_split_set", "host_pieces", "host_split0".."host_split3",
  * "fold_table_after", "graph_cache", "pow_e", "dot_blocks", "spin_us", "graphs", "memory_budget" (MiB, -1 unset), "trace", "tagged"; -1 for an
- * unknown name.  Host only. */
+ * unknown name.  Also "commit_batch_group": that hook of halo_dev_hook as it stands now (0 after "reset").  Host only. */
 long halo_dev_tuning(const char *name);
 
 /* `reps` back-to-back launches of one bandwidth-side Fr kernel over n elements of the context's scratch memory (no host

@@ -60,6 +60,15 @@ extern "C" {
     pub fn halo_pcdl_open_batch(ctx: *mut HaloCtx, rng_state: *mut u64, d: usize, coeffs: *const u64, m: usize, cs: *const u64, zs: *const u64,
                                 ws: *const u64, proofs_out: *mut u64, status: *mut c_int) -> c_int;
     pub fn halo_random_instance_batch(ctx: *mut HaloCtx, rng_state: *mut u64, d: usize, m: usize, instances_out: *mut u64) -> c_int;
+    // pcdl::commit of m polynomials at once: host rows of d + 1 scalars, or device pointers and lengths (ws, status may be null)
+    pub fn halo_pcdl_commit_batch(ctx: *mut HaloCtx, d: usize, coeffs: *const u64, m: usize, ws: *const u64, out_jac: *mut u64) -> c_int;
+    pub fn halo_pcdl_commit_dev_batch(ctx: *mut HaloCtx, d: usize, d_coeffs: *const *const c_void, lens: *const usize, m: usize, ws: *const u64,
+                                      out_jac: *mut u64, status: *mut c_int) -> c_int;
+    // benches/acc.rs:15-29 for polynomials the caller holds: commit, evaluate, open, pack (w / ws, rng_state, status may be null)
+    pub fn halo_instance_from_poly(ctx: *mut HaloCtx, rng_state: *mut u64, coeffs: *const u64, len: usize, d: usize, z: *const u64, w: *const u64,
+                                   instance_out: *mut u64) -> c_int;
+    pub fn halo_instance_from_poly_batch(ctx: *mut HaloCtx, rng_state: *mut u64, d: usize, coeffs: *const u64, m: usize, zs: *const u64,
+                                         ws: *const u64, instances_out: *mut u64, status: *mut c_int) -> c_int;
     // m wire blobs -> m library blobs at `stride_words` (ctx, lg_out, status may be null; member i = bytes offs[i]..offs[i + 1])
     pub fn halo_proof_decode_batch(ctx: *mut HaloCtx, input: *const u8, offs: *const usize, m: usize, out: *mut u64, stride_words: usize,
                                    lg_out: *mut usize, status: *mut c_int) -> c_int;
