@@ -176,6 +176,8 @@ _DEV_SIGS = {
     "halo_dev_batch_to_affine": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p]),
     "halo_dev_fq_sqrt": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, u32p]),
     "halo_dev_fold_points": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_int, u64p, C.c_int, C.c_int, u64p]),
+    "halo_dev_fold_points_batch": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_int, u64p, C.c_int, C.c_int, C.c_int, u64p]),
+    "halo_dev_msm_offsets": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.c_size_t, u64p, C.c_int, C.c_int, u64p]),
     "halo_dev_sqrt_tables": (C.c_int, [u32p, C.c_size_t]),
     "halo_dev_table_read": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, u64p]),
     "halo_test_lazy_field_op": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t, u32p]),
@@ -537,7 +539,8 @@ class Context:
         check(self.lib.halo_set_fold_table(self.h, mode))
 
     def info(self, what: int) -> int:
-        """0: MSM table bytes, 1: fold table bytes, 2: fold table build time in microseconds"""
+        """0: MSM table bytes, 1: fold table bytes, 2: fold table build time in microseconds, ..., 10: members of the last open-type
+        batch call that ran through member-batched launches (halo_ctx_info)"""
         return self.lib.halo_ctx_info(self.h, what)
 
     def set_memory_budget(self, nbytes: int):
@@ -580,6 +583,29 @@ class Context:
         assert scalars.shape[0] == (3 if levels == 2 else 1)
         out = np.zeros((max(n // (4 if levels == 2 else 2), 1), 8), dtype=np.uint64)
         check(self.lib.halo_dev_fold_points(self.h, ptr(key), n, int(levels), ptr(scalars), int(form), int(bool(in_place)), ptr(out)))
+        return out
+
+    def fold_points_batch(self, key, levels, scalars, members, shared=True, form=0, n=None):
+        """halo_dev_fold_points_batch: `members` folds in one launch.  key: None (the first n points of the context's key, shared), n x 8
+        words (one key for all, shared) or members x n x 8 words (shared=False: folded in place); scalars: members x (1 | 3) x 4 words
+        -> members x m x 8 affine words"""
+        if key is not None:
+            key = np.ascontiguousarray(key, dtype=np.uint64).reshape(-1, 8)
+            n = key.shape[0] // (1 if shared else members)
+        n = self.size if n is None else int(n)
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        assert scalars.shape[0] == members * (3 if levels == 2 else 1)
+        out = np.zeros((members, max(n // (4 if levels == 2 else 2), 1), 8), dtype=np.uint64)
+        check(self.lib.halo_dev_fold_points_batch(self.h, ptr(key), n, int(levels), ptr(scalars), int(members), int(bool(shared)), int(form), ptr(out)))
+        return out
+
+    def msm_offsets(self, offs, n, scalars, mont=False):
+        """halo_dev_msm_offsets: len(offs) MSMs of n points as ONE batched launch sequence, member b over the key's points
+        [offs[b], offs[b] + n) with scalars[b] -> len(offs) x 12 Jacobian words (normalised, as halo_msm's)"""
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(len(offs), int(n), 4)
+        co = (C.c_size_t * len(offs))(*[int(o) for o in offs])
+        out = np.zeros((len(offs), 12), dtype=np.uint64)
+        check(self.lib.halo_dev_msm_offsets(self.h, co, int(n), ptr(scalars), len(offs), int(bool(mont)), ptr(out)))
         return out
 
     def table_read(self, row, off=0, n=None):

@@ -1473,13 +1473,15 @@ int halo_set_memory_budget(halo_ctx *ctx, size_t bytes) {
  * table memory on this context's device, 4 = bytes of it in use (all contexts of the process), 5 / 6 = status of the fold table / the
  * MSM table: 0 nothing yet, 1 memory requested, 2 built, 3 over the budget, 4 allocation failed (tried again later), 5 off,
  * 7 = microseconds the MSM table's build took, 8 = its rows (13 / 15: fixed windows, 255: every shift, the sliding-window plan),
- * 9 = plan of the launch enqueued last: 0 no table pipeline, 1 its fixed windows, w + 1 sliding windows of at most w bits */
+ * 9 = plan of the launch enqueued last: 0 no table pipeline, 1 its fixed windows, w + 1 sliding windows of at most w bits,
+ * 10 = members of the last open-type batch call that went through member-batched launches (0: one at a time) */
 size_t halo_ctx_info(const halo_ctx *ctx, int what) {
     if (!ctx) return 0;
     if (what == 0) return ctx->d_table ? (size_t)ctx->tbl.rows * ctx->n * 128 : 0;
     if (what == 7) return (size_t)(ctx->share ? ctx->share->table_build_ms * 1e3 : 0);
     if (what == 8) return ctx->d_table ? (size_t)ctx->tbl.rows : 0;
     if (what == 9) return (size_t)(ctx->last_table_plan + 1);
+    if (what == 10) return ctx->open_batch_members;
     if (what == 1) return ctx->foldtab_bytes;
     if (what == 2) return (size_t)(ctx->foldtab_build_ms * 1e3);
     if (what == 3 || what == 4) {

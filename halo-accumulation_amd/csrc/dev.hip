@@ -203,6 +203,7 @@ long halo_dev_tuning(const char *name) {
     if (!std::strcmp(name, "trace")) return t.trace ? 1 : 0;
     if (!std::strcmp(name, "tagged")) return t.tagged ? 1 : 0;
     if (!std::strcmp(name, "commit_batch_group")) return dev_hooks().commit_group;  // (the hook as it stands: a CPU test sees "reset" clear it)
+    if (!std::strcmp(name, "open_batch_fold")) return dev_hooks().open_fold;
     return -1;
 }
 
@@ -217,6 +218,10 @@ int halo_dev_hook(const char *name, long value) {
     else if (!std::strcmp(name, "check_batch_group")) h.check_group = (int)value;
     else if (!std::strcmp(name, "open_batch_group")) h.open_group = (int)value;
     else if (!std::strcmp(name, "commit_batch_group")) h.commit_group = (int)value;
+    else if (!std::strcmp(name, "open_batch_fold")) {
+        if (value < 0 || value > 2) { set_error("dev_hook: open_batch_fold is 0 (the measured default), 1 (the folded schedule wherever it applies) or 2 (never: the loop)"); return HALO_E_ARG; }
+        h.open_fold = (int)value;
+    }
     else if (!std::strcmp(name, "verifier_batch_min")) h.verifier_min = (int)value;
     else if (!std::strcmp(name, "decode_batch_min")) h.decode_min = value;
     else if (!std::strcmp(name, "table_slide_min")) h.slide_min = value > 0 && value < 4096 ? 4096 : value;
@@ -232,7 +237,7 @@ int halo_dev_hook(const char *name, long value) {
         h.poly_blocks = (int)value;
     }
     else if (!std::strcmp(name, "reset")) h = DevHooks();
-    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, commit_batch_group, verifier_batch_min, decode_batch_min, table_slide_min, pow_e, dot_blocks, poly_blocks, reset)"); return HALO_E_ARG; }
+    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, open_batch_fold, commit_batch_group, verifier_batch_min, decode_batch_min, table_slide_min, pow_e, dot_blocks, poly_blocks, reset)"); return HALO_E_ARG; }
     return HALO_OK;
 }
 
@@ -640,6 +645,85 @@ int halo_dev_fold_points(halo_ctx *ctx, const uint64_t *key_affine, size_t n, in
     e = hipStreamSynchronize(ctx->stream);  // (also on failure: nothing of this call may be in flight when its buffers go)
     if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
     (void)hipFree(d);
+    return rc;
+}
+
+// The member-batched key folds through the product's launchers (include/halo_accumulation_dev.h).  Device buffers of this call only;
+// every copy and launch in order on the context's stream.  A shared source (the context's key, or one uploaded key) is folded into
+// a destination of members x m points; per-member sources are folded in place, member b's key at b * n points, as the open batch
+// folds a staged key a second time.
+int halo_dev_fold_points_batch(halo_ctx *ctx, const uint64_t *key_affine, size_t n, int levels, const uint64_t *scalars, int members, int shared, int form,
+                               uint64_t *out_affine) {
+    HALO_CTX(ctx);
+    if (levels != 1 && levels != 2) { set_error("dev_fold_points_batch: levels must be 1 or 2"); return HALO_E_ARG; }
+    const size_t parts = 2 * (size_t)levels;
+    if (n == 0 || n % parts || n > ((size_t)1 << 24)) { set_error("dev_fold_points_batch: n must be a positive multiple of 2 (levels 1) or 4 (levels 2), at most 2^24"); return HALO_E_ARG; }
+    if (!scalars || !out_affine) { set_error("dev_fold_points_batch: null pointer"); return HALO_E_ARG; }
+    if (members < 1 || members > OPEN_MAX_GROUP) { set_error("dev_fold_points_batch: 1 .. 4 members"); return HALO_E_ARG; }
+    if (!key_affine && !shared) { set_error("dev_fold_points_batch: the context's key (key_affine = NULL) is a shared source"); return HALO_E_ARG; }
+    if (!key_affine && n > ctx->n) { set_error("dev_fold_points_batch: n exceeds the context's key"); return HALO_E_ARG; }
+    if (form < 0 || form > 3 || (levels == 1 && form > 2)) { set_error("dev_fold_points_batch: form is 0, 1 or 2 for levels 1; 0 .. 3 for levels 2"); return HALO_E_ARG; }
+    const size_t m = n / parts, G = (size_t)members, keys = shared ? 1 : G;
+    const size_t src_words = key_affine ? keys * n * (size_t)AFF_STRIDE : 0, dst_words = shared ? G * m * (size_t)AFF_STRIDE : 0;
+    const size_t in_words = key_affine ? keys * n * 8 : 0, out_words = G * m * 8;
+    uint32_t *d = nullptr;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d, (src_words + dst_words + G * FOLD_DIG_WORDS) * 4 + (in_words + out_words) * 8));
+    uint32_t *d_src = d, *d_dst = d + src_words, *d_digs = d_dst + dst_words;  // (every part a multiple of 128 bytes or of 64)
+    uint64_t *d_in = reinterpret_cast<uint64_t *>(d_digs + G * FOLD_DIG_WORDS), *d_out = d_in + in_words;
+    std::vector<uint32_t> digs(G * FOLD_DIG_WORDS);
+    const size_t per = levels == 1 ? 1 : 3;  // scalars per member
+    for (size_t b = 0; b < G; ++b) {
+        host::Fr sc[3];
+        for (size_t t = 0; t < per; ++t) sc[t] = host::Fr::load(scalars + 4 * (b * per + t));
+        fold_digits(sc, levels, &digs[b * FOLD_DIG_WORDS]);
+    }
+    int rc = HALO_OK;
+    hipError_t e = hipMemcpyAsync(d_digs, digs.data(), digs.size() * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+    if (!rc && key_affine) {
+        e = hipMemcpyAsync(d_in, key_affine, in_words * 8, hipMemcpyHostToDevice, ctx->stream);
+        rc = e == hipSuccess ? aff_words_to_native(ctx, d_in, keys * n, d_src) : hip_fail(e, "hipMemcpyAsync");
+    }
+    const uint32_t *src = key_affine ? d_src : ctx->d_bases;
+    uint32_t *dst = shared ? d_dst : d_src;
+    const size_t src_stride = shared ? 0 : n, dst_stride = shared ? m : n;
+    if (!rc) rc = levels == 1 ? ipa_fold_points_batch(ctx, members, src, src_stride, dst, dst_stride, m, d_digs, form)
+                              : ipa_fold_points4_batch(ctx, members, src, src_stride, dst, dst_stride, m, d_digs, form);
+    for (size_t b = 0; b < G && !rc; ++b) rc = aff_native_to_words(ctx, dst + b * dst_stride * AFF_STRIDE, m, d_out + b * m * 8);
+    if (!rc && (e = hipMemcpyAsync(out_affine, d_out, out_words * 8, hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) rc = hip_fail(e, "hipMemcpyAsync");
+    e = hipStreamSynchronize(ctx->stream);  // (also on failure: nothing of this call may be in flight when its buffers go)
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    (void)hipFree(d);
+    return rc;
+}
+
+// One batched MSM launch sequence over the context's key with one base offset per member, on slot 0 (include/halo_accumulation_dev.h)
+int halo_dev_msm_offsets(halo_ctx *ctx, const size_t *offs, size_t n, const uint64_t *scalars, int count, int scalars_are_mont, uint64_t *out_jac) {
+    HALO_CTX(ctx);
+    if (count < 1 || count > MSM_MAX_BATCH) { set_error("dev_msm_offsets: 1 .. 8 members"); return HALO_E_ARG; }
+    if (!offs || !out_jac || (n && !scalars)) { set_error("dev_msm_offsets: null pointer"); return HALO_E_ARG; }
+    for (int b = 0; b < count; ++b)
+        if (offs[b] > ctx->n || n > ctx->n - offs[b]) { set_error("dev_msm_offsets: range exceeds the context's key"); return HALO_E_ARG; }
+    if (ctx->wss[0].in_flight || ctx->wss[0].lent_from >= 0 || ctx->fan[0].active) { set_error("dev_msm_offsets: slot 0 has an MSM in flight"); return HALO_E_ARG; }
+    uint64_t *d_sc = nullptr;
+    const size_t words = (size_t)count * n * 4;
+    if (words) {
+        alloc_epoch_bump(ctx);
+        HALO_HIP(hipMalloc(&d_sc, words * 8));
+    }
+    int rc = HALO_OK;
+    hipError_t e = words ? hipMemcpy(d_sc, scalars, words * 8, hipMemcpyHostToDevice) : hipSuccess;
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    MsmBatch mb;
+    mb.count = count;
+    for (int b = 0; b < count; ++b) { mb.scalars[b] = d_sc + (size_t)b * n * 4; mb.base_off[b] = (uint32_t)offs[b]; }
+    host::Point pts[MSM_MAX_BATCH];
+    if (!rc) rc = msm_enqueue_batch(ctx, 0, ctx->d_bases, mb, scalars_are_mont != 0, n);
+    if (!rc) rc = msm_finish_batch(ctx, 0, pts, count);
+    (void)hipStreamSynchronize(ctx->streams[0]);  // (also on failure: nothing of this call may be in flight when its buffer goes)
+    if (d_sc) (void)hipFree(d_sc);
+    for (int b = 0; b < count && !rc; ++b) pts[b].store_normalized(out_jac + 12 * b);
     return rc;
 }
 

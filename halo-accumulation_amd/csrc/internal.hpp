@@ -115,6 +115,7 @@ struct MsmBatch {
     // behind the copy of its own scalars): takes the c = 20 table plan although n is below its usual 2^20 points.
     bool sub = false;
 };
+struct MemberOffsets { uint32_t v[MSM_MAX_BATCH]; };  // ... as a kernel argument (the sort kernels of msm_general.hip and smsm.hip)
 inline int msm_outputs(const MsmBatch &m) { return m.tagged ? 2 : m.count; }
 inline MsmBatch msm_one(const uint64_t *scalars) { MsmBatch one; one.scalars[0] = scalars; return one; }
 MsmPlan msm_plan(size_t n, int forced_c);
@@ -361,6 +362,7 @@ struct halo_ctx {
     halo::HostWorker worker;      // host arithmetic overlapped with the caller's (see HostWorker; multi.hip also runs a shard's HIP calls on it)
     IpaBuffers ipa_bufs;          // reused by every halo_ipa of this context (one at a time; a second one allocates its own)
     uint64_t alloc_epoch = 0;     // bumped whenever this context allocates or frees device memory (see msm.hip, launch graphs)
+    size_t open_batch_members = 0;  // members of the last open-type batch call that ran through member-batched launches (0: one at a time; halo_ctx_info 10)
     int last_table_plan = -1;     // the launch enqueued last: -1 no table pipeline, 0 its fixed windows, else the sliding plan's window width (halo_ctx_info 9)
     int may_borrow = 0;           // > 0 inside a synchronous MSM call: a large MSM may run its odd pieces on the neighbouring slot (msm.hip)
     hipEvent_t ev_piece[HALO_SLOTS][2] = {};  // fork / join of those pieces (created on first use)
@@ -533,7 +535,8 @@ int msm_end_slot(halo_ctx *ctx, int slot, size_t count, uint64_t *out);  // `cou
 int quad_final_enqueue(halo_ctx *ctx, MsmWorkspace &ws, uint32_t Wt, uint32_t nseg, int k, uint64_t *winsum, uint64_t *winsum_plain,
                        const uint32_t *seg = nullptr, uint32_t *done = nullptr);
 int rc_mid_enqueue(halo_ctx *ctx, const uint32_t *entries, uint32_t blocks, uint64_t *winsum, uint32_t *done = nullptr, uint32_t *ticket = nullptr);
-int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, uint32_t base_off, size_t n, const MsmPlan &p, uint32_t Wt,
+// (offs: one base offset per member, in points; a block of k_smsm_sort sorts one window, so one member)
+int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MemberOffsets &offs, size_t n, const MsmPlan &p, uint32_t Wt,
                  uint32_t kmax);
 int smsm_prepare();
 
@@ -625,6 +628,16 @@ int open_batch_dots(halo_ctx *ctx, int G, const uint64_t *d_c, const uint64_t *d
 // s_out[2t + u] = s_in[t] xi^u (t < s_len), then c' = c_l + xi^-1 c_r, z' = z_l + xi z_r over m
 int open_batch_fold(halo_ctx *ctx, int G, uint64_t *d_c, uint64_t *d_z, const uint64_t *d_s_in, uint64_t *d_s_out, size_t ms, size_t m,
                     size_t s_len, const uint64_t *d_consts);
+// ---- ipa.hip: the member-batched key folds (blockIdx.y = member).  Member b reads d_src + b * src_stride points (0: one key for
+// all) and writes d_dst + b * dst_stride (may be its source); its digits are record b of d_digs, FOLD_DIG_WORDS 32-bit words of
+// device memory that fold_digits fills on the host from the fold's scalars: xi (levels 1) or s1 | s2 | s3 (levels 2).
+// form: 0 = the single launchers' rule over all G x m outputs; 1 / 2 = one / two outputs per lane; 3 = one per quad (4 only)
+constexpr size_t FOLD_DIG_WORDS = 64;
+void fold_digits(const host::Fr *s, int levels, uint32_t *rec);
+int ipa_fold_points_batch(halo_ctx *ctx, int G, const uint32_t *d_src, size_t src_stride, uint32_t *d_dst, size_t dst_stride, size_t m,
+                          const uint32_t *d_digs, int form = 0);
+int ipa_fold_points4_batch(halo_ctx *ctx, int G, const uint32_t *d_src, size_t src_stride, uint32_t *d_dst, size_t dst_stride, size_t m,
+                           const uint32_t *d_digs, int form = 0);
 // ---- ipa.hip: the member-batched padding of halo_pcdl_commit_dev_batch (pcdl_batch.hip).  Entry k of the table: src[k], len[k]
 // Montgomery scalars in device memory (32-byte aligned), copied to d_out + row[k] * ms words and zero-padded to n scalars.  The
 // table travels as a kernel argument; count <= MSM_MAX_BATCH entries, one launch on ctx->stream.

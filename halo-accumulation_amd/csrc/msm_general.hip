@@ -469,11 +469,9 @@ int msm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_base
                 spread_mod, top_bit, d_digits, ws.d_meta, ws.d_blockoff, ws.d_tblockoff);
     // chain bound per lane of the bucket kernel: 64 where the launch is throughput-bound, 16 where it is latency-bound
     uint32_t kmax = msm_kmax(ctx, n);
-    bool same_bases = true;  // the small pipeline takes one base offset: members over the same points (the L and R of an IPA round)
-    for (int b = 1; b < p.batch; ++b) same_bases = same_bases && members.base_off[b] == members.base_off[0];
-    if (ctx->small_path != 0 && n <= ((size_t)1 << 16) && same_bases && p.B <= 16384 &&
+    if (ctx->small_path != 0 && n <= ((size_t)1 << 16) && p.B <= 16384 &&
         (size_t)Wt * p.B + n * (size_t)Wt / kmax + 1 <= (ws.cap_counts < ws.cap_tasks ? ws.cap_counts : ws.cap_tasks)) {  // smsm.hip: 4-5 launches in all
-        int rc = smsm_enqueue(ctx, ws, d_bases, members.base_off[0], n, p, Wt, kmax);
+        int rc = smsm_enqueue(ctx, ws, d_bases, offs, n, p, Wt, kmax);  // (one base offset per member, as the scatter below)
         if (rc) return rc;
         HALO_HIP(hipGetLastError());
         if (!ctx->sink_done) HALO_HIP(hipMemcpyAsync(ws.h_winsum, ws.d_winsum, (size_t)Wt * 96, hipMemcpyDeviceToHost, s));

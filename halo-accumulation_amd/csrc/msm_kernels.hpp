@@ -43,7 +43,6 @@ constexpr uint32_t TBL_ORDER_RUN = 8;  // consecutive ranks of one range in a wa
 constexpr uint32_t META_OVF = 141;        // table pipeline: records reserved in the overflow region of `order`
 
 struct MemberScalars { const uint64_t *p[MSM_MAX_BATCH]; };
-struct MemberOffsets { uint32_t v[MSM_MAX_BATCH]; };
 struct TblScalars { const uint64_t *p[MSM_MAX_BATCH]; };
 struct RcShape { int lg_rows = 0, lg_cols = 0, per = 0; };
 static inline uint32_t rc_points(const RcShape &r) { return r.per ? 2u * ((1u << r.lg_rows) + (1u << r.lg_cols)) / 64u : 0u; }  // (S, T) pairs x 2, per set

@@ -3,6 +3,7 @@
 // open / random-instance batch, the prover batch -- and their entry points.  What they share with the single calls is declared
 // in pcdl_internal.hpp; the slots, streams and outcome reports they share with each other (and with wire.hip's decode batch) in
 // internal.hpp: idle_slots, StreamGuard, report_members.
+#include "curve.hpp"  // (AFF_STRIDE: the staged keys of the folded schedule)
 #include "pcdl_internal.hpp"
 
 namespace halo {
@@ -486,6 +487,13 @@ static int acc_verifier_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, 
 // pool for the group's members -- the other slots' groups run on the device.  Every group runs through all its rounds before
 // its slot takes the next one, so the staging holds G x S members.  Host arithmetic is the single open's, term for term
 // (pcdl_open_dev, halo_ipa_finish's last-round U), so every proof word is the one halo_pcdl_open writes.
+//
+// Above the no-fold size (n up to OPEN_MAX_N, where open_fold_route says so) the group takes the single open's folded schedule:
+// while the key has more points than the no-fold size, k = 1 or 2 rounds in the no-fold form over it, then ONE member-batched fold
+// launch of k levels (ipa.hip k_fold_points*_batch) into the members' staged keys, n / 2 points each in the group's staging.
+// From the first fold on a member's key is its own: the batched MSMs run over the staged keys with one base offset per member
+// (MsmBatch::base_off; the small pipeline takes them, smsm.hip).  The folded key does not depend on the schedule and every point
+// written is normalised, so the proofs are still the loop's.
 struct OpenJob {
     size_t idx = 0, deg = 0;
     uint64_t s_start = 0;                // rng state before the member's first draw (the single call's *rng_state)
@@ -504,19 +512,42 @@ static size_t open_group_size(const halo_ctx *ctx, size_t n) {
     // (development library: the sweep of tools/time_open_batch.py)
     return (size_t)group_size(ctx, n, dev_hooks().open_group, OPEN_MAX_GROUP, 2);
 }
+// s'[2t + u] = s[t] xi^u: the newest challenge is the lowest index bit (what k_nofold_s_update computes on the device)
+static void open_fold_products(std::vector<Fr> &s, const Fr &xi) {
+    std::vector<Fr> out(2 * s.size());
+    for (size_t t = 0; t < s.size(); ++t) { out[2 * t] = s[t]; out[2 * t + 1] = s[t] * xi; }
+    s.swap(out);
+}
+// Does a batch of n-point opens above the no-fold size take the folded schedule (OpenGroups::fold_keys), or the loop?  The hook
+// "open_batch_fold" forces either (1 / 2); the default follows the measurements of tools/time_open_batch.py --fold (DESIGN.md
+// 4.5): the folded schedule only at the sizes where every run of it was faster than every run of the loop -- 2^15 and 2^16
+// points (2.7 - 3.2 times the loop's speed for 8 and for 64 members, all three entry points).  Smaller sizes come above the no-fold
+// size only under a lowered switch (halo_set_ipa_switch, the development library): not measured, so the loop unless forced.
+static bool open_fold_route(size_t n) {
+    const int forced = dev_hooks().open_fold;
+    if (forced) return forced == 1;
+    return n >= ((size_t)1 << 15);
+}
 constexpr size_t OPEN_AUX_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS + OPEN_PART_WORDS + OPEN_OUT_WORDS);
 // (the prover batch's third coefficient source: up to HACC_TABLES polynomials h_i per pass of a group, see h_accumulate_group)
 constexpr size_t HACC_TABLES = 32;
 constexpr size_t HACC_PIN_WORDS = OPEN_MAX_GROUP * HACC_REC_WORDS + HACC_TABLES * (16 + 2) * 4;  // lg n <= 16 (OPEN_MAX_N)
-constexpr size_t OPEN_PIN_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS + OPEN_OUT_WORDS) + HACC_PIN_WORDS + 4;  // per slot; + the element one
+constexpr size_t FOLD_PIN_WORDS = OPEN_MAX_GROUP * FOLD_DIG_WORDS / 2;  // the members' digit records of a key fold (32-bit words, two to a word here)
+constexpr size_t OPEN_PIN_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS + OPEN_OUT_WORDS) + HACC_PIN_WORDS + FOLD_PIN_WORDS + 4;  // per slot; + the element one
 
 // Slot j's regions of the staging.  Device (`per` words a slot): the group's member vectors (G x ms: c | z | s | s' | F_L | F_R |
 // p_bar of n scalars each), then its window tables | constants | partial sums | results | the prover batch's tables.  Pinned
 // (OPEN_PIN_WORDS a slot): the tables | constants (one upload) | results (one download) | the prover batch's records | the
-// element one.  Cached launch graphs and the kernels of ipa.hip (OPEN_*_WORDS) know this layout.
+// fold digit records | the element one.  Cached launch graphs and the kernels of ipa.hip (OPEN_*_WORDS) know this layout.
+// A group above the no-fold size (keystride > 0) has two more device regions behind the others, at `fold_off` words: the members'
+// folded keys, keystride = n / 2 points of AFF_STRIDE words each, and their digit records (FOLD_PIN_WORDS).
 struct OpenStage {
     uint64_t *d_base = nullptr, *h_base = nullptr;
     size_t per = 0, n = 0, ms = 0, G = 0;
+    size_t fold_off = 0, keystride = 0;
+    uint32_t *d_keys(int j) const { return reinterpret_cast<uint32_t *>(d_base + (size_t)j * per + fold_off); }
+    uint32_t *d_digs(int j) const { return d_keys(j) + G * keystride * AFF_STRIDE; }
+    uint32_t *h_digs(int j) const { return reinterpret_cast<uint32_t *>(h_one(j) - FOLD_PIN_WORDS); }
     uint64_t *vec(int j, int k) const { return d_base + (size_t)j * per + 4 * n * (size_t)k; }  // member 0's vector k; member b at + b * ms
     uint64_t *d_tabs(int j) const { return d_base + (size_t)j * per + G * ms; }
     uint64_t *d_consts(int j) const { return d_tabs(j) + OPEN_MAX_GROUP * OPEN_TAB_WORDS; }
@@ -543,7 +574,21 @@ struct OpenGroups {
     size_t n, lg, G, ms;
     bool draw, commit, hiding, accumulated, u_from_last_round;  // draw: p from the stream; commit: C = commit(p) rides in step 0's MSM
     OpenStage st;
-    struct Flight { long g = -1; size_t first = 0, cnt = 0, step = 0; int msm = 0; bool flip = false; std::vector<size_t> need_u; };
+    size_t nofold;  // the key size from which on the rounds fold no more (>= n: never folded, the no-fold form throughout)
+    // M: points of the key the group's MSMs run over -- n over the context's key until the first fold, then each member's own staged
+    // key (OpenStage::d_keys).  s_len: entries of s, the products of the challenges since the key was last folded (s_host: the
+    // host's copy while a fold is ahead); fold_k: levels of the next fold (0: none ahead), due after fold_k rounds over this key.
+    struct Flight {
+        long g = -1;
+        size_t first = 0, cnt = 0, step = 0;
+        int msm = 0;
+        bool flip = false;
+        std::vector<size_t> need_u;
+        size_t M = 0, s_len = 1;
+        int fold_k = 0;
+        bool staged = false;
+        std::vector<Fr> s_host[OPEN_MAX_GROUP];
+    };
     std::vector<Flight> fl;
 
     hipStream_t stream(int j) const { return ctx->streams[slots[j]]; }
@@ -556,10 +601,24 @@ struct OpenGroups {
         HALO_HIP(hipMemcpyAsync(st.d_consts(j), st.h_consts(j), fl[j].cnt * OPEN_CONST_WORDS * 8, hipMemcpyHostToDevice, stream(j)));
         return HALO_OK;
     }
-    int enqueue_msm(int j, const MsmBatch &mb) {  // the step's MSMs over the key as one batched launch sequence
-        int rc = msm_enqueue_batch(ctx, slots[j], ctx->d_bases, mb, true, n);
+    // the step's MSMs over the key as one batched launch sequence; member_of[k]: the member array k belongs to (its own key once folded)
+    int enqueue_msm(int j, MsmBatch &mb, const size_t *member_of) {
+        const Flight &f = fl[j];
+        for (int k = 0; k < mb.count && f.staged; ++k) mb.base_off[k] = (uint32_t)(member_of[k] * st.keystride);
+        int rc = msm_enqueue_batch(ctx, slots[j], f.staged ? st.d_keys(j) : ctx->d_bases, mb, true, f.M);
         if (!rc) fl[j].msm = mb.count;
         return rc;
+    }
+    // levels of the fold that follows the next rounds over a key of M points: two at a time down to the no-fold size
+    int fold_levels_at(size_t M) const {
+        if (M <= nofold) return 0;
+        return M / nofold >= 4 ? 2 : 1;
+    }
+    void key_reset(Flight &f, size_t M) {  // a fresh key: s = (1)
+        f.M = M;
+        f.s_len = 1;
+        f.fold_k = fold_levels_at(M);
+        for (size_t b = 0; b < f.cnt; ++b) f.s_host[b].assign(1, Fr::one());
     }
 
     // step 0: coefficients (copied, generated, or accumulated), p(z), the powers of z, p_bar; the commits as one batched MSM
@@ -569,6 +628,7 @@ struct OpenGroups {
         f.g = (long)g;
         f.first = g * G;
         f.cnt = jobs.size() - f.first < G ? jobs.size() - f.first : G;
+        key_reset(f, n);
         for (size_t b = 0; b < f.cnt; ++b) {
             const OpenJob &jb = jobs[f.first + b];
             OpenConst &k = st.h_consts(j)[b];
@@ -612,7 +672,7 @@ struct OpenGroups {
             for (size_t b = 0; b < f.cnt; ++b) mb.scalars[mb.count++] = st.vec(j, 0) + b * ms;
         if (hiding)
             for (size_t b = 0; b < f.cnt; ++b) mb.scalars[mb.count++] = st.vec(j, 6) + b * ms;
-        return mb.count ? enqueue_msm(j, mb) : HALO_OK;
+        return mb.count ? enqueue_msm(j, mb, nullptr) : HALO_OK;  // (the context's key: no member has one of its own yet)
     }
     // round r of slot j's group: F_L, F_R from c and s, the dot products, L and R of every member as one batched MSM
     int enqueue_round(int j, size_t r) {
@@ -621,7 +681,7 @@ struct OpenGroups {
         int rc;
         {
             StreamGuard on_slot(ctx, stream(j));
-            rc = open_batch_expand(ctx, (int)f.cnt, st.vec(j, 0), s_cur(j), ms, mcur, n, st.vec(j, 4), st.vec(j, 5));
+            rc = open_batch_expand(ctx, (int)f.cnt, st.vec(j, 0), s_cur(j), ms, mcur, f.M, st.vec(j, 4), st.vec(j, 5));
             if (!rc) rc = open_batch_dots(ctx, (int)f.cnt, st.vec(j, 0), st.vec(j, 1), ms, mcur / 2, st.d_parts(j), st.d_outs(j));
             if (!rc && mcur == 2)  // the last round: c0, c1 travel with its results (halo_ipa_finish's U from this round's MSMs)
                 for (size_t b = 0; b < f.cnt; ++b)
@@ -630,9 +690,13 @@ struct OpenGroups {
         }
         if (!rc) {
             MsmBatch mb;  // L, R of member 0, L, R of member 1, ..
+            size_t member_of[MSM_MAX_BATCH];
             mb.count = 2 * (int)f.cnt;
-            for (int k = 0; k < mb.count; ++k) mb.scalars[k] = st.vec(j, 4 + (k & 1)) + (size_t)(k >> 1) * ms;
-            rc = enqueue_msm(j, mb);
+            for (int k = 0; k < mb.count; ++k) {
+                member_of[k] = (size_t)(k >> 1);
+                mb.scalars[k] = st.vec(j, 4 + (k & 1)) + member_of[k] * ms;
+            }
+            rc = enqueue_msm(j, mb, member_of);
         }
         f.step = 1 + r;
         return rc;
@@ -685,11 +749,15 @@ struct OpenGroups {
         return enqueue_round(j, 0);
     }
     // after round r = step - 1 (:203-224): L, R with their H' terms, the next challenge and its inverse; the fold; the next round,
-    // or, after the last one, U and c
+    // or, after the last one, U and c.  Above the no-fold size the KEY is folded here too, every fold_k rounds: the host keeps each
+    // member's challenge products (s'[2t + u] = s[t] xi^u, what k_nofold_s_update_batch computes) and, when the fold is due, turns
+    // s[1] (one level) or s[1..3] (two) into the member's digit record -- the scalars and digits of the single open's deferred fold
+    // (abi.hip ipa_round_fold_impl) -- then ONE batched fold launch writes every member's key and s starts again from (1).
     int after_round(int j, const Point *pts, bool *through) {
         Flight &f = fl[j];
         const size_t r = f.step - 1;
         const bool last = r + 1 == lg;
+        const bool fold_key = f.fold_k && 2 * f.s_len == ((size_t)1 << f.fold_k);  // this round's challenge completes the fold's scalars
         pool_run(f.cnt, [&](size_t b) {
             OpenJob &jb = jobs[f.first + b];
             const uint64_t *o = st.out_of(j, b);
@@ -704,16 +772,39 @@ struct OpenGroups {
             jb.xi = xi_next;
             if (last) { jb.last_xi = xi_next; jb.last_xi_inv = xi_inv; }
             open_const_xi(&st.h_consts(j)[b], xi_next, xi_inv);
+            if (f.fold_k) {
+                open_fold_products(f.s_host[b], xi_next);
+                if (fold_key) fold_digits(&f.s_host[b][1], f.fold_k, st.h_digs(j) + FOLD_DIG_WORDS * b);
+            }
         });
         {
             StreamGuard on_slot(ctx, stream(j));  // :216-224
             int rc = upload_consts(j);
             const uint64_t *s_in = s_cur(j);
             f.flip = !f.flip;
-            if (!rc) rc = open_batch_fold(ctx, (int)f.cnt, st.vec(j, 0), st.vec(j, 1), s_in, s_cur(j), ms, n >> (r + 1), (size_t)1 << r, st.d_consts(j));
+            if (!rc) rc = open_batch_fold(ctx, (int)f.cnt, st.vec(j, 0), st.vec(j, 1), s_in, s_cur(j), ms, n >> (r + 1), f.s_len, st.d_consts(j));
+            f.s_len *= 2;
+            if (!rc && fold_key) rc = fold_keys(j);
             if (rc) return rc;
         }
         return last ? finish_u(j, through) : enqueue_round(j, r + 1);
+    }
+    // The members' keys of M points folded fold_k levels into their staged keys (:218 applied fold_k times): from the context's key
+    // the first time (one source for all), then each member's own, in place (a lane reads the indices j + t m and writes j).
+    // On the slot's stream, behind the round's scalar folds; s = (1) again for the rounds over the new key.
+    int fold_keys(int j) {
+        Flight &f = fl[j];
+        const size_t m = f.M >> f.fold_k;
+        HALO_HIP(hipMemcpyAsync(st.d_digs(j), st.h_digs(j), f.cnt * FOLD_DIG_WORDS * 4, hipMemcpyHostToDevice, stream(j)));
+        const uint32_t *src = f.staged ? st.d_keys(j) : ctx->d_bases;
+        const size_t src_stride = f.staged ? st.keystride : 0;
+        int rc = f.fold_k == 2 ? ipa_fold_points4_batch(ctx, (int)f.cnt, src, src_stride, st.d_keys(j), st.keystride, m, st.d_digs(j))
+                               : ipa_fold_points_batch(ctx, (int)f.cnt, src, src_stride, st.d_keys(j), st.keystride, m, st.d_digs(j));
+        for (size_t b = 0; b < f.cnt && !rc; ++b)
+            HALO_HIP(hipMemcpyAsync(s_cur(j) + b * ms, st.h_one(j), 32, hipMemcpyHostToDevice, stream(j)));
+        f.staged = true;
+        key_reset(f, m);
+        return rc;
     }
     // :230-231 as halo_ipa_finish: U from the last round's MSMs where both coefficients are non-zero, else U = <s, G> (one more step)
     int finish_u(int j, bool *through) {
@@ -742,7 +833,7 @@ struct OpenGroups {
             MsmBatch mb;
             mb.count = (int)f.need_u.size();
             for (int k = 0; k < mb.count; ++k) mb.scalars[k] = s_cur(j) + f.need_u[(size_t)k] * ms;
-            rc = enqueue_msm(j, mb);
+            rc = enqueue_msm(j, mb, f.need_u.data());
         }
         f.step = lg + 1;
         return rc;
@@ -798,15 +889,24 @@ struct OpenGroups {
 static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, bool draw, bool commit, const int *slots_in, int S, bool *ran) {
     *ran = false;
     const size_t n = d + 1, lg = ilog2(n), A = jobs.size();
-    if (A == 0 || n < 2 || n > ctx->nofold_size || n > OPEN_MAX_N) return HALO_OK;
+    if (A == 0 || n < 2 || n > OPEN_MAX_N || ctx->nofold_size < 2) return HALO_OK;  // (a switch of 0 / 1: always fold, the loop)
+    const bool folds = n > ctx->nofold_size;  // the rounds fold the key down to the no-fold size: each member into a staged key of its own
+    const bool accumulated = jobs[0].hs != nullptr;
+    if (folds && (accumulated || !open_fold_route(n))) return HALO_OK;  // (the prover batch keeps its own gate)
     size_t G = open_group_size(ctx, n);
+    for (size_t M = n; folds && M > ctx->nofold_size;) {  // ... within the bucket limit at every key size the rounds run over
+        M >>= M / ctx->nofold_size >= 4 ? 2 : 1;
+        const size_t g = open_group_size(ctx, M);
+        if (g < G) G = g;
+    }
     if (G > A) G = A;
     const size_t ng = (A + G - 1) / G;
     if ((size_t)S > ng) S = (int)ng;
     const size_t ms = 7 * 4 * n;  // words of one member's vectors: c | z | s | s' | F_L | F_R | p_bar
-    const bool accumulated = jobs[0].hs != nullptr;
     const size_t hacc_words = accumulated ? hacc_stage_words(OPEN_MAX_GROUP, lg, HACC_TABLES) : 0;
-    const size_t per = G * ms + OPEN_AUX_WORDS + hacc_words;  // words of one slot's group
+    const size_t fold_off = G * ms + OPEN_AUX_WORDS + hacc_words, keystride = folds ? n / 2 : 0;
+    // words of one slot's group (+ above the no-fold size: n / 2 points of 128 bytes per member for its key, and the digit records)
+    const size_t per = fold_off + (folds ? G * keystride * (AFF_STRIDE / 2) + FOLD_PIN_WORDS : 0);
     size_t have = check_stage(ctx, (size_t)S, per * 8);
     if (have == 0) return HALO_OK;
     if ((size_t)S > have) S = (int)have;
@@ -819,9 +919,9 @@ static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, b
         for (int k = 0; k < HALO_SLOTS; ++k) Fr::one().store(ctx->h_open_pinned + k * OPEN_PIN_WORDS + OPEN_PIN_WORDS - 4);
     }
     *ran = true;
-    const OpenStage st{ctx->d_check_stage, ctx->h_open_pinned, per, n, ms, G};
+    const OpenStage st{ctx->d_check_stage, ctx->h_open_pinned, per, n, ms, G, fold_off, keystride};
     // (hiding: the same for every member of a batch)
-    OpenGroups groups{ctx, jobs, slots_in, S, n, lg, G, ms, draw, commit, jobs[0].hiding, accumulated, tuning().u_from_last_round, st, {}};
+    OpenGroups groups{ctx, jobs, slots_in, S, n, lg, G, ms, draw, commit, jobs[0].hiding, accumulated, tuning().u_from_last_round, st, ctx->nofold_size, {}};
     return groups.run();
 }
 
@@ -880,8 +980,10 @@ static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const 
     // (the single call's body runs on slots 0 and 1: only with both idle)
     const bool alone = commit && !gen && jobs.size() == 1 && dev_hooks().open_group <= 0 && S >= 2 && slots[0] == 0 && slots[1] == 1;
     bool ran = false;
+    ctx->open_batch_members = 0;  // (halo_ctx_info 10)
     int rc = alone ? HALO_OK : open_batch_dev(ctx, d, jobs, gen, commit, slots, S, &ran);  // (no jobs: nothing runs)
     if (rc) return rc;
+    if (ran) ctx->open_batch_members = jobs.size();
     if (!ran) {
         for (OpenJob &jb : jobs) {
             uint64_t st = jb.s_start;

@@ -41,9 +41,11 @@ HALO_DEV uint32_t bucket_tasks(uint32_t c, uint32_t kmax, uint32_t wave_task) { 
 // has 256 - c (W - 1) bits left) and scalars below the group order only reach the first top_rb * R of them, so its R
 // blocks split THAT stretch (top_rb buckets each, the last one takes the rest up to top_span) instead of idling while
 // block 0 sorts the whole window.
+// offs: one base offset (in points) per member of a batch, added to the point indices a block writes; a block sorts one window,
+// so one member's (the members need not share their points: the open batch's folded keys).
 __global__ __launch_bounds__(1024) void k_smsm_sort(const uint16_t *__restrict__ digits, uint32_t n, uint32_t B, uint32_t R, uint32_t kmax, uint32_t wave_task,
                                                     uint32_t top_w, uint32_t Wm, uint32_t top_span, uint32_t top_rb,
-                                                    uint32_t base_off, uint32_t *__restrict__ sorted, uint32_t *__restrict__ bk_first,
+                                                    MemberOffsets offs, uint32_t *__restrict__ sorted, uint32_t *__restrict__ bk_first,
                                                     uint32_t *__restrict__ bk_nt, uint32_t *__restrict__ task_rec, uint32_t *__restrict__ wt,
                                                     uint32_t *__restrict__ order, uint32_t *__restrict__ meta) {
     // One private histogram per wave: the top window keeps only a few scalar bits, so all n of its digits fall into ~100
@@ -63,6 +65,7 @@ __global__ __launch_bounds__(1024) void k_smsm_sort(const uint16_t *__restrict__
             for (uint32_t b = top_span + tid; b < B; b += 1024) { bk_first[w * B + b] = 0; bk_nt[w * B + b] = 0; }
     }
     uint32_t NB = hi_b - lo_b;  // buckets this block owns (<= RB)
+    const uint32_t base_off = offs.v[w / Wm];  // this window's member: the same for the whole block
     const uint16_t *dg = digits + (size_t)w * n;
 #ifdef SMSM_TIMING
     uint64_t tm[8]; int tmi = 0;
@@ -497,7 +500,7 @@ __global__ __launch_bounds__(256, 2) void k_smsm_final(const uint32_t *__restric
 // Called from msm_enqueue_launches (msm.hip) after k_msm_recode; digits are in ws.d_canon.  Buffer reuse: d_sorted
 // (entries), d_starts (first task of a bucket), d_counts (tasks of a bucket), d_task_g (task records), d_buckets
 // (partials), d_seg, d_meta[0] (task count), d_meta[64 + w] (tickets), d_winsum.
-int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, uint32_t base_off, size_t n, const MsmPlan &p, uint32_t Wt,
+int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MemberOffsets &offs, size_t n, const MsmPlan &p, uint32_t Wt,
                  uint32_t kmax) {
     const uint16_t *d_digits = reinterpret_cast<const uint16_t *>(ws.d_canon);
     // entries per wave task: 8 per lane where the launch is throughput-bound, 2 per lane for the latency-bound small ones
@@ -525,7 +528,7 @@ int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, uint3
         }
     }
     HALO_LAUNCH(ctx, "k_smsm_sort", k_smsm_sort, dim3(Wt * R), dim3(1024), lds, d_digits, (uint32_t)n, p.B, R, kmax, wave_task, top_w, Wm, top_span, top_rb,
-                base_off, ws.d_sorted, ws.d_starts, ws.d_counts, ws.d_task_g, ws.d_order, ws.d_biglist, ws.d_meta);
+                offs, ws.d_sorted, ws.d_starts, ws.d_counts, ws.d_task_g, ws.d_order, ws.d_biglist, ws.d_meta);
     size_t max_tasks = (size_t)Wt * p.B + n * (size_t)Wt / kmax + 1;
     if (max_tasks > ws.cap_tasks || max_tasks > ws.cap_counts) { set_error("msm: small-path tasks exceed the workspace"); return HALO_E_ARG; }
     // wave tasks: one per bucket of more than 4 kmax entries plus one per further WAVE_TASK entries (3 words each in d_order)

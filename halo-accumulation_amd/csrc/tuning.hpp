@@ -58,6 +58,7 @@ struct DevHooks {
     int batch_stage_fail = 0;  // "batch_stage_fail"   the staging of the check and open batches is refused: one member at a time
     int check_group = 0;       // "check_batch_group"  members per MSM launch of halo_pcdl_check_batch (1..8; 0: the measured default)
     int open_group = 0;        // "open_batch_group"   members per launch of halo_pcdl_open_batch (1..4; 0: the measured default)
+    int open_fold = 0;         // "open_batch_fold"    the open batches above the no-fold size: 1 the folded schedule wherever it applies, 2 the loop (0: the measured default)
     int commit_group = 0;      // "commit_batch_group" members per MSM launch of halo_pcdl_commit_batch / _dev_batch (1..8; 0: the rule of the check batch)
     int verifier_min = 0;      // "verifier_batch_min" relations from which halo_acc_verifier_batch launches (>= 1; 0: the measured default)
     long slide_min = 0;        // "table_slide_min"    keys from this many points take the c = 20 table plans and the all-shifts table (>= 4096; 0: 2^20)

@@ -359,16 +359,21 @@ int halo_random_instance(halo_ctx *ctx, uint64_t *rng_state, size_t d, uint64_t 
  * - Before any work (status not written, *rng_state unchanged): a null ctx or a null array with m > 0: HALO_E_ARG; d + 1 not a
  *   power of two or above the key: HALO_E_ASSERT with the single call's messages.  m = 0: HALO_OK, nothing touched.
  * - Where the single open takes its no-fold form (2 <= d + 1 <= the no-fold size, 2^14 by default) groups of up to 4 members run
- *   in member-batched launches: one batched MSM per round for the L and R of the whole group.  Groups rotate over the slots that
+ *   in member-batched launches: one batched MSM per round for the L and R of the whole group.  At d + 1 = 2^15 and 2^16 a group
+ *   also folds its keys as the single open does -- two rounds over the unfolded key, then one member-batched fold launch that
+ *   writes every member's folded key into the group's device state (n / 2 points of 128 bytes per member more), the later rounds
+ *   over those keys -- measured 2.7 - 3.2 times as fast as the loop; halo_ctx_info(ctx, 10) says how many
+ *   members of the last call ran this way.  Groups rotate over the slots that
  *   are idle on entry (a caller's MSM in flight on another slot is left alone; no idle slot: HALO_E_ARG).  Their device state is
- *   optional memory (halo_set_memory_budget; it only grows and goes with the context): without it, and above the no-fold size,
+ *   optional memory (halo_set_memory_budget; it only grows and goes with the context): without it, and above 2^16 points,
  *   the members run one at a time as halo_pcdl_open runs them, with the same results.  A multi-device context runs the batch
  *   on its first device, with the proofs halo_pcdl_open gives there. */
 int halo_pcdl_open_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *Cs,
                          const uint64_t *zs, const uint64_t *ws /*nullable*/, uint64_t *proofs_out, int *status /*nullable*/);
 /* benches/acc.rs:15-29 random_instance, m times: instances_out = m Instance blobs at stride halo_instance_words(lg(d+1)), every
  * word and the final *rng_state as m calls of halo_random_instance in order (draws per member: d', w, the d' + 1 coefficients,
- * z, then its hiding open's).  The conventions of halo_pcdl_open_batch; d < 2: the single call's assert. */
+ * z, then its hiding open's).  The conventions of halo_pcdl_open_batch, its batched sizes (d + 1 up to 2^16) included; d < 2: the
+ * single call's assert. */
 int halo_random_instance_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, size_t m, uint64_t *instances_out);
 
 /* pcdl::commit (pcdl.rs:99-110) of m polynomials of degree bound d at once.  coeffs = m x (d + 1) x 4 words in the layout of
@@ -409,10 +414,10 @@ int halo_instance_from_poly(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *
  * member order (draws per member are the open's only: a hiding member draws deg scalars for q, then w_bar).  A hiding member with a
  * constant polynomial fails as halo_pcdl_open does: no randomness consumed, blob zero-filled, status[i] = HALO_E_ASSERT, the others
  * unaffected.  The conventions of halo_pcdl_open_batch, with the commit's messages for d + 1 not a power of two or above the key.
- * Where that call batches (2 <= d + 1 <= the no-fold size, staging available) the members' commits join the first batched MSM
+ * Where that call batches (2 <= d + 1 <= 2^16, staging available) the members' commits join the first batched MSM
  * of their group; elsewhere, and for m = 1 with slots 0 and 1 idle (measured faster alone), the members run one at a time
  * through halo_instance_from_poly's body.  That body, like halo_pcdl_open's in halo_pcdl_open_batch, runs on slot 0 and may
- * borrow slot 1: above the no-fold size and without the staging, a caller's MSM in flight on one of these two makes the call
+ * borrow slot 1: above 2^16 points and without the staging, a caller's MSM in flight on one of these two makes the call
  * return HALO_E_ARG ("slot already has an MSM in flight") at the first member that needs the slot. */
 int halo_instance_from_poly_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *zs,
                                   const uint64_t *ws /*nullable*/, uint64_t *instances_out, int *status /*nullable*/);
@@ -497,7 +502,9 @@ int halo_set_memory_budget(halo_ctx *ctx, size_t bytes);
  * that device), 5 = status of the fold table, 6 = status of the MSM table: 0 nothing yet, 1 memory requested, 2 built,
  * 3 over the budget, 4 allocation failed (tried again later), 5 switched off; 7 = microseconds the MSM table took to build
  * (without its allocation), 8 = rows of the MSM table (13 / 15: fixed windows; 255: every shift), 9 = plan of the launch
- * enqueued last (0: no table pipeline, 1: its fixed windows, w + 1: sliding windows of at most w bits) */
+ * enqueued last (0: no table pipeline, 1: its fixed windows, w + 1: sliding windows of at most w bits), 10 = how many members of
+ * the last halo_pcdl_open_batch / halo_random_instance_batch / halo_instance_from_poly_batch on this context went through
+ * member-batched launches (0: they ran one at a time) */
 size_t halo_ctx_info(const halo_ctx *ctx, int what);
 /* MSM tuning: fixed-base tables.  -1 (default): an MSM of n >= 2^20 points over the context's own key uses the table
  * T[w][i] = 2^(20 w) G_i (13 x 128 bytes per point of the key, built on the first such MSM): 13 instead of 16 mixed

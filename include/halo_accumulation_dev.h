@@ -26,7 +26,9 @@ extern "C" {
  * halo_pcdl_commit_batch / halo_pcdl_commit_dev_batch / halo_instance_from_poly_batch is refused, as over the
  * memory budget: one member at a time; halo_acc_verifier_batch: its sums on the host pool), "check_batch_group" (members per MSM launch of the check batch, 1..8; 0: the measured
  * default), "open_batch_group" (members per launch of the open and prover batches and of halo_instance_from_poly_batch, 1..4; 0: the
- * measured default), "commit_batch_group" (members per MSM launch of halo_pcdl_commit_batch / halo_pcdl_commit_dev_batch, 1..8; 0: the
+ * measured default), "open_batch_fold" (halo_pcdl_open_batch / halo_random_instance_batch / halo_instance_from_poly_batch above the
+ * no-fold size: 0 the measured default, 1 the folded schedule with member-batched key folds wherever it applies, 2 never: one member
+ * at a time; another value is HALO_E_ARG), "commit_batch_group" (members per MSM launch of halo_pcdl_commit_batch / halo_pcdl_commit_dev_batch, 1..8; 0: the
  * rule of the check batch), "verifier_batch_min" (relations
  * from which halo_acc_verifier_batch runs its sums on the device, >= 1; 0: the measured default), "table_slide_min" (keys from this many points, >= 4096, take the c = 20 table plans and
  * the all-shifts table with its sliding-window recode; 0: 2^20), "decode_batch_min" (finite points
@@ -56,7 +58,8 @@ int halo_dev_fr_plan(halo_ctx *ctx, int which, size_t n, long out[4]);
 int halo_dev_dot2_cross(halo_ctx *ctx, const uint64_t *c, const uint64_t *z, size_t m, uint64_t out[8]);
 /* What the library read from the environment at its first use (csrc/tuning.hip), by field: "host_split_set", "host_pieces", "host_split0".."host_split3",
  * "fold_table_after", "graph_cache", "pow_e", "dot_blocks", "spin_us", "graphs", "memory_budget" (MiB, -1 unset), "trace", "tagged"; -1 for an
- * unknown name.  Also "commit_batch_group": that hook of halo_dev_hook as it stands now (0 after "reset").  Host only. */
+ * unknown name.  Also "commit_batch_group" and "open_batch_fold": those hooks of halo_dev_hook as they stand now (0 after "reset").
+ * Host only. */
 long halo_dev_tuning(const char *name);
 
 /* `reps` back-to-back launches of one bandwidth-side Fr kernel over n elements of the context's scratch memory (no host
@@ -148,6 +151,27 @@ int halo_dev_batch_to_affine(halo_ctx *ctx, const uint64_t *pts_jac, size_t m, u
  * form the levels do not have, a table form with a foreign key, another size or in_place. */
 int halo_dev_fold_points(halo_ctx *ctx, const uint64_t *key_affine, size_t n, int levels, const uint64_t *scalars, int form, int in_place,
                          uint64_t *out_affine);
+
+/* The member-batched key folds of the open batches (k_fold_points_batch, k_fold_points4_batch, k_fold_points4_quad_batch: blockIdx.y =
+ * member, each member's digits in a record in device memory) on their own, through the product's launchers ipa_fold_points_batch /
+ * ipa_fold_points4_batch: `members` (1 .. 4) folds in ONE launch, member b's result -- out_affine + b * m * 8 words -- the one
+ * halo_dev_fold_points gives for its key and its scalars.  scalars: members x (xi | s1 s2 s3) x 4 Montgomery words.
+ * key_affine = NULL: the first n points of the context's own key, read by every member (shared must be non-zero); else n x 8 words
+ * read by every member (shared != 0), or members x n x 8 words, member b's key at b * n points (shared == 0).  A shared source is
+ * folded into a destination of members x m points; per-member sources are folded in place, as the open batch folds its staged keys.
+ * The context's own key is never written.  form: 0 = the launchers' rule over all members x m outputs; 1 / 2 = one / two outputs per
+ * lane; 3 = one output per quad (levels 2).  n, levels and the null checks as for halo_dev_fold_points; HALO_E_ARG also for members
+ * outside 1 .. 4, a form the levels do not have, key_affine = NULL with shared == 0. */
+int halo_dev_fold_points_batch(halo_ctx *ctx, const uint64_t *key_affine /*NULL: the context's key, shared*/, size_t n, int levels,
+                               const uint64_t *scalars /*members x (1 | 3) x 4*/, int members /*1..4*/, int shared /*0: key_affine holds members x n points*/,
+                               int form, uint64_t *out_affine /*members x m x 8*/);
+
+/* One batched MSM launch sequence (msm_enqueue_batch) over the context's key with one base offset per member, on slot 0: member b
+ * is sum_i scalars[b][i] * G[offs[b] + i], i < n -- what halo_msm(ctx, offs[b], n, scalars_b) gives, limb for limb.  Up to 2^16
+ * points the members run through the small pipeline whatever their offsets (k_smsm_sort takes one per member).  HALO_E_ARG: count
+ * outside 1 .. 8, a null pointer, a range that leaves the key, slot 0 busy. */
+int halo_dev_msm_offsets(halo_ctx *ctx, const size_t *offs /*count entries, points*/, size_t n, const uint64_t *scalars /*host, count x n x 4*/,
+                         int count /*1..8*/, int scalars_are_mont, uint64_t *out_jac /*count x 12*/);
 
 /* Entries [off, off + count) of row `row` of the context's MSM table (csrc/msm_table.hip: T[w][i] = 2^(c w) G_i for the 13 and 15
  * rows, T[j][i] = 2^j G_i for the 255) as arkworks affine words, count x 8, Montgomery form, (0, 0) = infinity: what

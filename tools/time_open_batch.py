@@ -4,7 +4,12 @@ halo_random_instance against one halo_random_instance_batch.  A 2^14-point URS c
 k in {10, 100, 1000}; a sweep of the members per launch (the development hook open_batch_group) at k = 100; with --big a k = 4
 leg at n = 2^20 on a 2^20-point context with the fold table fixed off (halo_set_fold_table 0), so that no table build lands
 inside a timed run.  The proofs, instances and final RNG states of both ways must be equal.  Prints one JSON line; every time
-is the median of --reps alternating runs, in ms."""
+is the median of --reps alternating runs, in ms.
+With --fold (alone: the other legs are skipped) the sizes ABOVE the no-fold size, n = 2^15 and 2^16 on a 2^16-point context, m in
+{8, 64} hiding members, for the open batch, halo_random_instance_batch and halo_instance_from_poly_batch: the same batched call
+with the development hook open_batch_fold = 2 (the loop over the single calls' bodies) and = 1 (the folded schedule with
+member-batched key folds), alternating in one process; medians of --reps (at least 5) runs with the least and the greatest, and
+"won" where every run of the folded schedule was faster than every run of the loop."""
 import argparse
 import ctypes as C
 import json
@@ -81,6 +86,62 @@ def ri_batched(ctx, d, k, state):
     return ms, out, st.value
 
 
+def ifp_batched(ctx, d, args, k, state):
+    ps, _, zs, ws = (np.ascontiguousarray(a[:k]) for a in args)
+    out = np.zeros((k, ctx.lib.halo_instance_words((d + 1).bit_length() - 1)), dtype=np.uint64)
+    status = (C.c_int * k)()
+    st = C.c_uint64(state)
+    t = time.perf_counter()
+    rc = ctx.lib.halo_instance_from_poly_batch(ctx.h, C.byref(st), d, ptr(ps), k, ptr(zs), ptr(ws), ptr(out), status)
+    ms = (time.perf_counter() - t) * 1e3
+    assert rc == 0, ctx.lib.halo_last_error()
+    return ms, out, st.value
+
+
+def fold_leg(reps):
+    """the folded schedule against the loop above the no-fold size (see the module's text)"""
+    reps = max(reps, 5)
+    ctx = h._lib.Context(urs_n=1 << 16)
+    rows = []
+
+    def hooked(value, call, want_batched):
+        def run():
+            h._lib.dev_hook("open_batch_fold", value)
+            try:
+                r = call()
+                assert ctx.info(10) == want_batched, (value, ctx.info(10))
+                return r
+            finally:
+                h._lib.dev_hook("reset", 0)
+        return run
+
+    try:
+        for lg in (15, 16):
+            n, d = 1 << lg, (1 << lg) - 1
+            args = inputs(ctx, n, 64, 0x48414C4F00000500 + n)
+            for m in (8, 64):
+                shapes = {"open_batch": lambda: batched(ctx, d, args, m, 7 + m), "random_instance_batch": lambda: ri_batched(ctx, d, m, 11 + m),
+                          "instance_from_poly_batch": lambda: ifp_batched(ctx, d, args, m, 13 + m)}
+                for name, call in shapes.items():
+                    loop, fold = hooked(2, call, 0), hooked(1, call, m)
+                    a, b = loop(), fold()
+                    assert a[1].tolist() == b[1].tolist() and a[2] == b[2], "the two ways differ"
+                    l_ms, f_ms = [], []
+                    for _ in range(reps):
+                        l_ms.append(loop()[0])
+                        f_ms.append(fold()[0])
+                    rows.append({"shape": name, "n": n, "m": m, "loop_ms": round(statistics.median(l_ms), 3), "fold_ms": round(statistics.median(f_ms), 3),
+                                 "loop_min_max_ms": [round(min(l_ms), 3), round(max(l_ms), 3)], "fold_min_max_ms": [round(min(f_ms), 3), round(max(f_ms), 3)],
+                                 "speedup": round(statistics.median(l_ms) / statistics.median(f_ms), 2), "won": max(f_ms) < min(l_ms)})
+                    print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+    finally:
+        ctx.close()
+    print(json.dumps({"tool": "tools/time_open_batch.py --fold", "workload": "m hiding opens / random instances / Instances from the caller's polynomials "
+                      "(full degree) above the no-fold size, 1 GPU, context of 2^16 points, default switch 2^14", "reps": reps,
+                      "statistic": "median of alternating runs, ms; loop = open_batch_fold 2, fold = open_batch_fold 1, same process",
+                      "rows": rows, "equal": "proofs, instances and final RNG states: loop == folded schedule for every row"}))
+
+
 def alternate(one, two, reps):
     """a warm-up of each, then `reps` alternating runs; both ways must give the same outputs and final state"""
     a, b = one(), two()
@@ -104,7 +165,10 @@ def main():
     ap.add_argument("--ks", default="10,100,1000")
     ap.add_argument("--sweep", type=int, default=1, help="members-per-launch sweep at k = 100 (0: off)")
     ap.add_argument("--big", action="store_true", help="add the 2^20-point leg (k = 4)")
+    ap.add_argument("--fold", action="store_true", help="only the folded schedule against the loop at n = 2^15, 2^16")
     a = ap.parse_args()
+    if a.fold:
+        return fold_leg(a.reps)
     ks = [int(x) for x in a.ks.split(",")]
     ctx = h._lib.Context(urs_n=1 << 14)
     rows, ri_rows, sweep = [], [], []
