@@ -1,6 +1,6 @@
 // extern "C" surface of libhalo_hip.so (include/halo_accumulation.h): context, error
 // reporting, profiling hooks and the group.rs / pcdl.rs-level entry points.  All compute goes
-// to the HIP kernels in msm.hip / ipa.hip; there is no CPU fallback.
+// to the HIP kernels in msm.hip / key_fold.hip / fr_vec.hip / hpoly.hip / small_sums.hip; there is no CPU fallback.
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -98,7 +98,7 @@ int download_words(halo_ctx *ctx, uint64_t *dst, const uint64_t *src, size_t wor
 }
 
 
-// Key size at which the IPA stops folding G and switches to MSMs over the fixed key (ipa.hip).
+// Key size at which the IPA stops folding G and switches to MSMs over the fixed key (fr_vec.hip).
 #define kNoFoldSize (ctx->nofold_size)
 static int ipa_enter_nofold(halo_ipa *st) {
     halo_ctx *ctx = st->ctx;

@@ -242,7 +242,7 @@ int halo_dev_hook(const char *name, long value) {
 }
 
 // host only: the launch plan of one Fr kernel family at size n as its launcher computes it NOW (hooks, environment, defaults):
-// the plan_* functions of fr_plan.hpp, which are the ones the launchers of ipa.hip call.  which = 1 is the single open's p(z)
+// the plan_* functions of fr_plan.hpp, which are the ones the launchers of fr_vec.hip and hpoly.hip call.  which = 1 is the single open's p(z)
 // (fr_poly_eval: up to FR_GRID_CAP blocks), 4 the batched open's (open_batch_table / open_batch_eval: a member's OPEN_PART_WORDS / 4)
 int halo_dev_fr_plan(halo_ctx *ctx, int which, size_t n, long out[4]) {
     (void)ctx;  // (no plan depends on the context today)

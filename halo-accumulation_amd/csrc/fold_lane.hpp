@@ -1,5 +1,5 @@
 // One lane's share of the key folds of pcdl::open (pcdl.rs:216-219): G[j] + xi G[j+m] and its two-round form, with the digit
-// strings they walk.  ipa.hip's k_fold_points and k_fold_points4 call them once or twice per lane; tests/native/fold_host.cpp
+// strings they walk.  key_fold.hip's k_fold_points and k_fold_points4 call them once or twice per lane; tests/native/fold_host.cpp
 // compiles the same text for the CPU (HALO_DEV = inline, field.hpp) and runs it under ASan + UBSan.  Needs curve.hpp only.
 #pragma once
 #include "curve.hpp"

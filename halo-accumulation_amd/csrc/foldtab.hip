@@ -1,4 +1,4 @@
-// Fixed-base comb tables for the FIRST fold of pcdl::open (pcdl.rs:216-219 applied twice, ipa.hip k_fold_points4):
+// Fixed-base comb tables for the FIRST fold of pcdl::open (pcdl.rs:216-219 applied twice, key_fold.hip k_fold_points4):
 //     G''[j] = G[j] + s1 G[j+m] + s2 G[j+2m] + s3 G[j+3m],   m = n / 4,
 // where G is the context's own key -- a constant (consts.rs:68), like the bases of the MSM tables of msm.hip.  The generic
 // kernel multiplies each of the three points by its scalar with a shared 128-step doubling chain (Straus over GLV digit

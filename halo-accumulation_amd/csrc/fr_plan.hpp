@@ -1,5 +1,5 @@
-// The launch plan of the scalar-side kernels of ipa.hip (K4 - K9): chain length, window count, grid and trips per lane as
-// functions of the size.  Host code only.  The launchers of ipa.hip take their numbers from the plan_* functions below and
+// The launch plan of the scalar-side kernels of fr_vec.hip and hpoly.hip (K4 - K9): chain length, window count, grid and trips per lane as
+// functions of the size.  Host code only.  The launchers there take their numbers from the plan_* functions below and
 // halo_dev_fr_plan (dev.hip) reports the same functions' results: a test that asserts a plan asserts what the launcher runs.
 //
 // Every plan gives the same field elements (the sums are exact); the development hooks "pow_e", "dot_blocks" and

@@ -1,0 +1,255 @@
+// h(X) of pcdl.rs:56-91 and pcdl.rs:496-505: its coefficients from three 256-entry tables (K7), the sum of several scaled
+// polynomials per member (K7b, acc.rs:85-94) and HPoly::eval, one polynomial per lane (K8).  The launch plan of the coefficient
+// kernels is fr_plan.hpp's plan_h_coeffs.
+#include "fr29.hpp"
+#include "fr_plan.hpp"
+#include "internal.hpp"
+
+namespace halo {
+
+// ------------------------------------------------------------------ K7: h coefficients from three 256-entry tables
+constexpr size_t H_TAB_WORDS = H_TABLES_WORDS;  // one polynomial's low | mid | high tables
+// tab = low (A-form) | mid | high (N-form), 256 x 4 words each; coefficient k = low[k & 255] * mid[(k >> 8) & 255] * high[k >> 16].
+// Lane l of a wave takes k = base + l + 64 j: (k >> 8) is the same for the whole wave and changes every fourth step,
+// so mid * high is one product per four elements and low * (mid high) the only product per element.
+HALO_DEV void h_coeffs_wave(const uint64_t *__restrict__ tab, uint32_t n, int E, int accumulate, uint64_t *__restrict__ out) {
+    uint32_t wave = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    uint32_t k = wave * (64u * (uint32_t)E) + lane;
+    if (k >= n) return;
+    Fs<4> hm = fs_zero<4>();
+#pragma unroll 1
+    for (int j = 0; j < E && k < n; j++, k += 64) {
+        if ((j & 3) == 0) {
+            uint32_t kk = __builtin_amdgcn_readfirstlane(k);  // wave-uniform: (k >> 8) does not depend on the lane
+            hm = fs_widen<4>(fs_mul(fs_load(tab + 4 * (size_t)(256 + ((kk >> 8) & 255u))), fs_load(tab + 4 * (size_t)(512 + ((kk >> 16) & 255u)))));
+        }
+        Fs<2> v = fs_mul(fs_load(tab + 4 * (size_t)(k & 255u)), hm);
+        if (accumulate) fs_store(out + 4 * (size_t)k, fs_add(v, fs_load(out + 4 * (size_t)k)));
+        else fs_store(out + 4 * (size_t)k, v);
+    }
+}
+__global__ __launch_bounds__(256) void k_h_coeffs(const uint64_t *__restrict__ tab, uint32_t n, int E, int accumulate, uint64_t *__restrict__ out) {
+    h_coeffs_wave(tab, n, E, accumulate, out);
+}
+// The same for a batch of polynomials: blockIdx.y = member, its own table (3 x 256 x 4 words) and its own n x 4 output words
+__global__ __launch_bounds__(256) void k_h_coeffs_batch(const uint64_t *__restrict__ tabs, uint32_t n, int E, uint64_t *__restrict__ outs, uint64_t out_stride) {
+    h_coeffs_wave(tabs + (size_t)blockIdx.y * H_TAB_WORDS, n, E, 0, outs + (size_t)blockIdx.y * out_stride);
+}
+// The three tables of k_h_coeffs built on the device, one block per polynomial (challenges: lg_n + 1 Montgomery elements per
+// polynomial, contiguous).  Thread k of level L (bits 8L .. 8L + 7 of the coefficient index) multiplies the challenges of the set
+// bits of k, xis[lg_n - (8L + b)] -- the same field element the host's doubling construction in h_coeffs_dev reaches, and both
+// are canonical Montgomery limbs, so the tables are bit-identical.  Entries past a level's 2^bits stay one as on the host; the
+// mid and high levels are N-form multipliers (32 x, five doublings), the low one A-form.
+// scaled = 1: a record is lg_n + 2 elements, the last one the polynomial's scale (alpha^(i+1) of acc.rs:85-94), folded into the
+// high table exactly as h_coeffs_dev(xis, lg_n, scale, ..) folds it on the host.
+__global__ __launch_bounds__(256) void k_h_tables(const uint64_t *__restrict__ xis, int lg_n, int scaled, uint64_t *__restrict__ tabs) {
+    const uint64_t *x = xis + (size_t)blockIdx.x * 4 * (size_t)(lg_n + 1 + scaled);
+    uint64_t *tab = tabs + (size_t)blockIdx.x * H_TAB_WORDS;
+    const uint32_t k = threadIdx.x;
+#pragma unroll 1
+    for (int level = 0; level < 3; level++) {
+        int bits = lg_n - 8 * level;
+        bits = bits < 0 ? 0 : (bits > 8 ? 8 : bits);
+        Fe t = fe_one<FrCfg>();
+        if ((k >> bits) == 0) {
+            if (level == 2 && scaled) t = fe_load(x + 4 * (size_t)(lg_n + 1));
+#pragma unroll 1
+            for (int b = 0; b < bits; b++)
+                if ((k >> b) & 1u) t = fe_mul<FrCfg>(t, fe_load(x + 4 * (size_t)(lg_n - (8 * level + b))));
+        }
+        if (level > 0) {
+#pragma unroll
+            for (int d = 0; d < 5; d++) t = fe_dbl<FrCfg>(t);
+        }
+        fe_store(tab + 4 * (size_t)(256 * level + k), t);
+    }
+}
+
+// ------------------------------------------------------------------ K7b: h(X) = h_0 + sum_i alpha^(i+1) h_i(X) of several members
+// (acc.rs:85-94, halo_acc_prover_batch).  blockIdx.y = member; its record (HACC_REC_WORDS words) names its tables of this launch:
+//     word 0 = first table | count << 32, word 1 = mode, words 2..9 = h_0 (two Montgomery elements)
+// mode 0: nothing to do in this launch; 1: out = h_0 + the sum (count 0: h_0 and zeros); 2: out += the sum (a member with more
+// tables than one launch holds).  Everything read from the record is the same for every lane of the grid row.
+// Lane l of a wave takes the coefficients base + l + 64 j as h_coeffs_wave does.  Four steps share (k >> 8), so for every table
+// mid * high is ONE wave-uniform product per four coefficients and low * (mid high) the only product per coefficient and table.
+// The four running sums stay in the lazy 29-bit form: a product is < 2 r, sum + product < 4 r is brought back below 2 r at once
+// (fs_tighten: ~30 VALU against ~230 of the product), so the bound never depends on the count -- a member of 64 instances works
+// like one of 2 -- and fs_add's static_assert holds it.  Every coefficient is stored ONCE, canonical (fs_store): field sums are
+// exact, so the words equal m accumulate passes of k_h_coeffs in any order.  The tables are read through L2: 24 KiB per
+// instance, the same lines for every wave of a member.
+HALO_DEV void h_acc_step(Fs<2> &acc, const uint64_t *__restrict__ tab, uint32_t k, const Fs<4> &hm) {
+    acc = fs_tighten(fs_add(acc, fs_mul(fs_load(tab + 4 * (size_t)(k & 255u)), hm)));
+}
+HALO_DEV void h_acc_store(uint64_t *__restrict__ out, const uint64_t *__restrict__ rec, uint32_t mode, uint32_t k, uint32_t n, const Fs<2> &acc) {
+    if (k >= n) return;
+    Fs<4> extra = fs_zero<4>();
+    if (mode == 2) extra = fs_load(out + 4 * (size_t)k);
+    else if (k < 2) extra = fs_load(rec + 2 + 4 * (size_t)k);
+    fs_store(out + 4 * (size_t)k, fs_add(acc, extra));
+}
+__global__ __launch_bounds__(256) void k_h_accumulate_batch(const uint64_t *__restrict__ tabs, const uint64_t *__restrict__ recs, uint32_t n, int E,
+                                                            uint64_t *__restrict__ outs, uint64_t out_stride) {
+    const uint64_t *rec = recs + HACC_REC_WORDS * (size_t)blockIdx.y;
+    const uint32_t first = (uint32_t)rec[0], count = (uint32_t)(rec[0] >> 32), mode = (uint32_t)rec[1];
+    if (mode == 0) return;
+    uint64_t *out = outs + (size_t)blockIdx.y * out_stride;
+    const uint32_t wave = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    uint32_t k = wave * (64u * (uint32_t)E) + lane;
+#pragma unroll 1
+    for (int j = 0; j < E && k < n; j += 4, k += 256) {  // (E is a multiple of four: pow_chain_len)
+        const uint32_t kk = __builtin_amdgcn_readfirstlane(k);  // wave-uniform: (k >> 8) does not depend on the lane
+        Fs<2> a0 = fs_zero<2>(), a1 = fs_zero<2>(), a2 = fs_zero<2>(), a3 = fs_zero<2>();
+#pragma unroll 1
+        for (uint32_t t = 0; t < count; t++) {
+            const uint64_t *tab = tabs + (size_t)(first + t) * H_TAB_WORDS;
+            const Fs<4> hm = fs_widen<4>(fs_mul(fs_load(tab + 4 * (size_t)(256 + ((kk >> 8) & 255u))), fs_load(tab + 4 * (size_t)(512 + ((kk >> 16) & 255u)))));
+            // (a step past n multiplies a valid table entry and is never stored: no divergence around the products)
+            h_acc_step(a0, tab, k, hm);
+            h_acc_step(a1, tab, k + 64, hm);
+            h_acc_step(a2, tab, k + 128, hm);
+            h_acc_step(a3, tab, k + 192, hm);
+        }
+        h_acc_store(out, rec, mode, k, n, a0);
+        h_acc_store(out, rec, mode, k + 64, n, a1);
+        h_acc_store(out, rec, mode, k + 128, n, a2);
+        h_acc_store(out, rec, mode, k + 192, n, a3);
+    }
+}
+
+// ------------------------------------------------------------------ K8: HPoly::eval, one polynomial per lane
+// polynomial i (lg_n + 1 challenges at xis) at the point z
+HALO_DEV void h_eval_lane(const uint64_t *__restrict__ xis, uint32_t i, int lg_n, const Fe &z, uint64_t *__restrict__ out) {
+    const uint64_t *x = xis + 4 * (size_t)i * (size_t)(lg_n + 1);
+    Fe one = fe_one<FrCfg>();
+    Fe v = fe_add<FrCfg>(one, fe_mul<FrCfg>(fe_load(x + 4 * (size_t)lg_n), z));
+    Fe zi = z;
+#pragma unroll 1
+    for (int k = 1; k < lg_n; k++) {
+        zi = fe_sqr<FrCfg>(zi);
+        v = fe_mul<FrCfg>(v, fe_add<FrCfg>(one, fe_mul<FrCfg>(fe_load(x + 4 * (size_t)(lg_n - k)), zi)));
+    }
+    fe_store(out + 4 * (size_t)i, v);
+}
+__global__ __launch_bounds__(256) void k_h_eval(const uint64_t *__restrict__ xis, uint32_t m, int lg_n, FeArg zarg,
+                                                uint64_t *__restrict__ out) {
+    uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    h_eval_lane(xis, i, lg_n, from_arg(zarg), out);
+}
+// HPoly::eval for m polynomials, each at its own point (the m succinct checks of acc.rs:158-170 have their own z_i)
+__global__ __launch_bounds__(256) void k_h_eval_z(const uint64_t *__restrict__ xis, const uint64_t *__restrict__ zs, uint32_t m, int lg_n,
+                                                  uint64_t *__restrict__ out) {
+    uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= m) return;
+    h_eval_lane(xis, i, lg_n, fe_load(zs + 4 * (size_t)i), out);
+}
+
+// ================================================================== host launchers
+int h_coeffs_dev(halo_ctx *ctx, const host::Fr *xis, size_t lg_n, const host::Fr &scale, bool accumulate, uint64_t *d_out) {
+    if (lg_n > 24) { set_error("h_coeffs: lg_n > 24 unsupported"); return HALO_E_ARG; }
+    // coefficient k = prod over set bits i of k of xis[lg_n - i]  (pcdl.rs:496-505)
+    std::vector<uint64_t> tab(3 * 256 * 4);
+    for (int level = 0; level < 3; ++level) {
+        std::vector<host::Fr> t(256, host::Fr::one());
+        if (level == 2) t[0] = scale;
+        size_t len = 1;
+        for (int b = 0; b < 8; ++b) {
+            size_t bit = (size_t)level * 8 + b;
+            if (bit >= lg_n) break;
+            const host::Fr &x = xis[lg_n - bit];
+            for (size_t k = 0; k < len; ++k) t[len + k] = t[k] * x;
+            len *= 2;
+        }
+        if (level == 2 && len == 1) t[0] = scale;
+        // low table in A-form (what the kernel multiplies INTO), mid and high as N-form multipliers (fr29.hpp): 32 x
+        const host::Fr k32 = host::Fr::from_u64(32);
+        for (size_t k = 0; k < 256; ++k) (level == 0 ? t[k] : t[k] * k32).store(&tab[((size_t)level * 256 + k) * 4]);
+    }
+    uint64_t *d_tab = ctx->d_tmp_c + 8 * 1024 + 1024;  // (the window table of fr_powers / fr_poly_eval sits below)
+    HALO_HIP(hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+    HALO_HIP(hipStreamSynchronize(ctx->stream));  // `tab` is pageable and dies at return
+    size_t n = (size_t)1 << lg_n;
+    const FrPlan p = plan_h_coeffs(n);
+    HALO_LAUNCH(ctx, "k_h_coeffs", k_h_coeffs, dim3(p.blocks), dim3(256), 0, d_tab, (uint32_t)n, p.E, accumulate ? 1 : 0, d_out);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
+// m polynomials at once (scale one, no accumulation): member b's coefficients go to d_out + b * out_stride words, bit-identical
+// to h_coeffs_dev(xis_b, lg_n, 1, false).  Two launches on ctx->stream whatever m is: the tables (d_tabs: m x H_TAB_WORDS) from
+// the challenges already in device memory (d_xis: m x (lg_n + 1) x 4 words), then the coefficients.
+int h_coeffs_batch_dev(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg_n, uint64_t *d_tabs, uint64_t *d_out, size_t out_stride) {
+    if (lg_n > 24) { set_error("h_coeffs: lg_n > 24 unsupported"); return HALO_E_ARG; }
+    if (m == 0) return HALO_OK;
+    if (m > 65535) { set_error("h_coeffs_batch: at most 65535 members per launch"); return HALO_E_ARG; }
+    size_t n = (size_t)1 << lg_n;
+    const FrPlan p = plan_h_coeffs(n);
+    HALO_LAUNCH(ctx, "k_h_tables", k_h_tables, dim3((unsigned)m), dim3(256), 0, d_xis, (int)lg_n, 0, d_tabs);
+    HALO_LAUNCH(ctx, "k_h_coeffs_batch", k_h_coeffs_batch, dim3(p.blocks, (unsigned)m), dim3(256), 0, d_tabs, (uint32_t)n, p.E, d_out,
+                (uint64_t)out_stride);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
+// h(X) = h_0 + sum_i scale_i h_i(X) of G members at once (acc.rs:85-94 for each), member b's n coefficients stored once at
+// d_out + b * out_stride.  Staging, the same layout in pinned (h_stage) and device memory (d_stage): G records of
+// HACC_REC_WORDS, then one record of lg_n + 2 elements per table (the challenges, then the scale); the device staging holds
+// cap x H_TAB_WORDS of tables behind that (hacc_stage_words).  Per pass ONE copy from pinned memory, k_h_tables over the
+// pass's polynomials and k_h_accumulate_batch over the members: one pass unless the members bring more than `cap` polynomials,
+// then the later passes add to what is there (mode 2) after the stream has drained the pinned records.  On ctx->stream.
+int h_accumulate_group(halo_ctx *ctx, const HAccMember *mem, size_t G, size_t lg_n, size_t cap, uint64_t *h_stage, uint64_t *d_stage, uint64_t *d_out,
+                       size_t out_stride) {
+    if (lg_n > 24) { set_error("h_coeffs: lg_n > 24 unsupported"); return HALO_E_ARG; }
+    if (G == 0) return HALO_OK;
+    if (G > 65535 || cap == 0) { set_error("h_accumulate: 1..65535 members, at least one table"); return HALO_E_ARG; }
+    const size_t n = (size_t)1 << lg_n, head = G * HACC_REC_WORDS, tw = (lg_n + 2) * 4;
+    const FrPlan p = plan_h_coeffs(n);
+    uint64_t *d_tabs = d_stage + head + cap * tw;
+    std::vector<size_t> done(G, 0);
+    for (bool first_pass = true;; first_pass = false) {
+        size_t T = 0;
+        bool more = false;
+        for (size_t b = 0; b < G; ++b) {
+            const HAccMember &m = mem[b];
+            size_t take = m.count - done[b];
+            if (take > cap - T) take = cap - T;
+            uint64_t *rec = h_stage + b * HACC_REC_WORDS;
+            rec[0] = (uint64_t)T | ((uint64_t)take << 32);
+            rec[1] = first_pass ? 1 : (take ? 2 : 0);
+            m.h0[0].store(rec + 2);
+            m.h0[1].store(rec + 6);
+            for (size_t t = 0; t < take; ++t) {
+                uint64_t *x = h_stage + head + (T + t) * tw;
+                const host::Fr *xi = m.xis[done[b] + t];
+                for (size_t q = 0; q <= lg_n; ++q) xi[q].store(x + 4 * q);
+                m.scales[done[b] + t].store(x + 4 * (lg_n + 1));
+            }
+            T += take;
+            done[b] += take;
+            if (done[b] < m.count) more = true;
+        }
+        HALO_HIP(hipMemcpyAsync(d_stage, h_stage, (head + T * tw) * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (T) HALO_LAUNCH(ctx, "k_h_tables", k_h_tables, dim3((unsigned)T), dim3(256), 0, d_stage + head, (int)lg_n, 1, d_tabs);
+        HALO_LAUNCH(ctx, "k_h_accumulate_batch", k_h_accumulate_batch, dim3(p.blocks, (unsigned)G), dim3(256), 0, d_tabs, d_stage, (uint32_t)n, p.E,
+                    d_out, (uint64_t)out_stride);
+        HALO_HIP(hipGetLastError());
+        if (!more) return HALO_OK;
+        HALO_HIP(hipStreamSynchronize(ctx->stream));  // (the next pass rewrites the pinned records)
+    }
+}
+
+int h_eval_batch(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg_n, const host::Fr &z, uint64_t *d_out) {
+    if (m == 0) return HALO_OK;
+    HALO_LAUNCH(ctx, "k_h_eval", k_h_eval, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, d_xis, (uint32_t)m, (int)lg_n, to_arg(z), d_out);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
+int h_eval_each(halo_ctx *ctx, const uint64_t *d_xis, const uint64_t *d_zs, size_t m, size_t lg_n, uint64_t *d_out) {
+    if (m == 0) return HALO_OK;
+    HALO_LAUNCH(ctx, "k_h_eval_z", k_h_eval_z, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, d_xis, d_zs, (uint32_t)m, (int)lg_n, d_out);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
+}  // namespace halo

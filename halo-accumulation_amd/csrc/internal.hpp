@@ -18,6 +18,7 @@
 
 #include "../../include/halo_accumulation.h"
 #include "host_math.hpp"
+#include "kernel_args.hpp"
 #include "tuning.hpp"
 
 namespace halo {
@@ -345,7 +346,7 @@ struct halo_ctx {
     uint64_t *d_tmp_a = nullptr, *d_tmp_b = nullptr, *d_tmp_c = nullptr;
     size_t tmp_words = 0;
     uint64_t *h_pinned = nullptr;  // small pinned staging (4 KiB)
-    uint64_t *h_wintab = nullptr;  // pinned staging of a window table of powers (ipa.hip upload_window_table), 8 KiB
+    uint64_t *h_wintab = nullptr;  // pinned staging of a window table of powers (fr_vec.hip upload_window_table), 8 KiB
     uint64_t *d_slot_scalars[HALO_SLOTS] = {};  // scalar staging per slot (abi.hip slot_scalars): host scalars, a shard's peer copies
     size_t slot_scalars_bytes[HALO_SLOTS] = {};
     uint64_t *d_verify = nullptr;  // staging of the batched verifier (points, scalars, challenges, results), grown on demand
@@ -388,7 +389,7 @@ struct halo_ipa {
     bool hp_from_scalar = false;          // H' = hp_scalar * H: terms k * H' come from the process-wide table of H as (k * hp_scalar) * H
     halo::host::Fr hp_scalar;
     hipEvent_t ev = nullptr;  // orders slot 1's stream after the folds queued on stream 0
-    // no-fold mode (ipa.hip): G stays at M points, s holds the challenge products
+    // no-fold mode (fr_vec.hip): G stays at M points, s holds the challenge products
     bool nofold = false;
     bool deferred = false;                   // the no-fold phase ends in a two-level fold once s_len reaches 4
     std::vector<halo::host::Fr> s_host;      // host copy of s while deferred (<= 4 entries)
@@ -540,10 +541,11 @@ int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const
                  uint32_t kmax);
 int smsm_prepare();
 
-// ---- ipa.hip
+// ---- key_fold.hip
 // (form: 0 in the product -- the sizes pick the kernel form; halo_dev_fold_points forces one, include/halo_accumulation_dev.h)
 int ipa_fold_points(halo_ctx *ctx, uint32_t *d_G, size_t m, const host::Fr &xi_mont, int form = 0);
 int ipa_fold_points4(halo_ctx *ctx, const uint32_t *d_src, uint32_t *d_dst, size_t m, const host::Fr s[3], int form = 0);
+// ---- fr_vec.hip
 int ipa_fold_scalars(halo_ctx *ctx, uint64_t *d_c, uint64_t *d_z, size_t m, const host::Fr &xi, const host::Fr &xi_inv);
 // out[0] = <xs0, ys0>, out[1] = <xs1, ys1> (either pair may be null to skip)
 int fr_dot2(halo_ctx *ctx, const uint64_t *xs0, const uint64_t *ys0, const uint64_t *xs1, const uint64_t *ys1, size_t m,
@@ -554,6 +556,17 @@ int fr_powers(halo_ctx *ctx, const host::Fr &z, size_t n, uint64_t *d_out);
 // d_v[i] *= a
 int fr_scale(halo_ctx *ctx, uint64_t *d_v, size_t n, const host::Fr &a);
 int fr_poly_eval(halo_ctx *ctx, const uint64_t *d_coeffs, size_t len, const host::Fr &z, host::Fr *out);
+// SplitMix64 stream -> n Montgomery scalars (element i = draws 4i+1..4i+4 after state0)
+int rng_scalars_dev(halo_ctx *ctx, uint64_t state0, size_t n, uint64_t *d_out);
+int pbar_dev(halo_ctx *ctx, const uint64_t *d_q, size_t deg, const host::Fr &z, uint64_t *d_out);
+int axpy_dev(halo_ctx *ctx, uint64_t *d_y, const uint64_t *d_x, size_t n, const host::Fr &a);
+int pbar_stream_dev(halo_ctx *ctx, uint64_t state0, size_t deg, const host::Fr &z, uint64_t stride, uint64_t offset, size_t n_local,
+                    uint64_t *d_out);
+int bench_fr_kernel(halo_ctx *ctx, int which, size_t n, int reps);
+int nofold_expand(halo_ctx *ctx, const uint64_t *d_c, const uint64_t *d_s, size_t m, size_t M, uint64_t *d_L, uint64_t *d_R);
+int nofold_expand_tagged(halo_ctx *ctx, const uint64_t *d_c, const uint64_t *d_s, size_t m, size_t M, uint64_t *d_F);  // one array for a tagged launch
+int nofold_s_update(halo_ctx *ctx, const uint64_t *d_s_in, size_t len, const host::Fr &xi, uint64_t *d_s_out);
+// ---- hpoly.hip
 // d_out[k] (+)= scale * prod_{bit i of k} xis[lg_n - i]
 int h_coeffs_dev(halo_ctx *ctx, const host::Fr *xis, size_t lg_n, const host::Fr &scale, bool accumulate, uint64_t *d_out);
 // m of them at once, scale one: tables (d_tabs, m x 3072 words) built on the device from d_xis (m x (lg_n + 1) x 4), member b's
@@ -575,36 +588,27 @@ inline size_t hacc_stage_words(size_t G, size_t lg_n, size_t cap) { return hacc_
 int h_accumulate_group(halo_ctx *ctx, const HAccMember *mem, size_t G, size_t lg_n, size_t cap, uint64_t *h_stage, uint64_t *d_stage, uint64_t *d_out,
                        size_t out_stride);
 int h_eval_batch(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg_n, const host::Fr &z, uint64_t *d_out);
-// m polynomials h_i at their own points z_i; m sums of K scalar multiples (canonical scalars, affine points) -> m Jacobian points
+// m polynomials h_i at their own points z_i
 int h_eval_each(halo_ctx *ctx, const uint64_t *d_xis, const uint64_t *d_zs, size_t m, size_t lg_n, uint64_t *d_out);
+// ---- small_sums.hip: m sums of K scalar multiples (canonical scalars, affine points) -> m Jacobian points
 int batch_small_msm(halo_ctx *ctx, const uint64_t *d_points, const uint64_t *d_scalars, size_t m, size_t K, uint64_t *d_out);
 // sums of 1..64 terms each, several to a wave (k_small_msm_seg): sum s holds terms sum_off[s] .. sum_off[s + 1] (same term
 // format as above).  plan: the lane descriptor (64 words per wave) -> the number of waves; the launch writes nsums Jacobian points
 size_t small_msm_seg_plan(const uint32_t *sum_off, size_t nsums, std::vector<uint32_t> &desc);
 int small_msm_seg(halo_ctx *ctx, const uint64_t *d_points, const uint64_t *d_scalars, const uint32_t *d_sum_off, const uint32_t *d_desc, size_t waves,
                   uint64_t *d_out);
-// SplitMix64 stream -> n Montgomery scalars (element i = draws 4i+1..4i+4 after state0)
-int rng_scalars_dev(halo_ctx *ctx, uint64_t state0, size_t n, uint64_t *d_out);
-int pbar_dev(halo_ctx *ctx, const uint64_t *d_q, size_t deg, const host::Fr &z, uint64_t *d_out);
-int axpy_dev(halo_ctx *ctx, uint64_t *d_y, const uint64_t *d_x, size_t n, const host::Fr &a);
-int pbar_stream_dev(halo_ctx *ctx, uint64_t state0, size_t deg, const host::Fr &z, uint64_t stride, uint64_t offset, size_t n_local,
-                    uint64_t *d_out);
-int bench_fr_kernel(halo_ctx *ctx, int which, size_t n, int reps);
-int nofold_expand(halo_ctx *ctx, const uint64_t *d_c, const uint64_t *d_s, size_t m, size_t M, uint64_t *d_L, uint64_t *d_R);
-int nofold_expand_tagged(halo_ctx *ctx, const uint64_t *d_c, const uint64_t *d_s, size_t m, size_t M, uint64_t *d_F);  // one array for a tagged launch
-int nofold_s_update(halo_ctx *ctx, const uint64_t *d_s_in, size_t len, const host::Fr &xi, uint64_t *d_s_out);
 
-// ---- ipa.hip: the member-batched kernels of halo_pcdl_open_batch (pcdl_batch.hip).  G <= OPEN_MAX_GROUP members per launch,
+// ---- fr_vec.hip: the member-batched kernels of halo_pcdl_open_batch (pcdl_batch.hip).  G <= OPEN_MAX_GROUP members per launch,
 // blockIdx.y = member.  Member b's vectors sit at b * ms words from the base pointers; its window table, constants, partial sums
 // and results at b * OPEN_*_WORDS in the group's own regions.
 constexpr int OPEN_MAX_GROUP = 4;
 constexpr size_t OPEN_TAB_WORDS = 1024, OPEN_CONST_WORDS = 32, OPEN_PART_WORDS = 1024, OPEN_OUT_WORDS = 32;
 constexpr size_t OPEN_MAX_N = (size_t)1 << 16;  // the batched kernels' partial sums and window tables are sized for this
 // One member's constants in device memory (uploaded once per step of a group, never kernel arguments): N-form multipliers
-// (ipa.hip FsArg: 9 x 29-bit limbs) and Montgomery limbs (FeArg: 8 x 32 bits)
+// (kernel_args.hpp FsArg: 9 x 29-bit limbs) and Montgomery limbs (FeArg: 8 x 32 bits)
 struct OpenConst {
-    uint32_t xi_n[9], xi_inv_n[9], alpha_n[9], z64_n[9];
-    uint32_t xi_m[8], z_m[8];
+    FsArg xi_n, xi_inv_n, alpha_n, z64_n;
+    FeArg xi_m, z_m;
     uint64_t s_q;  // rng state before q of p_bar (deg scalars)
     uint64_t s_p;  // rng state before p of random_instance (deg + 1 scalars)
     uint32_t deg;  // the member's degree
@@ -628,7 +632,7 @@ int open_batch_dots(halo_ctx *ctx, int G, const uint64_t *d_c, const uint64_t *d
 // s_out[2t + u] = s_in[t] xi^u (t < s_len), then c' = c_l + xi^-1 c_r, z' = z_l + xi z_r over m
 int open_batch_fold(halo_ctx *ctx, int G, uint64_t *d_c, uint64_t *d_z, const uint64_t *d_s_in, uint64_t *d_s_out, size_t ms, size_t m,
                     size_t s_len, const uint64_t *d_consts);
-// ---- ipa.hip: the member-batched key folds (blockIdx.y = member).  Member b reads d_src + b * src_stride points (0: one key for
+// ---- key_fold.hip: the member-batched key folds (blockIdx.y = member).  Member b reads d_src + b * src_stride points (0: one key for
 // all) and writes d_dst + b * dst_stride (may be its source); its digits are record b of d_digs, FOLD_DIG_WORDS 32-bit words of
 // device memory that fold_digits fills on the host from the fold's scalars: xi (levels 1) or s1 | s2 | s3 (levels 2).
 // form: 0 = the single launchers' rule over all G x m outputs; 1 / 2 = one / two outputs per lane; 3 = one per quad (4 only)
@@ -638,7 +642,7 @@ int ipa_fold_points_batch(halo_ctx *ctx, int G, const uint32_t *d_src, size_t sr
                           const uint32_t *d_digs, int form = 0);
 int ipa_fold_points4_batch(halo_ctx *ctx, int G, const uint32_t *d_src, size_t src_stride, uint32_t *d_dst, size_t dst_stride, size_t m,
                            const uint32_t *d_digs, int form = 0);
-// ---- ipa.hip: the member-batched padding of halo_pcdl_commit_dev_batch (pcdl_batch.hip).  Entry k of the table: src[k], len[k]
+// ---- fr_vec.hip: the member-batched padding of halo_pcdl_commit_dev_batch (pcdl_batch.hip).  Entry k of the table: src[k], len[k]
 // Montgomery scalars in device memory (32-byte aligned), copied to d_out + row[k] * ms words and zero-padded to n scalars.  The
 // table travels as a kernel argument; count <= MSM_MAX_BATCH entries, one launch on ctx->stream.
 struct PadMembers {

@@ -480,7 +480,7 @@ static int acc_verifier_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, 
 //
 // Device path (2 <= n <= the context's no-fold size, at most OPEN_MAX_N): the open in its no-fold form (abi.hip ipa_round_lr_points:
 // the key is never folded, every round's L and R are two MSMs over the same n points with expanded scalars) for a GROUP of up to
-// OPEN_MAX_GROUP members at a time.  Each step of a group is one set of member-batched launches (ipa.hip *_batch, blockIdx.y =
+// OPEN_MAX_GROUP members at a time.  Each step of a group is one set of member-batched launches (fr_vec.hip *_batch, blockIdx.y =
 // member) and ONE batched MSM launch sequence over the key (L and R of every member: up to 8 scalar arrays; the C_bar commits of the
 // hiding branch, and random_instance's commits, likewise).  Groups rotate over the slots that were idle on entry: while this
 // thread waits for one group's step and runs its host half -- window combines, H' terms, Fiat-Shamir hashes, xi^-1, on the host
@@ -490,7 +490,7 @@ static int acc_verifier_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, 
 //
 // Above the no-fold size (n up to OPEN_MAX_N, where open_fold_route says so) the group takes the single open's folded schedule:
 // while the key has more points than the no-fold size, k = 1 or 2 rounds in the no-fold form over it, then ONE member-batched fold
-// launch of k levels (ipa.hip k_fold_points*_batch) into the members' staged keys, n / 2 points each in the group's staging.
+// launch of k levels (key_fold.hip k_fold_points*_batch) into the members' staged keys, n / 2 points each in the group's staging.
 // From the first fold on a member's key is its own: the batched MSMs run over the staged keys with one base offset per member
 // (MsmBatch::base_off; the small pipeline takes them, smsm.hip).  The folded key does not depend on the schedule and every point
 // written is normalised, so the proofs are still the loop's.
@@ -538,7 +538,7 @@ constexpr size_t OPEN_PIN_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_
 // Slot j's regions of the staging.  Device (`per` words a slot): the group's member vectors (G x ms: c | z | s | s' | F_L | F_R |
 // p_bar of n scalars each), then its window tables | constants | partial sums | results | the prover batch's tables.  Pinned
 // (OPEN_PIN_WORDS a slot): the tables | constants (one upload) | results (one download) | the prover batch's records | the
-// fold digit records | the element one.  Cached launch graphs and the kernels of ipa.hip (OPEN_*_WORDS) know this layout.
+// fold digit records | the element one.  Cached launch graphs and the kernels of fr_vec.hip (OPEN_*_WORDS) know this layout.
 // A group above the no-fold size (keystride > 0) has two more device regions behind the others, at `fold_off` words: the members'
 // folded keys, keystride = n / 2 points of AFF_STRIDE words each, and their digit records (FOLD_PIN_WORDS).
 struct OpenStage {

@@ -1,4 +1,4 @@
-// One lane's share of the small MSMs of the verifier (pcdl.rs:288-310): k P by a 256-step ladder.  ipa.hip's k_batch_small_msm and
+// One lane's share of the small MSMs of the verifier (pcdl.rs:288-310): k P by a 256-step ladder.  small_sums.hip's k_batch_small_msm and
 // k_small_msm_seg call it once per lane; tests/native/small_msm_host.cpp compiles the same text for the CPU (HALO_DEV = inline,
 // field.hpp) and runs it under ASan + UBSan.  Needs curve.hpp only.
 #pragma once

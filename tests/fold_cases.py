@@ -1,4 +1,4 @@
-"""Cases for the key folds of pcdl::open (ipa.hip k_fold_points, k_fold_points4, k_fold_points4_quad; foldtab.hip k_fold_tab4,
+"""Cases for the key folds of pcdl::open (key_fold.hip k_fold_points, k_fold_points4, k_fold_points4_quad; foldtab.hip k_fold_tab4,
 k_foldtab_build), shared by the host build (tests/test_fold_host.py, tests/native/fold_host.cpp) and the device hook
 (tests/test_gpu_fold_points.py, halo_dev_fold_points).  Not a test module.
 

@@ -1,7 +1,7 @@
 """The cases of the Fr kernels' launch plans (csrc/fr_plan.hpp), shared by tests/test_fr_plan_cases_cpu.py and
 tests/test_gpu_fr_plans.py: one seeded builder, no case skipped or sampled.
 
-The kernels of csrc/ipa.hip K4 - K9 are exact, so only their indexing can be wrong, and the indexing follows a plan that depends
+The kernels of csrc/fr_vec.hip and csrc/hpoly.hip K4 - K9 are exact, so only their indexing can be wrong, and the indexing follows a plan that depends
 on the size: the chain length E (elements per lane), the number of 4-bit windows of the exponent (nwin), the grid and -- where
 the grid is capped -- the trips of a lane through its loop.  A case names a kernel, a size, the hooks it runs under and the plan
 it claims; `model_plan` is this file's own restatement of fr_plan.hpp, which the CPU test holds against halo_dev_fr_plan for

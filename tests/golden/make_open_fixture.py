@@ -2,13 +2,13 @@
 """Generates tests/golden/open_2_<lg>.json: pcdl::open proofs at n = 2^lg from the CPU oracle (lg = 19 and 20 are committed).
 
 Why: the HIP fold kernel switches to two points per lane sharing one inversion once a round folds
-m >= 2^18 points (ipa.hip ipa_fold_points), i.e. from n = 2^19 on; the oracle (double-and-add fold,
+m >= 2^18 points (key_fold.hip ipa_fold_points), i.e. from n = 2^19 on; the oracle (double-and-add fold,
 one into_affine inversion per point -- pcdl.rs:204-224, group.rs:19) needs minutes at that size, so
 its output is committed as a fixture instead of being recomputed in the GPU test.  The fixture is
 data: seeds, the proof blob's SHA-256 and a few of its fields for diagnosis.
 
 n = 2^20 is BASELINE config 3's size: the only size at which an open runs the tagged L/R launch over the c = 20 table
-(msm.hip MsmBatch::tagged, ipa.hip k_nofold_expand_tagged) and the c = 20 table plan.  With --acc the file also holds one
+(msm.hip MsmBatch::tagged, fr_vec.hip k_nofold_expand_tagged) and the c = 20 table plan.  With --acc the file also holds one
 acc::prover step (acc.rs:190-220) over two random instances (benches/acc.rs:15-29) at the same size: SHA-256 of both
 instance blobs and of the accumulator blob, plus the accumulator's fields.
 

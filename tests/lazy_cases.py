@@ -102,7 +102,7 @@ FIELD_TABLE = [
     (19, "fq_muls<4>(2)", "q", [2], ("limbs", 8), _muls(4), False, "curve.hpp xyzz_dbl V = 4Y^2, jac_madd I = 4H^2"),
     (20, "fq_muls<3>(2)", "q", [2], ("limbs", 6), _muls(3), False, "curve.hpp xyzz_dbl M = 3X^2, jac_dbl E"),
     (21, "fq_neg<8>(8)", "q", [8], ("neg", 8), _neg, False, "curve.hpp xyzz_madd / jac_madd 8p - Y1"),
-    (22, "fq_neg<2>(2)", "q", [2], ("neg", 2), _neg, False, "curve.hpp xyzz_add 2p - S1, aff_cneg, aff_store; ipa.hip signed digits"),
+    (22, "fq_neg<2>(2)", "q", [2], ("neg", 2), _neg, False, "curve.hpp xyzz_add 2p - S1, aff_cneg, aff_store; key_fold.hip signed digits"),
     (23, "fq_tighten<18>", "q", [18], ("limbs", 2), _id, False, "curve.hpp jac_dbl X3 = tighten(F - 2D + 16p)"),
     (24, "fq_tighten<16>", "q", [16], ("limbs", 2), _id, False, "curve.hpp jac_dbl tighten(8C)"),
     (25, "fq_tighten<14>", "q", [14], ("limbs", 2), _id, False, "curve.hpp jac_madd X3"),
@@ -112,21 +112,21 @@ FIELD_TABLE = [
     (29, "fq_is_zero_modp<10>", "q", [10], ("flag",), _zero, False, "curve.hpp xyzz_madd / jac_madd P = +-Q tests"),
     (30, "fq_is_zero_modp<4>", "q", [4], ("flag",), _zero, False, "curve.hpp xyzz_add, curve_quad.hpp xyzz_add_quad"),
     (31, "fq_eq_modp<2,2>", "q", [2, 2], ("flag",), _eq, False, "dev.hip aff_same"),
-    (32, "fq_inv<4>", "q", [4], ("limbs", 2), _inv, False, "curve.hpp jac_to_aff 1/Z; ipa.hip 1/(Za Zb)"),
+    (32, "fq_inv<4>", "q", [4], ("limbs", 2), _inv, False, "curve.hpp jac_to_aff 1/Z; key_fold.hip 1/(Za Zb)"),
     (33, "fq_from_words", "q", ["W"], ("limbs", 2), _from_words, False, "curve.hpp aff_from_words / jac_from_words (any 256-bit pattern is < 4p)"),
     (34, "fq_to_words<8>", "q", [8], ("words",), _to_words, False, "curve.hpp jac_store_words X, Y"),
     (35, "fq_to_words<60>", "q", [60], ("words",), _to_words, False, "fq29.hpp: the largest bound the static_assert admits"),
-    (40, "fs_mul<4,4>", "s", [4, 4], ("limbs", 2), _mul, True, "ipa.hip folds of c and z, k_axpy, h(X) tables: loaded element times loaded element"),
+    (40, "fs_mul<4,4>", "s", [4, 4], ("limbs", 2), _mul, True, "fr_vec.hip folds of c and z, k_axpy; hpoly.hip h(X) tables: loaded element times loaded element"),
     (41, "fs_mul<10,10>", "s", [10, 10], ("limbs", 2), _mul, True, "fr29.hpp: 100 of 120, the headroom the Fq side uses"),
-    (42, "fs_mul_add_mul<4,4,4,4>", "s", [4, 4, 4, 4], ("limbs", 2), _mam, True, "ipa.hip dot products and p(z): two loaded pairs per reduction"),
-    (43, "fs_add<4,2>", "s", [4, 2], ("limbs", 6), _add, False, "ipa.hip k_fold_scalars / k_axpy: loaded element + product"),
-    (44, "fs_add<2,4>", "s", [2, 4], ("limbs", 6), _add, False, "ipa.hip p(z): h + (t0 + t1)"),
-    (45, "fs_tighten<6>", "s", [6], ("limbs", 2), _id, False, "ipa.hip p(z) h = tighten(h + t0 + t1)"),
+    (42, "fs_mul_add_mul<4,4,4,4>", "s", [4, 4, 4, 4], ("limbs", 2), _mam, True, "fr_vec.hip dot products and p(z): two loaded pairs per reduction"),
+    (43, "fs_add<4,2>", "s", [4, 2], ("limbs", 6), _add, False, "fr_vec.hip k_fold_scalars / k_axpy: loaded element + product"),
+    (44, "fs_add<2,4>", "s", [2, 4], ("limbs", 6), _add, False, "fr_vec.hip p(z): h + (t0 + t1)"),
+    (45, "fs_tighten<6>", "s", [6], ("limbs", 2), _id, False, "fr_vec.hip p(z) h = tighten(h + t0 + t1)"),
     (46, "fs_tighten<60>", "s", [60], ("limbs", 2), _id, False, "fr29.hpp: the largest bound the static_assert admits"),
     (47, "fs_from_fe", "s", ["W"], ("limbs_exact", 4), _id, False, "fr29.hpp fs_load: repacking only, any 256-bit pattern is < 4r"),
-    (48, "fs_to_fe<6>", "s", [6], ("words",), _id, False, "ipa.hip fs_store(fs_add(loaded, product))"),
+    (48, "fs_to_fe<6>", "s", [6], ("words",), _id, False, "fr_vec.hip fs_store(fs_add(loaded, product))"),
     (49, "fs_to_fe<60>", "s", [60], ("words",), _id, False, "fr29.hpp: the largest bound the static_assert admits"),
-    (50, "fs_to_fe<2>", "s", [2], ("words",), _id, False, "ipa.hip block sums of accumulators"),
+    (50, "fs_to_fe<2>", "s", [2], ("words",), _id, False, "fr_vec.hip block sums of accumulators"),
     (51, "fs_to_fe<1>", "s", [1], ("words",), _id, False, "fr29.hpp fs_below_2r<1> specialisation"),
     (52, "fs_below_2r<6>", "s", [6], ("limbs", 2), _id, False, "fr29.hpp fs_to_fe"),
     (53, "fs_below_2r<2>", "s", [2], ("limbs", 2), _id, False, "fr29.hpp specialisation: a product's result is returned as it is"),

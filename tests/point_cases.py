@@ -1,5 +1,5 @@
 """Cases for the kernels that take points from the caller or derive the key: k_batch_to_affine (urs.hip, the normalisation of
-halo_msm_points), k_batch_small_msm and k_small_msm_seg (ipa.hip, the relations and member sums of the device-side verifiers),
+halo_msm_points), k_batch_small_msm and k_small_msm_seg (small_sums.hip, the relations and member sums of the device-side verifiers),
 k_urs_scalars and k_urs (urs.hip).  tests/test_gpu_point_paths.py runs them on the device, tests/test_small_msm_host.py through the
 lanes compiled for the CPU under ASan + UBSan; the generators and checkers test themselves in tests/test_point_cases_cpu.py.  Not a
 test module.  Plain Python and numpy over pallas_model and orc: importable without a GPU.

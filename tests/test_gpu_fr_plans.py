@@ -1,4 +1,4 @@
-"""The scalar-side kernels of csrc/ipa.hip (K4 - K9) at every size where their launch plan changes (csrc/fr_plan.hpp): chain
+"""The scalar-side kernels of csrc/fr_vec.hip and csrc/hpoly.hip (K4 - K9) at every size where their launch plan changes (csrc/fr_plan.hpp): chain
 lengths 4 .. 64 with short chains and idle lanes in the last wave, 1 .. 5 windows of the exponent, several trips through the
 capped grids of k_poly_eval_partial and k_dot2_partial with full, ragged and idle last trips, and the third table of h(X).  The
 cases are tests/fr_plan_cases.py's (tests/test_fr_plan_cases_cpu.py prints their coverage table); the development hooks "pow_e",

@@ -555,7 +555,7 @@ def test_acc_chain_2_20_64_instances(hal):
 def test_open_2_19_matches_oracle_fixture(hal):
     """pcdl::open at n = 2^19 against the oracle's proof (tests/golden/open_2_19.json, generated in the build
     container by tests/golden/make_open_fixture.py): the first fold of this size runs k_fold_points with two
-    points per lane sharing one inversion (m = 2^18, ipa.hip ipa_fold_points) -- compared bit for bit with the
+    points per lane sharing one inversion (m = 2^18, key_fold.hip ipa_fold_points) -- compared bit for bit with the
     CPU restatement's double-and-add fold (pcdl.rs:216-224), hiding and non-hiding."""
     import hashlib, json, os
     from halo_accumulation_amd import pcdl
@@ -621,7 +621,7 @@ def _open_fixture_cases(hal, fx, c, coeffs, zw, label):
 def test_open_2_20_matches_oracle_fixture(hal):
     """BASELINE config 3 at its own size against the ORACLE's proof (tests/golden/open_2_20.json: orc_pcdl_open, 4.5 minutes of CPU
     per proof in the build container, tests/golden/make_open_fixture.py 20 --acc) -- pcdl.rs:120-242.  n = 2^20 is the only
-    size at which an open takes the tagged L/R launch over the c = 20 table (msm.hip MsmBatch::tagged, ipa.hip
+    size at which an open takes the tagged L/R launch over the c = 20 table (msm.hip MsmBatch::tagged, fr_vec.hip
     k_nofold_expand_tagged), the c = 20 table plan inside an open and (from the K-th open on) the comb-table fold.  Compared,
     hiding and not: (a) the default configuration as a fresh context runs it, (b) with the fold table forced in, (c) with
     neither table (halo_set_table_mode(0), halo_set_fold_table(0): general pipeline, Straus fold)."""
@@ -731,7 +731,7 @@ def test_open_with_fold_table_matches_oracle(hal, lg):
 
 def test_open_2_20_first_rounds_as_one_tagged_launch_equal_two_plain_launches(hal):
     """Rounds 0 and 1 of an open over the full 2^20-point key: L and R from ONE launch sequence over the fixed-base table (one
-    scalar array, bit 255 of an element = its bucket set: msm.hip MsmBatch::tagged, ipa.hip k_nofold_expand_tagged) against the
+    scalar array, bit 255 of an element = its bucket set: msm.hip MsmBatch::tagged, fr_vec.hip k_nofold_expand_tagged) against the
     same open with the table switched off (two plain launches through the table-free pipeline): proofs equal word for word,
     for a dense, a hiding, a half-empty (zero scalars carry a tag too) and a constant-coefficient polynomial (every point of a
     set in ONE bucket per window: the oversized-run and many-task paths of the sort with two sets); all verify."""

@@ -81,7 +81,7 @@ def test_negation_bound_is_counted_where_a_negated_operand_is_used():
         ("curve.hpp", "xyzz_madd", 8, "acc.y"): "fused", ("curve.hpp", "jac_madd", 8, "p.y"): "fused", ("curve.hpp", "xyzz_add", 2, "S1"): "fused",
         ("curve.hpp", "aff_cneg", 2, "p.y"): "sign of y", ("curve.hpp", "aff_store", 2, "a.y"): "sign of y",
         ("fold_lane.hpp", "fold_one", 2, "hi.y"): "sign of y", ("fold_lane.hpp", "fold_one4", 2, "p.y"): "sign of y",
-        ("ipa.hip", "k_fold_points4_quad", 2, "p.y"): "sign of y",
+        ("key_fold.hip", "fold_points4_quad_lane", 2, "p.y"): "sign of y",
     }
     sites = lz.neg_call_sites()
     assert set(sites) == set(reviewed) and len(sites) == len(reviewed), sorted(set(sites) ^ set(reviewed))

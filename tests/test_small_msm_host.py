@@ -27,9 +27,9 @@ def test_the_host_program_restates_the_kernels_constants():
     csrc = os.path.join(pc.ROOT, "halo-accumulation_amd", "csrc")
     assert re.search(r"constexpr int TBL_E = %d;" % pc.HOST_TBL_E, open(os.path.join(csrc, "msm_kernels.hpp")).read())
     assert re.search(r"constexpr int TBL_E = %d;" % pc.HOST_TBL_E, open(os.path.join(pc.ROOT, "tests", "native", "small_msm_host.cpp")).read())
-    ipa = open(os.path.join(csrc, "ipa.hip")).read()
-    assert '#include "small_msm_lane.hpp"' in ipa and "JacN small_msm_ladder(" not in ipa, "the kernels run the header's ladder"
-    assert ipa.count("small_msm_ladder(p, k, live)") == 2
+    sums = open(os.path.join(csrc, "small_sums.hip")).read()
+    assert '#include "small_msm_lane.hpp"' in sums and "JacN small_msm_ladder(" not in sums, "the kernels run the header's ladder"
+    assert sums.count("small_msm_ladder(p, k, live)") == 2
 
 
 def test_ladders_and_trees_match_the_oracle_and_are_sanitizer_clean(host_run):
