@@ -180,6 +180,8 @@ _DEV_SIGS = {
     "halo_dev_msm_offsets": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.c_size_t, u64p, C.c_int, C.c_int, u64p]),
     "halo_dev_sqrt_tables": (C.c_int, [u32p, C.c_size_t]),
     "halo_dev_table_read": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, u64p]),
+    "halo_dev_msm_last_plan": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_long)]),
+    "halo_dev_msm_window_sums": (C.c_int, [C.c_void_p, C.c_int, u64p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "halo_test_lazy_field_op": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t, u32p]),
     "halo_test_lazy_point_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, u32p, u32p, C.c_size_t, u32p]),
 }
@@ -614,6 +616,32 @@ class Context:
         out = np.zeros((n, 8), dtype=np.uint64)
         check(self.lib.halo_dev_table_read(self.h, int(row), int(off), int(n), ptr(out)))
         return out
+
+    MSM_PLAN_FIELDS = ("pipeline", "c", "W", "B", "members", "sets", "pieces", "kmax", "form", "L", "logL", "nseg", "live_seg", "vw", "vw_bits")
+
+    def msm_last_plan(self, slot=0) -> dict:
+        """halo_dev_msm_last_plan: the plan of the launch enqueued last on `slot`, as its launch sequence noted it.  pipeline: 0 general,
+        1 small, 2 table with fixed windows, 3 table sliding; form: 0 k_msm_reduce1 + k_smsm_final, 1 k_smsm_reduce, 2 k_msm_reduce_rc +
+        k_rc_mid (then lg_rows, lg_cols, per; else 0).  Host only."""
+        out = (C.c_long * 16)()
+        check(self.lib.halo_dev_msm_last_plan(self.h, int(slot), out))
+        d = dict(zip(self.MSM_PLAN_FIELDS, [int(v) for v in out]))
+        rc = int(out[15])
+        d.update(lg_rows=rc & 255, lg_cols=(rc >> 8) & 255, per=rc >> 16)
+        return d
+
+    def msm_window_sums(self, slot=0, cap=None):
+        """halo_dev_msm_window_sums: the records the slot's last finished launch left for the host's combination -> (count, 12)
+        Jacobian words (layout per form: include/halo_accumulation_dev.h).  cap: room offered, in points (None: what it takes)."""
+        cnt = C.c_size_t(0)
+        if cap is None:
+            rc = self.lib.halo_dev_msm_window_sums(self.h, int(slot), None, 0, C.byref(cnt))  # (refused for its room: tells the count)
+            if rc != HALO_E_ARG or (cnt.value == 0 and b"null pointer" not in self.lib.halo_last_error()):
+                check(rc)  # (a bad slot, a slot in flight, no launch: that message, at once)
+            cap = cnt.value
+        out = np.zeros((max(int(cap), 1), 12), dtype=np.uint64)
+        check(self.lib.halo_dev_msm_window_sums(self.h, int(slot), ptr(out), int(cap), C.byref(cnt)))
+        return out[:cnt.value]
 
     def batch_to_affine(self, pts_jac):
         """halo_dev_batch_to_affine: m x 12 Jacobian words through the product's batch_to_affine -> m x 8 affine words"""

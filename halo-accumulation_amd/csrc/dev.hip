@@ -751,6 +751,49 @@ int halo_dev_table_read(halo_ctx *ctx, size_t row, size_t off, size_t count, uin
     return rc;
 }
 
+// The two read-only views of a slot's last MSM launch (include/halo_accumulation_dev.h): host only, nothing is enqueued or waited for.
+static int msm_slot_idle(halo_ctx *ctx, int slot, const char *who) {
+    if (slot < 0 || slot >= HALO_SLOTS) { set_error(std::string(who) + ": slot out of range"); return HALO_E_ARG; }
+    if (ctx->wss[slot].in_flight || ctx->wss[slot].lent_from >= 0 || ctx->fan[slot].active) { set_error(std::string(who) + ": the slot has an MSM in flight"); return HALO_E_ARG; }
+    if (!ctx->wss[slot].launched) { set_error(std::string(who) + ": no launch on this slot yet"); return HALO_E_ARG; }
+    return HALO_OK;
+}
+// records the plan's launch left in h_winsum: what msm_combine_member walks over
+static size_t msm_winsum_records(const MsmPlan &p) {
+    if (p.W == 0) return 0;
+    if (p.table_vw > 0 && p.table_rc)
+        return (size_t)p.table_pieces * p.table_sets * 2 * (size_t)(((1 << p.table_rc_lg_cols) + (1 << p.table_rc_lg_rows)) / 64);
+    if (p.table_vw > 0) return (size_t)p.table_pieces * 2 * p.table_sets * p.table_vw;
+    return (size_t)(p.w1 - p.w0) * p.batch;
+}
+int halo_dev_msm_last_plan(halo_ctx *ctx, int slot, long out[16]) {
+    HALO_CTX(ctx);
+    if (!out) { set_error("dev_msm_last_plan: null pointer"); return HALO_E_ARG; }
+    int rc = msm_slot_idle(ctx, slot, "dev_msm_last_plan");
+    if (rc) return rc;
+    const MsmPlan &p = ctx->wss[slot].plan;
+    const long v[16] = {p.pipeline, p.c, p.W, (long)p.B, p.batch, p.table_sets, p.table_pieces, (long)p.kmax, p.winsum_form, (long)p.red_L, p.red_logL,
+                        (long)p.red_nseg, p.red_live_seg, p.table_vw, p.table_vw_bits,
+                        p.table_rc ? (long)p.table_rc_lg_rows | (long)p.table_rc_lg_cols << 8 | (long)p.table_rc_per << 16 : 0};
+    for (int k = 0; k < 16; ++k) out[k] = v[k];
+    return HALO_OK;
+}
+int halo_dev_msm_window_sums(halo_ctx *ctx, int slot, uint64_t *out_jac, size_t cap_points, size_t *count) {
+    HALO_CTX(ctx);
+    if (!count) { set_error("dev_msm_window_sums: null pointer"); return HALO_E_ARG; }
+    *count = 0;
+    int rc = msm_slot_idle(ctx, slot, "dev_msm_window_sums");
+    if (rc) return rc;
+    const MsmWorkspace &ws = ctx->wss[slot];
+    const size_t records = msm_winsum_records(ws.plan);
+    *count = records;
+    if (records > cap_points) { set_error("dev_msm_window_sums: room for fewer points than the launch left (see *count)"); return HALO_E_ARG; }
+    if (!out_jac) { set_error("dev_msm_window_sums: null pointer"); return HALO_E_ARG; }
+    if (records > ws.cap_windows) { set_error("dev_msm_window_sums: the plan names more records than the slot's buffer holds"); return HALO_E_ARG; }
+    for (size_t k = 0; k < 12 * records; ++k) out_jac[k] = ws.h_winsum[k];
+    return HALO_OK;
+}
+
 int halo_test_lazy_field_op(halo_ctx *ctx, int op, const uint32_t *in, size_t n, uint32_t *out) {
     HALO_CTX(ctx);
     if (n == 0) return HALO_OK;

@@ -84,6 +84,14 @@ struct MsmPlan {
     // pinned counter when its last block is through (MsmWorkspace::h_done; one per piece); msm_wait polls the counter.  0: a copy
     // and a stream wait.
     int publishers = 0;
+    // What the launch sequence chose for its window sums, noted where it computes them.  Nothing in the product reads these: the
+    // development library reports them (halo_dev_msm_last_plan), so that a test can assert the plan its case was built for.
+    int pipeline = 0;          // 0 general, 1 small (smsm.hip), 2 table with fixed windows, 3 table sliding
+    int winsum_form = 0;       // 0 k_msm_reduce1 + k_smsm_final, 1 k_smsm_reduce (+ k_smsm_final, or fused), 2 k_msm_reduce_rc + k_rc_mid
+    uint32_t kmax = 0;         // longest chain of the bucket kernel: a bucket of more entries is several tasks
+    uint32_t red_L = 0, red_nseg = 0;  // forms 0, 1: buckets per lane / quad, segments per window
+    int red_logL = 0, red_live_seg = 0;
+    int table_rc_per = 0;      // form 2: buckets per lane of k_msm_reduce_rc
 };
 constexpr int MSM_MAX_BATCH = 8;
 // fixed-base table plan of a context (msm.hip: table_plan)
@@ -143,6 +151,7 @@ struct MsmWorkspace {
     size_t cap_counts = 0, cap_sorted = 0, cap_tasks = 0, cap_hist = 0, cap_windows = 0;
     MsmPlan plan{};          // plan of the MSM in flight on this slot
     bool in_flight = false;
+    bool launched = false;   // a launch has been enqueued on this workspace: `plan` is that launch's (halo_dev_msm_last_plan)
     int lent_from = -1;      // this slot's workspace and stream run the odd pieces of the large MSM in flight on slot `lent_from`
     int borrowed = -1;       // ... and that slot remembers which one it borrowed (msm_wait gives it back)
     // hipGraph of the launch sequence, replayed while the same (bases, scalars, n, form, window) repeats
@@ -537,7 +546,7 @@ int quad_final_enqueue(halo_ctx *ctx, MsmWorkspace &ws, uint32_t Wt, uint32_t ns
                        const uint32_t *seg = nullptr, uint32_t *done = nullptr);
 int rc_mid_enqueue(halo_ctx *ctx, const uint32_t *entries, uint32_t blocks, uint64_t *winsum, uint32_t *done = nullptr, uint32_t *ticket = nullptr);
 // (offs: one base offset per member, in points; a block of k_smsm_sort sorts one window, so one member)
-int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MemberOffsets &offs, size_t n, const MsmPlan &p, uint32_t Wt,
+int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MemberOffsets &offs, size_t n, MsmPlan &p, uint32_t Wt,
                  uint32_t kmax);
 int smsm_prepare();
 

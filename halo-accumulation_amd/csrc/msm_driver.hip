@@ -172,15 +172,16 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
     MsmWorkspace &ws = ctx->wss[slot];
     if (ws.in_flight) { set_error("msm: slot already has an MSM in flight"); return HALO_E_ARG; }
     ws.plan = MsmPlan{0, 0, 0, msm_outputs(members), 0, 0};
+    ws.launched = false;  // (until this launch is on its way: a refused one leaves no plan to report)
     if (members.tagged && (members.count != 1 || mont || !msm_tagged_ready(ctx, d_bases, n))) {
         set_error("msm: a tagged launch is one canonical scalar array over the context's key with the c = 20 table in place (msm_tagged_ready)");
         return HALO_E_ARG;
     }
     if (members.parts < 1 || members.part < 0 || members.part >= members.parts) { set_error("msm: window shard out of range"); return HALO_E_ARG; }
-    if (n == 0) { ws.in_flight = true; return HALO_OK; }
+    if (n == 0) { ws.in_flight = ws.launched = true; return HALO_OK; }
     if (members.parts > 1) {  // a shard that owns no window (more shards than windows) contributes the point at infinity
         MsmPlan p = msm_plan(n, launch_c(ctx, members));
-        if (p.W * members.part / members.parts == p.W * (members.part + 1) / members.parts) { ws.in_flight = true; return HALO_OK; }
+        if (p.W * members.part / members.parts == p.W * (members.part + 1) / members.parts) { ws.in_flight = ws.launched = true; return HALO_OK; }
     }
     {
         // A batch lays the members' windows side by side and a forced task length multiplies the tasks: grow
@@ -285,7 +286,7 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
         ws.plan = hit->plan;
         ctx->last_table_plan = ws.plan.table_vw > 0 ? ws.plan.table_slide : -1;
         ws.done_expect += (uint32_t)ws.plan.publishers;
-        ws.in_flight = true;
+        ws.in_flight = ws.launched = true;
         if (partner >= 0) { ws.borrowed = partner; ctx->wss[partner].in_flight = true; ctx->wss[partner].lent_from = slot; }
         return HALO_OK;
     }
@@ -332,7 +333,7 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
     }
     ctx->last_table_plan = ws.plan.table_vw > 0 ? ws.plan.table_slide : -1;
     ws.done_expect += (uint32_t)ws.plan.publishers;
-    ws.in_flight = true;
+    ws.in_flight = ws.launched = true;
     if (partner >= 0) { ws.borrowed = partner; ctx->wss[partner].in_flight = true; ctx->wss[partner].lent_from = slot; }
     return HALO_OK;
 }

@@ -553,6 +553,8 @@ int msm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_base
         nseg = p.B / (64 * L);
     }
     while ((1u << logL) < L) logL++;
+    p.pipeline = 0; p.winsum_form = 0; p.kmax = kmax; p.red_L = L; p.red_nseg = nseg; p.red_logL = logL;
+    for (p.red_live_seg = 1; (uint32_t)p.red_live_seg < nseg;) p.red_live_seg <<= 1;  // (quad_final_enqueue's)
     HALO_LAUNCH(ctx, "k_msm_reduce1", k_msm_reduce1, dim3((unsigned)(Wt * nseg)), dim3(64), 0, ws.d_buckets, ws.d_ntask, ws.d_toff,
                 ws.d_tblockoff, p.B, L, logL, nseg, ws.d_seg);
     {

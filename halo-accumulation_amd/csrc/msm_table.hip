@@ -832,6 +832,20 @@ static uint32_t tmsm_kmax(const halo_ctx *ctx, size_t entries) {
 // records in front of the static layout of `order`: one per kmax entries at most (the bound of the tasks beyond one per
 // bucket), rounded so that the blocks of the bucket kernel line up with the static layout
 static size_t tmsm_ovf_records(size_t entries, uint32_t kmax) { return (entries / kmax + 1 + 255) / 256 * 256; }
+// What a piece of `entries` digits takes for its bucket kernel and -- without the row / column sums -- for k_msm_reduce1 over virtual
+// windows of 2^vw_bits buckets: computed here for the piece that launches and for the plan that reports it (MsmPlan, one place each).
+struct TblWinsum { uint32_t kmax, L, nseg; int logL; };
+static TblWinsum tmsm_winsum(const halo_ctx *ctx, const TblPlan &tp, size_t entries) {
+    TblWinsum w;
+    w.kmax = tmsm_kmax(ctx, entries);
+    const uint32_t vwB = 1u << tp.vw_bits;
+    w.L = vwB / 4096 ? vwB / 4096 : 1;
+    w.nseg = vwB / (64 * w.L);
+    if (tp.vw_bits == 15 && (ctx->reduce_span == 16 || ctx->reduce_span == 32 || ctx->reduce_span == 64)) { w.L = (uint32_t)ctx->reduce_span; w.nseg = 512 / w.L; }
+    w.logL = 0;
+    while ((1u << w.logL) < w.L) w.logL++;
+    return w;
+}
 int tmsm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MsmBatch &members, bool mont, size_t n, int partner) {
     const TblPlan tp = table_launch_plan(ctx, members, n);
     size_t pieces = tp.c == 20 ? (n + TBL_PIECE - 1) / TBL_PIECE : 1;
@@ -877,6 +891,17 @@ int tmsm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bas
     p.table_rc_lg_rows = rcs.lg_rows;
     p.table_rc_lg_cols = rcs.lg_cols;
     p.table_slide = tp.slide;
+    {   // the window sums every piece took (the pieces are of one length but for the last: the same task length class is noted from the first)
+        const TblWinsum w = tmsm_winsum(ctx, tp, (size_t)tp.W * (len < n ? len : n) * members.count);
+        p.pipeline = tp.slide ? 3 : 2;
+        p.kmax = w.kmax;
+        p.winsum_form = rcs.per ? 2 : 0;
+        p.table_rc_per = rcs.per;
+        if (!rcs.per) {
+            p.red_L = w.L; p.red_nseg = w.nseg; p.red_logL = w.logL;
+            for (p.red_live_seg = 1; (uint32_t)p.red_live_seg < w.nseg;) p.red_live_seg <<= 1;  // (quad_final_enqueue's)
+        }
+    }
     ws.plan = p;
     return HALO_OK;
 }
@@ -908,7 +933,8 @@ static int tmsm_enqueue_piece(halo_ctx *ctx, MsmWorkspace &ws, const TblPlan &pl
     chunk_len = (chunk_len + 3) / 4 * 4;
     dim3 gridc((unsigned)(rows * nchunks)), b1024(1024), b256(256);
     uint32_t *chist = ws.d_hist, *cstart = ws.d_hist + (size_t)rows * nchunks * tp.ranges;  // <= 255 * 512 + 513 words <= cap_hist
-    const uint32_t kmax = tmsm_kmax(ctx, entries);
+    const TblWinsum wsum = tmsm_winsum(ctx, plan, entries);
+    const uint32_t kmax = wsum.kmax;
     const bool wide = tp.ranges > TBL_MAX_RANGES;  // (two bucket sets of the c = 20 plan: 1024 coarse ranges)
     if (wide) HALO_LAUNCH(ctx, "k_tmsm_coarse_hist2", k_tmsm_coarse_hist2, gridc, b1024, 0, d_digits, (uint32_t)n, nchunks, chunk_len, tp, chist);
     else HALO_LAUNCH(ctx, "k_tmsm_coarse_hist", k_tmsm_coarse_hist, gridc, b1024, 0, d_digits, (uint32_t)n, nchunks, chunk_len, tp, chist);
@@ -947,11 +973,8 @@ static int tmsm_enqueue_piece(halo_ctx *ctx, MsmWorkspace &ws, const TblPlan &pl
         return HALO_OK;
     }
     uint64_t *d_out = ws.d_winsum + (size_t)piece * 2 * tp.vw * 12;
-    uint32_t vwB = 1u << tp.vw_bits;
-    uint32_t L = vwB / 4096 ? vwB / 4096 : 1, nseg = vwB / (64 * L);
-    if (tp.vw_bits == 15 && (ctx->reduce_span == 16 || ctx->reduce_span == 32 || ctx->reduce_span == 64)) { L = (uint32_t)ctx->reduce_span; nseg = 512 / L; }
-    int logL = 0;
-    while ((1u << logL) < L) logL++;
+    const uint32_t vwB = 1u << tp.vw_bits, L = wsum.L, nseg = wsum.nseg;
+    const int logL = wsum.logL;
     HALO_LAUNCH(ctx, "k_msm_reduce1", k_msm_reduce1, dim3(tp.vw * nseg), dim3(64), 0, ws.d_buckets, ws.d_ntask, ws.d_toff, ws.d_tblockoff, vwB, L, logL,
                 nseg, ws.d_seg);
     {

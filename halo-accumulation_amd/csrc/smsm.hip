@@ -500,7 +500,7 @@ __global__ __launch_bounds__(256, 2) void k_smsm_final(const uint32_t *__restric
 // Called from msm_enqueue_launches (msm.hip) after k_msm_recode; digits are in ws.d_canon.  Buffer reuse: d_sorted
 // (entries), d_starts (first task of a bucket), d_counts (tasks of a bucket), d_task_g (task records), d_buckets
 // (partials), d_seg, d_meta[0] (task count), d_meta[64 + w] (tickets), d_winsum.
-int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MemberOffsets &offs, size_t n, const MsmPlan &p, uint32_t Wt,
+int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MemberOffsets &offs, size_t n, MsmPlan &p, uint32_t Wt,
                  uint32_t kmax) {
     const uint16_t *d_digits = reinterpret_cast<const uint16_t *>(ws.d_canon);
     // entries per wave task: 8 per lane where the launch is throughput-bound, 2 per lane for the latency-bound small ones
@@ -554,6 +554,7 @@ int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const
     int logL = 0, live_seg = 1;
     while ((1u << logL) < L) logL++;
     while ((uint32_t)live_seg < nseg) live_seg <<= 1;
+    p.pipeline = 1; p.winsum_form = 1; p.kmax = kmax; p.red_L = L; p.red_nseg = nseg; p.red_logL = logL; p.red_live_seg = live_seg;
     // (the fused form's per-window tickets are done[w] = d_meta[64 + w]: d_meta has 256 words, all zeroed by the recode, and word
     // 255 is the publish ticket -- more than 191 windows keep the two-launch form)
     const bool fused = tuning().smsm_fused && Wt <= 191;

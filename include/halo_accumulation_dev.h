@@ -180,6 +180,32 @@ int halo_dev_msm_offsets(halo_ctx *ctx, const size_t *offs /*count entries, poin
  * leaves the key, an MSM in flight on any slot. */
 int halo_dev_table_read(halo_ctx *ctx, size_t row, size_t off, size_t count, uint64_t *out_affine);
 
+/* Host only: the plan of the MSM launch enqueued last on `slot`, as the launch sequence noted it (MsmPlan: reported, not
+ * recomputed; a graph replay reports the plan it was captured with).  out =
+ *   [0] pipeline: 0 general, 1 small (smsm.hip), 2 table with fixed windows, 3 table sliding
+ *   [1] c  [2] W  [3] B            window bits, windows, buckets per window (table plans: per set)
+ *   [4] members  [5] sets          MSMs of the launch; bucket sets of a table launch (members rounded up to a power of two)
+ *   [6] pieces                     consecutive pieces of a large table MSM
+ *   [7] kmax                       longest chain of the bucket kernel: a bucket of more entries is several tasks
+ *   [8] window-sum form: 0 k_msm_reduce1 + k_smsm_final, 1 k_smsm_reduce (+ k_smsm_final, or fused), 2 k_msm_reduce_rc + k_rc_mid
+ *   [9] L  [10] logL  [11] nseg  [12] live_seg    forms 0 and 1: buckets per lane (quad), segments per window, the final stage's width
+ *   [13] vw  [14] vw_bits          table with fixed windows: virtual windows per set, log2 of their buckets
+ *   [15] form 2: lg_rows | lg_cols << 8 | per << 16 (rows x columns of the bucket index, buckets per lane); else 0
+ * A launch of no points, or a window shard without windows, reports W = 0.  HALO_E_ARG: a slot out of range, a slot in flight, no
+ * launch on the slot yet (or its last one refused), a null `out`. */
+int halo_dev_msm_last_plan(halo_ctx *ctx, int slot, long out[16]);
+/* Host only: the records the last finished launch of `slot` left in the slot's pinned buffer, copied as they are -- 12-word Jacobian
+ * points (X | Y | Z, Montgomery words, Z = 0: infinity), exactly what the host's combination (msm_combine_member) reads.  *count =
+ * their number; by window-sum form of halo_dev_msm_last_plan:
+ *   general and small pipeline   members x (w1 - w0) weighted sums sum_b (b + 1) B_b, [member][w]
+ *   table, fixed windows         per piece: sets x vw weighted sums [set][v] (weights 1 .. 2^vw_bits inside virtual window v), then
+ *                                sets x vw plain sums sum_b B_b in the same order
+ *   table, rows and columns      per piece and set: the pairs (S, T) = (sum_Q E_Q, sum_Q (Q + 1) E_Q) of the 64-entry blocks of the
+ *                                columns' plain sums C_lo (2^lg_cols / 64 pairs), then those of the rows' R_hi (2^lg_rows / 64 pairs)
+ * HALO_E_ARG: a slot out of range, a slot in flight, no launch yet, a null pointer, cap_points below the number of records -- *count
+ * is set in that case too. */
+int halo_dev_msm_window_sums(halo_ctx *ctx, int slot, uint64_t *out_jac, size_t cap_points, size_t *count);
+
 /* The decode batch's square root in Fq (the routine of k_point_decompress) on its own, one lane per element: a = m x 4
  * Montgomery words; ok_out[i] = 1 and root_out[i]^2 = a[i] if a[i] is a square, else ok_out[i] = 0 */
 int halo_dev_fq_sqrt(halo_ctx *ctx, const uint64_t *a, size_t m, uint64_t *root_out, uint32_t *ok_out);
