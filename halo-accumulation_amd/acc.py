@@ -5,7 +5,7 @@ import numpy as np
 
 from halo_accumulation_amd import _lib
 from halo_accumulation_amd._lib import check, ptr
-from halo_accumulation_amd.pcdl import _a, _check_batch, _pack_polys, _pack_rows, lg_of
+from halo_accumulation_amd.pcdl import _a, _check_batch, _pack_polys, _pack_rows, _seed32, lg_of
 
 
 def _cat(qs):
@@ -129,3 +129,9 @@ def decider_batch(ctx, d, accs):
     """acc::decider (acc.rs:245-255) of m accumulators of degree bound d at once (benches/acc.rs:100-106 in one call) -> status
     list; raises HaloReject as pcdl.check_batch does"""
     return _check_batch(ctx, ctx.lib.halo_acc_decider_batch, d, accs)
+
+
+def decider_batch_combined(ctx, d, accs, seed=None):
+    """decider_batch with ONE MSM for all accepted members (halo_acc_decider_batch_combined; seed: 32 bytes or None) -> status
+    list; statuses and HaloReject as decider_batch whenever a member is bad"""
+    return _check_batch(ctx, lambda h, dd, qs, m, st: ctx.lib.halo_acc_decider_batch_combined(h, dd, qs, m, _seed32(seed), st), d, accs)

@@ -15,6 +15,7 @@
 #include "dev_lazy_ops.hpp"
 #include "fr_plan.hpp"
 #include "internal.hpp"
+#include "pcdl_internal.hpp"
 
 namespace halo {
 
@@ -222,6 +223,12 @@ int halo_dev_hook(const char *name, long value) {
         if (value < 0 || value > 2) { set_error("dev_hook: open_batch_fold is 0 (the measured default), 1 (the folded schedule wherever it applies) or 2 (never: the loop)"); return HALO_E_ARG; }
         h.open_fold = (int)value;
     }
+    else if (!std::strcmp(name, "check_combined_parts")) h.combined_parts = value > 0 ? (int)value : 0;
+    else if (!std::strcmp(name, "check_combined_cap")) h.combined_cap = value > 0 ? (int)value : 0;
+    else if (!std::strcmp(name, "check_combined_usum")) {
+        if (value < 0 || value > 2) { set_error("dev_hook: check_combined_usum is 0 (by the member count), 1 (the host pool) or 2 (the device)"); return HALO_E_ARG; }
+        h.combined_usum = (int)value;
+    }
     else if (!std::strcmp(name, "verifier_batch_min")) h.verifier_min = (int)value;
     else if (!std::strcmp(name, "decode_batch_min")) h.decode_min = value;
     else if (!std::strcmp(name, "table_slide_min")) h.slide_min = value > 0 && value < 4096 ? 4096 : value;
@@ -237,7 +244,7 @@ int halo_dev_hook(const char *name, long value) {
         h.poly_blocks = (int)value;
     }
     else if (!std::strcmp(name, "reset")) h = DevHooks();
-    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, open_batch_fold, commit_batch_group, verifier_batch_min, decode_batch_min, table_slide_min, pow_e, dot_blocks, poly_blocks, reset)"); return HALO_E_ARG; }
+    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, open_batch_fold, commit_batch_group, check_combined_parts, check_combined_cap, check_combined_usum, verifier_batch_min, decode_batch_min, table_slide_min, pow_e, dot_blocks, poly_blocks, reset)"); return HALO_E_ARG; }
     return HALO_OK;
 }
 
@@ -331,6 +338,42 @@ int halo_dev_h_accumulate_batch(halo_ctx *ctx, const uint64_t *h0s, const uint64
     if (!rc && (e = hipMemcpy(out, d_out, members * n * 32, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     if (rc) (void)hipStreamSynchronize(ctx->stream);
     (void)hipHostFree(h);
+    (void)hipFree(d);
+    return rc;
+}
+
+// host only: the weights of the combined check batch as the product computes them (tests/test_check_combined_cpu.py restates the rule)
+int halo_dev_check_weights(const uint64_t *blobs, size_t stride_words, const size_t *idx, size_t A, size_t d, const uint8_t seed[32], uint64_t *out) {
+    if (A == 0) return HALO_OK;
+    if (!blobs || !idx || !out) { set_error("check_weights: null pointer"); return HALO_E_ARG; }
+    if (!is_pow2(d + 1) || stride_words < instance_words(ilog2(d + 1))) { set_error("check_weights: d + 1 is a power of two, the stride at least an Instance"); return HALO_E_ARG; }
+    std::vector<host::Fr> r;
+    check_combined_weights(blobs, stride_words, idx, A, d, seed, r);
+    for (size_t a = 0; a < A; ++a) r[a].store(out + 4 * a);
+    return HALO_OK;
+}
+
+// the combined check's scalar step on its own (tests/test_gpu_check_combined.py holds it against Python integers): temporary
+// device buffers of this call only
+int halo_dev_check_combined_scalars(halo_ctx *ctx, const uint64_t *xis, const uint64_t *weights, size_t A, size_t lg_n, uint64_t *out) {
+    HALO_CTX(ctx);
+    if (!xis || !weights || !out) { set_error("check_combined_scalars: null pointer"); return HALO_E_ARG; }
+    if (A < 1 || A > 65535) { set_error("check_combined_scalars: 1..65535 polynomials"); return HALO_E_ARG; }
+    if (lg_n < 1 || lg_n > 24 || ((size_t)1 << lg_n) > (ctx->n < 64 ? 64 : ctx->n)) { set_error("check_combined_scalars: 2^lg_n exceeds context size"); return HALO_E_ARG; }
+    const size_t n = (size_t)1 << lg_n, xw = (lg_n + 1) * 4, tw = xw + 4;
+    const size_t P = check_combined_parts(n, A), cap = check_combined_cap(A);
+    std::vector<uint64_t> recs(A * tw);
+    for (size_t a = 0; a < A; ++a) {
+        std::memcpy(&recs[a * tw], xis + a * xw, xw * 8);
+        std::memcpy(&recs[a * tw + xw], weights + 4 * a, 32);
+    }
+    uint64_t *d = nullptr;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d, hcomb_stage_words(A, lg_n, P, cap) * 8));
+    int rc = h_combine_rows(ctx, recs.data(), A, lg_n, P, cap, d);
+    hipError_t e = hipStreamSynchronize(ctx->stream);  // (also on failure: nothing of this call may be in flight when its buffer goes)
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    if (!rc && (e = hipMemcpy(out, d + hcomb_rows_offset(A, lg_n, P, cap), n * 32, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d);
     return rc;
 }

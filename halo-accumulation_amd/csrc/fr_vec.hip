@@ -419,6 +419,20 @@ __global__ __launch_bounds__(256) void k_pad_members_batch(PadMembers t, uint32_
     reinterpret_cast<uint4 *>(out + ms * t.row[blockIdx.y])[i] = v;
 }
 
+// ------------------------------------------------------------------ the partial rows of the combined check's scalars
+// rows[0][k] = sum_p rows[p][k] over P rows of n elements at `stride` words (halo_pcdl_check_batch_combined: the parts of
+// sum_a r_a h_a(X), hpoly.hip h_combine_rows).  One element per lane; the running sum stays in the lazy 29-bit form, brought back
+// below 2 r after every addition as h_acc_step does (a canonical element is < r, the sum < 6 r before fs_tighten), so the bound
+// does not depend on P; ONE canonical store per element.  Field sums are exact: the words do not depend on P.
+__global__ __launch_bounds__(256) void k_fr_sum_rows(uint64_t *__restrict__ rows, uint64_t stride, uint32_t P, uint32_t n) {
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    Fs<2> acc = fs_tighten(fs_load(rows + 4 * (size_t)k));
+#pragma unroll 1
+    for (uint32_t p = 1; p < P; p++) acc = fs_tighten(fs_add(acc, fs_load(rows + (size_t)p * stride + 4 * (size_t)k)));
+    fs_store(rows + 4 * (size_t)k, acc);
+}
+
 // ================================================================== host launchers
 int ipa_fold_scalars(halo_ctx *ctx, uint64_t *d_c, uint64_t *d_z, size_t m, const host::Fr &xi, const host::Fr &xi_inv) {
     if (m == 0) return HALO_OK;
@@ -660,6 +674,14 @@ int pad_members_batch(halo_ctx *ctx, const PadMembers &t, int count, size_t n, u
         if (t.len[k] > n || t.row[k] >= (uint32_t)MSM_MAX_BATCH || (t.len[k] && !t.src[k])) { set_error("pad_members: bad member"); return HALO_E_ARG; }
     HALO_LAUNCH(ctx, "k_pad_members_batch", k_pad_members_batch, dim3((unsigned)((2 * n + 255) / 256), (unsigned)count), dim3(256), 0, t, (uint32_t)n,
                 d_out, (uint64_t)ms);
+    HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
+int fr_sum_rows(halo_ctx *ctx, uint64_t *d_rows, size_t stride, size_t P, size_t n) {
+    if (P <= 1 || n == 0) return HALO_OK;  // (one row is the sum)
+    if (P > 65535 || n > ((size_t)1 << 30) || stride < n * 4) { set_error("fr_sum_rows: bad shape"); return HALO_E_ARG; }
+    HALO_LAUNCH(ctx, "k_fr_sum_rows", k_fr_sum_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, d_rows, (uint64_t)stride, (uint32_t)P, (uint32_t)n);
     HALO_HIP(hipGetLastError());
     return HALO_OK;
 }

@@ -238,6 +238,44 @@ int h_accumulate_group(halo_ctx *ctx, const HAccMember *mem, size_t G, size_t lg
     }
 }
 
+// s = sum_a r_a h_a(X) over A polynomials (halo_pcdl_check_batch_combined), n canonical elements in row 0 of d_stage's rows.
+// One member row of k_h_accumulate_batch would be plan_h_coeffs(n).blocks x 1 blocks walking all A tables in turn: a handful of
+// waves at n = 512.  So the polynomials are cut into P PARTS, blockIdx.y = part, each with its own first / count record (h_0 = 0)
+// and its own n-element partial row; k_fr_sum_rows then adds the rows into row 0 (P = 1: nothing to add).  The tables are built
+// `cap` at a time (k_h_tables, scaled: r_a folded into the high table); a later pass adds to the rows (mode 2).  Field sums are
+// exact and every stored element canonical, so the words of s depend neither on P nor on cap.
+// h_recs: A records of lg_n + 2 Montgomery elements (the challenges, then r_a) in host memory.  d_stage (hcomb_stage_words):
+// the A records | passes x P part records | cap tables | P rows.  The uploads are complete when the call returns (hipMemcpy),
+// the launches are on ctx->stream.
+int h_combine_rows(halo_ctx *ctx, const uint64_t *h_recs, size_t A, size_t lg_n, size_t P, size_t cap, uint64_t *d_stage) {
+    if (lg_n > 24) { set_error("h_coeffs: lg_n > 24 unsupported"); return HALO_E_ARG; }
+    if (A == 0 || A > 65535 || P == 0 || P > A || cap == 0) { set_error("h_combine: 1..65535 polynomials, 1..A parts, at least one table"); return HALO_E_ARG; }
+    if (cap > A) cap = A;
+    const size_t n = (size_t)1 << lg_n, tw = (lg_n + 2) * 4, passes = (A + cap - 1) / cap;
+    const FrPlan p = plan_h_coeffs(n);
+    uint64_t *d_recs = d_stage, *d_parts = d_recs + A * tw, *d_tabs = d_parts + hcomb_part_words(A, P, cap), *d_rows = d_tabs + cap * H_TAB_WORDS;
+    std::vector<uint64_t> parts(passes * P * HACC_REC_WORDS, 0);  // (h_0 = 0 in every record)
+    for (size_t pass = 0; pass < passes; ++pass) {
+        const size_t T = A - pass * cap < cap ? A - pass * cap : cap;
+        for (size_t q = 0; q < P; ++q) {  // part q: tables [q T / P, (q + 1) T / P) of this pass
+            const size_t lo = q * T / P, hi = (q + 1) * T / P;
+            uint64_t *rec = &parts[(pass * P + q) * HACC_REC_WORDS];
+            rec[0] = (uint64_t)lo | ((uint64_t)(hi - lo) << 32);
+            rec[1] = pass == 0 ? 1 : (hi > lo ? 2 : 0);
+        }
+    }
+    HALO_HIP(hipMemcpy(d_recs, h_recs, A * tw * 8, hipMemcpyHostToDevice));
+    HALO_HIP(hipMemcpy(d_parts, parts.data(), parts.size() * 8, hipMemcpyHostToDevice));
+    for (size_t pass = 0; pass < passes; ++pass) {
+        const size_t T = A - pass * cap < cap ? A - pass * cap : cap;
+        HALO_LAUNCH(ctx, "k_h_tables", k_h_tables, dim3((unsigned)T), dim3(256), 0, d_recs + pass * cap * tw, (int)lg_n, 1, d_tabs);
+        HALO_LAUNCH(ctx, "k_h_accumulate_batch", k_h_accumulate_batch, dim3(p.blocks, (unsigned)P), dim3(256), 0, d_tabs, d_parts + pass * P * HACC_REC_WORDS,
+                    (uint32_t)n, p.E, d_rows, (uint64_t)(n * 4));
+    }
+    HALO_HIP(hipGetLastError());
+    return fr_sum_rows(ctx, d_rows, n * 4, P, n);
+}
+
 int h_eval_batch(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg_n, const host::Fr &z, uint64_t *d_out) {
     if (m == 0) return HALO_OK;
     HALO_LAUNCH(ctx, "k_h_eval", k_h_eval, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, d_xis, (uint32_t)m, (int)lg_n, to_arg(z), d_out);

@@ -596,6 +596,20 @@ inline size_t hacc_pin_words(size_t G, size_t lg_n, size_t cap) { return G * HAC
 inline size_t hacc_stage_words(size_t G, size_t lg_n, size_t cap) { return hacc_pin_words(G, lg_n, cap) + cap * H_TABLES_WORDS; }
 int h_accumulate_group(halo_ctx *ctx, const HAccMember *mem, size_t G, size_t lg_n, size_t cap, uint64_t *h_stage, uint64_t *d_stage, uint64_t *d_out,
                        size_t out_stride);
+// s = sum_a r_a h_a(X) over A polynomials in P parts, `cap` tables per pass (hpoly.hip; halo_pcdl_check_batch_combined): the
+// device staging's layout is the A records | the part records (rounded up to 32 bytes) | cap tables | P rows of n elements,
+// and row 0 (hcomb_rows) holds s when the launches on ctx->stream are through
+inline size_t hcomb_part_words(size_t A, size_t P, size_t cap) {
+    if (cap > A) cap = A;
+    return (((A + cap - 1) / cap) * P * HACC_REC_WORDS + 3) & ~(size_t)3;
+}
+inline size_t hcomb_rows_offset(size_t A, size_t lg_n, size_t P, size_t cap) {
+    return A * (lg_n + 2) * 4 + hcomb_part_words(A, P, cap) + (cap > A ? A : cap) * H_TABLES_WORDS;
+}
+inline size_t hcomb_stage_words(size_t A, size_t lg_n, size_t P, size_t cap) { return hcomb_rows_offset(A, lg_n, P, cap) + P * (((size_t)1 << lg_n) * 4); }
+int h_combine_rows(halo_ctx *ctx, const uint64_t *h_recs, size_t A, size_t lg_n, size_t P, size_t cap, uint64_t *d_stage);
+// fr_vec.hip: rows[0] = the sum of P rows of n elements at `stride` words (k_fr_sum_rows; P = 1 launches nothing), on ctx->stream
+int fr_sum_rows(halo_ctx *ctx, uint64_t *d_rows, size_t stride, size_t P, size_t n);
 int h_eval_batch(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg_n, const host::Fr &z, uint64_t *d_out);
 // m polynomials h_i at their own points z_i
 int h_eval_each(halo_ctx *ctx, const uint64_t *d_xis, const uint64_t *d_zs, size_t m, size_t lg_n, uint64_t *d_out);

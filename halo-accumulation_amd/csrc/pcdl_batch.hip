@@ -4,6 +4,7 @@
 // in pcdl_internal.hpp; the slots, streams and outcome reports they share with each other (and with wire.hip's decode batch) in
 // internal.hpp: idle_slots, StreamGuard, report_members.
 #include "curve.hpp"  // (AFF_STRIDE: the staged keys of the folded schedule)
+#include "fr_plan.hpp"
 #include "pcdl_internal.hpp"
 
 namespace halo {
@@ -37,6 +38,54 @@ size_t check_stage(halo_ctx *ctx, size_t want, size_t per_bytes) {
         }
     }
     return ctx->check_stage_bytes / per_bytes;
+}
+
+// ------------------------------------------------------------------ the weights and the launch shape of the combined check
+// (pcdl_internal.hpp: the development library calls these too)
+void check_combined_weights(const uint64_t *blobs, size_t stride, const size_t *idx, size_t A, size_t d, const uint8_t *seed, std::vector<Fr> &out) {
+    static const char kDomain[] = "halo-accumulation/check-batch-combined/v1";
+    static const uint8_t kZeros[32] = {};
+    const size_t W = instance_words(ilog2(d + 1));
+    const uint64_t d64 = d, A64 = A;
+    uint8_t D[32];
+    host::Sha3_256 h;
+    h.update(kDomain, sizeof(kDomain) - 1);
+    h.update(seed ? seed : kZeros, 32);
+    h.update(&d64, 8);  // (the words of a blob are little-endian in memory on every host this library builds for)
+    h.update(&A64, 8);
+    for (size_t a = 0; a < A; ++a) {
+        const uint64_t i64 = idx[a];
+        h.update(&i64, 8);
+        h.update(blobs + idx[a] * stride, W * 8);
+    }
+    h.finalize(D);
+    out.resize(A);
+    for (size_t a = 0; a < A; ++a) {
+        const uint64_t a64 = a;
+        uint8_t dig[32];
+        host::Sha3_256 g;
+        g.update(D, 32);
+        g.update(&a64, 8);
+        g.finalize(dig);
+        out[a] = Fr::from_le_bytes_mod_order(dig);
+    }
+}
+// P: one row of parts is plan_h_coeffs(n).blocks x 4 waves; enough parts for a wave per SIMD (1024) where the members allow
+size_t check_combined_parts(size_t n, size_t A) {
+    const int forced = dev_hooks().combined_parts;
+    size_t P;
+    if (forced >= 1) P = (size_t)forced;
+    else {
+        const size_t waves = (size_t)plan_h_coeffs(n).blocks * 4;
+        P = (1024 + waves - 1) / waves;
+    }
+    return P > A ? A : (P < 1 ? 1 : P);
+}
+// tables per pass: 256 x 24 KiB = 6 MiB of staging, and a pass of 256 tables is long enough to hide the next launch
+size_t check_combined_cap(size_t A) {
+    const int forced = dev_hooks().combined_cap;
+    const size_t cap = forced >= 1 ? (size_t)forced : 256;
+    return cap > A ? A : cap;
 }
 
 namespace {  // (everything below is local to this file; the entry points at the end are the way in)
@@ -108,20 +157,11 @@ static int check_group_size(const halo_ctx *ctx, size_t n) {
     if (forced <= 0 && n >= ((size_t)1 << 20) && ctx->n >= ((size_t)1 << 20) && ctx->table_mode != 0) return 1;
     return group_size(ctx, n, forced, MSM_MAX_BATCH, 1);
 }
-// blobs: m Instances (or Accumulators, whose Instance prefix is checked) at `stride` words, all of degree bound d (checked by
-// the caller); status[i] (nullable) = what halo_pcdl_check returns for member i alone
-static int pcdl_check_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t stride, size_t m, int *status) {
-    const size_t n = d + 1, lg = ilog2(n);
-    int slots[HALO_SLOTS], S = idle_slots(ctx, slots);
-    if (!S) { set_error("check_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
-    // 1. the succinct half (pcdl.rs:333)
-    std::vector<BatchCheck> res;
-    int rc = succinct_half(ctx, d, [&](size_t i) { return qs + i * stride; }, m, res);
-    if (rc) return rc;
-    std::vector<size_t> ok;  // the accepted members, in order
-    for (size_t i = 0; i < m; ++i)
-        if (!res[i].rc) ok.push_back(i);
-    const size_t A = ok.size();
+// The exact MSM half (steps 2 and 3 above) for the members `ok` the succinct half accepted, over the slots idle at entry: a member
+// whose point differs from its U gets its reject in res
+static int check_members_exact(halo_ctx *ctx, size_t n, const int *slots, int S, std::vector<BatchCheck> &res, const std::vector<size_t> &ok) {
+    const size_t lg = ilog2(n), A = ok.size();
+    int rc = HALO_OK;
     if (A) {
         if (lg > 24) { set_error("h_coeffs: lg_n > 24 unsupported"); return HALO_E_ARG; }
         // 2. their challenges in device memory, in that order (one copy)
@@ -170,17 +210,135 @@ static int pcdl_check_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, si
             });
         if (rc) return rc;
     }
+    return HALO_OK;
+}
+// ------------------------------------------------------------------ ... as ONE relation (halo_pcdl_check_batch_combined)
+// pcdl.rs:338-339 is linear in h: <h_i, G> = U_i.  So the A >= 2 members the succinct half accepted are checked as
+// <sum_a r_a h_a, G> = sum_a r_a U_a with the weights of check_combined_weights (the rule: include/halo_accumulation.h):
+//   scalars    s = sum_a r_a h_a(X) on the device (hpoly.hip h_combine_rows: the polynomials in P parts, k_fr_sum_rows), in the
+//              context's check staging (optional memory; none: *held stays false and the caller runs the exact batch);
+//   left side  ONE n-point MSM of s over the key on the first idle slot (the table pipeline where the key has one);
+//   right side T = sum_a r_a U_a while that MSM runs: on the host pool, or from kCombinedUsumDeviceMin members on -- and with a
+//              second idle slot -- as a variable-base MSM on the device (k_batch_to_affine + the small pipeline: the path of
+//              halo_msm_points).  The hook "check_combined_usum" forces either side.
+// *held = the two sides are the same point.  If they are not, the caller runs the exact batch over the same members, so which
+// members a call rejects never depends on the weights.
+// kCombinedUsumDeviceMin is measured (tools/time_decider_batch.py --combined, its right-side sweep; HISTORY.md): from 64 members on
+// every run with the device sum was faster than every run with the pool's (0.2 - 1.0 ms of the call); at 4 members the pool won
+// every run, and at 2, 8, 16 and 32 the ranges overlap -- there the pool stays, which needs no second slot.
+constexpr size_t kCombinedUsumDeviceMin = 64;
+
+static int combined_usum_device(halo_ctx *ctx, int slot, const std::vector<BatchCheck> &res, const std::vector<size_t> &ok, const std::vector<Fr> &r,
+                                uint64_t *d_region, Point *T) {
+    const size_t A = ok.size();
+    uint32_t *d_native = reinterpret_cast<uint32_t *>(d_region);  // A x AFF_STRIDE 32-bit words | A x 12 | A x 4
+    uint64_t *d_jac = d_region + A * (AFF_STRIDE / 2), *d_sc = d_jac + A * 12;
+    std::vector<uint64_t> jac(A * 12), sc(A * 4);
+    for (size_t a = 0; a < A; ++a) {
+        res[ok[a]].st.U.store(&jac[12 * a]);
+        r[a].store(&sc[4 * a]);
+    }
+    HALO_HIP(hipMemcpy(d_jac, jac.data(), jac.size() * 8, hipMemcpyHostToDevice));
+    HALO_HIP(hipMemcpy(d_sc, sc.data(), sc.size() * 8, hipMemcpyHostToDevice));
+    int rc;
+    {
+        StreamGuard on_slot(ctx, ctx->streams[slot]);
+        rc = batch_to_affine(ctx, d_jac, A, d_native);
+    }
+    if (!rc) rc = msm_enqueue_batch(ctx, slot, d_native, msm_one(d_sc), true, A);
+    if (!rc) rc = msm_finish_batch(ctx, slot, T, 1);
+    return rc;
+}
+
+static int check_members_combined(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t stride, const uint8_t *seed, const int *slots, int S,
+                                  const std::vector<BatchCheck> &res, const std::vector<size_t> &ok, bool *held) {
+    const size_t n = d + 1, lg = ilog2(n), A = ok.size(), tw = (lg + 2) * 4;
+    *held = false;
+    if (lg > 24) { set_error("h_coeffs: lg_n > 24 unsupported"); return HALO_E_ARG; }
+    if (A > 65535) return HALO_OK;  // (h_combine_rows takes at most 65535 polynomials: the exact batch)
+    const int forced = dev_hooks().combined_usum;
+    const bool usum_dev = S >= 2 && A <= (ctx->n < 64 ? 64 : ctx->n) && (forced ? forced == 2 : A >= kCombinedUsumDeviceMin);
+    // the staging: the scalar step's regions, then (128-byte aligned) the right side's points and weights
+    const size_t cap = check_combined_cap(A);
+    size_t P = check_combined_parts(n, A), u_off = 0;
+    for (;; P = (P + 1) / 2) {  // (fewer parts if the staging cannot hold their rows)
+        u_off = (hcomb_stage_words(A, lg, P, cap) + 15) & ~(size_t)15;
+        if (check_stage(ctx, 1, (u_off + (usum_dev ? A * (AFF_STRIDE / 2 + 16) : 0)) * 8) >= 1) break;
+        if (P == 1) return HALO_OK;
+    }
+    std::vector<Fr> r;
+    check_combined_weights(qs, stride, ok.data(), A, d, seed, r);
+    std::vector<uint64_t> recs(A * tw);
+    for (size_t a = 0; a < A; ++a) {
+        for (size_t k = 0; k <= lg; ++k) res[ok[a]].st.xis[k].store(&recs[a * tw + 4 * k]);
+        r[a].store(&recs[a * tw + 4 * (lg + 1)]);
+    }
+    int rc;
+    {
+        StreamGuard on_slot(ctx, ctx->streams[slots[0]]);
+        rc = h_combine_rows(ctx, recs.data(), A, lg, P, cap, ctx->d_check_stage);
+    }
+    if (!rc) rc = msm_enqueue_batch(ctx, slots[0], ctx->d_bases, msm_one(ctx->d_check_stage + hcomb_rows_offset(A, lg, P, cap)), true, n);  // asynchronous
+    if (rc) return rc;
+    Point T = Point::infinity();
+    int rc_t = HALO_OK;
+    if (usum_dev) rc_t = combined_usum_device(ctx, slots[1], res, ok, r, ctx->d_check_stage + u_off, &T);
+    else {  // one multi-scalar sum per pool thread
+        const size_t chunks = A < 16 ? A : 16;
+        std::vector<Point> part(chunks, Point::infinity());
+        pool_run(chunks, [&](size_t c) {
+            std::vector<Point> p;
+            std::vector<Fr> k;
+            for (size_t a = c * A / chunks; a < (c + 1) * A / chunks; ++a) { p.push_back(res[ok[a]].st.U); k.push_back(r[a]); }
+            part[c] = host::small_msm(p, k);
+        });
+        for (const Point &q : part) T = T + q;
+    }
+    const std::string err_t = rc_t ? halo_last_error() : "";
+    Point left;
+    rc = msm_finish_batch(ctx, slots[0], &left, 1);  // (collected whatever happened to the right side: nothing stays in flight)
+    if (rc_t) { set_error(err_t); return rc_t; }
+    if (rc) return rc;
+    *held = left == T;
+    return HALO_OK;
+}
+
+// blobs: m Instances (or Accumulators, whose Instance prefix is checked) at `stride` words, all of degree bound d (checked by
+// the caller); status[i] (nullable) = what halo_pcdl_check returns for member i alone
+// seed: the combined call's 32 bytes (or null); combined = false: the exact batch
+static int pcdl_check_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t stride, size_t m, int *status, bool combined = false,
+                                 const uint8_t *seed = nullptr) {
+    const size_t n = d + 1;
+    int slots[HALO_SLOTS], S = idle_slots(ctx, slots);
+    if (!S) { set_error("check_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
+    // 1. the succinct half (pcdl.rs:333)
+    std::vector<BatchCheck> res;
+    int rc = succinct_half(ctx, d, [&](size_t i) { return qs + i * stride; }, m, res);
+    if (rc) return rc;
+    std::vector<size_t> ok;  // the accepted members, in order
+    for (size_t i = 0; i < m; ++i)
+        if (!res[i].rc) ok.push_back(i);
+    bool held = false;
+    if (combined && ok.size() >= 2 && n >= 2) {  // (one member, or a constant: nothing to combine)
+        rc = check_members_combined(ctx, d, qs, stride, seed, slots, S, res, ok, &held);
+        if (rc) return rc;
+    }
+    if (!held) {  // the exact batch; after a combined relation that failed: which members fail does not depend on the weights
+        rc = check_members_exact(ctx, n, slots, S, res, ok);
+        if (rc) return rc;
+    }
     return report_members("instance", m, [&](size_t i) { return res[i].rc; }, [&](size_t i) { return res[i].err; }, status, [](size_t) {});
 }
 // the argument checks of both entry points (halo_pcdl_succinct_check_batch's), then the batch; acc: Accumulator blobs
-static int check_batch_entry(halo_ctx *ctx, size_t d, const uint64_t *blobs, size_t m, int *status, bool acc) {
+static int check_batch_entry(halo_ctx *ctx, size_t d, const uint64_t *blobs, size_t m, int *status, bool acc, bool combined = false,
+                             const uint8_t *seed = nullptr) {
     if (m && !blobs) { set_error("check_batch: null pointer"); return HALO_E_ARG; }
     if (!is_pow2(d + 1)) return fail_reject("d+1 is not a power of 2!");
     size_t lg = ilog2(d + 1), stride = acc ? acc_words(lg) : instance_words(lg);
     for (size_t i = 0; i < m; ++i)
         if ((size_t)(blobs + i * stride)[12] != d || (blobs + i * stride)[22] != lg) return fail_reject("d_i != d");
     if (m == 0) return HALO_OK;
-    return pcdl_check_batch_host(ctx, d, blobs, stride, m, status);
+    return pcdl_check_batch_host(ctx, d, blobs, stride, m, status, combined, seed);
 }
 
 // ------------------------------------------------------------------ pcdl::commit of m polynomials at once
@@ -1181,6 +1339,12 @@ int halo_pcdl_check_batch(halo_ctx *ctx, size_t d, const uint64_t *instances, si
     return check_batch_entry(ctx, d, instances, m, status, false);
 }
 
+// ... as one combined relation over the accepted members (see check_members_combined; the contract: include/halo_accumulation.h)
+int halo_pcdl_check_batch_combined(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, const uint8_t seed[32], int *status) {
+    HALO_CTX(ctx);
+    return check_batch_entry(ctx, d, instances, m, status, false, true, seed);
+}
+
 // acc::prover of k members at once (see acc_prover_batch_dev).  The argument checks are the whole call's and come before any work.
 int halo_acc_prover_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *instances, const size_t *counts, size_t k, uint64_t *accs_out,
                           int *status) {
@@ -1210,6 +1374,11 @@ int halo_acc_verifier_batch(halo_ctx *ctx, size_t d, const uint64_t *instances, 
 int halo_acc_decider_batch(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, int *status) {
     HALO_CTX(ctx);
     return check_batch_entry(ctx, d, accs, m, status, true);
+}
+
+int halo_acc_decider_batch_combined(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, const uint8_t seed[32], int *status) {
+    HALO_CTX(ctx);
+    return check_batch_entry(ctx, d, accs, m, status, true, true, seed);
 }
 
 // pcdl::open of m polynomials at once (see open_batch_dev)

@@ -79,6 +79,14 @@ int succinct_check_batch(halo_ctx *ctx, size_t d, const BlobAt &blob_at, size_t 
 int succinct_half(halo_ctx *ctx, size_t d, const BlobAt &blob_at, size_t m, std::vector<BatchCheck> &res);
 int verify_staging(halo_ctx *ctx, size_t words);  // ctx->d_verify holds at least `words`
 
+// ---- pcdl_batch.hip: the combined check batch (halo_pcdl_check_batch_combined; the development library runs its steps alone)
+// The weights r_a of the A accepted members idx[0 .. A) of the blobs at `stride` words, degree bound d, seed = 32 bytes or null
+// (32 zero bytes): the rule of include/halo_accumulation.h, Montgomery form
+void check_combined_weights(const uint64_t *blobs, size_t stride, const size_t *idx, size_t A, size_t d, const uint8_t *seed, std::vector<host::Fr> &out);
+// parts and tables per pass of the scalar step for A polynomials of n coefficients (the hooks "check_combined_parts" / "_cap" first)
+size_t check_combined_parts(size_t n, size_t A);
+size_t check_combined_cap(size_t A);
+
 // ---- pcdl_acc.hip: acc.rs
 struct AccHPolys {  // acc.rs:61-66
     host::Fr h0[2];

@@ -182,6 +182,22 @@ def check_batch(ctx, d, instances):
     return _check_batch(ctx, ctx.lib.halo_pcdl_check_batch, d, instances)
 
 
+def _seed32(seed):
+    if seed is None:
+        return None
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("seed: 32 bytes or None")
+    return seed
+
+
+def check_batch_combined(ctx, d, instances, seed=None):
+    """check_batch with ONE MSM for all accepted members (halo_pcdl_check_batch_combined: <sum r_i h_i, G> = sum r_i U_i with
+    hashed weights; seed: 32 bytes of the caller's randomness or None) -> status list; statuses and HaloReject as check_batch
+    whenever a member is bad"""
+    return _check_batch(ctx, lambda h, dd, qs, m, st: ctx.lib.halo_pcdl_check_batch_combined(h, dd, qs, m, _seed32(seed), st), d, instances)
+
+
 def check_partial(ctx, Cm, d, z, v, pi, stride, offset):
     """One rank's half of pcdl::check over a cyclically sharded key (halo_pcdl_check_partial): -> (U, this rank's share of
     CM.Commit(ck, h)).  The caller adds the shares in rank order and accepts iff the sum is U (sharded.ShardedOpen.check)."""

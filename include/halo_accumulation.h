@@ -248,6 +248,36 @@ int halo_pcdl_check(halo_ctx *ctx, const uint64_t C[12], size_t d, const uint64_
  * HALO_E_REJECT ("d_i != d") before any work, status not written.  m = 0: HALO_OK.  The staging of the members in flight is
  * optional memory (halo_set_memory_budget): without it the members run one at a time, same results. */
 int halo_pcdl_check_batch(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, int *status /*nullable*/);
+/* The same m checks with ONE MSM: the second half of pcdl::check (pcdl.rs:338-339) is the linear relation <h_i, G> = U_i, so the
+ * members are checked together as <sum r_i h_i, G> = sum r_i U_i with unpredictable weights r_i.  Layouts, whole-call errors
+ * (null ctx, null blobs, d + 1 not a power of two, d_i != d, m = 0, no idle slot), the "instance i: ..." message and the return
+ * rule are halo_pcdl_check_batch's.  The contract:
+ *  1. The succinct half runs for every member exactly as in halo_pcdl_check_batch.  A member it rejects gets its status there
+ *     and takes no further part.
+ *  2. A = the number of accepted members.  A <= 1 (or d = 0): the exact path of halo_pcdl_check_batch, nothing to combine.
+ *     A >= 2: the combined relation over the accepted members -- the scalars sum_a r_a h_a(X) formed on the device, one n-point
+ *     MSM over the key (the fixed-base table where the key has one), sum_a r_a U_a on the host pool or as a small MSM beside it.
+ *  3. If the combined relation HOLDS, every accepted member's status is 0.
+ *  4. If it FAILS, the accepted members go through the exact per-member path of halo_pcdl_check_batch and get its statuses.  So
+ *     a reject never depends on the weights, and whenever any member is bad, status[] and the return code equal
+ *     halo_pcdl_check_batch's on the same blobs.
+ *  5. The one difference from the exact batch: a set of blobs in which some accepted member has <h_i, G> != U_i is wrongly
+ *     accepted with probability 1/r (r = the group order, ~2^-254) per hash evaluation an adversary spends: the weights are a
+ *     random-oracle output over ALL the blobs, and the relation is linear in them.
+ *  6. The scalars live in optional staging memory (halo_set_memory_budget): without it the exact path runs, with the same
+ *     statuses.  A multi-device context runs the call on its own device (devices[0]); a caller's MSM in flight on another slot
+ *     is left alone.
+ * Weight rule.  lg = log2(d + 1), W = halo_instance_words(lg), seed32 = the caller's 32 bytes or, for seed = NULL, 32 zero bytes.
+ *   D   = SHA3-256("halo-accumulation/check-batch-combined/v1" || seed32 || LE64(d) || LE64(A) || for every accepted member in
+ *         member order: LE64(i) || its W Instance words as little-endian bytes)     (i = its index among the m members)
+ *   r_a = (SHA3-256(D || LE64(a)) read as a little-endian integer) mod r,  a = 0 .. A - 1 its position among the accepted ones.
+ * A caller that wants weights no prover could have anticipated passes fresh random bytes as seed; the result never depends on it.
+ * When to call it (one MI355X, tools/time_decider_batch.py --combined): on a key of 2^20 points, where the exact
+ * batch runs one table MSM per member -- 4.0 times its speed at m = 10, 10.9 times at m = 100; on keys of 2^9 .. 2^14 points from
+ * about a hundred members on -- 1.3 to 1.7 times at m = 100, 1.5 to 2.1 times at m = 1000, where the succinct half is what remains.
+ * At m = 10 on those keys it is NOT faster than halo_pcdl_check_batch (the runs' ranges overlap). */
+int halo_pcdl_check_batch_combined(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, const uint8_t seed[32] /*nullable*/,
+                                   int *status /*nullable*/);
 /* One rank's half of pcdl::check over a key sharded cyclically (halo_ctx_create_urs_strided: point i on rank i mod stride,
  * offset = the rank): the succinct check (pcdl.rs:333, the same on every rank; d + 1 may be up to stride * the shard's size)
  * and this rank's share of CM.Commit(ck, h) (pcdl.rs:338) over its own points.  U_out = the proof's U after the succinct
@@ -306,6 +336,10 @@ int halo_acc_decider(halo_ctx *ctx, const uint64_t *acc);
 /* acc::decider (acc.rs:245-255) of m accumulators at once: benches/acc.rs:100-106 in one call.  accs = m Accumulator blobs at
  * stride halo_accumulator_words(lg(d+1)); halo_pcdl_check_batch over their Instance prefixes, with its conventions. */
 int halo_acc_decider_batch(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, int *status /*nullable*/);
+/* ... as one combined relation: halo_pcdl_check_batch_combined over the accumulators' Instance prefixes, with its contract (the
+ * words hashed into the weights are each accumulator's Instance prefix) */
+int halo_acc_decider_batch_combined(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, const uint8_t seed[32] /*nullable*/,
+                                    int *status /*nullable*/);
 /* acc::verifier (acc.rs:223-243) of k accumulators at once: benches/acc.rs:64-74's loop in one call.  accs = k Accumulator blobs
  * at stride halo_accumulator_words(lg(d+1)); counts[j] = the number of Instances member j verifies against accs[j] (0 allowed);
  * instances = sum(counts) Instance blobs at stride halo_instance_words(lg(d+1)), member j's right after member j - 1's.

@@ -33,7 +33,11 @@ extern "C" {
  * from which halo_acc_verifier_batch runs its sums on the device, >= 1; 0: the measured default), "table_slide_min" (keys from this many points, >= 4096, take the c = 20 table plans and
  * the all-shifts table with its sliding-window recode; 0: 2^20), "decode_batch_min" (finite points
  * from which halo_*_decode_batch decompresses on the device, >= 1; 0: the measured default; "batch_stage_fail" refuses its staging
- * too: the host pool), "reset" (all off).
+ * too: the host pool), "check_combined_parts" (parts the polynomials of halo_pcdl_check_batch_combined's
+ * scalars are cut into, >= 1, clamped to the accepted members; 0: a wave per SIMD), "check_combined_cap" (their tables per pass, >= 1;
+ * 0: the default) -- the scalars are the same words under every value of the two --, "check_combined_usum" (the right side
+ * sum r_a U_a of a combined check: 1 the host pool, 2 the device where a second slot is idle; 0: by the member count; another
+ * value is HALO_E_ARG; "batch_stage_fail" makes the combined calls take the exact path), "reset" (all off).
  * The launch plan of the Fr kernels (csrc/fr_plan.hpp), each taken before the environment's value and the measured default, every
  * plan giving the same field elements: "pow_e" (elements per lane of k_powers, k_poly_eval_partial, k_h_coeffs and
  * k_h_accumulate_batch and of their batch forms: a power of two in [4, 64], the rule of HALO_POW_E), "dot_blocks" (block cap of
@@ -80,6 +84,18 @@ int halo_dev_h_coeffs_batch(halo_ctx *ctx, const uint64_t *xis, size_t m, size_t
  * passes add to what is there).  1 <= lg_n, 2^lg_n <= the context's size (64 at least). */
 int halo_dev_h_accumulate_batch(halo_ctx *ctx, const uint64_t *h0s, const uint64_t *xis, const uint64_t *alphas, const size_t *counts,
                                 size_t members, size_t lg_n, size_t max_tables, uint64_t *out);
+
+/* The weights of halo_pcdl_check_batch_combined / halo_acc_decider_batch_combined (the rule: include/halo_accumulation.h) for
+ * the A accepted members idx[0 .. A) of the blobs at stride_words, degree bound d, seed = 32 bytes or NULL: out = A x 4
+ * Montgomery words.  Host only, no context.  HALO_E_ARG: a null pointer, d + 1 not a power of two, stride_words below
+ * halo_instance_words(lg(d + 1)). */
+int halo_dev_check_weights(const uint64_t *blobs, size_t stride_words, const size_t *idx, size_t A, size_t d, const uint8_t seed[32] /*nullable*/,
+                           uint64_t *out);
+/* The scalar step of the combined check on its own (k_h_tables with scales, k_h_accumulate_batch over the parts, k_fr_sum_rows):
+ * xis = A x (lg_n + 1) x 4 and weights = A x 4 Montgomery words, out = 2^lg_n x 4 words = sum_a weights_a h_a(X), canonical.  Parts
+ * and tables per pass are the product's (the hooks "check_combined_parts" / "check_combined_cap" first).  1 <= A <= 65535,
+ * 1 <= lg_n, 2^lg_n <= the context's size (64 at least); temporary device buffers of this call only. */
+int halo_dev_check_combined_scalars(halo_ctx *ctx, const uint64_t *xis, const uint64_t *weights, size_t A, size_t lg_n, uint64_t *out);
 
 /* replay cached hipGraphs of the MSM launch sequence when the same shape repeats (default on) */
 int halo_set_graphs(halo_ctx *ctx, int on);  /* also: environment HALO_GRAPHS=0 at context creation; HALO_TRACE=1 logs every launch */

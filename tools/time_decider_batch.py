@@ -3,7 +3,14 @@ halo_acc_decider_batch, alternating in the same process after a warm-up of each 
 1000 accumulators (random_instance + prover, benches/acc.rs:76-98) on a 2^14-point URS context; k in {10, 100, 1000} of its
 accumulators.  Also a sweep of the batch's members per MSM launch (the development hook check_batch_group) at k = 100, and with
 --big a 2^20-point leg (a chain of 10 on a 2^20-point context).  Statuses of both ways must be equal and all 0.  Prints one
-JSON line; every time is the median of --reps alternating runs, in ms."""
+JSON line; every time is the median of --reps alternating runs, in ms.
+
+--combined: the three-way leg instead -- loop / exact batch (halo_acc_decider_batch) / combined batch
+(halo_acc_decider_batch_combined: ONE MSM for all members), alternating in one process, over k independent accumulators
+(random_instance_batch + prover_batch: a decider's work does not depend on what its accumulator accumulated).  n in --sizes with k
+in {10, 100, 1000}; with --big n = 2^20 on its own context with k in {10, 100}.  Every row keeps median, least and greatest of
+--reps runs of each way, and says whether the combined call's range lies below the exact batch's.  Also the sweep of the combined
+call's right side (the development hook check_combined_usum: 1 the host pool, 2 the device) over the member count."""
 import argparse
 import ctypes as C
 import json
@@ -72,14 +79,116 @@ def time_shape(ctx, d, accs, k, reps):
     return statistics.median(s_ms), statistics.median(b_ms)
 
 
+def combined(ctx, d, blob, k):
+    st = (C.c_int * k)()
+    t = time.perf_counter()
+    rc = ctx.lib.halo_acc_decider_batch_combined(ctx.h, d, ptr(blob), k, None, st)
+    ms = (time.perf_counter() - t) * 1e3
+    assert rc == 0, ctx.lib.halo_last_error()
+    return ms, list(st)
+
+
+def stats(ms):
+    return {"median": round(statistics.median(ms), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)}
+
+
+def independent_accs(ctx, n, k, seed):
+    d = n - 1
+    rng = [seed]
+    qs = A.random_instance_batch(ctx, rng, d, k)
+    accs, codes = A.prover_batch(ctx, rng, d, [[q] for q in qs])
+    assert codes == [0] * k
+    return accs
+
+
+def time_three(ctx, d, accs, k, reps):
+    """-> {"loop": stats, "batch": stats, "combined": stats} of `reps` alternating runs after a warm-up of each"""
+    ptrs = [ptr(a) for a in accs[:k]]
+    blob = np.ascontiguousarray(np.concatenate(accs[:k]))
+    ways = {"loop": lambda: serial(ctx, ptrs), "batch": lambda: batched(ctx, d, blob, k), "combined": lambda: combined(ctx, d, blob, k)}
+    ms = {w: [] for w in ways}
+    for fn in ways.values():
+        fn()
+    for _ in range(reps):
+        for w, fn in ways.items():
+            t, st = fn()
+            assert st == [0] * k, "a member was rejected"
+            ms[w].append(t)
+    row = {w: stats(v) for w, v in ms.items()}
+    row["combined_faster_than_batch"] = max(ms["combined"]) < min(ms["batch"])  # the ranges apart
+    row["batch_faster_than_combined"] = max(ms["batch"]) < min(ms["combined"])
+    row["batch_over_combined"] = round(statistics.median(ms["batch"]) / statistics.median(ms["combined"]), 2)
+    return row
+
+
+def usum_sweep(ctx, d, accs, reps):
+    """the combined call with its right side forced to the pool (1) and to the device (2), alternating, by member count"""
+    out = []
+    for k in (2, 4, 8, 16, 32, 64, 128, 256, 512, 1000):
+        if k > len(accs):
+            continue
+        blob = np.ascontiguousarray(np.concatenate(accs[:k]))
+        ms = {1: [], 2: []}
+        for warm in (True, False):
+            for _ in range(1 if warm else reps):
+                for side in (1, 2):
+                    h._lib.dev_hook("check_combined_usum", side)
+                    try:
+                        t, st = combined(ctx, d, blob, k)
+                    finally:
+                        h._lib.dev_hook("reset", 0)
+                    assert st == [0] * k
+                    if not warm:
+                        ms[side].append(t)
+        out.append({"k": k, "pool_ms": stats(ms[1]), "device_ms": stats(ms[2]), "pool_runs": [round(v, 3) for v in ms[1]],
+                    "device_runs": [round(v, 3) for v in ms[2]],
+                    "every_device_run_beats_every_pool_run": max(ms[2]) < min(ms[1]),
+                    "every_pool_run_beats_every_device_run": max(ms[1]) < min(ms[2])})
+    return out
+
+
+def main_combined(a):
+    rows, sweep = [], []
+    sizes = [int(x) for x in a.sizes.split(",")]
+    ctx = h._lib.Context(urs_n=1 << 14)
+    try:
+        for n in sizes:
+            accs = independent_accs(ctx, n, a.chain, 0x48414C4F00000300 + n)
+            for k in (10, 100, 1000):
+                if k <= len(accs):
+                    rows.append({"n": n, "k": k, **time_three(ctx, n - 1, accs, k, a.reps)})
+                    print(rows[-1], file=sys.stderr, flush=True)
+            if a.sweep and n == sizes[0]:
+                sweep = usum_sweep(ctx, n - 1, accs, a.reps)
+    finally:
+        ctx.close()
+    if a.big:
+        n = 1 << 20
+        c = h._lib.Context(urs_n=n)
+        try:
+            accs = independent_accs(c, n, 100, 0x48414C4F00000400)
+            for k in (10, 100):
+                rows.append({"n": n, "k": k, **time_three(c, n - 1, accs, k, a.reps)})
+                print(rows[-1], file=sys.stderr, flush=True)
+        finally:
+            c.close()
+    print(json.dumps({"tool": "tools/time_decider_batch.py --combined", "workload": "k x acc::decider over k independent accumulators, 1 GPU: "
+                      "the halo_acc_decider loop, halo_acc_decider_batch and halo_acc_decider_batch_combined, alternating; contexts of 2^14 "
+                      "points (n = 2^20: its own)", "reps": a.reps, "unit": "ms", "rows": rows, "right_side_sweep_n": sizes[0] if sweep else None,
+                      "right_side_sweep": sweep, "statuses": "all 0 in every run of every way"}))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--combined", action="store_true", help="loop / exact batch / combined batch, three ways alternating (see the module text)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--chain", type=int, default=1000)
     ap.add_argument("--sizes", default=",".join(map(str, SIZES)))
     ap.add_argument("--sweep", type=int, default=1, help="members-per-launch sweep at k = 100 (0: off)")
     ap.add_argument("--big", action="store_true", help="add the 2^20-point leg (chain of 10)")
     a = ap.parse_args()
+    if a.combined:
+        return main_combined(a)
     ctx = h._lib.Context(urs_n=1 << 14)
     rows, sweep = [], []
     t_chain = {}
