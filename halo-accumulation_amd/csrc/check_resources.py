@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Build gate: no kernel of libhalo_hip.so may use scratch (private segment) memory.
 
-Why: launch sequences are replayed as hipGraphs (msm.hip msm_enqueue_batch).  On ROCm 7.2 a kernel with
+Why: launch sequences are replayed as hipGraphs (msm_driver.hip msm_enqueue_batch).  On ROCm 7.2 a kernel with
 scratch inside a replayed graph faulted once the queue's scratch had been re-assigned by other work
 (round 1: k_msm_reduce1 carried 12 B/lane of spill at 256 VGPRs; DESIGN.md section 4 "Launch graphs").
 k_msm_accumulate sits at the 256-VGPR cap, so one compiler or code change is enough to spill again:

@@ -265,7 +265,7 @@ int halo_dev_fr_plan(halo_ctx *ctx, int which, size_t n, long out[4]) {
 int halo_dev_dot2_cross(halo_ctx *ctx, const uint64_t *c, const uint64_t *z, size_t m, uint64_t out[8]) {
     HALO_CTX(ctx);
     if (!out || (m && (!c || !z))) { set_error("dev_dot2_cross: null pointer"); return HALO_E_ARG; }
-    if (2 * m > (ctx->n < 64 ? 64 : ctx->n)) { set_error("dev_dot2_cross: 2 m exceeds context size"); return HALO_E_ARG; }
+    if (2 * m > ctx_capacity(ctx)) { set_error("dev_dot2_cross: 2 m exceeds context size"); return HALO_E_ARG; }
     if (m == 0) { std::memset(out, 0, 64); return HALO_OK; }
     int rc = upload_words(ctx, ctx->d_tmp_a, c, m * 8);
     if (!rc) rc = upload_words(ctx, ctx->d_tmp_b, z, m * 8);
@@ -284,7 +284,7 @@ int halo_dev_h_coeffs_batch(halo_ctx *ctx, const uint64_t *xis, size_t m, size_t
     HALO_CTX(ctx);
     if (m == 0) return HALO_OK;
     if (!xis || !out) { set_error("h_coeffs_batch: null pointer"); return HALO_E_ARG; }
-    if (lg_n > 24 || ((size_t)1 << lg_n) > (ctx->n < 64 ? 64 : ctx->n)) { set_error("h_coeffs_batch: 2^lg_n exceeds context size"); return HALO_E_ARG; }
+    if (lg_n > 24 || ((size_t)1 << lg_n) > ctx_capacity(ctx)) { set_error("h_coeffs_batch: 2^lg_n exceeds context size"); return HALO_E_ARG; }
     if (m > 65535) { set_error("h_coeffs_batch: at most 65535 members"); return HALO_E_ARG; }
     const size_t n = (size_t)1 << lg_n, xw = (lg_n + 1) * 4;
     uint64_t *d = nullptr;
@@ -306,7 +306,7 @@ int halo_dev_h_accumulate_batch(halo_ctx *ctx, const uint64_t *h0s, const uint64
     HALO_CTX(ctx);
     if (members == 0) return HALO_OK;
     if (!h0s || !counts || !out) { set_error("h_accumulate_batch: null pointer"); return HALO_E_ARG; }
-    if (lg_n < 1 || lg_n > 24 || ((size_t)1 << lg_n) > (ctx->n < 64 ? 64 : ctx->n)) { set_error("h_accumulate_batch: 2^lg_n exceeds context size"); return HALO_E_ARG; }
+    if (lg_n < 1 || lg_n > 24 || ((size_t)1 << lg_n) > ctx_capacity(ctx)) { set_error("h_accumulate_batch: 2^lg_n exceeds context size"); return HALO_E_ARG; }
     if (members > 65535) { set_error("h_accumulate_batch: at most 65535 members"); return HALO_E_ARG; }
     const size_t n = (size_t)1 << lg_n, xw = (lg_n + 1) * 4;
     size_t total = 0;
@@ -359,7 +359,7 @@ int halo_dev_check_combined_scalars(halo_ctx *ctx, const uint64_t *xis, const ui
     HALO_CTX(ctx);
     if (!xis || !weights || !out) { set_error("check_combined_scalars: null pointer"); return HALO_E_ARG; }
     if (A < 1 || A > 65535) { set_error("check_combined_scalars: 1..65535 polynomials"); return HALO_E_ARG; }
-    if (lg_n < 1 || lg_n > 24 || ((size_t)1 << lg_n) > (ctx->n < 64 ? 64 : ctx->n)) { set_error("check_combined_scalars: 2^lg_n exceeds context size"); return HALO_E_ARG; }
+    if (lg_n < 1 || lg_n > 24 || ((size_t)1 << lg_n) > ctx_capacity(ctx)) { set_error("check_combined_scalars: 2^lg_n exceeds context size"); return HALO_E_ARG; }
     const size_t n = (size_t)1 << lg_n, xw = (lg_n + 1) * 4, tw = xw + 4;
     const size_t P = check_combined_parts(n, A), cap = check_combined_cap(A);
     std::vector<uint64_t> recs(A * tw);
@@ -574,7 +574,7 @@ int halo_set_task_len(halo_ctx *ctx, int len) {
 
 int halo_test_field_op(halo_ctx *ctx, int field, int op, const uint64_t *a, const uint64_t *b, size_t n, uint64_t *out) {
     HALO_CTX(ctx);
-    if (n > (ctx->n < 64 ? 64 : ctx->n)) { set_error("test_field_op: n exceeds context size"); return HALO_E_ARG; }
+    if (n > ctx_capacity(ctx)) { set_error("test_field_op: n exceeds context size"); return HALO_E_ARG; }
     int rc = upload_words(ctx, ctx->d_tmp_a, a, n * 4);
     if (!rc && b) rc = upload_words(ctx, ctx->d_tmp_b, b, n * 4);
     if (rc) return rc;
@@ -585,7 +585,7 @@ int halo_test_field_op(halo_ctx *ctx, int field, int op, const uint64_t *a, cons
 
 int halo_test_point_op(halo_ctx *ctx, int op, const uint64_t *a_jac, const uint64_t *b, size_t n, uint64_t *out_jac) {
     HALO_CTX(ctx);
-    if (n > (ctx->n < 64 ? 64 : ctx->n) / 2) { set_error("test_point_op: n exceeds half the context size"); return HALO_E_ARG; }
+    if (n > ctx_capacity(ctx) / 2) { set_error("test_point_op: n exceeds half the context size"); return HALO_E_ARG; }
     size_t bw = (op == 0 || op == 4 || op == 6) ? 12 : (op == 1 ? 8 : 4);
     int rc = upload_words(ctx, ctx->d_tmp_a, a_jac, n * 12);
     if (!rc && b && op != 2 && op != 5) rc = upload_words(ctx, ctx->d_tmp_b, b, n * bw);

@@ -1,6 +1,6 @@
 // Fixed-base comb tables for the FIRST fold of pcdl::open (pcdl.rs:216-219 applied twice, key_fold.hip k_fold_points4):
 //     G''[j] = G[j] + s1 G[j+m] + s2 G[j+2m] + s3 G[j+3m],   m = n / 4,
-// where G is the context's own key -- a constant (consts.rs:68), like the bases of the MSM tables of msm.hip.  The generic
+// where G is the context's own key -- a constant (consts.rs:68), like the bases of the MSM tables of msm_table.hip.  The generic
 // kernel multiplies each of the three points by its scalar with a shared 128-step doubling chain (Straus over GLV digit
 // strings: ~128 doublings + ~213 mixed additions, ~3240 field products per output).  With
 //     E[w][d][i] = d * 64^w * G_i   (w < 22, d = 1..32, i in [n/4, n), affine, 64 bytes each, 44 KiB per point)

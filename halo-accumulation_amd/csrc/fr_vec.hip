@@ -376,7 +376,7 @@ __global__ __launch_bounds__(256) void k_nofold_expand_batch(const uint64_t *__r
     const size_t o = ms * blockIdx.y;
     nofold_expand_body(c + o, sv + o, m, log2m, M, outL + o, outR + o);
 }
-// The same two vectors as ONE array for a tagged launch (msm.hip, MsmBatch::tagged): L's and R's non-zero scalars sit on
+// The same two vectors as ONE array for a tagged launch (msm_table.hip, MsmBatch::tagged): L's and R's non-zero scalars sit on
 // disjoint points, so F[b] = c[(b mod m) +- m/2] * s[b div m] in canonical form with bit 255 (free: r < 2^255) set on R's half
 // says everything -- half the bytes written, and one launch sequence computes both sums.
 __global__ __launch_bounds__(256) void k_nofold_expand_tagged(const uint64_t *__restrict__ c, const uint64_t *__restrict__ sv, uint32_t m,
@@ -702,7 +702,7 @@ int open_batch_fold(halo_ctx *ctx, int G, uint64_t *d_c, uint64_t *d_z, const ui
 // (which = 4 measures a kernel of hpoly.hip)
 __global__ __launch_bounds__(256) void k_h_coeffs(const uint64_t *__restrict__ tab, uint32_t n, int E, int accumulate, uint64_t *__restrict__ out);
 int bench_fr_kernel(halo_ctx *ctx, int which, size_t n, int reps) {
-    if (n == 0 || n > (ctx->n < 64 ? 64 : ctx->n) || reps < 1) { set_error("bench_fr_kernel: n must be in [1, context size]"); return HALO_E_ARG; }
+    if (n == 0 || n > ctx_capacity(ctx) || reps < 1) { set_error("bench_fr_kernel: n must be in [1, context size]"); return HALO_E_ARG; }
     if (which < 0 || which > 6) { set_error("bench_fr_kernel: which must be 0..6"); return HALO_E_ARG; }
     uint64_t *a = ctx->d_tmp_a, *b = ctx->d_tmp_b, *c = ctx->d_tmp_b + 4 * n, *d = ctx->d_tmp_b + 8 * n;  // n x 4 words each (d_tmp_b: 16 n words)
     host::Fr z = host::Fr::from_u64(0x1234567) * host::Fr::from_u64(0x89abcdef), z64;

@@ -75,7 +75,7 @@ struct MsmPlan {
     int table_vw_bits = 15;  // log2 of the buckets per virtual window
     int table_pieces = 1;    // a large table MSM runs as this many consecutive pieces: 2 * table_sets * table_vw sums each
     int table_sets = 1;      // bucket sets side by side in a batched table launch (members, rounded up to a power of two)
-    bool table_rc = false;   // window sums by rows and columns of the bucket index (msm.hip k_msm_reduce_rc): (S, T) pairs per set
+    bool table_rc = false;   // window sums by rows and columns of the bucket index (msm_buckets.hip k_msm_reduce_rc): (S, T) pairs per set
     int table_rc_lg_rows = 0, table_rc_lg_cols = 0;
     // the sliding odd-digit plan over the all-shifts table (TblPlan::slide): bucket index = range * 2^lg_cols + fine holds the
     // digits of magnitude 2 (fine * 2^lg_rows + range) + 1 -- other constants in msm_combine_member, same (S, T) pairs
@@ -94,7 +94,7 @@ struct MsmPlan {
     int table_rc_per = 0;      // form 2: buckets per lane of k_msm_reduce_rc
 };
 constexpr int MSM_MAX_BATCH = 8;
-// fixed-base table plan of a context (msm.hip: table_plan)
+// fixed-base table plan of a context (msm_table.hip: table_plan)
 struct TblPlan {
     int c, W, fbits, vw_bits;        // window bits, windows, fine-bucket bits of a coarse range, log2 buckets per virtual window
     uint32_t B, ranges, vw, spread;  // buckets (2^(c-1)), coarse ranges, virtual windows, modulus of the top-window spread (0: none)
@@ -296,7 +296,7 @@ struct KeyShare {
     bool table_busy = false, foldtab_busy = false;
     bool table_fixed_only = false;  // the key's all-shifts MSM table made room for the fold table: table_build keeps to the fixed windows (until halo_set_fold_table(ctx, 0) or a new budget)
     long full_opens = 0;     // full-size opens over this key by any of its contexts while no fold table existed (the automatic mode builds from tuning().fold_table_after on)
-    size_t budget_held = 0;  // bytes of optional memory reserved for this key (abi.hip table_budget_*)
+    size_t budget_held = 0;  // bytes of optional memory reserved for this key (budget.hip table_budget_*)
 };
 
 struct halo_ctx {
@@ -356,7 +356,7 @@ struct halo_ctx {
     size_t tmp_words = 0;
     uint64_t *h_pinned = nullptr;  // small pinned staging (4 KiB)
     uint64_t *h_wintab = nullptr;  // pinned staging of a window table of powers (fr_vec.hip upload_window_table), 8 KiB
-    uint64_t *d_slot_scalars[HALO_SLOTS] = {};  // scalar staging per slot (abi.hip slot_scalars): host scalars, a shard's peer copies
+    uint64_t *d_slot_scalars[HALO_SLOTS] = {};  // scalar staging per slot (msm_entry.hip slot_scalars): host scalars, a shard's peer copies
     size_t slot_scalars_bytes[HALO_SLOTS] = {};
     uint64_t *d_verify = nullptr;  // staging of the batched verifier (points, scalars, challenges, results), grown on demand
     size_t verify_words = 0;
@@ -371,10 +371,10 @@ struct halo_ctx {
     uint64_t *d_poly = nullptr, *d_poly2 = nullptr;
     halo::HostWorker worker;      // host arithmetic overlapped with the caller's (see HostWorker; multi.hip also runs a shard's HIP calls on it)
     IpaBuffers ipa_bufs;          // reused by every halo_ipa of this context (one at a time; a second one allocates its own)
-    uint64_t alloc_epoch = 0;     // bumped whenever this context allocates or frees device memory (see msm.hip, launch graphs)
+    uint64_t alloc_epoch = 0;     // bumped whenever this context allocates or frees device memory (see msm_driver.hip, launch graphs)
     size_t open_batch_members = 0;  // members of the last open-type batch call that ran through member-batched launches (0: one at a time; halo_ctx_info 10)
     int last_table_plan = -1;     // the launch enqueued last: -1 no table pipeline, 0 its fixed windows, else the sliding plan's window width (halo_ctx_info 9)
-    int may_borrow = 0;           // > 0 inside a synchronous MSM call: a large MSM may run its odd pieces on the neighbouring slot (msm.hip)
+    int may_borrow = 0;           // > 0 inside a synchronous MSM call: a large MSM may run its odd pieces on the neighbouring slot (msm_driver.hip)
     hipEvent_t ev_piece[HALO_SLOTS][2] = {};  // fork / join of those pieces (created on first use)
     // multi-device contexts (multi.hip): one shard context per device over its index block of the key; MSMs over the key fan out
     std::vector<halo_ctx *> shards;
@@ -386,14 +386,16 @@ struct halo_ctx {
     Fan fan[HALO_SLOTS];
 };
 
+// Elements that the context's temporaries (d_tmp_a / _b) and each slot's scalar staging hold: the key's size, at least 64
+inline size_t ctx_capacity(const halo_ctx *ctx) { return ctx->n < 64 ? 64 : ctx->n; }
+
 struct halo_ipa {
     halo_ctx *ctx = nullptr;
     size_t n = 0, m = 0;  // m = current length (n, n/2, ...)
-    uint32_t *d_G = nullptr;  // m x 20 words native affine (in-place)
+    IpaBuffers buf;  // the context's own set (borrowed: returned by halo_ipa_destroy) or a private one (freed there); d_G is folded in
+                     // place, d_c / d_z hold the m live elements, d_s .. d_FR are the no-fold vectors (M x 4), d_pbar this shard of p_bar
     const uint32_t *G_src = nullptr;  // where the current key is read from: the context's own table of bases until the first real
                                       // fold (no copy, and its MSMs may use the context's fixed-base table), d_G afterwards
-    uint64_t *d_c = nullptr;  // m x 4
-    uint64_t *d_z = nullptr;  // m x 4
     halo::host::FixedBaseTable hp_table;  // window table of the H' this open uses (pcdl.rs:181)
     bool hp_from_scalar = false;          // H' = hp_scalar * H: terms k * H' come from the process-wide table of H as (k * hp_scalar) * H
     halo::host::Fr hp_scalar;
@@ -403,17 +405,15 @@ struct halo_ipa {
     bool deferred = false;                   // the no-fold phase ends in a two-level fold once s_len reaches 4
     std::vector<halo::host::Fr> s_host;      // host copy of s while deferred (<= 4 entries)
     size_t M = 0, s_len = 0;
-    uint64_t *d_s = nullptr, *d_s2 = nullptr, *d_FL = nullptr, *d_FR = nullptr;  // M x 4 each
-    uint64_t *d_pbar = nullptr;  // n x 4: this shard of p_bar (hiding branch of the sharded open)
-    bool pbar_valid = false;     // halo_ipa_hiding_partial has filled d_pbar for this state
-    // The LAST round of a no-fold phase already holds U (abi.hip halo_ipa_finish): with two coefficients c0, c1 left, its MSMs are
+    bool pbar_valid = false;     // halo_ipa_hiding_partial has filled buf.d_pbar for this state
+    // The LAST round of a no-fold phase already holds U (ipa_state.hip halo_ipa_finish): with two coefficients c0, c1 left, its MSMs are
     // L' = c1 A and R' = c0 B over the even / odd points of the key, and U = G_final[0] = A + xi B.  Kept here: L', R' before
     // their H' terms, c0, c1 (copied to the host with the round's results) and the round's challenge.
     bool last_valid = false, last_folded = false;
     halo::host::Point last_L, last_R;
     halo::host::Fr last_c0, last_c1, last_xi, last_xi_inv;
     // A two-level fold of a key of at most 2^18 points is a latency chain on one wave per SIMD (1.6 and 1.1 ms in a 2^20 open):
-    // it runs on the context's fourth stream BESIDE the next two rounds, which keep reading the unfolded key (abi.hip
+    // it runs on the context's fourth stream BESIDE the next two rounds, which keep reading the unfolded key (ipa_state.hip
     // ipa_round_fold_impl).  fold_pending: launched, not yet switched to; fold_dst / fold_m: its output; tail_host: the products
     // of the challenges hashed since (they are the first entries of d_s and the scalars of the fold after this one);
     // g_off: points of d_G already taken by earlier keys (the folds no longer run in place).
@@ -423,12 +423,12 @@ struct halo_ipa {
     std::vector<halo::host::Fr> tail_host;
     hipEvent_t ev_fold = nullptr;
     bool counted_hot = false;    // this state is counted in ctx->worker's hot count (undone by halo_ipa_destroy)
-    bool borrowed = false;       // buffers belong to ctx->ipa_bufs (returned, not freed, by halo_ipa_destroy)
+    bool borrowed = false;       // buf is ctx->ipa_bufs (returned, not freed, by halo_ipa_destroy)
 };
 
 namespace halo {
 
-// ---- msm.hip
+// ---- msm_driver.hip (the fixed-base table: msm_table.hip)
 // scope of a synchronous MSM call (nothing else of the caller's can be in flight on the context's other slots meanwhile)
 struct BorrowScope {
     halo_ctx *c;
@@ -500,6 +500,7 @@ inline void pool_run(size_t m, const std::function<void(size_t)> &fn) {
     worker();
     for (auto &t : th) t.join();
 }
+// ---- urs.hip (key generation and the affine layouts), dev.hip (the test_* kernels)
 int urs_generate(halo_ctx *ctx, uint64_t first_index, uint64_t stride, size_t n, uint32_t *d_out_native);
 int batch_to_affine(halo_ctx *ctx, const uint64_t *d_jac_words, size_t n, uint32_t *d_out_native);
 int aff_words_to_native(halo_ctx *ctx, const uint64_t *d_in, size_t n, uint32_t *d_out);
@@ -507,7 +508,7 @@ int aff_native_to_words(halo_ctx *ctx, const uint32_t *d_in, size_t n, uint64_t 
 int test_field_op(halo_ctx *ctx, int field, int op, const uint64_t *d_a, const uint64_t *d_b, size_t n, uint64_t *d_out);
 int test_point_op(halo_ctx *ctx, int op, const uint64_t *d_a, const uint64_t *d_b, size_t n, uint64_t *d_out);
 
-// ---- abi.hip: the budget for OPTIONAL device memory (the MSM fixed-base table, the fold table and its temporary), per device and
+// ---- budget.hip: the budget for OPTIONAL device memory (the MSM fixed-base table, the fold table and its temporary), per device and
 // process-wide: reserve() succeeds if what all contexts of this process hold on ctx's device plus `bytes` stays within the
 // device's budget (halo_set_memory_budget; default 1/6 of the device's memory) and at least 2 x bytes are free right now
 bool table_budget_reserve(halo_ctx *ctx, size_t bytes);
@@ -534,7 +535,9 @@ int multi_batch_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const MsmBa
 int multi_batch_end(halo_ctx *ctx, int slot, host::Point *out, int count);
 int multi_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *dev_scalars, bool mont, host::Point *out);
 int multi_host_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars, bool mont, host::Point *out);  // synchronous, host scalars, per shard msm_host_run
-// ---- abi.hip: host-scalar MSMs and the scalar staging buffers
+// ---- msm_entry.hip: the checked request path, host-scalar MSMs and the scalar staging buffers
+// (out null: the range check alone, halo_ctx_read_bases)
+int msm_request(const halo_ctx *ctx, int slot, bool fan, size_t off, size_t n, const void *const *scalars, size_t count, MsmBatch *out);
 uint64_t *slot_scalars(halo_ctx *ctx, int slot, int members, int m);  // member m's array in slot `slot`'s buffer (null: allocation failed)
 int msm_host_begin(halo_ctx *ctx, int slot, size_t off, size_t n, const uint64_t *scalars, bool mont);
 int msm_host_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars, size_t valid, int mont, host::Point *out);  // synchronous, zero-padded beyond `valid`
@@ -686,15 +689,20 @@ int fq_sqrt_dev(halo_ctx *ctx, const uint64_t *d_a, size_t n, const uint32_t *d_
 // allows; returns how many units of per_bytes it holds (0: none)
 size_t check_stage(halo_ctx *ctx, size_t want, size_t per_bytes);
 
-// ---- abi.hip (device-pointer forms used by pcdl_acc.hip and pcdl_batch.hip)
-// H' = xi0 * H for this state (pcdl.rs:181): lets the rounds use the process-wide window table of H
-void ipa_set_hprime_scalar(halo_ipa *st, const host::Fr &xi0);
+// ---- ctx.hip
 // process-wide window table of the public point H (consts.rs:45-65), built on first use
 const host::FixedBaseTable &public_h_table();
 const host::FixedBaseTable &public_s_table();  // (k S and k H from the process-wide window tables: ~14 us against ~80 for a generic double-and-add)
-int ipa_begin_dev(halo_ctx *ctx, size_t n, const uint64_t *d_coeffs_padded, const host::Fr &z, halo_ipa **out);
+// synchronous copies of 64-bit words on ctx->stream
 int upload_words(halo_ctx *ctx, uint64_t *dst, const uint64_t *src, size_t words);
 int download_words(halo_ctx *ctx, uint64_t *dst, const uint64_t *src, size_t words);
+// ---- ipa_state.hip
+// halo_ipa_begin over coefficients in device memory (padded to n); the z vector: d_z_vec if given, else z_base^j (times *z_scale if given)
+int ipa_begin_dev(halo_ctx *ctx, size_t n, const uint64_t *d_coeffs_padded, const host::Fr &z_base, halo_ipa **out, const host::Fr *z_scale = nullptr,
+                  const uint64_t *d_z_vec = nullptr);
+// H' = xi0 * H for this state (pcdl.rs:181): lets the rounds use the process-wide window table of H
+void ipa_set_hprime_scalar(halo_ipa *st, const host::Fr &xi0);
+void ipa_bufs_release(halo_ctx *ctx);  // frees the context's own IPA buffers (no state may be borrowing them)
 
 
 // ---- pcdl_acc.hip, msm_sharded.hip: the collectives of the sharded entry points (include/halo_accumulation.h, "sharded open /

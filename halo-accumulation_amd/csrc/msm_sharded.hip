@@ -1,7 +1,7 @@
 // point_dot_affine (group.rs:24-26) sharded over one process per GPU, in one call (include/halo_accumulation.h, "sharded MSM").
 //
 // Each rank runs ITS share of the MSM through the ordinary entry points (halo_msm, halo_msm_dev, the begin / end halves: the
-// one checked request path of abi.hip, a multi-device context fanning out as it always does), then the P partial points are
+// one checked request path of msm_entry.hip, a multi-device context fanning out as it always does), then the P partial points are
 // exchanged in ONE call of the caller's all-gather -- 12 words per member plus the status word of the sharded open / check
 // (internal.hpp StatusGather) -- and every rank adds them in rank order on the host, halo_point_sum's rule.  That is at most
 // 64 additions of 96-byte records: no kernel, no extra copy.

@@ -108,7 +108,7 @@ static int on_shards(halo_ctx *ctx, size_t off, size_t n, F fn) {
 }
 
 // Enqueue the stretches of `members.count` MSMs over GS[off, off + n) on the shards' slot `slot`: every shard runs ITS stretch of
-// all members as one batched launch sequence (which is what makes a 2^17-point block a full launch: msm.hip, small-key table
+// all members as one batched launch sequence (which is what makes a 2^17-point block a full launch: msm_table.hip, small-key table
 // plan).  host: the one member's scalars are in host memory -- every device has its own PCIe link, so each shard's helper
 // thread copies its stretch (msm_host_begin); else the shard on the scalars' device reads them in place and the others copy
 // theirs peer-to-peer (xGMI) into member m's place in their slot's staging buffer, in front of their launches.  batch: begun by
@@ -184,7 +184,7 @@ int multi_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *dev_scalars, 
 
 // The synchronous host-scalar form (halo_msm, pcdl::commit with host coefficients): every shard's helper thread runs its block of
 // GS[off, off + n) through msm_host_run on its own device -- its scalars over its own PCIe link, in stretches where that pays
-// (abi.hip: a shard's block of 2^21 points of an n = 2^24 MSM copies under its own kernels) -- and the partial points are added in
+// (msm_entry.hip: a shard's block of 2^21 points of an n = 2^24 MSM copies under its own kernels) -- and the partial points are added in
 // block order.  Same point as multi_batch_begin + multi_batch_end give.
 int multi_host_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars, bool mont, host::Point *out) {
     std::vector<host::Point> part(ctx->shards.size(), host::Point::infinity());

@@ -26,7 +26,7 @@ static const PublicPoints &public_points() {  // main.rs:35-45 / consts.rs:26-65
 }
 
 static int ensure_poly_buffers(halo_ctx *ctx) {
-    size_t n = ctx->n < 64 ? 64 : ctx->n;
+    size_t n = ctx_capacity(ctx);
     if (!ctx->d_poly || !ctx->d_poly2) alloc_epoch_bump(ctx);
     if (!ctx->d_poly) HALO_HIP(hipMalloc(&ctx->d_poly, n * 32));
     if (!ctx->d_poly2) HALO_HIP(hipMalloc(&ctx->d_poly2, n * 32));
@@ -64,7 +64,7 @@ int pcdl_commit_host(halo_ctx *ctx, const uint64_t *coeffs, size_t len, size_t d
     if (d + 1 > ctx->n) return fail_assert("commit: d > D");
     size_t used = deg + 1 < len ? deg + 1 : len;
     if (used <= 16) return commit_short_host(ctx, coeffs, used, w, out);
-    // pedersen::commit over GS[0..n) (pedersen.rs:6-20) with the coefficients still in host memory: halo_msm's path (abi.hip
+    // pedersen::commit over GS[0..n) (pedersen.rs:6-20) with the coefficients still in host memory: halo_msm's path (msm_entry.hip
     // msm_host_run: the copy in stretches under the kernels where that pays), zero-padded beyond the polynomial
     Point acc;
     int rc = msm_host_run(ctx, 0, n, coeffs, used, 1, &acc);
@@ -520,7 +520,7 @@ int halo_pedersen_commit(halo_ctx *ctx, const uint64_t *w, size_t n_bases, const
     if (n_bases != n_ms) return fail_assert("Length did not match for pedersen commitment");  // pedersen.rs:7-12
     if (n_bases > ctx->n) return fail_assert("pedersen commit: more bases than the key holds");
     if (!out || (n_ms && !ms)) { set_error("pedersen commit: null pointer"); return HALO_E_ARG; }
-    // pedersen.rs:14-17 with the scalars in host memory: the host-scalar MSM path of halo_msm (abi.hip msm_host_run)
+    // pedersen.rs:14-17 with the scalars in host memory: the host-scalar MSM path of halo_msm (msm_entry.hip msm_host_run)
     Point r;
     int rc = msm_host_run(ctx, 0, n_ms, ms, n_ms, 1, &r);
     if (rc) return rc;

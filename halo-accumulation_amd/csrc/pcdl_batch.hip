@@ -257,7 +257,7 @@ static int check_members_combined(halo_ctx *ctx, size_t d, const uint64_t *qs, s
     if (lg > 24) { set_error("h_coeffs: lg_n > 24 unsupported"); return HALO_E_ARG; }
     if (A > 65535) return HALO_OK;  // (h_combine_rows takes at most 65535 polynomials: the exact batch)
     const int forced = dev_hooks().combined_usum;
-    const bool usum_dev = S >= 2 && A <= (ctx->n < 64 ? 64 : ctx->n) && (forced ? forced == 2 : A >= kCombinedUsumDeviceMin);
+    const bool usum_dev = S >= 2 && A <= ctx_capacity(ctx) && (forced ? forced == 2 : A >= kCombinedUsumDeviceMin);
     // the staging: the scalar step's regions, then (128-byte aligned) the right side's points and weights
     const size_t cap = check_combined_cap(A);
     size_t P = check_combined_parts(n, A), u_off = 0;
@@ -636,7 +636,7 @@ static int acc_verifier_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, 
 // degrees (a hiding open draws deg scalars for q, then w_bar; random_instance draws d', w, the d' + 1 coefficients, z, then the
 // open's draws).  So the host computes every member's start state first, and the members run side by side.
 //
-// Device path (2 <= n <= the context's no-fold size, at most OPEN_MAX_N): the open in its no-fold form (abi.hip ipa_round_lr_points:
+// Device path (2 <= n <= the context's no-fold size, at most OPEN_MAX_N): the open in its no-fold form (ipa_state.hip ipa_round_lr_points:
 // the key is never folded, every round's L and R are two MSMs over the same n points with expanded scalars) for a GROUP of up to
 // OPEN_MAX_GROUP members at a time.  Each step of a group is one set of member-batched launches (fr_vec.hip *_batch, blockIdx.y =
 // member) and ONE batched MSM launch sequence over the key (L and R of every member: up to 8 scalar arrays; the C_bar commits of the
@@ -910,7 +910,7 @@ struct OpenGroups {
     // or, after the last one, U and c.  Above the no-fold size the KEY is folded here too, every fold_k rounds: the host keeps each
     // member's challenge products (s'[2t + u] = s[t] xi^u, what k_nofold_s_update_batch computes) and, when the fold is due, turns
     // s[1] (one level) or s[1..3] (two) into the member's digit record -- the scalars and digits of the single open's deferred fold
-    // (abi.hip ipa_round_fold_impl) -- then ONE batched fold launch writes every member's key and s starts again from (1).
+    // (ipa_state.hip ipa_round_fold_impl) -- then ONE batched fold launch writes every member's key and s starts again from (1).
     int after_round(int j, const Point *pts, bool *through) {
         Flight &f = fl[j];
         const size_t r = f.step - 1;

@@ -1,5 +1,5 @@
 // Shared by the pcdl / acc level of the library: pcdl_acc.hip (the single calls, the sharded open and check), pcdl_batch.hip (the
-// batched calls) and, for the blob layout alone, wire.hip and abi.hip.
+// batched calls) and, for the blob layout alone, wire.hip; for the transcript's hashes open_host.hip, for is_pow2 ipa_state.hip.
 #pragma once
 #include "internal.hpp"
 

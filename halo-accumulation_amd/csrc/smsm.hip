@@ -1,9 +1,9 @@
 // Small MSMs (n <= 2^16 points): the 2 lg n L/R products of every pcdl::open (pcdl.rs:203-208), the alpha-weighted
 // point_dot of acc.rs:178, commitments of short keys.  At this size an MSM is a latency chain, not a throughput
-// problem: the general pipeline of msm.hip spends it in ~22 dependent launches and ~45 serial point additions in
+// problem: the general pipeline of msm_general.hip spends it in ~22 dependent launches and ~45 serial point additions in
 // the window sums (0.33 - 0.6 ms whatever n is).  Here the same Pippenger MSM is 4 launches:
 //
-//   k_msm_recode        (msm.hip)  signed digits, u16 [window][i]
+//   k_msm_recode        (msm_general.hip)  signed digits, u16 [window][i]
 //   k_smsm_sort         one block per window: counting sort of the window's digits with the whole histogram in
 //                       LDS (<= 2^14 counters), point references grouped by bucket, buckets cut into tasks of
 //                       <= kmax entries (balanced), task ids reserved with one atomic per window
@@ -19,7 +19,7 @@
 
 namespace halo {
 
-constexpr uint32_t DIGIT_NONE16 = 0xFFFFu;  // msm.hip: zero digit
+constexpr uint32_t DIGIT_NONE16 = 0xFFFFu;  // k_msm_recode (msm_general.hip): zero digit
 constexpr uint32_t SMSM_HEAVY = 4;          // buckets with more partials than this are summed by the whole block first
 constexpr uint32_t WAVE_TASK = 512;         // entries one wave task covers at most (8 per lane, then a 6-step shuffle tree)
 constexpr uint32_t TASK_IS_WAVE = 0xFFFFFFFFu;
@@ -497,7 +497,7 @@ __global__ __launch_bounds__(256, 2) void k_smsm_final(const uint32_t *__restric
 }
 
 // ------------------------------------------------------------------------------ launch sequence
-// Called from msm_enqueue_launches (msm.hip) after k_msm_recode; digits are in ws.d_canon.  Buffer reuse: d_sorted
+// Called from msm_enqueue_launches (msm_general.hip) after k_msm_recode; digits are in ws.d_canon.  Buffer reuse: d_sorted
 // (entries), d_starts (first task of a bucket), d_counts (tasks of a bucket), d_task_g (task records), d_buckets
 // (partials), d_seg, d_meta[0] (task count), d_meta[64 + w] (tickets), d_winsum.
 int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MemberOffsets &offs, size_t n, MsmPlan &p, uint32_t Wt,
@@ -572,7 +572,7 @@ int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const
     return HALO_OK;
 }
 
-// The last step of the sorted pipelines of msm.hip as well: the (S, T) records k_msm_reduce1 left per segment (nseg <= 64
+// The last step of the sorted pipelines of msm_general.hip and msm_table.hip as well: the (S, T) records k_msm_reduce1 left per segment (nseg <= 64
 // per window, 2^k buckets each) -> window sums.  A chain of ~20 dependent point operations run by Wt blocks: the quad
 // form takes 80 us where one wave per window took 130.
 int quad_final_enqueue(halo_ctx *ctx, MsmWorkspace &ws, uint32_t Wt, uint32_t nseg, int k, uint64_t *winsum, uint64_t *winsum_plain,
@@ -584,7 +584,7 @@ int quad_final_enqueue(halo_ctx *ctx, MsmWorkspace &ws, uint32_t Wt, uint32_t ns
     return HALO_OK;
 }
 
-// Last device step of the row / column window sums (msm.hip k_msm_reduce_rc): block w takes 64 consecutive entries E_0..E_63
+// Last device step of the row / column window sums (msm_buckets.hip k_msm_reduce_rc): block w takes 64 consecutive entries E_0..E_63
 // (single points) and leaves (S, T) = (sum E_Q, sum (Q + 1) E_Q) as Jacobian words at winsum[2 w], winsum[2 w + 1]: the same
 // quad-parallel weighted sum as k_smsm_final, fed with S = T = E.  The 24 pairs are combined on the host (msm_combine_member:
 // ~70 additions; a second launch for them was 66 us of latency chain).

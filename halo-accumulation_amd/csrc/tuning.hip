@@ -85,6 +85,7 @@ const Tuning &tuning() {
     static const Tuning t = read_env();
     return t;
 }
+namespace host { bool host_inv_fermat() { return tuning().host_inv_fermat; } }  // (host_math.hpp Fp::inv)
 DevHooks &dev_hooks() {
     static DevHooks h;
     return h;

@@ -79,7 +79,7 @@ def test_multi_ctx_2_20_equals_single_context(hal, P):
 
 def test_multi_ctx_host_scalars_in_stretches_per_shard(hal):
     """halo_msm on a multi-device context with shard blocks of 2^20 points: every shard's helper thread runs its block through the
-    host-scalar path of a plain context (multi.hip multi_host_run -> abi.hip msm_host_run: its copy in stretches under its own
+    host-scalar path of a plain context (multi.hip multi_host_run -> msm_entry.hip msm_host_run: its copy in stretches under its own
     kernels).  Equal to the plain context's point; a stretch of the key that cuts through both blocks; pcdl::commit with host
     coefficients shorter than d + 1 (zero-padded on the device)."""
     import torch

@@ -387,7 +387,7 @@ def test_msm_2_20_vs_oracle(ctx1m):
 
 def test_host_scalar_msm_in_stretches(hal, ctx1m):
     """halo_msm on scalars in pageable host memory (what integration/ffi.rs point_dot_affine calls) runs a large MSM over the
-    c = 20 table as index stretches on several slots, each behind the copy of its own scalars (abi.hip msm_host_pieces).  Against
+    c = 20 table as index stretches on several slots, each behind the copy of its own scalars (msm_entry.hip msm_host_pieces).  Against
     the oracle, against halo_msm_dev, with adversarial scalars, on a stretch of the key that does not start at 0, and at sizes
     that do not take the path (not a multiple of 64; below 2^19); other splits in child processes (the split is read once)."""
     import subprocess, sys, torch

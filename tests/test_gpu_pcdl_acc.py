@@ -152,6 +152,101 @@ def test_ipa_rounds_vs_oracle(hal, ctx, pp, n, ipa_mode):
     assert canon(U) == canon(gj[0]) and c.tolist() == cs[0].tolist()
 
 
+@pytest.fixture(scope="module")
+def ctx8(hal):
+    c = hal._lib.Context(urs_n=8)
+    yield c
+    c.close()
+
+
+def _first_round_model(gs, cs, zs, Hp):
+    """L, R of the first round by the CPU restatement: gs the affine key, cs and zs of its length"""
+    n = len(gs)
+    gj = np.zeros((n, 12), dtype=np.uint64)
+    for i in range(n):
+        orc.lib().orc_affine_to_jac(orc.ptr(gs[i]), orc.ptr(gj[i]))
+    cs, zs = np.ascontiguousarray(cs).copy(), np.ascontiguousarray(zs).copy()
+    Lw, Rw = orc.z(12), orc.z(12)
+    orc.lib().orc_ipa_round_lr(orc.ptr(gj), orc.ptr(cs), orc.ptr(zs), orc.C.c_size_t(n // 2), orc.ptr(Hp), orc.ptr(Lw), orc.ptr(Rw))
+    return Lw.tolist(), Rw.tolist()
+
+
+def test_ipa_begin_forms_share_their_asserts(hal, ctx8):
+    """halo_ipa_begin / _strided / _vectors over an 8-point key: the asserts of pcdl.rs:130-132 with their code and message (n not a
+    power of two, n beyond the key, more coefficients than n) and no state left behind; the vectors form's first round against
+    the CPU restatement."""
+    import ctypes as C
+    L = hal._lib
+    lib, ptr = ctx8.lib, L.ptr
+    sc, _ = orc.rng_scalars(0x49504142, 16)
+    z = np.ascontiguousarray(sc[0])
+
+    def begin(n, length):
+        h = C.c_void_p()
+        rc = lib.halo_ipa_begin(ctx8.h, n, ptr(sc), length, ptr(z), C.byref(h))
+        return rc, lib.halo_last_error().decode(), h.value
+
+    def begin_strided(n, length):
+        h = C.c_void_p()
+        rc = lib.halo_ipa_begin_strided(ctx8.h, n, ptr(sc), length, ptr(z), 2, 1, C.byref(h))
+        return rc, lib.halo_last_error().decode(), h.value
+
+    def begin_vectors(n):
+        h = C.c_void_p()
+        rc = lib.halo_ipa_begin_vectors(ctx8.h, n, ptr(sc), ptr(sc), C.byref(h))
+        return rc, lib.halo_last_error().decode(), h.value
+
+    pow2 = "ipa_begin: n is not a power of two"
+    key = "ipa_begin: n exceeds the commitment key (d <= D)"
+    deg = "ipa_begin: more coefficients than n (p.degree() <= d)"
+    for got, want in ((begin(6, 4), pow2), (begin(0, 0), pow2), (begin(16, 4), key), (begin(4, 5), deg), (begin(8, 9), deg),
+                      (begin_strided(6, 4), pow2), (begin_strided(16, 4), key), (begin_strided(4, 5), deg),
+                      (begin_vectors(6), pow2), (begin_vectors(16), key)):
+        assert got == (L.HALO_E_ASSERT, want, None)
+    gs = ctx8.read_bases()
+    Hp = np.ascontiguousarray(L.public_points()[1], dtype=np.uint64)
+    cs, zs = np.ascontiguousarray(sc[:8]), np.ascontiguousarray(sc[8:])
+    ipa = L.Ipa(ctx8, 8, cs, None, z_vec=zs)
+    Lg, Rg = ipa.round_lr(Hp)
+    ipa.close()
+    assert (Lg.tolist(), Rg.tolist()) == _first_round_model(gs, cs, zs, Hp)
+
+
+def test_two_live_ipa_states_on_one_context_then_an_open(hal, ctx8):
+    """Two halo_ipa states alive on one 8-point context: the first borrows the context's buffer set, the second allocates a private
+    one, and each gets its p_bar buffer on demand (the hiding branch of a sharded open).  Both compute the CPU restatement's
+    share of C_bar and first round; destroyed in either order they leave the context's set whole: a third open afterwards gives
+    the oracle's proof."""
+    from halo_accumulation_amd import pcdl
+    L = hal._lib
+    n, d = 8, 7
+    gs = ctx8.read_bases()
+    pp8 = orc.make_pp(gs)
+    Hp = np.ascontiguousarray(L.public_points()[1], dtype=np.uint64)
+    sc, _ = orc.rng_scalars(0x54574F53, 2 * n + 3)
+    za, zb, zq = sc[2 * n], sc[2 * n + 1], sc[2 * n + 2]
+    seed = 0x50424152
+    q = [orc.fr_from_mont(x) for x in orc.rng_scalars(seed, d)[0]]
+    zqi = orc.fr_from_mont(zq)
+    pbar = [(-zqi * q[0]) % pm.R_ORDER] + [(q[i - 1] - zqi * q[i]) % pm.R_ORDER for i in range(1, d)] + [q[d - 1]]  # q (X - zq)
+    part_want = canon(orc.msm_affine(gs, orc.scalars_to_mont(pbar)))
+    for first_goes_first in (True, False):
+        a = L.Ipa(ctx8, n, sc[:n], za)
+        b = L.Ipa(ctx8, n, sc[n:2 * n], zb)
+        for ipa, cs, z in ((b, sc[n:2 * n], zb), (a, sc[:n], za)):
+            assert canon(ipa.hiding_partial(seed, d, zq, 1, 0)) == part_want
+            Lg, Rg = ipa.round_lr(Hp)
+            assert (Lg.tolist(), Rg.tolist()) == _first_round_model(gs, cs, orc.powers(z, n), Hp)
+        for ipa in ((a, b) if first_goes_first else (b, a)):
+            ipa.close()
+        coeffs = np.ascontiguousarray(sc[:d])
+        Cm = pcdl.commit(ctx8, coeffs, d, None)
+        rng = [77]
+        pi = pcdl.open(ctx8, rng, coeffs, Cm, d, za, None)
+        pi_ref, st_ref = orc.pcdl_open(pp8, 77, coeffs, Cm, d, za, None)
+        assert pi.tolist() == pi_ref.tolist() and rng[0] == st_ref
+
+
 # The same round-by-round comparison over a key of exceptional points and a chosen challenge schedule: the folded key cannot be
 # read, so a wrong output point of a fold kernel shows as a wrong L, R of a later round or a wrong U
 @pytest.fixture(scope="module")
