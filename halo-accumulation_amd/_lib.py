@@ -120,6 +120,13 @@ _SIGS = {
     "halo_pcdl_commit_dev_batch": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, u64p, u64p, C.POINTER(C.c_int)]),
     "halo_instance_from_poly": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), u64p, C.c_size_t, C.c_size_t, u64p, u64p, u64p]),
     "halo_instance_from_poly_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, u64p, C.c_size_t, u64p, u64p, u64p, C.POINTER(C.c_int)]),
+    "halo_poly_degrees_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "halo_poly_eval_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, u64p, u64p]),
+    "halo_instance_from_poly_dev": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p, C.c_size_t, C.c_size_t, u64p, u64p, u64p]),
+    "halo_pcdl_open_dev_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t, u64p, u64p,
+                                           u64p, u64p, C.POINTER(C.c_int)]),
+    "halo_instance_from_poly_dev_batch": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_size_t,
+                                                    u64p, u64p, u64p, C.POINTER(C.c_int)]),
     "halo_proof_encoded_size": (C.c_size_t, [C.c_size_t, C.c_int]),
     "halo_instance_encoded_size": (C.c_size_t, [C.c_size_t, C.c_int]),
     "halo_accumulator_encoded_size": (C.c_size_t, [C.c_size_t]),
@@ -189,6 +196,16 @@ _DEV_SIGS = {
     "halo_test_lazy_field_op": (C.c_int, [C.c_void_p, C.c_int, u32p, C.c_size_t, u32p]),
     "halo_test_lazy_point_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, u32p, u32p, C.c_size_t, u32p]),
 }
+
+
+def dev_rows(dptrs, lens, who):
+    """m device addresses and lengths as the C arrays of the entry points over device rows (0 / None: a null pointer)"""
+    m = len(dptrs)
+    if len(lens) != m:
+        raise ValueError("%s: %d lengths for %d pointers" % (who, len(lens), m))
+    ptrs = (C.c_void_p * max(m, 1))(*[C.c_void_p(int(p or 0)) for p in dptrs])
+    ln = (C.c_size_t * max(m, 1))(*[int(k) for k in lens])
+    return ptrs, ln
 
 
 def declared_symbols():
@@ -457,6 +474,20 @@ class Context:
         out = np.zeros(4, dtype=np.uint64)
         check(self.lib.halo_poly_eval(self.h, ptr(coeffs), coeffs.shape[0], ptr(np.ascontiguousarray(z, dtype=np.uint64)), ptr(out)))
         return out
+
+    def poly_eval_dev(self, dptr, length, z):
+        """p(z) for `length` coefficients resident in device memory (halo_poly_eval_dev)"""
+        out = np.zeros(4, dtype=np.uint64)
+        check(self.lib.halo_poly_eval_dev(self.h, C.c_void_p(int(dptr)), length, ptr(np.ascontiguousarray(z, dtype=np.uint64)), ptr(out)))
+        return out
+
+    def poly_degrees_dev(self, dptrs, lens):
+        """the degrees of m device-resident rows, found on the device (halo_poly_degrees_dev) -> list of m ints"""
+        ptrs, ln = dev_rows(dptrs, lens, "poly_degrees_dev")
+        m = len(dptrs)
+        out = (C.c_size_t * max(m, 1))()
+        check(self.lib.halo_poly_degrees_dev(self.h, ptrs, ln, m, out))
+        return [int(out[i]) for i in range(m)]
 
     # ---- h(X)
     def h_coeffs(self, xis):

@@ -68,6 +68,36 @@ def instance_from_poly_batch(ctx, rng, ps, d, zs, ws=None):
     return [out[i].copy() for i in range(m)]
 
 
+def instance_from_poly_dev(ctx, rng, dptr, length, d, z, w=None):
+    """instance_from_poly for `length` coefficients resident in device memory, trailing zeros allowed (halo_instance_from_poly_dev)"""
+    st = C.c_uint64(rng[0])
+    inst = np.zeros(ctx.lib.halo_instance_words(max(lg_of(d), 0)), dtype=np.uint64)
+    check(ctx.lib.halo_instance_from_poly_dev(ctx.h, C.byref(st), C.c_void_p(int(dptr or 0)), length, d, ptr(_a(z)), ptr(_a(w)), ptr(inst)))
+    rng[0] = st.value
+    return inst
+
+
+def instance_from_poly_dev_batch(ctx, rng, dptrs, lens, d, zs, ws=None):
+    """instance_from_poly_batch for m device-resident polynomials (halo_instance_from_poly_dev_batch): dptrs[i] = device address of
+    lens[i] coefficients -> the Instances, rng[0] updated, as instance_from_poly_batch for the same rows; raises as it does"""
+    m = len(dptrs)
+    ptrs, ln = _lib.dev_rows(dptrs, lens, "instance_from_poly_dev_batch")
+    zs = _pack_rows(zs, m, 4, "instance_from_poly_dev_batch", "zs")
+    if zs is None:
+        raise ValueError("instance_from_poly_dev_batch: zs is required")
+    ws = _pack_rows(ws, m, 4, "instance_from_poly_dev_batch", "ws")
+    st = C.c_uint64(rng[0])
+    out = np.zeros((max(m, 1), ctx.lib.halo_instance_words(max(lg_of(d), 0))), dtype=np.uint64)
+    status = (C.c_int * max(m, 1))()
+    rc = ctx.lib.halo_instance_from_poly_dev_batch(ctx.h, C.byref(st), d, ptrs, ln, m, ptr(zs), ptr(ws), ptr(out), status)
+    if rc in (_lib.HALO_OK, _lib.HALO_E_ASSERT):
+        rng[0] = st.value
+    if rc == _lib.HALO_E_ASSERT:
+        raise AssertionError(ctx.lib.halo_last_error().decode(), [status[i] for i in range(m)], [out[i].copy() for i in range(m)])
+    check(rc)
+    return [out[i].copy() for i in range(m)]
+
+
 def prover(ctx, rng, d, qs):
     """acc.rs:190-220"""
     st = C.c_uint64(rng[0])

@@ -193,6 +193,7 @@ void halo_ctx_destroy(halo_ctx *ctx) {
     (void)hipFree(ctx->d_poly);
     (void)hipFree(ctx->d_poly2);
     (void)hipFree(ctx->d_verify);
+    (void)hipFree(ctx->d_degree_rows);
     for (auto p : ctx->d_slot_scalars) (void)hipFree(p);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
     if (ctx->h_wintab) (void)hipHostFree(ctx->h_wintab);

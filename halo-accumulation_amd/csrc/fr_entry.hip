@@ -46,6 +46,33 @@ int halo_poly_eval(halo_ctx *ctx, const uint64_t *coeffs, size_t len, const uint
     return HALO_OK;
 }
 
+// ... over coefficients in device memory, read in place (no staging: len is not bound by the context's size)
+int halo_poly_eval_dev(halo_ctx *ctx, const void *d_coeffs, size_t len, const uint64_t z[4], uint64_t out[4]) {
+    HALO_CTX(ctx);
+    if (!z || !out) { set_error("poly_eval_dev: null pointer"); return HALO_E_ARG; }
+    int rc = dev_rows_ok("poly_eval_dev", &d_coeffs, &len, 1);
+    if (rc) return rc;
+    if (len >= ((size_t)1 << 32)) { set_error("poly_eval_dev: len exceeds 2^32 - 1"); return HALO_E_ARG; }
+    host::Fr r;
+    rc = fr_poly_eval(ctx, static_cast<const uint64_t *>(d_coeffs), len, host::Fr::load(z), &r);
+    if (rc) return rc;
+    r.store(out);
+    return HALO_OK;
+}
+
+// DensePolynomial::degree of m device-resident rows (fr_vec.hip k_poly_degree_batch)
+int halo_poly_degrees_dev(halo_ctx *ctx, const void *const *d_coeffs, const size_t *lens, size_t m, size_t *degrees_out) {
+    HALO_CTX(ctx);
+    if (m && !degrees_out) { set_error("poly_degrees_dev: null pointer"); return HALO_E_ARG; }
+    int rc = dev_rows_ok("poly_degrees_dev", d_coeffs, lens, m);
+    if (rc) return rc;
+    std::vector<size_t> degs(m);  // (nothing is written unless the whole call succeeds)
+    rc = poly_degrees_dev(ctx, d_coeffs, lens, m, degs.data());
+    if (rc) return rc;
+    for (size_t i = 0; i < m; ++i) degrees_out[i] = degs[i];
+    return HALO_OK;
+}
+
 // ------------------------------------------------------------------ h(X)
 int halo_h_coeffs(halo_ctx *ctx, const uint64_t *xis, size_t lg_n, uint64_t *out) {
     HALO_CTX(ctx);

@@ -419,6 +419,32 @@ __global__ __launch_bounds__(256) void k_pad_members_batch(PadMembers t, uint32_
     reinterpret_cast<uint4 *>(out + ms * t.row[blockIdx.y])[i] = v;
 }
 
+// DensePolynomial::degree of m device-resident rows in ONE launch (halo_poly_degrees_dev; host_poly_degree on the host): blockIdx.y =
+// row of the table in device memory, blockIdx.x = the row's chunk of DEG_CHUNK scalars, a lane reads 16 bytes (half a scalar) per
+// pass of DEG_LANES lanes.  A wave keeps the highest scalar of its lanes with a non-zero half (the ballot's top bit; the passes
+// ascend) and publishes index + 1 with one atomicMax into the row's `top`, which arrives zeroed: 0 stays "no non-zero scalar".
+// The rows are only read; no shared memory, no scratch.
+__global__ __launch_bounds__(256) void k_poly_degree_batch(DegreeRow *rows) {
+    DegreeRow *r = rows + blockIdx.y;
+    const uint64_t len = r->len, lo = (uint64_t)blockIdx.x * DEG_CHUNK;
+    if (lo >= len) return;
+    const uint64_t end = 2 * (lo + DEG_CHUNK < len ? lo + DEG_CHUNK : len);  // in halves
+    const uint4 *src = reinterpret_cast<const uint4 *>(r->src);
+    const uint32_t wave0 = threadIdx.x & ~63u;
+    uint32_t top = 0;
+    for (uint64_t base = 2 * lo; base < end; base += DEG_LANES) {  // (uniform over the block: every lane reaches the ballot)
+        const uint64_t i = base + threadIdx.x;
+        bool nz = false;
+        if (i < end) {
+            const uint4 v = src[i];
+            nz = (v.x | v.y | v.z | v.w) != 0;
+        }
+        const uint64_t mask = __ballot(nz);
+        if (mask) top = (uint32_t)((base + wave0 + (63 - __clzll((long long)mask))) >> 1) + 1;
+    }
+    if ((threadIdx.x & 63) == 0 && top) atomicMax(&r->top, top);
+}
+
 // ------------------------------------------------------------------ the partial rows of the combined check's scalars
 // rows[0][k] = sum_p rows[p][k] over P rows of n elements at `stride` words (halo_pcdl_check_batch_combined: the parts of
 // sum_a r_a h_a(X), hpoly.hip h_combine_rows).  One element per lane; the running sum stays in the lazy 29-bit form, brought back
@@ -675,6 +701,43 @@ int pad_members_batch(halo_ctx *ctx, const PadMembers &t, int count, size_t n, u
     HALO_LAUNCH(ctx, "k_pad_members_batch", k_pad_members_batch, dim3((unsigned)((2 * n + 255) / 256), (unsigned)count), dim3(256), 0, t, (uint32_t)n,
                 d_out, (uint64_t)ms);
     HALO_HIP(hipGetLastError());
+    return HALO_OK;
+}
+
+// The degrees of m device rows (pointers and lengths checked by the caller: dev_rows_ok): the table goes up in one copy, with
+// every `top` zero, and comes back in one; launches of at most 65535 rows (the grid's y limit), each as wide as its longest row.
+// On ctx->stream, which is idle again on return.  The table's buffer is the context's own and only grows (24 bytes a row).
+int poly_degrees_dev(halo_ctx *ctx, const void *const *d_coeffs, const size_t *lens, size_t m, size_t *degrees_out) {
+    if (m == 0) return HALO_OK;
+    if (m > ((size_t)1 << 40) / sizeof(DegreeRow)) { set_error("poly_degrees: too many rows"); return HALO_E_ARG; }
+    std::vector<DegreeRow> rows(m);
+    for (size_t i = 0; i < m; ++i) {
+        if (lens[i] >= ((size_t)1 << 32) - 1) { set_error("poly_degrees: a row of 2^32 - 1 scalars or more"); return HALO_E_ARG; }
+        rows[i] = DegreeRow{static_cast<const uint64_t *>(d_coeffs[i]), lens[i], 0, 0};
+    }
+    const size_t bytes = m * sizeof(DegreeRow);
+    if (bytes > ctx->degree_bytes) {
+        alloc_epoch_bump(ctx);
+        (void)hipFree(ctx->d_degree_rows);
+        ctx->d_degree_rows = nullptr;
+        ctx->degree_bytes = 0;
+        HALO_HIP(hipMalloc(&ctx->d_degree_rows, bytes));
+        ctx->degree_bytes = bytes;
+    }
+    HALO_HIP(hipMemcpyAsync(ctx->d_degree_rows, rows.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+    constexpr size_t kGridY = 65535;
+    for (size_t first = 0; first < m; first += kGridY) {
+        const size_t cnt = m - first < kGridY ? m - first : kGridY;
+        size_t longest = 0;
+        for (size_t i = first; i < first + cnt; ++i) longest = lens[i] > longest ? lens[i] : longest;
+        if (longest == 0) continue;  // (zero polynomials only: their `top` stays 0)
+        HALO_LAUNCH(ctx, "k_poly_degree_batch", k_poly_degree_batch, dim3((unsigned)((longest + DEG_CHUNK - 1) / DEG_CHUNK), (unsigned)cnt),
+                    dim3(DEG_LANES), 0, ctx->d_degree_rows + first);
+    }
+    HALO_HIP(hipGetLastError());
+    HALO_HIP(hipMemcpyAsync(rows.data(), ctx->d_degree_rows, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HALO_HIP(hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < m; ++i) degrees_out[i] = rows[i].top ? rows[i].top - 1 : 0;
     return HALO_OK;
 }
 

@@ -265,6 +265,15 @@ class HostWorker {
     std::atomic<bool> pending_{false}, done_{true}, quit_{false};
     std::atomic<int> hot_{0};
 };
+// ---- fr_vec.hip: a row of k_poly_degree_batch's table in device memory -- len Montgomery scalars at src (32-byte aligned, only
+// read); top: 0 on the way in, index + 1 of the row's last non-zero scalar (0: none) on the way out
+struct DegreeRow {
+    const uint64_t *src;
+    uint64_t len;
+    uint32_t top, pad;
+};
+constexpr uint32_t DEG_LANES = 256;   // lanes of a block: DEG_LANES / 2 scalars a pass
+constexpr uint32_t DEG_CHUNK = 1024;  // scalars of a row per block
 }  // namespace halo
 
 // Device buffers of one pcdl::open (pcdl.rs:183-186 state + the no-fold vectors), owned by the context and reused
@@ -360,6 +369,8 @@ struct halo_ctx {
     size_t slot_scalars_bytes[HALO_SLOTS] = {};
     uint64_t *d_verify = nullptr;  // staging of the batched verifier (points, scalars, challenges, results), grown on demand
     size_t verify_words = 0;
+    halo::DegreeRow *d_degree_rows = nullptr;  // the table of halo_poly_degrees_dev and of the device-row batches (fr_vec.hip poly_degrees_dev), grown on demand
+    size_t degree_bytes = 0;
     // staging of halo_pcdl_check_batch / halo_acc_decider_batch (pcdl_batch.hip): h coefficients and tables of the members in flight.
     // Optional memory (on the budget of halo_set_memory_budget; released at destroy), only grown, so its address stays put
     uint64_t *d_check_stage = nullptr;
@@ -677,6 +688,17 @@ struct PadMembers {
     uint32_t row[MSM_MAX_BATCH];
 };
 int pad_members_batch(halo_ctx *ctx, const PadMembers &t, int count, size_t n, uint64_t *d_out, size_t ms);
+// ---- fr_vec.hip: degrees_out[i] = the index of row i's last non-zero scalar, 0 for none (host_poly_degree, found on the device:
+// k_poly_degree_batch); rows as dev_rows_ok accepts them
+int poly_degrees_dev(halo_ctx *ctx, const void *const *d_coeffs, const size_t *lens, size_t m, size_t *degrees_out);
+// the pointer conventions of every entry point over device rows: lens[i] = 0 with a null pointer is the zero polynomial; a null
+// pointer with a length, a misaligned pointer or a null table is HALO_E_ARG ("<who>: null or misaligned pointer")
+inline int dev_rows_ok(const char *who, const void *const *d_coeffs, const size_t *lens, size_t m) {
+    bool ok = m == 0 || (d_coeffs && lens);
+    for (size_t i = 0; i < m && ok; ++i) ok = !((lens[i] && !d_coeffs[i]) || ((uintptr_t)d_coeffs[i] & 31));
+    if (!ok) set_error(std::string(who) + ": null or misaligned pointer");
+    return ok ? HALO_OK : HALO_E_ARG;
+}
 
 // ---- decompress.hip: point decompression of the wire format on the device (wire.hip halo_*_decode_batch)
 constexpr size_t DECOMP_IN_WORDS = 6;    // a point's 33 wire bytes, zero-padded to 48

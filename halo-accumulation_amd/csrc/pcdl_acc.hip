@@ -505,6 +505,61 @@ int instance_from_poly_one(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *c
     return rc;
 }
 
+// A device-resident row of len scalars (degree deg <= d, found by the caller) into ctx->d_poly, zero-padded to d + 1: a
+// device-to-device copy of the deg + 1 scalars that count, the row itself is only read.  -> scalars copied
+static int poly_from_dev_row(halo_ctx *ctx, const void *d_coeffs, size_t len, size_t deg, size_t d, size_t *used) {
+    const size_t n = d + 1;
+    *used = deg + 1 < len ? deg + 1 : len;
+    int rc = ensure_poly_buffers(ctx);
+    if (rc) return rc;
+    if (*used) HALO_HIP(hipMemcpyAsync(ctx->d_poly, d_coeffs, *used * 32, hipMemcpyDeviceToDevice, ctx->stream));
+    if (*used < n) HALO_HIP(hipMemsetAsync(ctx->d_poly + 4 * *used, 0, (n - *used) * 32, ctx->stream));
+    return HALO_OK;
+}
+
+// the body of halo_pcdl_open_dev after its argument checks, and the device-row batches' member run alone (len <= d + 1, any deg < len
+// or 0): what pcdl_open_host does for the same coefficients in host memory
+int pcdl_open_dev_row(halo_ctx *ctx, uint64_t *rng_state, const void *d_coeffs, size_t len, size_t deg, const uint64_t C[12], size_t d,
+                      const uint64_t z[4], const uint64_t *w, uint64_t *proof_out) {
+    size_t used;
+    int rc = poly_from_dev_row(ctx, d_coeffs, len, deg, d, &used);
+    if (rc) return rc;
+    host::Rng rng{rng_state ? *rng_state : 0};
+    Fr wf = w ? Fr::load(w) : Fr::zero();
+    rc = pcdl_open_dev(ctx, &rng, deg, Point::load(C), d, Fr::load(z), w ? &wf : nullptr, proof_out);
+    if (rng_state) *rng_state = rng.state;
+    return rc;
+}
+
+// ... and instance_from_poly_one for such a row.  The commit of a short polynomial takes the host shortcut as there: its (at
+// most 16) scalars are read back from the padded copy, the only words of a polynomial that ever reach the host.
+int instance_from_poly_dev_row(halo_ctx *ctx, uint64_t *rng_state, const void *d_coeffs, size_t len, size_t deg, size_t d, const uint64_t z[4],
+                               const uint64_t *w, uint64_t *inst) {
+    const size_t n = d + 1, lg = ilog2(n);
+    size_t used;
+    int rc = poly_from_dev_row(ctx, d_coeffs, len, deg, d, &used);
+    if (rc) return rc;
+    const Fr zf = Fr::load(z), wf = w ? Fr::load(w) : Fr::zero();
+    Point C;
+    if (used == 0) C = w ? public_s_table().mul(wf) : Point::infinity();
+    else if (used <= 16) {
+        uint64_t few[16 * 4];
+        rc = download_words(ctx, few, ctx->d_poly, used * 4);
+        if (!rc) rc = commit_short_host(ctx, few, used, w ? &wf : nullptr, &C);
+    } else rc = pedersen_commit_dev(ctx, w ? &wf : nullptr, ctx->d_poly, n, &C);
+    if (rc) return rc;
+    C = C.normalized();
+    Fr v;
+    rc = fr_poly_eval(ctx, ctx->d_poly, deg + 1, zf, &v);  // p.evaluate(&z)
+    if (rc) return rc;
+    std::memset(inst, 0, 8 * instance_words(lg));
+    store_instance_head(inst, C, d, zf, v);
+    host::Rng rng{rng_state ? *rng_state : 0};
+    rc = pcdl_open_dev(ctx, &rng, deg, C, d, zf, w ? &wf : nullptr, inst + 21, &v);
+    if (rng_state) *rng_state = rng.state;
+    return rc;
+}
+
 }  // namespace halo
 
 using namespace halo;
@@ -587,15 +642,24 @@ int halo_pcdl_open_dev(halo_ctx *ctx, uint64_t *rng_state, const void *d_coeffs,
     if (len == 0 || !d_coeffs || !C || !z || !proof_out) { set_error("open_dev: null pointer or empty polynomial"); return HALO_E_ARG; }
     if (len - 1 > d) return fail_assert("open: p.degree() > d");                // pcdl.rs:131
     if (n > ctx->n) return fail_assert("open: d > D");                          // pcdl.rs:132
-    int rc = ensure_poly_buffers(ctx);
+    return pcdl_open_dev_row(ctx, rng_state, d_coeffs, len, len - 1, C, d, z, w, proof_out);
+}
+
+// benches/acc.rs:15-29 for a polynomial in device memory: halo_instance_from_poly without the upload, the degree found on the device.
+// The checks are those of halo_pcdl_commit_dev, the first of the three calls it stands for.
+int halo_instance_from_poly_dev(halo_ctx *ctx, uint64_t *rng_state, const void *d_coeffs, size_t len, size_t d, const uint64_t z[4], const uint64_t *w,
+                                uint64_t *instance_out) {
+    HALO_CTX(ctx);
+    if (!instance_out || !z) { set_error("instance_from_poly_dev: null pointer"); return HALO_E_ARG; }
+    int rc = dev_rows_ok("instance_from_poly_dev", &d_coeffs, &len, 1);
     if (rc) return rc;
-    HALO_HIP(hipMemcpyAsync(ctx->d_poly, d_coeffs, len * 32, hipMemcpyDeviceToDevice, ctx->stream));
-    if (len < n) HALO_HIP(hipMemsetAsync(ctx->d_poly + 4 * len, 0, (n - len) * 32, ctx->stream));
-    host::Rng rng{rng_state ? *rng_state : 0};
-    Fr wf = w ? Fr::load(w) : Fr::zero();
-    rc = pcdl_open_dev(ctx, &rng, len - 1, Point::load(C), d, Fr::load(z), w ? &wf : nullptr, proof_out);
-    if (rng_state) *rng_state = rng.state;
-    return rc;
+    size_t n = d + 1, deg = 0;
+    if (!is_pow2(n)) return fail_assert("commit: d + 1 is not a power of two");
+    if (len > n) return fail_assert("commit: p.degree() > d");
+    if (n > ctx->n) return fail_assert("commit: d > D");
+    rc = poly_degrees_dev(ctx, &d_coeffs, &len, 1, &deg);
+    if (rc) return rc;
+    return instance_from_poly_dev_row(ctx, rng_state, d_coeffs, len, deg, d, z, w, instance_out);
 }
 // pcdl::commit for device-resident coefficients (len <= d + 1)
 int halo_pcdl_commit_dev(halo_ctx *ctx, const void *d_coeffs, size_t len, size_t d, const uint64_t *w, uint64_t out[12]) {

@@ -656,7 +656,10 @@ struct OpenJob {
     size_t idx = 0, deg = 0;
     uint64_t s_start = 0;                // rng state before the member's first draw (the single call's *rng_state)
     uint64_t s_p = 0, s_q = 0;           // rng state before p's coefficients (random_instance) / before q's (hiding)
-    const uint64_t *coeffs = nullptr;    // the caller's n coefficients (null: p generated or accumulated on the device)
+    const uint64_t *coeffs = nullptr;    // the caller's n coefficients (null: p generated or accumulated on the device, or a device row)
+    bool dev_row = false;                // the caller's device-resident row: len scalars at d_src (null: the zero polynomial), only read
+    const uint64_t *d_src = nullptr;
+    size_t len = 0;
     const AccHPolys *hs = nullptr;       // acc::prover's h_0, challenges and alpha powers: p = h.get_poly() accumulated on the device
     bool hiding = false;
     Point C, last_L, last_R;
@@ -730,7 +733,7 @@ struct OpenGroups {
     const int *slots;  // the slots idle at entry; S of them are used
     int S;
     size_t n, lg, G, ms;
-    bool draw, commit, hiding, accumulated, u_from_last_round;  // draw: p from the stream; commit: C = commit(p) rides in step 0's MSM
+    bool draw, commit, hiding, accumulated, dev_rows, u_from_last_round;  // draw: p from the stream; commit: C = commit(p) rides in step 0's MSM
     OpenStage st;
     size_t nofold;  // the key size from which on the rounds fold no more (>= n: never folded, the no-fold form throughout)
     // M: points of the key the group's MSMs run over -- n over the context's key until the first fold, then each member's own staged
@@ -779,7 +782,7 @@ struct OpenGroups {
         for (size_t b = 0; b < f.cnt; ++b) f.s_host[b].assign(1, Fr::one());
     }
 
-    // step 0: coefficients (copied, generated, or accumulated), p(z), the powers of z, p_bar; the commits as one batched MSM
+    // step 0: coefficients (copied, generated, accumulated, or padded from the caller's device rows), p(z), the powers of z, p_bar; the commits as one batched MSM
     int start(int j, size_t g) {
         Flight &f = fl[j];
         f = Flight();
@@ -813,6 +816,15 @@ struct OpenGroups {
                     for (const std::vector<Fr> &x : hs.xis) hm[b].xis.push_back(x.data());
                 }
                 rc = h_accumulate_group(ctx, hm, f.cnt, lg, HACC_TABLES, st.h_hacc(j), st.d_hacc(j), st.vec(j, 0), ms);
+            } else if (dev_rows) {  // the caller's device rows, zero-padded to n in ONE launch (a full-length member too: the open overwrites its copy)
+                PadMembers t{};
+                for (size_t b = 0; b < f.cnt; ++b) {
+                    const OpenJob &jb = jobs[f.first + b];
+                    t.src[b] = jb.d_src;
+                    t.len[b] = (uint32_t)jb.len;
+                    t.row[b] = (uint32_t)b;
+                }
+                rc = pad_members_batch(ctx, t, (int)f.cnt, n, st.vec(j, 0), ms);
             } else
                 for (size_t b = 0; b < f.cnt; ++b)
                     HALO_HIP(hipMemcpyAsync(st.vec(j, 0) + b * ms, jobs[f.first + b].coeffs, n * 32, hipMemcpyHostToDevice, stream(j)));
@@ -1041,8 +1053,9 @@ struct OpenGroups {
 };
 
 // jobs: the members that do not fail up front, in member order.  *ran = false: the device path does not apply (nothing done)
-// Coefficients of a member: the caller's host array (jb.coeffs), generated on the device (draw), or -- jb.hs set, for every member
-// alike -- acc::prover's h(X) accumulated on the device straight into the member's coefficient vector.  commit: jb.C is not given
+// Coefficients of a member: the caller's host array (jb.coeffs), generated on the device (draw), -- jb.hs set, for every member
+// alike -- acc::prover's h(X) accumulated on the device straight into the member's coefficient vector, or -- jb.dev_row, for
+// every member alike -- the caller's device row padded into it (k_pad_members_batch).  commit: jb.C is not given
 // but computed, the members' commits riding in step 0's batched MSM
 static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, bool draw, bool commit, const int *slots_in, int S, bool *ran) {
     *ran = false;
@@ -1079,20 +1092,37 @@ static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, b
     *ran = true;
     const OpenStage st{ctx->d_check_stage, ctx->h_open_pinned, per, n, ms, G, fold_off, keystride};
     // (hiding: the same for every member of a batch)
-    OpenGroups groups{ctx, jobs, slots_in, S, n, lg, G, ms, draw, commit, jobs[0].hiding, accumulated, tuning().u_from_last_round, st, ctx->nofold_size, {}};
+    OpenGroups groups{ctx, jobs, slots_in, S, n, lg, G, ms, draw, commit, jobs[0].hiding, accumulated, jobs[0].dev_row, tuning().u_from_last_round, st, ctx->nofold_size, {}};
     return groups.run();
 }
 
 // halo_pcdl_open_batch (coeffs and Cs given), halo_instance_from_poly_batch (coeffs without Cs: the commits are computed and `out`
 // holds Instance blobs) and halo_random_instance_batch (neither: the polynomials are drawn as well) after their argument checks:
-// the members' draws, then the device path or, where it does not apply, the members one at a time
-static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *Cs, const uint64_t *zs,
+// the members' draws, then the device path or, where it does not apply, the members one at a time.
+// The same three calls over device-resident rows (halo_pcdl_open_dev_batch, halo_instance_from_poly_dev_batch): the draws need every
+// member's degree, so the degrees are found on the device first (ONE k_poly_degree_batch launch) and nothing else differs before
+// step 0 of a group, where the rows are padded into the staging instead of copied.  Run alone, a member is copied device to device
+// into the context's polynomial buffer (pcdl_open_dev_row, instance_from_poly_dev_row).  No route brings a polynomial to the host.
+struct OpenSource {  // the caller's polynomials: m x (d + 1) scalars in host memory, or m device rows (dev_rows_ok); neither: drawn
+    const uint64_t *coeffs = nullptr;
+    const void *const *d_coeffs = nullptr;
+    const size_t *lens = nullptr;
+};
+static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const OpenSource &src, size_t m, const uint64_t *Cs, const uint64_t *zs,
                             const uint64_t *ws, uint64_t *out, int *status) {
     const size_t n = d + 1, lg = ilog2(n);
-    const bool gen = coeffs == nullptr, commit = Cs == nullptr, hiding = gen || ws != nullptr;
+    const uint64_t *coeffs = src.coeffs;
+    const bool dev = src.d_coeffs != nullptr, gen = !coeffs && !dev, commit = Cs == nullptr, hiding = gen || ws != nullptr;
     const size_t stride = commit ? instance_words(lg) : proof_words(lg);
     int slots[HALO_SLOTS], S = idle_slots(ctx, slots);
     if (!S) { set_error("open_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
+    // 0. device rows: every member's degree (a member longer than d + 1 fails below and is not scanned)
+    std::vector<size_t> degs(dev ? m : 0), scan(dev ? m : 0);
+    if (dev) {
+        for (size_t i = 0; i < m; ++i) scan[i] = src.lens[i] <= n ? src.lens[i] : 0;
+        int rc = poly_degrees_dev(ctx, src.d_coeffs, scan.data(), m, degs.data());
+        if (rc) return rc;
+    }
     // 1. every member's draws, in member order (the loop's order)
     host::Rng rng{rng_state ? *rng_state : 0};
     std::vector<OpenJob> jobs;
@@ -1114,8 +1144,20 @@ static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const 
             rng.skip_scalars(jb.deg + 1);
             jb.z = rng.scalar();
         } else {
-            jb.coeffs = coeffs + i * n * 4;
-            jb.deg = host_poly_degree(jb.coeffs, n);
+            if (dev) {
+                if (src.lens[i] > n) {  // (alone, before any draw: the single calls' assert on the length)
+                    codes[i] = HALO_E_ASSERT;
+                    errs[i] = commit ? "commit: p.degree() > d" : "open: p.degree() > d";
+                    continue;
+                }
+                jb.dev_row = true;
+                jb.d_src = static_cast<const uint64_t *>(src.d_coeffs[i]);
+                jb.len = src.lens[i];
+                jb.deg = degs[i];
+            } else {
+                jb.coeffs = coeffs + i * n * 4;
+                jb.deg = host_poly_degree(jb.coeffs, n);
+            }
             if (Cs) jb.C = Point::load(Cs + 12 * i);
             jb.z = Fr::load(zs + 4 * i);
             if (ws) jb.w = Fr::load(ws + 4 * i);
@@ -1134,7 +1176,8 @@ static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const 
         jb.proof[1] = lg;
     }
     // (ONE polynomial of the caller's: the single call's body is faster than a group of one -- 2.94 against 3.47 ms at 2^10, 5.10
-    // against 5.93 at 2^14; "open_batch_group" forces the group)
+    // against 5.93 at 2^14; "open_batch_group" forces the group.  A device row keeps the rule: 2.84 against 3.46 ms
+    // at 2^10, 4.99 against 5.96 at 2^14, 6.98 against 8.09 at 2^16, tools/time_open_batch.py --dev)
     // (the single call's body runs on slots 0 and 1: only with both idle)
     const bool alone = commit && !gen && jobs.size() == 1 && dev_hooks().open_group <= 0 && S >= 2 && slots[0] == 0 && slots[1] == 1;
     bool ran = false;
@@ -1145,9 +1188,12 @@ static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const 
     if (!ran) {
         for (OpenJob &jb : jobs) {
             uint64_t st = jb.s_start;
+            const uint64_t *w = ws ? ws + 4 * jb.idx : nullptr;
             if (gen) rc = random_instance_one(ctx, &st, d, out + jb.idx * stride);
-            else if (commit) rc = instance_from_poly_one(ctx, &st, jb.coeffs, n, jb.deg, d, zs + 4 * jb.idx, ws ? ws + 4 * jb.idx : nullptr, out + jb.idx * stride);
-            else rc = pcdl_open_host(ctx, &st, jb.coeffs, jb.deg, Cs + 12 * jb.idx, d, zs + 4 * jb.idx, ws ? ws + 4 * jb.idx : nullptr, jb.proof);
+            else if (dev && commit) rc = instance_from_poly_dev_row(ctx, &st, jb.d_src, jb.len, jb.deg, d, zs + 4 * jb.idx, w, out + jb.idx * stride);
+            else if (dev) rc = pcdl_open_dev_row(ctx, &st, jb.d_src, jb.len, jb.deg, Cs + 12 * jb.idx, d, zs + 4 * jb.idx, w, jb.proof);
+            else if (commit) rc = instance_from_poly_one(ctx, &st, jb.coeffs, n, jb.deg, d, zs + 4 * jb.idx, w, out + jb.idx * stride);
+            else rc = pcdl_open_host(ctx, &st, jb.coeffs, jb.deg, Cs + 12 * jb.idx, d, zs + 4 * jb.idx, w, jb.proof);
             if (rc == HALO_E_ASSERT) { jb.rc = rc; jb.err = halo_last_error(); }
             else if (rc) return rc;
         }
@@ -1390,7 +1436,21 @@ int halo_pcdl_open_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uin
     const size_t n = d + 1;
     if (!is_pow2(n)) return fail_assert("open: d + 1 is not a power of two");  // pcdl.rs:130 (p.degree() <= d: the arrays hold d + 1)
     if (n > ctx->n) return fail_assert("open: d > D");                         // pcdl.rs:132
-    return open_batch_entry(ctx, rng_state, d, coeffs, m, Cs, zs, ws, proofs_out, status);
+    return open_batch_entry(ctx, rng_state, d, OpenSource{coeffs}, m, Cs, zs, ws, proofs_out, status);
+}
+
+// ... of m device-resident ones (see open_batch_entry): a member longer than d + 1 fails alone, as in halo_pcdl_commit_dev_batch
+int halo_pcdl_open_dev_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const void *const *d_coeffs, const size_t *lens, size_t m, const uint64_t *Cs,
+                             const uint64_t *zs, const uint64_t *ws, uint64_t *proofs_out, int *status) {
+    HALO_CTX(ctx);
+    if (m == 0) return HALO_OK;
+    if (!d_coeffs || !lens || !Cs || !zs || !proofs_out) { set_error("open_dev_batch: null pointer"); return HALO_E_ARG; }
+    int rc = dev_rows_ok("open_dev_batch", d_coeffs, lens, m);
+    if (rc) return rc;
+    const size_t n = d + 1;
+    if (!is_pow2(n)) return fail_assert("open: d + 1 is not a power of two");
+    if (n > ctx->n) return fail_assert("open: d > D");
+    return open_batch_entry(ctx, rng_state, d, OpenSource{nullptr, d_coeffs, lens}, m, Cs, zs, ws, proofs_out, status);
 }
 
 // pcdl::commit of m host polynomials at once (see commit_batch_run)
@@ -1434,7 +1494,21 @@ int halo_instance_from_poly_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, 
     const size_t n = d + 1;
     if (!is_pow2(n)) return fail_assert("commit: d + 1 is not a power of two");  // (the first of the loop's three calls)
     if (n > ctx->n) return fail_assert("commit: d > D");
-    return open_batch_entry(ctx, rng_state, d, coeffs, m, nullptr, zs, ws, instances_out, status);
+    return open_batch_entry(ctx, rng_state, d, OpenSource{coeffs}, m, nullptr, zs, ws, instances_out, status);
+}
+
+// ... for m device-resident polynomials (see open_batch_entry)
+int halo_instance_from_poly_dev_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const void *const *d_coeffs, const size_t *lens, size_t m,
+                                      const uint64_t *zs, const uint64_t *ws, uint64_t *instances_out, int *status) {
+    HALO_CTX(ctx);
+    if (m == 0) return HALO_OK;
+    if (!d_coeffs || !lens || !zs || !instances_out) { set_error("instance_from_poly_dev_batch: null pointer"); return HALO_E_ARG; }
+    int rc = dev_rows_ok("instance_from_poly_dev_batch", d_coeffs, lens, m);
+    if (rc) return rc;
+    const size_t n = d + 1;
+    if (!is_pow2(n)) return fail_assert("commit: d + 1 is not a power of two");
+    if (n > ctx->n) return fail_assert("commit: d > D");
+    return open_batch_entry(ctx, rng_state, d, OpenSource{nullptr, d_coeffs, lens}, m, nullptr, zs, ws, instances_out, status);
 }
 
 // benches/acc.rs:15-29 random_instance, m times (see open_batch_dev)
@@ -1444,7 +1518,7 @@ int halo_random_instance_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, siz
     if (!instances_out) { set_error("random_instance_batch: null pointer"); return HALO_E_ARG; }
     if (!is_pow2(d + 1) || d < 2) return fail_assert("random_instance: bad d");
     if (d + 1 > ctx->n) return fail_assert("random_instance: d > D");
-    return open_batch_entry(ctx, rng_state, d, nullptr, m, nullptr, nullptr, nullptr, instances_out, nullptr);
+    return open_batch_entry(ctx, rng_state, d, OpenSource{}, m, nullptr, nullptr, nullptr, instances_out, nullptr);
 }
 
 }  // extern "C"

@@ -112,5 +112,11 @@ int random_instance_one(halo_ctx *ctx, uint64_t *rng_state, size_t d, uint64_t *
 int pcdl_commit_host(halo_ctx *ctx, const uint64_t *coeffs, size_t len, size_t d, const host::Fr *w, host::Point *out);
 int instance_from_poly_one(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *coeffs, size_t len, size_t deg, size_t d, const uint64_t z[4],
                            const uint64_t *w, uint64_t *inst);
+// ... of halo_pcdl_open_dev, and instance_from_poly_one's counterpart, for a device-resident row: len <= d + 1 scalars of degree deg
+// (poly_degrees_dev), copied device to device into the context's polynomial buffer and never modified
+int pcdl_open_dev_row(halo_ctx *ctx, uint64_t *rng_state, const void *d_coeffs, size_t len, size_t deg, const uint64_t C[12], size_t d,
+                      const uint64_t z[4], const uint64_t *w, uint64_t *proof_out);
+int instance_from_poly_dev_row(halo_ctx *ctx, uint64_t *rng_state, const void *d_coeffs, size_t len, size_t deg, size_t d, const uint64_t z[4],
+                               const uint64_t *w, uint64_t *inst);
 
 }  // namespace halo

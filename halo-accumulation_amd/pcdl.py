@@ -134,6 +134,40 @@ def open_dev(ctx, rng, dptr, length, Cm, d, z, w=None):
     return proof
 
 
+def poly_degrees_dev(ctx, dptrs, lens):
+    """DensePolynomial::degree of m device-resident rows, found on the device (halo_poly_degrees_dev) -> list of m ints"""
+    return ctx.poly_degrees_dev(dptrs, lens)
+
+
+def poly_eval_dev(ctx, dptr, length, z):
+    """p(z) for `length` coefficients resident in device memory (halo_poly_eval_dev)"""
+    return ctx.poly_eval_dev(dptr, length, z)
+
+
+def open_dev_batch(ctx, rng, dptrs, lens, Cs, d, zs, ws=None):
+    """pcdl::open of m device-resident polynomials at once (halo_pcdl_open_dev_batch): dptrs[i] = device address of lens[i]
+    coefficients, trailing zeros allowed -> list of EvalProof blobs, rng[0] updated, as open_batch for the same rows.  A failing
+    member (a constant that hides, more than d + 1 coefficients) raises as open_batch does, with the status list as the
+    exception's second argument and the blobs (that member's zero-filled) as its third."""
+    m, lg = len(dptrs), max(lg_of(d), 0)
+    ptrs, ln = _lib.dev_rows(dptrs, lens, "open_dev_batch")
+    Cs = _pack_rows(Cs, m, 12, "open_dev_batch", "Cs")
+    zs = _pack_rows(zs, m, 4, "open_dev_batch", "zs")
+    if Cs is None or zs is None:
+        raise ValueError("open_dev_batch: Cs and zs are required")
+    ws = _pack_rows(ws, m, 4, "open_dev_batch", "ws")
+    st = C.c_uint64(rng[0])
+    out = np.zeros((max(m, 1), ctx.lib.halo_proof_words(lg)), dtype=np.uint64)
+    status = (C.c_int * max(m, 1))()
+    rc = ctx.lib.halo_pcdl_open_dev_batch(ctx.h, C.byref(st), d, ptrs, ln, m, ptr(Cs), ptr(zs), ptr(ws), ptr(out), status)
+    if rc in (_lib.HALO_OK, _lib.HALO_E_ASSERT):
+        rng[0] = st.value
+    if rc == _lib.HALO_E_ASSERT:
+        raise AssertionError(ctx.lib.halo_last_error().decode(), [status[i] for i in range(m)], [out[i].copy() for i in range(m)])
+    check(rc)
+    return [out[i].copy() for i in range(m)]
+
+
 def succinct_check(ctx, Cm, d, z, v, pi):
     """pcdl.rs:252-314 -> (xis of h, U); raises HaloReject where the reference returns Err"""
     lg = max(lg_of(d), 0)

@@ -223,7 +223,8 @@ int halo_pcdl_open(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *coeffs, s
                    const uint64_t z[4], const uint64_t *w /*nullable*/, uint64_t *proof_out);
 /* The same two for a polynomial already resident in device memory (len x 4 limbs, Montgomery; len = p.degree() + 1,
  * i.e. the top coefficient is non-zero as ark-poly's DensePolynomial guarantees).  The coefficients are read, not
- * modified.  No host-to-device transfer of the polynomial: this is the form whose rate bench.py reports. */
+ * modified.  No host-to-device transfer of the polynomial: this is the form whose rate bench.py reports.  (A zero-padded
+ * buffer: halo_poly_degrees_dev gives len without a download; halo_pcdl_open_dev_batch takes the padded buffer as it is.) */
 int halo_pcdl_commit_dev(halo_ctx *ctx, const void *d_coeffs, size_t len, size_t d, const uint64_t *w /*nullable*/, uint64_t out[12]);
 int halo_pcdl_open_dev(halo_ctx *ctx, uint64_t *rng_state, const void *d_coeffs, size_t len, const uint64_t C[12], size_t d,
                        const uint64_t z[4], const uint64_t *w /*nullable*/, uint64_t *proof_out);
@@ -455,6 +456,48 @@ int halo_instance_from_poly(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *
  * return HALO_E_ARG ("slot already has an MSM in flight") at the first member that needs the slot. */
 int halo_instance_from_poly_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *zs,
                                   const uint64_t *ws /*nullable*/, uint64_t *instances_out, int *status /*nullable*/);
+
+/* ---- the same over device-resident polynomials: no polynomial crosses to the host or back --------
+ * Rows as in halo_pcdl_commit_dev_batch: d_coeffs[i] = a 32-byte aligned device pointer to lens[i] Montgomery scalars, read and
+ * never modified, the caller's writes to them complete on entry; lens[i] = 0 with a null pointer is the zero polynomial.  A null
+ * pointer with a non-zero length, a misaligned pointer, or a null lens or d_coeffs with m > 0: HALO_E_ARG, nothing written.  On a
+ * multi-device context the pointers belong to devices[0].  A row's degree is that of its lens[i] scalars, found on the device
+ * (one kernel launch for all m rows): trailing zeros are allowed, a zero-padded buffer needs no download to learn its degree. */
+/* degrees_out[i] = the index of row i's last non-zero scalar, 0 for a row without one or of length 0 (DensePolynomial::degree).
+ * The table of rows goes to the device in one copy and the results come back in one (24 m bytes of context-owned memory that
+ * only grows); m is not bounded; a row of 2^32 - 1 scalars or more: HALO_E_ARG.  degrees_out is written only on success. */
+int halo_poly_degrees_dev(halo_ctx *ctx, const void *const *d_coeffs, const size_t *lens, size_t m, size_t *degrees_out);
+/* halo_poly_eval for len coefficients in device memory (a pointer as above), read in place: out = what halo_poly_eval writes for
+ * the downloaded coefficients.  len is not bound by the context's size (nothing is staged); len >= 2^32: HALO_E_ARG. */
+int halo_poly_eval_dev(halo_ctx *ctx, const void *d_coeffs, size_t len, const uint64_t z[4], uint64_t out[4]);
+/* halo_instance_from_poly for such a row: the blob and the final *rng_state of halo_instance_from_poly over the downloaded row
+ * (equally: of halo_pcdl_commit_dev, halo_poly_eval_dev and halo_pcdl_open_dev over its degree + 1 scalars).  Errors: a null ctx,
+ * z or instance_out, or a bad pointer: HALO_E_ARG; then halo_pcdl_commit_dev's asserts in its order ("commit: d + 1 is not a
+ * power of two", "commit: p.degree() > d" for len > d + 1, "commit: d > D"); then halo_pcdl_open's own ("open: hiding needs
+ * p.degree() >= 1": no randomness consumed). */
+int halo_instance_from_poly_dev(halo_ctx *ctx, uint64_t *rng_state, const void *d_coeffs, size_t len, size_t d, const uint64_t z[4],
+                                const uint64_t *w /*nullable*/, uint64_t *instance_out);
+/* halo_pcdl_open_batch over m such rows.  Every proof word, every status and the final *rng_state equal halo_pcdl_open_batch for
+ * the same rows downloaded and zero-padded to d + 1 scalars; where every row's last scalar is non-zero they also equal the loop
+ * over halo_pcdl_open_dev (which takes len for degree + 1).
+ * - A member with lens[i] > d + 1 fails alone, as in halo_pcdl_commit_dev_batch: HALO_E_ASSERT, "open: p.degree() > d", no
+ *   randomness consumed, blob zero-filled; a hiding member of degree 0 fails as in halo_pcdl_open_batch.
+ * - Whole-call checks, messages and precedence are halo_pcdl_open_batch's, the pointer errors above among its null checks.
+ * - Routes: where halo_pcdl_open_batch runs member-batched launches (2 <= d + 1 <= 2^16, staging available) every group's rows
+ *   reach its device state by ONE padding launch on the group's stream (a full-length row too: the open overwrites its copy);
+ *   elsewhere each member is copied device to device into the context's polynomial buffer and runs through halo_pcdl_open_dev's
+ *   body with the degree found.  halo_ctx_info(ctx, 10) counts the member-batched members as there. */
+int halo_pcdl_open_dev_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const void *const *d_coeffs, const size_t *lens, size_t m,
+                             const uint64_t *Cs, const uint64_t *zs, const uint64_t *ws /*nullable*/, uint64_t *proofs_out,
+                             int *status /*nullable*/);
+/* halo_instance_from_poly_batch over m such rows, with the same equalities against it, the routes of halo_pcdl_open_dev_batch (the
+ * commits join the first batched MSM of their group) and "commit: p.degree() > d" for a member with lens[i] > d + 1.  m = 1 with
+ * slots 0 and 1 idle runs alone through halo_instance_from_poly_dev's body, the host form's rule (measured faster alone for
+ * device rows too; a short polynomial's commit reads its at most 16 scalars back, as the host form's shortcut
+ * computes it). */
+int halo_instance_from_poly_dev_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const void *const *d_coeffs, const size_t *lens,
+                                      size_t m, const uint64_t *zs, const uint64_t *ws /*nullable*/, uint64_t *instances_out,
+                                      int *status /*nullable*/);
 
 /* ---- wire format (no device needed) ----------------------------------------------------------
  * EvalProof (pcdl.rs:22-30), Instance (acc.rs:21-28) and Accumulator (acc.rs:43-59) in the byte layout a derived

@@ -72,6 +72,16 @@ extern "C" {
                                    instance_out: *mut u64) -> c_int;
     pub fn halo_instance_from_poly_batch(ctx: *mut HaloCtx, rng_state: *mut u64, d: usize, coeffs: *const u64, m: usize, zs: *const u64,
                                          ws: *const u64, instances_out: *mut u64, status: *mut c_int) -> c_int;
+    // the same over device-resident rows (32-byte aligned device pointers and lengths, trailing zeros allowed): the degrees are
+    // found on the device, no polynomial crosses to the host (w / ws, rng_state, status may be null)
+    pub fn halo_poly_degrees_dev(ctx: *mut HaloCtx, d_coeffs: *const *const c_void, lens: *const usize, m: usize, degrees_out: *mut usize) -> c_int;
+    pub fn halo_poly_eval_dev(ctx: *mut HaloCtx, d_coeffs: *const c_void, len: usize, z: *const u64, out: *mut u64) -> c_int;
+    pub fn halo_instance_from_poly_dev(ctx: *mut HaloCtx, rng_state: *mut u64, d_coeffs: *const c_void, len: usize, d: usize, z: *const u64,
+                                       w: *const u64, instance_out: *mut u64) -> c_int;
+    pub fn halo_pcdl_open_dev_batch(ctx: *mut HaloCtx, rng_state: *mut u64, d: usize, d_coeffs: *const *const c_void, lens: *const usize, m: usize,
+                                    cs: *const u64, zs: *const u64, ws: *const u64, proofs_out: *mut u64, status: *mut c_int) -> c_int;
+    pub fn halo_instance_from_poly_dev_batch(ctx: *mut HaloCtx, rng_state: *mut u64, d: usize, d_coeffs: *const *const c_void, lens: *const usize,
+                                             m: usize, zs: *const u64, ws: *const u64, instances_out: *mut u64, status: *mut c_int) -> c_int;
     // m wire blobs -> m library blobs at `stride_words` (ctx, lg_out, status may be null; member i = bytes offs[i]..offs[i + 1])
     pub fn halo_proof_decode_batch(ctx: *mut HaloCtx, input: *const u8, offs: *const usize, m: usize, out: *mut u64, stride_words: usize,
                                    lg_out: *mut usize, status: *mut c_int) -> c_int;

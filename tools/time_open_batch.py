@@ -9,7 +9,12 @@ With --fold (alone: the other legs are skipped) the sizes ABOVE the no-fold size
 {8, 64} hiding members, for the open batch, halo_random_instance_batch and halo_instance_from_poly_batch: the same batched call
 with the development hook open_batch_fold = 2 (the loop over the single calls' bodies) and = 1 (the folded schedule with
 member-batched key folds), alternating in one process; medians of --reps (at least 5) runs with the least and the greatest, and
-"won" where every run of the folded schedule was faster than every run of the loop."""
+"won" where every run of the folded schedule was faster than every run of the loop.
+With --dev (alone) polynomials that live in device memory: n in {2^10, 2^14, 2^16} on a 2^16-point context, m in {8, 64} hiding
+members at full degree, three ways alternating in one process -- the loop over halo_pcdl_open_dev, ONE halo_pcdl_open_dev_batch, and
+halo_pcdl_open_batch behind the download a device-side caller needs in front of it (timed separately) -- medians of --reps (at least
+5) runs with the least and the greatest; and ONE Instance from a device row (halo_instance_from_poly_dev_batch, m = 1) alone, the
+host form's rule, against a forced group of one.  --out writes the JSON line to a file as well."""
 import argparse
 import ctypes as C
 import json
@@ -142,6 +147,105 @@ def fold_leg(reps):
                       "rows": rows, "equal": "proofs, instances and final RNG states: loop == folded schedule for every row"}))
 
 
+def dev_leg(reps):
+    """device-resident polynomials: the loop of single device opens, the device batch, the host batch behind a download"""
+    import torch
+    reps = max(reps, 5)
+    ctx = h._lib.Context(urs_n=1 << 16)
+    rows, alone = [], []
+
+    def stats(ms):
+        return round(statistics.median(ms), 3), [round(min(ms), 3), round(max(ms), 3)]
+
+    try:
+        for lg in (10, 14, 16):
+            n, d = 1 << lg, (1 << lg) - 1
+            words = ctx.lib.halo_proof_words(lg)
+            ps, Cs, zs, ws = inputs(ctx, n, 64, 0x48414C4F00000600 + n)
+            dev = torch.from_numpy(ps.reshape(-1).view(np.int64)).cuda()
+            torch.cuda.synchronize()
+            for m in (8, 64):
+                ptrs = (C.c_void_p * m)(*[dev.data_ptr() + 32 * n * i for i in range(m)])
+                lens = (C.c_size_t * m)(*([n] * m))
+
+                def loop():
+                    out = np.zeros((m, words), dtype=np.uint64)
+                    st = C.c_uint64(7 + m)
+                    calls = [(C.c_void_p(ptrs[i]), ptr(Cs[i]), ptr(zs[i]), ptr(ws[i]), ptr(out[i])) for i in range(m)]
+                    t = time.perf_counter()
+                    for p, c, z, w, o in calls:
+                        assert ctx.lib.halo_pcdl_open_dev(ctx.h, C.byref(st), p, n, c, d, z, w, o) == 0
+                    return (time.perf_counter() - t) * 1e3, out, st.value
+
+                def dev_batch():
+                    out = np.zeros((m, words), dtype=np.uint64)
+                    status = (C.c_int * m)()
+                    st = C.c_uint64(7 + m)
+                    t = time.perf_counter()
+                    rc = ctx.lib.halo_pcdl_open_dev_batch(ctx.h, C.byref(st), d, ptrs, lens, m, ptr(Cs), ptr(zs), ptr(ws), ptr(out), status)
+                    ms = (time.perf_counter() - t) * 1e3
+                    assert rc == 0 and ctx.info(10) == m, ctx.lib.halo_last_error()
+                    return ms, out, st.value
+
+                def host_batch():
+                    t = time.perf_counter()
+                    down = dev[: 4 * n * m].cpu().numpy().view(np.uint64).reshape(m, n, 4)  # (synchronous: a pageable destination)
+                    dl = (time.perf_counter() - t) * 1e3
+                    ms, out, state = batched(ctx, d, (down, Cs, zs, ws), m, 7 + m)
+                    return ms + dl, out, state, dl
+
+                a, b, c3 = loop(), dev_batch(), host_batch()
+                assert a[1].tolist() == b[1].tolist() == c3[1].tolist() and a[2] == b[2] == c3[2], "the three ways differ"
+                l_ms, d_ms, h_ms, dl_ms = [], [], [], []
+                for _ in range(reps):
+                    l_ms.append(loop()[0])
+                    d_ms.append(dev_batch()[0])
+                    r = host_batch()
+                    h_ms.append(r[0])
+                    dl_ms.append(r[3])
+                (l, lr), (dv, dr), (hb, hr), (dl, _) = stats(l_ms), stats(d_ms), stats(h_ms), stats(dl_ms)
+                rows.append({"n": n, "m": m, "loop_dev_ms": l, "dev_batch_ms": dv, "host_batch_with_download_ms": hb, "download_ms": dl,
+                             "loop_dev_min_max_ms": lr, "dev_batch_min_max_ms": dr, "host_batch_min_max_ms": hr,
+                             "dev_batch_over_loop": round(l / dv, 2), "host_batch_over_loop": round(l / hb, 2),
+                             "dev_batch_slower_than_host_batch_beyond_ranges": min(d_ms) > max(h_ms)})
+                print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+            # ONE Instance from a device row: alone through the single body (the host form's rule), against a group of one
+            iw = ctx.lib.halo_instance_words(lg)
+            one_p, one_l = (C.c_void_p * 1)(dev.data_ptr()), (C.c_size_t * 1)(n)
+
+            def instance(group, want_batched):
+                def run():
+                    h._lib.dev_hook("open_batch_group", group)
+                    try:
+                        out = np.zeros((1, iw), dtype=np.uint64)
+                        st = C.c_uint64(3)
+                        t = time.perf_counter()
+                        rc = ctx.lib.halo_instance_from_poly_dev_batch(ctx.h, C.byref(st), d, one_p, one_l, 1, ptr(zs[:1]), ptr(ws[:1]), ptr(out), None)
+                        ms = (time.perf_counter() - t) * 1e3
+                        assert rc == 0 and ctx.info(10) == want_batched, ctx.lib.halo_last_error()
+                        return ms, out, st.value
+                    finally:
+                        h._lib.dev_hook("reset", 0)
+                return run
+
+            single, grouped = instance(0, 0), instance(1, 1)
+            a, b = single(), grouped()
+            assert a[1].tolist() == b[1].tolist() and a[2] == b[2]
+            s_ms, g_ms = [], []
+            for _ in range(reps):
+                s_ms.append(single()[0])
+                g_ms.append(grouped()[0])
+            alone.append({"n": n, "alone_ms": stats(s_ms)[0], "group_of_one_ms": stats(g_ms)[0], "alone_min_max_ms": stats(s_ms)[1],
+                          "group_of_one_min_max_ms": stats(g_ms)[1]})
+            print(json.dumps(alone[-1]), file=sys.stderr, flush=True)
+    finally:
+        ctx.close()
+    return {"tool": "tools/time_open_batch.py --dev", "workload": "m hiding opens of full-degree polynomials resident in device memory, 1 GPU, "
+            "context of 2^16 points", "reps": reps, "statistic": "median of alternating runs, ms, least and greatest beside it; host batch = "
+            "download of the m rows + halo_pcdl_open_batch", "rows": rows, "one_instance_from_a_device_row": alone,
+            "equal": "proofs and final RNG states: loop == device batch == host batch for every row"}
+
+
 def alternate(one, two, reps):
     """a warm-up of each, then `reps` alternating runs; both ways must give the same outputs and final state"""
     a, b = one(), two()
@@ -166,9 +270,18 @@ def main():
     ap.add_argument("--sweep", type=int, default=1, help="members-per-launch sweep at k = 100 (0: off)")
     ap.add_argument("--big", action="store_true", help="add the 2^20-point leg (k = 4)")
     ap.add_argument("--fold", action="store_true", help="only the folded schedule against the loop at n = 2^15, 2^16")
+    ap.add_argument("--dev", action="store_true", help="only the device-resident legs at n = 2^10, 2^14, 2^16")
+    ap.add_argument("--out", default=None, help="with --dev: also write the JSON line to this file")
     a = ap.parse_args()
     if a.fold:
         return fold_leg(a.reps)
+    if a.dev:
+        line = json.dumps(dev_leg(a.reps))
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        print(line)
+        return
     ks = [int(x) for x in a.ks.split(",")]
     ctx = h._lib.Context(urs_n=1 << 14)
     rows, ri_rows, sweep = [], [], []
