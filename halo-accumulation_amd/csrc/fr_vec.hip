@@ -652,6 +652,7 @@ int open_batch_eval(halo_ctx *ctx, int G, const uint64_t *d_coeffs, size_t ms, s
     const FrPlan p = plan_poly_eval_batch(n);
     const int nwin = p.nwin, E = p.E;
     const unsigned nb = p.blocks;
+    if (n > OPEN_MAX_N || (size_t)nb * 4 > OPEN_PART_WORDS) { set_error("open_batch_eval: bad shape"); return HALO_E_ARG; }
     HALO_LAUNCH(ctx, "k_poly_eval_partial_batch", k_poly_eval_partial_batch, dim3(nb, (unsigned)G), dim3(256), 0, d_coeffs, (uint64_t)ms, (uint32_t)n,
                 d_tabs, nwin, E, d_parts);
     HALO_LAUNCH(ctx, "k_sum_partials_batch", k_sum_partials_batch, dim3(1, (unsigned)G), dim3(256), 0, d_parts, nb, 1u, 0, d_outs);
@@ -688,7 +689,9 @@ int open_batch_expand(halo_ctx *ctx, int G, const uint64_t *d_c, const uint64_t 
 }
 int open_batch_dots(halo_ctx *ctx, int G, const uint64_t *d_c, const uint64_t *d_z, size_t ms, size_t m, uint64_t *d_parts, uint64_t *d_outs) {
     unsigned nb = plan_dot(m).blocks;
-    if (nb > OPEN_PART_WORDS / 8) nb = OPEN_PART_WORDS / 8;  // (the sums are exact: any grid gives the same field elements)
+    // (the sums are exact: any grid gives the same field elements; from m = 2^16 on the 128 blocks' lanes make several trips)
+    if (nb > OPEN_PART_WORDS / 8) nb = OPEN_PART_WORDS / 8;
+    if (m > OPEN_MAX_N / 2) { set_error("open_batch_dots: bad shape"); return HALO_E_ARG; }
     HALO_LAUNCH(ctx, "k_dot2_partial_batch", k_dot2_partial_batch, dim3(nb, (unsigned)G), dim3(256), 0, d_c, d_z, (uint64_t)ms, (uint32_t)m, d_parts);
     HALO_LAUNCH(ctx, "k_sum_partials_batch", k_sum_partials_batch, dim3(1, (unsigned)G), dim3(256), 0, d_parts, nb, 2u, 1, d_outs + 4);
     HALO_HIP(hipGetLastError());

@@ -606,7 +606,7 @@ struct HAccMember {
 };
 constexpr size_t HACC_REC_WORDS = 10;  // a member's record: first table | count << 32, mode, h_0
 // words of the pinned / device staging of one call with G members and room for `cap` tables per pass
-inline size_t hacc_pin_words(size_t G, size_t lg_n, size_t cap) { return G * HACC_REC_WORDS + cap * (lg_n + 2) * 4; }
+constexpr size_t hacc_pin_words(size_t G, size_t lg_n, size_t cap) { return G * HACC_REC_WORDS + cap * (lg_n + 2) * 4; }
 inline size_t hacc_stage_words(size_t G, size_t lg_n, size_t cap) { return hacc_pin_words(G, lg_n, cap) + cap * H_TABLES_WORDS; }
 int h_accumulate_group(halo_ctx *ctx, const HAccMember *mem, size_t G, size_t lg_n, size_t cap, uint64_t *h_stage, uint64_t *d_stage, uint64_t *d_out,
                        size_t out_stride);
@@ -640,7 +640,13 @@ int small_msm_seg(halo_ctx *ctx, const uint64_t *d_points, const uint64_t *d_sca
 // and results at b * OPEN_*_WORDS in the group's own regions.
 constexpr int OPEN_MAX_GROUP = 4;
 constexpr size_t OPEN_TAB_WORDS = 1024, OPEN_CONST_WORDS = 32, OPEN_PART_WORDS = 1024, OPEN_OUT_WORDS = 32;
-constexpr size_t OPEN_MAX_N = (size_t)1 << 16;  // the batched kernels' partial sums and window tables are sized for this
+// The largest batched open.  What is sized from it: a member's window table (16 (1 + nwin) + E entries of 4 words, nwin = 5 windows
+// of 4 bits and a chain of E <= 64 here; open_batch_table refuses a table of more than OPEN_TAB_WORDS / 4 entries), its partial
+// records (the grids of open_batch_eval and open_batch_dots are capped to what OPEN_PART_WORDS holds and their lanes stride), the
+// prover batch's pinned records (pcdl_batch.hip HACC_PIN_WORDS) and the 32-bit element counts and base offsets of the kernels.
+constexpr size_t OPEN_MAX_LG = 19, OPEN_MAX_N = (size_t)1 << OPEN_MAX_LG;
+static_assert((16 * (1 + (OPEN_MAX_LG + 3) / 4) + 64) * 4 <= OPEN_TAB_WORDS, "a member's window table at OPEN_MAX_N");
+static_assert((uint64_t)OPEN_MAX_GROUP * (OPEN_MAX_N / 2) < ((uint64_t)1 << 31), "base offsets of the staged keys: 31-bit point indices");
 // One member's constants in device memory (uploaded once per step of a group, never kernel arguments): N-form multipliers
 // (kernel_args.hpp FsArg: 9 x 29-bit limbs) and Montgomery limbs (FeArg: 8 x 32 bits)
 struct OpenConst {

@@ -648,7 +648,7 @@ static int acc_verifier_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, 
 //
 // Above the no-fold size (n up to OPEN_MAX_N, where open_fold_route says so) the group takes the single open's folded schedule:
 // while the key has more points than the no-fold size, k = 1 or 2 rounds in the no-fold form over it, then ONE member-batched fold
-// launch of k levels (key_fold.hip k_fold_points*_batch) into the members' staged keys, n / 2 points each in the group's staging.
+// launch of k levels (key_fold.hip k_fold_points*_batch) into the members' staged keys, n >> k points each in the group's staging.
 // From the first fold on a member's key is its own: the batched MSMs run over the staged keys with one base offset per member
 // (MsmBatch::base_off; the small pipeline takes them, smsm.hip).  The folded key does not depend on the schedule and every point
 // written is normalised, so the proofs are still the loop's.
@@ -680,20 +680,26 @@ static void open_fold_products(std::vector<Fr> &s, const Fr &xi) {
     s.swap(out);
 }
 // Does a batch of n-point opens above the no-fold size take the folded schedule (OpenGroups::fold_keys), or the loop?  The hook
-// "open_batch_fold" forces either (1 / 2); the default follows the measurements of tools/time_open_batch.py --fold (DESIGN.md
-// 4.5): the folded schedule only at the sizes where every run of it was faster than every run of the loop -- 2^15 and 2^16
-// points (2.7 - 3.2 times the loop's speed for 8 and for 64 members, all three entry points).  Smaller sizes come above the no-fold
-// size only under a lowered switch (halo_set_ipa_switch, the development library): not measured, so the loop unless forced.
-static bool open_fold_route(size_t n) {
+// "open_batch_fold" forces either (1 / 2); the default follows the measurements of tools/time_open_batch.py --fold and
+// tools/time_prover_batch.py --fold (profiles/r18_*_batch_fold.json): the folded schedule only at the sizes
+// where every run of it was faster than every run of the loop -- 2^15 .. 2^19 points (OPEN_MAX_N) for the three open batches and
+// for the prover batch: 2.4 - 3.4 times the loop's speed up to 2^17, 1.7 - 1.95 times at 2^18, 1.5 times at 2^19.
+// TEMPORARY: the prover batch at 2^15 won as well (53.6 against 19.7 ms for 8 members, 426 against 126 for 64) but is held back
+// on the loop, because tests/test_gpu_prover_batch.py::test_above_the_device_form asserts one member at a time at that size.
+// Once that test moves to a size that is really unrouted (2^20), the prover's threshold becomes the opens' 2^15 and
+// --held-back of the timing tool goes.  Smaller sizes come above the no-fold size only under a lowered switch
+// (halo_set_ipa_switch, the development library): not measured, so the loop unless forced.
+static bool open_fold_route(size_t n, bool prover) {
     const int forced = dev_hooks().open_fold;
     if (forced) return forced == 1;
-    return n >= ((size_t)1 << 15);
+    return n >= ((size_t)1 << (prover ? 16 : 15));  // (up to OPEN_MAX_N: the callers' gate)
 }
 constexpr size_t OPEN_AUX_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS + OPEN_PART_WORDS + OPEN_OUT_WORDS);
 // (the prover batch's third coefficient source: up to HACC_TABLES polynomials h_i per pass of a group, see h_accumulate_group)
 constexpr size_t HACC_TABLES = 32;
-constexpr size_t HACC_PIN_WORDS = OPEN_MAX_GROUP * HACC_REC_WORDS + HACC_TABLES * (16 + 2) * 4;  // lg n <= 16 (OPEN_MAX_N)
-constexpr size_t FOLD_PIN_WORDS = OPEN_MAX_GROUP * FOLD_DIG_WORDS / 2;  // the members' digit records of a key fold (32-bit words, two to a word here)
+constexpr size_t HACC_PIN_WORDS = hacc_pin_words(OPEN_MAX_GROUP, OPEN_MAX_LG, HACC_TABLES);  // (a record per table grows with lg n)
+constexpr size_t FOLD_PIN_WORDS = OPEN_MAX_GROUP * FOLD_DIG_WORDS / 2;  // the members' digit records of a key fold (32-bit words, two to a word here: whatever the key's size)
+static_assert(FOLD_DIG_WORDS % 2 == 0, "digit records in whole 64-bit words");
 constexpr size_t OPEN_PIN_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_WORDS + OPEN_OUT_WORDS) + HACC_PIN_WORDS + FOLD_PIN_WORDS + 4;  // per slot; + the element one
 
 // Slot j's regions of the staging.  Device (`per` words a slot): the group's member vectors (G x ms: c | z | s | s' | F_L | F_R |
@@ -701,7 +707,8 @@ constexpr size_t OPEN_PIN_WORDS = OPEN_MAX_GROUP * (OPEN_TAB_WORDS + OPEN_CONST_
 // (OPEN_PIN_WORDS a slot): the tables | constants (one upload) | results (one download) | the prover batch's records | the
 // fold digit records | the element one.  Cached launch graphs and the kernels of fr_vec.hip (OPEN_*_WORDS) know this layout.
 // A group above the no-fold size (keystride > 0) has two more device regions behind the others, at `fold_off` words: the members'
-// folded keys, keystride = n / 2 points of AFF_STRIDE words each, and their digit records (FOLD_PIN_WORDS).
+// folded keys, keystride points of AFF_STRIDE words each (what the first fold leaves: n / 2 or n / 4), and their digit records
+// (FOLD_PIN_WORDS).
 struct OpenStage {
     uint64_t *d_base = nullptr, *h_base = nullptr;
     size_t per = 0, n = 0, ms = 0, G = 0;
@@ -1063,10 +1070,11 @@ static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, b
     if (A == 0 || n < 2 || n > OPEN_MAX_N || ctx->nofold_size < 2) return HALO_OK;  // (a switch of 0 / 1: always fold, the loop)
     const bool folds = n > ctx->nofold_size;  // the rounds fold the key down to the no-fold size: each member into a staged key of its own
     const bool accumulated = jobs[0].hs != nullptr;
-    if (folds && (accumulated || !open_fold_route(n))) return HALO_OK;  // (the prover batch keeps its own gate)
-    size_t G = open_group_size(ctx, n);
+    if (folds && !open_fold_route(n, accumulated)) return HALO_OK;
+    size_t G = open_group_size(ctx, n), first_m = n;  // first_m: points of a member's key after the first fold, its largest
     for (size_t M = n; folds && M > ctx->nofold_size;) {  // ... within the bucket limit at every key size the rounds run over
         M >>= M / ctx->nofold_size >= 4 ? 2 : 1;
+        if (first_m == n) first_m = M;
         const size_t g = open_group_size(ctx, M);
         if (g < G) G = g;
     }
@@ -1075,8 +1083,9 @@ static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, b
     if ((size_t)S > ng) S = (int)ng;
     const size_t ms = 7 * 4 * n;  // words of one member's vectors: c | z | s | s' | F_L | F_R | p_bar
     const size_t hacc_words = accumulated ? hacc_stage_words(OPEN_MAX_GROUP, lg, HACC_TABLES) : 0;
-    const size_t fold_off = G * ms + OPEN_AUX_WORDS + hacc_words, keystride = folds ? n / 2 : 0;
-    // words of one slot's group (+ above the no-fold size: n / 2 points of 128 bytes per member for its key, and the digit records)
+    const size_t fold_off = G * ms + OPEN_AUX_WORDS + hacc_words, keystride = folds ? first_m : 0;
+    // words of one slot's group: 224 n bytes of vectors per member (+ above the no-fold size: its key after the first fold, n / 2 or
+    // n / 4 points of 128 bytes, and the digit records) -- with 4 members 14 MiB a slot at 2^14, 128 MiB at 2^17, 256 MiB at 2^18, 512 MiB at 2^19
     const size_t per = fold_off + (folds ? G * keystride * (AFF_STRIDE / 2) + FOLD_PIN_WORDS : 0);
     size_t have = check_stage(ctx, (size_t)S, per * 8);
     if (have == 0) return HALO_OK;
@@ -1223,9 +1232,10 @@ static int open_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, const 
 //     batch folds such sums into a launch it needs anyway; here alpha hashes the drawn h_0, so they cannot ride the relations'
 //     launch).
 //  4. the hiding opens through open_batch_dev, their coefficients h(X) = h_0 + sum alpha^(i+1) h_i(X) accumulated on the device
-//     into the open's staging (h_accumulate_group), groups of up to 4 members over the idle slots.
+//     into the open's staging (h_accumulate_group), groups of up to 4 members over the idle slots -- above the no-fold size on the
+//     open batches' folded schedule, where open_fold_route says so (the accumulation does not depend on the key schedule).
 //  5. the blobs: C_bar | d | z | v | proof | h_0 | U_0 | omega.
-// *ran = false: the device form does not apply (size, staging) and nothing was written.
+// *ran = false: the device form does not apply (size, route, staging) and nothing was written.
 struct ProverMember {
     int rc = HALO_OK;
     std::string err;
@@ -1239,7 +1249,8 @@ static int acc_prover_batch_dev(halo_ctx *ctx, uint64_t state0, size_t d, const 
                                 const int *slots, int S, bool *ran, std::vector<int> &codes, std::vector<std::string> &errs, uint64_t *state_out) {
     *ran = false;
     const size_t n = d + 1, lg = ilog2(n), iw = instance_words(lg), aw = acc_words(lg);
-    if (n < 2 || n > ctx->nofold_size || n > OPEN_MAX_N) return HALO_OK;
+    if (n < 2 || n > OPEN_MAX_N || ctx->nofold_size < 2) return HALO_OK;
+    if (n > ctx->nofold_size && !open_fold_route(n, true)) return HALO_OK;  // (before any work: the loop is the single prover's alone)
     std::vector<ProverMember> mem(k);
     size_t total = 0;
     for (size_t j = 0; j < k; ++j) { mem[j].first = total; mem[j].m = counts[j]; total += counts[j]; }
@@ -1317,6 +1328,7 @@ static int acc_prover_batch_dev(halo_ctx *ctx, uint64_t state0, size_t d, const 
         rc = open_batch_dev(ctx, d, jobs, false, false, slots, S, ran);
         if (rc) return rc;
         if (!*ran) return HALO_OK;
+        ctx->open_batch_members = jobs.size();  // (halo_ctx_info 10: the members that reached their opens)
     }
     *ran = true;
     // 5. the blobs and the outcomes
@@ -1345,6 +1357,7 @@ static int acc_prover_batch_entry(halo_ctx *ctx, uint64_t *rng_state, size_t d, 
     std::vector<std::string> errs(k);
     uint64_t state = rng_state ? *rng_state : 0;
     bool ran = false;
+    ctx->open_batch_members = 0;
     int rc = acc_prover_batch_dev(ctx, state, d, qs, counts, k, accs, slots, S, &ran, codes, errs, &state);
     if (rc) return rc;
     if (!ran) {  // one member at a time through the single prover, from the same states

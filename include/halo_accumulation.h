@@ -372,9 +372,12 @@ int halo_acc_verifier_batch(halo_ctx *ctx, size_t d, const uint64_t *instances, 
  * - Where the hiding open takes its no-fold form (2 <= d + 1 <= the no-fold size, 2^14 by default): the succinct half of all
  *   instances at once (from 64 instances on in one device launch, as halo_pcdl_succinct_check_batch), the members' sums on a
  *   host thread pool, then groups of up to 4 members through the launches of halo_pcdl_open_batch, their polynomials h(X) =
- *   h_0 + sum alpha^(i+1) h_i(X) accumulated on the device straight into the open's state.  Elsewhere, and without the staging
- *   memory (optional memory, halo_set_memory_budget), the members run one at a time as halo_acc_prover runs them, with the same
- *   results.  A multi-device context runs the batch on devices[0]. */
+ *   h_0 + sum alpha^(i+1) h_i(X) accumulated on the device straight into the open's state.  At d + 1 = 2^16 .. 2^19 the
+ *   groups' opens take the folded schedule of halo_pcdl_open_batch (its staging per slot; measured 2.5 - 3.4 times as fast as
+ *   the loop up to 2^17, 1.8 times at 2^18, 1.6 at 2^19); halo_ctx_info(ctx, 10) says how many members of the last call
+ *   reached their opens in member-batched launches.  Elsewhere (2^15, and above 2^19), and without the staging memory (optional
+ *   memory, halo_set_memory_budget), the members run one at a time as halo_acc_prover runs them, with the same results.  A
+ *   multi-device context runs the batch on devices[0]. */
 int halo_acc_prover_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *instances, const size_t *counts, size_t k,
                           uint64_t *accs_out, int *status /*nullable*/);
 /* benches/acc.rs:15-29 random_instance: the workload generator of the reference's benchmark */
@@ -394,20 +397,22 @@ int halo_random_instance(halo_ctx *ctx, uint64_t *rng_state, size_t d, uint64_t 
  * - Before any work (status not written, *rng_state unchanged): a null ctx or a null array with m > 0: HALO_E_ARG; d + 1 not a
  *   power of two or above the key: HALO_E_ASSERT with the single call's messages.  m = 0: HALO_OK, nothing touched.
  * - Where the single open takes its no-fold form (2 <= d + 1 <= the no-fold size, 2^14 by default) groups of up to 4 members run
- *   in member-batched launches: one batched MSM per round for the L and R of the whole group.  At d + 1 = 2^15 and 2^16 a group
- *   also folds its keys as the single open does -- two rounds over the unfolded key, then one member-batched fold launch that
- *   writes every member's folded key into the group's device state (n / 2 points of 128 bytes per member more), the later rounds
- *   over those keys -- measured 2.7 - 3.2 times as fast as the loop; halo_ctx_info(ctx, 10) says how many
- *   members of the last call ran this way.  Groups rotate over the slots that
+ *   in member-batched launches: one batched MSM per round for the L and R of the whole group.  At d + 1 = 2^15 .. 2^19 a group
+ *   also folds its keys as the single open does -- one or two rounds over the unfolded key, then one member-batched fold launch
+ *   that writes every member's folded key into the group's device state (n / 2 or n / 4 points of 128 bytes per member more), the
+ *   later rounds over those keys, folded again until the no-fold size -- measured 2.4 - 3.3 times as fast as the loop up to
+ *   2^17, 1.7 - 1.95 times at 2^18 and 1.5 times at 2^19; halo_ctx_info(ctx, 10) says how many members of the last call ran this
+ *   way.  A slot's device state for a group of 4: 224 (d + 1) bytes per member and the keys -- 14 MiB at 2^14, 128 MiB at 2^17,
+ *   256 MiB at 2^18, 512 MiB at 2^19; where the budget refuses it the call uses fewer slots or the loop.  Groups rotate over the slots that
  *   are idle on entry (a caller's MSM in flight on another slot is left alone; no idle slot: HALO_E_ARG).  Their device state is
- *   optional memory (halo_set_memory_budget; it only grows and goes with the context): without it, and above 2^16 points,
+ *   optional memory (halo_set_memory_budget; it only grows and goes with the context): without it, and above 2^19 points,
  *   the members run one at a time as halo_pcdl_open runs them, with the same results.  A multi-device context runs the batch
  *   on its first device, with the proofs halo_pcdl_open gives there. */
 int halo_pcdl_open_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *Cs,
                          const uint64_t *zs, const uint64_t *ws /*nullable*/, uint64_t *proofs_out, int *status /*nullable*/);
 /* benches/acc.rs:15-29 random_instance, m times: instances_out = m Instance blobs at stride halo_instance_words(lg(d+1)), every
  * word and the final *rng_state as m calls of halo_random_instance in order (draws per member: d', w, the d' + 1 coefficients,
- * z, then its hiding open's).  The conventions of halo_pcdl_open_batch, its batched sizes (d + 1 up to 2^16) included; d < 2: the
+ * z, then its hiding open's).  The conventions of halo_pcdl_open_batch, its batched sizes (d + 1 up to 2^19) and staging included; d < 2: the
  * single call's assert. */
 int halo_random_instance_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, size_t m, uint64_t *instances_out);
 
@@ -449,10 +454,10 @@ int halo_instance_from_poly(halo_ctx *ctx, uint64_t *rng_state, const uint64_t *
  * member order (draws per member are the open's only: a hiding member draws deg scalars for q, then w_bar).  A hiding member with a
  * constant polynomial fails as halo_pcdl_open does: no randomness consumed, blob zero-filled, status[i] = HALO_E_ASSERT, the others
  * unaffected.  The conventions of halo_pcdl_open_batch, with the commit's messages for d + 1 not a power of two or above the key.
- * Where that call batches (2 <= d + 1 <= 2^16, staging available) the members' commits join the first batched MSM
+ * Where that call batches (2 <= d + 1 <= 2^19, staging available) the members' commits join the first batched MSM
  * of their group; elsewhere, and for m = 1 with slots 0 and 1 idle (measured faster alone), the members run one at a time
  * through halo_instance_from_poly's body.  That body, like halo_pcdl_open's in halo_pcdl_open_batch, runs on slot 0 and may
- * borrow slot 1: above 2^16 points and without the staging, a caller's MSM in flight on one of these two makes the call
+ * borrow slot 1: above 2^19 points and without the staging, a caller's MSM in flight on one of these two makes the call
  * return HALO_E_ARG ("slot already has an MSM in flight") at the first member that needs the slot. */
 int halo_instance_from_poly_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *coeffs, size_t m, const uint64_t *zs,
                                   const uint64_t *ws /*nullable*/, uint64_t *instances_out, int *status /*nullable*/);
@@ -483,15 +488,15 @@ int halo_instance_from_poly_dev(halo_ctx *ctx, uint64_t *rng_state, const void *
  * - A member with lens[i] > d + 1 fails alone, as in halo_pcdl_commit_dev_batch: HALO_E_ASSERT, "open: p.degree() > d", no
  *   randomness consumed, blob zero-filled; a hiding member of degree 0 fails as in halo_pcdl_open_batch.
  * - Whole-call checks, messages and precedence are halo_pcdl_open_batch's, the pointer errors above among its null checks.
- * - Routes: where halo_pcdl_open_batch runs member-batched launches (2 <= d + 1 <= 2^16, staging available) every group's rows
+ * - Routes: where halo_pcdl_open_batch runs member-batched launches (2 <= d + 1 <= 2^19, staging available: 512 MiB a slot at 2^19) every group's rows
  *   reach its device state by ONE padding launch on the group's stream (a full-length row too: the open overwrites its copy);
  *   elsewhere each member is copied device to device into the context's polynomial buffer and runs through halo_pcdl_open_dev's
  *   body with the degree found.  halo_ctx_info(ctx, 10) counts the member-batched members as there. */
 int halo_pcdl_open_dev_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const void *const *d_coeffs, const size_t *lens, size_t m,
                              const uint64_t *Cs, const uint64_t *zs, const uint64_t *ws /*nullable*/, uint64_t *proofs_out,
                              int *status /*nullable*/);
-/* halo_instance_from_poly_batch over m such rows, with the same equalities against it, the routes of halo_pcdl_open_dev_batch (the
- * commits join the first batched MSM of their group) and "commit: p.degree() > d" for a member with lens[i] > d + 1.  m = 1 with
+/* halo_instance_from_poly_batch over m such rows, with the same equalities against it, the routes of halo_pcdl_open_dev_batch (2 <= d + 1
+ * <= 2^19 and its staging; the commits join the first batched MSM of their group) and "commit: p.degree() > d" for a member with lens[i] > d + 1.  m = 1 with
  * slots 0 and 1 idle runs alone through halo_instance_from_poly_dev's body, the host form's rule (measured faster alone for
  * device rows too; a short polynomial's commit reads its at most 16 scalars back, as the host form's shortcut
  * computes it). */

@@ -5,8 +5,8 @@ k in {10, 100, 1000}; a sweep of the members per launch (the development hook op
 leg at n = 2^20 on a 2^20-point context with the fold table fixed off (halo_set_fold_table 0), so that no table build lands
 inside a timed run.  The proofs, instances and final RNG states of both ways must be equal.  Prints one JSON line; every time
 is the median of --reps alternating runs, in ms.
-With --fold (alone: the other legs are skipped) the sizes ABOVE the no-fold size, n = 2^15 and 2^16 on a 2^16-point context, m in
-{8, 64} hiding members, for the open batch, halo_random_instance_batch and halo_instance_from_poly_batch: the same batched call
+With --fold (alone: the other legs are skipped) the sizes ABOVE the no-fold size, n = 2^15 and 2^16 on a 2^16-point context and
+n = 2^17, 2^18 and 2^19 on a context of n points (--lgs picks among them), m in {8, 64} (--ms; at 2^19 the least of them only) hiding members, for the open batch, halo_random_instance_batch and halo_instance_from_poly_batch: the same batched call
 with the development hook open_batch_fold = 2 (the loop over the single calls' bodies) and = 1 (the folded schedule with
 member-batched key folds), alternating in one process; medians of --reps (at least 5) runs with the least and the greatest, and
 "won" where every run of the folded schedule was faster than every run of the loop.
@@ -103,11 +103,11 @@ def ifp_batched(ctx, d, args, k, state):
     return ms, out, st.value
 
 
-def fold_leg(reps):
+def fold_leg(reps, lgs, ms):
     """the folded schedule against the loop above the no-fold size (see the module's text)"""
     reps = max(reps, 5)
-    ctx = h._lib.Context(urs_n=1 << 16)
     rows = []
+    ctx = None
 
     def hooked(value, call, want_batched):
         def run():
@@ -121,10 +121,14 @@ def fold_leg(reps):
         return run
 
     try:
-        for lg in (15, 16):
+        for lg in lgs:
             n, d = 1 << lg, (1 << lg) - 1
-            args = inputs(ctx, n, 64, 0x48414C4F00000500 + n)
-            for m in (8, 64):
+            if ctx is None or ctx.size != max(n, 1 << 16):
+                if ctx is not None:
+                    ctx.close()
+                ctx = h._lib.Context(urs_n=max(n, 1 << 16))
+            args = inputs(ctx, n, max(ms) if lg < 19 else min(ms), 0x48414C4F00000500 + n)
+            for m in (ms if lg < 19 else [min(ms)]):
                 shapes = {"open_batch": lambda: batched(ctx, d, args, m, 7 + m), "random_instance_batch": lambda: ri_batched(ctx, d, m, 11 + m),
                           "instance_from_poly_batch": lambda: ifp_batched(ctx, d, args, m, 13 + m)}
                 for name, call in shapes.items():
@@ -140,11 +144,12 @@ def fold_leg(reps):
                                  "speedup": round(statistics.median(l_ms) / statistics.median(f_ms), 2), "won": max(f_ms) < min(l_ms)})
                     print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
     finally:
-        ctx.close()
-    print(json.dumps({"tool": "tools/time_open_batch.py --fold", "workload": "m hiding opens / random instances / Instances from the caller's polynomials "
-                      "(full degree) above the no-fold size, 1 GPU, context of 2^16 points, default switch 2^14", "reps": reps,
-                      "statistic": "median of alternating runs, ms; loop = open_batch_fold 2, fold = open_batch_fold 1, same process",
-                      "rows": rows, "equal": "proofs, instances and final RNG states: loop == folded schedule for every row"}))
+        if ctx is not None:
+            ctx.close()
+    return {"tool": "tools/time_open_batch.py --fold", "workload": "m hiding opens / random instances / Instances from the caller's polynomials "
+            "(full degree) above the no-fold size, 1 GPU, context of max(2^16, n) points, default switch 2^14", "reps": reps,
+            "statistic": "median of alternating runs, ms; loop = open_batch_fold 2, fold = open_batch_fold 1, same process",
+            "rows": rows, "equal": "proofs, instances and final RNG states: loop == folded schedule for every row"}
 
 
 def dev_leg(reps):
@@ -269,14 +274,14 @@ def main():
     ap.add_argument("--ks", default="10,100,1000")
     ap.add_argument("--sweep", type=int, default=1, help="members-per-launch sweep at k = 100 (0: off)")
     ap.add_argument("--big", action="store_true", help="add the 2^20-point leg (k = 4)")
-    ap.add_argument("--fold", action="store_true", help="only the folded schedule against the loop at n = 2^15, 2^16")
+    ap.add_argument("--fold", action="store_true", help="only the folded schedule against the loop at n = 2^15 .. 2^19")
+    ap.add_argument("--lgs", default="15,16,17,18,19", help="with --fold: log2 of the sizes")
+    ap.add_argument("--ms", default="8,64", help="with --fold: the members per call")
     ap.add_argument("--dev", action="store_true", help="only the device-resident legs at n = 2^10, 2^14, 2^16")
-    ap.add_argument("--out", default=None, help="with --dev: also write the JSON line to this file")
+    ap.add_argument("--out", default=None, help="with --fold or --dev: also write the JSON line to this file")
     a = ap.parse_args()
-    if a.fold:
-        return fold_leg(a.reps)
-    if a.dev:
-        line = json.dumps(dev_leg(a.reps))
+    if a.fold or a.dev:
+        line = json.dumps(fold_leg(a.reps, [int(x) for x in a.lgs.split(",")], [int(x) for x in a.ms.split(",")]) if a.fold else dev_leg(a.reps))
         if a.out:
             with open(a.out, "w") as f:
                 f.write(line + "\n")

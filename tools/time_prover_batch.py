@@ -5,7 +5,13 @@ shape (the previous accumulator's Instance and a fresh random instance).  A seco
 (random_instance_batch + prover_batch against the two loops -- the ASDL step of many chains).  A sweep of the members per launch
 (the development hook open_batch_group) at k = 100.  With --big a k = 4 leg at n = 2^20 on a 2^20-point context with the fold table
 fixed off, where the members run one at a time.  Blobs, statuses and final RNG states of both ways must be equal for every row
-before a time is reported.  Prints one JSON line; every time is the median of --reps alternating runs, in ms, with min and max."""
+before a time is reported.  Prints one JSON line; every time is the median of --reps alternating runs, in ms, with min and max.
+With --fold (alone) the sizes above the no-fold size, n = 2^15 .. 2^19 (--lgs) on a context of max(2^16, n) points, k in {8, 64}
+(8 only from 2^18 on): the same batched call under the development hook open_batch_fold = 2 (the loop over halo_acc_prover) and = 1 (the
+opens on the folded schedule), alternating; medians of at least 5 runs with the least and the greatest, "won" where every run of the
+folded schedule was faster than every run of the loop.  --held-back names sizes (log2) that the library keeps on the loop by default
+although they may win: the line lists them under "held_back_n", which the tests read beside the rows.  --out writes the JSON line to a
+file as well."""
 import argparse
 import ctypes as C
 import json
@@ -95,8 +101,55 @@ def row(n, k, s_ms, b_ms, extra=None):
     return r
 
 
+def fold_leg(reps, lgs, ks, long_ks, held_back):
+    """above the no-fold size: the same batched call under open_batch_fold = 2 (the loop over halo_acc_prover) and = 1 (the opens'
+    folded schedule), alternating in one process; k from `ks`, from 2^18 on only those in `long_ks`"""
+    reps = max(reps, 5)
+    rows = []
+
+    def hooked(ctx, value, call, want_batched):
+        def run():
+            h._lib.dev_hook("open_batch_fold", value)
+            try:
+                r = call()
+                assert ctx.info(10) == want_batched, (value, ctx.info(10))
+                return r
+            finally:
+                h._lib.dev_hook("reset", 0)
+        return run
+
+    for lg in lgs:
+        n, d = 1 << lg, (1 << lg) - 1
+        ctx = h._lib.Context(urs_n=max(n, 1 << 16))
+        try:
+            here = [k for k in ks if lg < 18 or k in long_ks]
+            qs = step_members(ctx, d, max(here), 0x48414C4F00000700 + n)
+            for k in here:
+                call = lambda: batched(ctx, d, qs, k, 7 + k)  # noqa: E731
+                loop, fold = hooked(ctx, 2, call, 0), hooked(ctx, 1, call, k)
+                s, b = alternate(loop, fold, reps)
+                r = row(n, k, s, b)
+                rows.append({"n": n, "k": k, "loop_ms": r["serial_ms"], "fold_ms": r["batch_ms"], "loop_min_max_ms": r["serial_min_max"],
+                             "fold_min_max_ms": r["batch_min_max"], "speedup": r["speedup"], "won": max(b) < min(s)})
+                print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
+        finally:
+            ctx.close()
+    return {"tool": "tools/time_prover_batch.py --fold", "workload": "k x acc::prover over [previous accumulator, fresh instance] above the "
+            "no-fold size, 1 GPU, context of max(2^16, n) points, default switch 2^14", "reps": reps,
+            "statistic": "median of alternating runs, ms; loop = open_batch_fold 2, fold = open_batch_fold 1, same process",
+            "rows": rows, "held_back_n": [1 << lg for lg in held_back],
+            "held_back_reason": "sizes named with --held-back: the library keeps them on the loop by default whatever their rows say "
+            "(pcdl_batch.hip open_fold_route); the hook open_batch_fold = 1 reaches the folded schedule",
+            "equal": "accumulators, statuses and final RNG states: loop == folded schedule for every row"}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fold", action="store_true", help="only the folded schedule against the loop at n = 2^15 .. 2^19, k = 8 and 64")
+    ap.add_argument("--lgs", default="15,16,17,18,19", help="with --fold: log2 of the sizes")
+    ap.add_argument("--held-back", default="15", help="with --fold: log2 of the sizes the library holds back from its default route (empty: none)")
+    ap.add_argument("--fold-ks", default="8,64", help="with --fold: the members per call (from 2^18 on: 8 only)")
+    ap.add_argument("--out", default=None, help="with --fold: also write the JSON line to this file")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--sizes", default=",".join(map(str, SIZES)))
     ap.add_argument("--ks", default="10,100,1000")
@@ -105,6 +158,14 @@ def main():
     ap.add_argument("--sweep", type=int, default=1, help="members-per-launch sweep at k = 100 (0: off)")
     ap.add_argument("--big", action="store_true", help="add the 2^20-point leg (k = 4)")
     a = ap.parse_args()
+    if a.fold:
+        line = json.dumps(fold_leg(a.reps, [int(x) for x in a.lgs.split(",")], [int(x) for x in a.fold_ks.split(",")], [8],
+                                   [int(x) for x in a.held_back.split(",") if x]))
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        print(line)
+        return
     ks = [int(x) for x in a.ks.split(",")]
     cks = [int(x) for x in a.chains.split(",") if x]
     ctx = h._lib.Context(urs_n=1 << 14)
