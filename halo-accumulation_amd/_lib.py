@@ -189,6 +189,7 @@ _DEV_SIGS = {
     "halo_dev_fold_points": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_int, u64p, C.c_int, C.c_int, u64p]),
     "halo_dev_fold_points_batch": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_int, u64p, C.c_int, C.c_int, C.c_int, u64p]),
     "halo_dev_msm_offsets": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.c_size_t, u64p, C.c_int, C.c_int, u64p]),
+    "halo_dev_msm_tagged": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, u64p, u64p]),
     "halo_dev_sqrt_tables": (C.c_int, [u32p, C.c_size_t]),
     "halo_dev_table_read": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, u64p]),
     "halo_dev_msm_last_plan": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_long)]),
@@ -643,6 +644,14 @@ class Context:
         co = (C.c_size_t * len(offs))(*[int(o) for o in offs])
         out = np.zeros((len(offs), 12), dtype=np.uint64)
         check(self.lib.halo_dev_msm_offsets(self.h, co, int(n), ptr(scalars), len(offs), int(bool(mont)), ptr(out)))
+        return out
+
+    def msm_tagged(self, scalars, off=0):
+        """halo_dev_msm_tagged: ONE tagged launch over the key's points [off, off + len(scalars)): scalars = n x 4 canonical words,
+        bit 255 of scalar i names its bucket set -> 2 x 12 Jacobian words (normalised), the sum of each set"""
+        scalars = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        out = np.zeros((2, 12), dtype=np.uint64)
+        check(self.lib.halo_dev_msm_tagged(self.h, int(off), scalars.shape[0], ptr(scalars), ptr(out)))
         return out
 
     def table_read(self, row, off=0, n=None):

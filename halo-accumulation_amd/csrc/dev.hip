@@ -770,6 +770,39 @@ int halo_dev_msm_offsets(halo_ctx *ctx, const size_t *offs, size_t n, const uint
     return rc;
 }
 
+// One tagged launch (MsmBatch::tagged) over a stretch of the context's key, on slot 0 (include/halo_accumulation_dev.h): the two
+// outputs are finished as ipa_state.hip finishes L and R of a batched round (msm_wait for two, msm_combine_member 0 and 1).  The
+// scalars go to a device buffer of this call only, with no word to alloc_epoch: a launch graph is keyed on the scalar pointer and
+// replays only while that very address holds this call's scalars again, so the second and third call of a test capture and replay
+// whenever the allocator hands the same block back (and run as plain launches, with the same results, when it does not).
+int halo_dev_msm_tagged(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars, uint64_t *out_jac) {
+    HALO_CTX(ctx);
+    if (!out_jac || (n && !scalars)) { set_error("dev_msm_tagged: null pointer"); return HALO_E_ARG; }
+    if (off > ctx->n || n > ctx->n - off) { set_error("dev_msm_tagged: range exceeds the context's key"); return HALO_E_ARG; }
+    if (ctx->wss[0].in_flight || ctx->wss[0].lent_from >= 0 || ctx->fan[0].active) { set_error("dev_msm_tagged: slot 0 has an MSM in flight"); return HALO_E_ARG; }
+    host::Point pts[2] = {host::Point::infinity(), host::Point::infinity()};
+    if (n == 0) {  // (nothing to launch: msm_tagged_ready takes no empty stretch)
+        for (int b = 0; b < 2; ++b) pts[b].store_normalized(out_jac + 12 * b);
+        return HALO_OK;
+    }
+    uint64_t *d_sc = nullptr;
+    HALO_HIP(hipMalloc(&d_sc, n * 32));
+    int rc = HALO_OK;
+    hipError_t e = hipMemcpy(d_sc, scalars, n * 32, hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    MsmBatch both;
+    both.count = 1;
+    both.scalars[0] = d_sc;
+    both.tagged = true;
+    if (!rc) rc = msm_enqueue_batch(ctx, 0, ctx->d_bases + (size_t)AFF_STRIDE * off, both, /*mont*/ false, n);
+    if (!rc) rc = msm_wait(ctx, 0, 2);
+    for (int b = 0; b < 2 && !rc; ++b) msm_combine_member(ctx, 0, b, &pts[b]);
+    (void)hipStreamSynchronize(ctx->streams[0]);  // (also on failure: nothing of this call may be in flight when its buffer goes)
+    (void)hipFree(d_sc);
+    for (int b = 0; b < 2 && !rc; ++b) pts[b].store_normalized(out_jac + 12 * b);
+    return rc;
+}
+
 // Entries [off, off + count) of row `row` of the context's MSM table as arkworks affine words (include/halo_accumulation_dev.h): the
 // conversion is halo_ctx_read_bases' (k_native_to_aff), the device buffer is this call's only.  Nothing may be in flight: a launch
 // enqueued with every slot idle may release or rebuild the table (table_demote), and its slot's stream is not the one waited for here.

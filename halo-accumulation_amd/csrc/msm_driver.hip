@@ -200,9 +200,11 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
             if (rc) return rc;
         }
         if (members.tagged) {  // two sets of 2^19 buckets: per-bucket arrays of 2^20, a task per non-empty bucket and per kmax entries beyond
+            // (at the task length the piece itself takes, tmsm_kmax: 16 or 32 for a stretch of few entries -- sized for 64, a tagged
+            // launch over a short stretch was refused by tmsm_enqueue_piece: its overflow region is up to four times as long)
             const TblPlan tp = ctx->tbl;
-            size_t counts = 2 * (size_t)tp.B, kmax = ctx->task_len > 0 ? (size_t)ctx->task_len : KMAX;
-            size_t tasks = counts + (size_t)tp.W * n / kmax + 256;
+            size_t counts = 2 * (size_t)tp.B;
+            size_t tasks = tmsm_order_records(ctx, (size_t)tp.W * n, counts);
             if (counts > ws.cap_counts || tasks > ws.cap_tasks) {
                 need.n = ws.cap_n; need.sorted = ws.cap_sorted; need.hist = ws.cap_hist; need.windows = ws.cap_windows;
                 need.counts = counts > ws.cap_counts ? counts : ws.cap_counts;

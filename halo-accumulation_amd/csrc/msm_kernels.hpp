@@ -85,6 +85,7 @@ int msm_general_prepare();                                              // msm_g
 int table_build(halo_ctx *ctx);                                         // msm_table.hip
 bool table_eligible(const halo_ctx *ctx, const uint32_t *d_bases, const MsmBatch &members, size_t n);
 int tmsm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MsmBatch &members, bool mont, size_t n, int partner);
+size_t tmsm_order_records(const halo_ctx *ctx, size_t entries, size_t buckets);  // records of d_order for one piece: overflow region + buckets
 int msm_table_prepare();
 
 }  // namespace halo

@@ -832,6 +832,9 @@ static uint32_t tmsm_kmax(const halo_ctx *ctx, size_t entries) {
 // records in front of the static layout of `order`: one per kmax entries at most (the bound of the tasks beyond one per
 // bucket), rounded so that the blocks of the bucket kernel line up with the static layout
 static size_t tmsm_ovf_records(size_t entries, uint32_t kmax) { return (entries / kmax + 1 + 255) / 256 * 256; }
+// records of `order` a piece of `entries` digits over `buckets` buckets takes (tmsm_enqueue_piece: overflow region + one per bucket):
+// what the slot's cap_tasks has to hold, at the task length the piece will run with
+size_t tmsm_order_records(const halo_ctx *ctx, size_t entries, size_t buckets) { return tmsm_ovf_records(entries, tmsm_kmax(ctx, entries)) + buckets; }
 // What a piece of `entries` digits takes for its bucket kernel and -- without the row / column sums -- for k_msm_reduce1 over virtual
 // windows of 2^vw_bits buckets: computed here for the piece that launches and for the plan that reports it (MsmPlan, one place each).
 struct TblWinsum { uint32_t kmax, L, nseg; int logL; };

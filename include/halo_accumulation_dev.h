@@ -189,6 +189,16 @@ int halo_dev_fold_points_batch(halo_ctx *ctx, const uint64_t *key_affine /*NULL:
 int halo_dev_msm_offsets(halo_ctx *ctx, const size_t *offs /*count entries, points*/, size_t n, const uint64_t *scalars /*host, count x n x 4*/,
                          int count /*1..8*/, int scalars_are_mont, uint64_t *out_jac /*count x 12*/);
 
+/* One tagged launch (MsmBatch::tagged: the L and R of an open's first rounds over 2^20 points) over the key's points [off, off + n),
+ * on slot 0, with scalars of the caller's choice: scalars = n x 4 canonical words whose bit 255 names the bucket set of point i, so
+ * out_jac[12 t ..] = sum over the i with tag t of (scalars[i] mod 2^255) * G[off + i], t = 0, 1 -- what halo_msm gives for the
+ * scalars of that tag with zeros elsewhere, limb for limb (normalised).  n = 0 gives two infinities.  The launch is the product's
+ * msm_enqueue_batch with its own refusals and messages (no table yet -- the first table MSM builds it --, table mode 0, a forced
+ * window size, the small-key plan, n no multiple of 4 or below the least table stretch).  HALO_E_ARG also: a null pointer, a
+ * range that leaves the key, slot 0 busy. */
+int halo_dev_msm_tagged(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars /*host, n x 4, canonical, bit 255 = set*/,
+                        uint64_t *out_jac /*2 x 12*/);
+
 /* Entries [off, off + count) of row `row` of the context's MSM table (csrc/msm_table.hip: T[w][i] = 2^(c w) G_i for the 13 and 15
  * rows, T[j][i] = 2^j G_i for the 255) as arkworks affine words, count x 8, Montgomery form, (0, 0) = infinity: what
  * halo_ctx_read_bases gives for the key, through the same conversion.  It reads and waits for the context's stream; it builds
