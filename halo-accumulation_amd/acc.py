@@ -165,3 +165,9 @@ def decider_batch_combined(ctx, d, accs, seed=None):
     """decider_batch with ONE MSM for all accepted members (halo_acc_decider_batch_combined; seed: 32 bytes or None) -> status
     list; statuses and HaloReject as decider_batch whenever a member is bad"""
     return _check_batch(ctx, lambda h, dd, qs, m, st: ctx.lib.halo_acc_decider_batch_combined(h, dd, qs, m, _seed32(seed), st), d, accs)
+
+
+def decider_batch_fused(ctx, d, accs, seed=None):
+    """decider_batch as ONE relation, the succinct relations included (halo_acc_decider_batch_fused; seed: 32 bytes or None) ->
+    status list; statuses and HaloReject as decider_batch whenever a member is bad"""
+    return _check_batch(ctx, lambda h, dd, qs, m, st: ctx.lib.halo_acc_decider_batch_fused(h, dd, qs, m, _seed32(seed), st), d, accs)

@@ -14,8 +14,9 @@ import sys
 
 # Kernels the gate must have SEEN: one whose remarks are missing (renamed, compiled out, its translation unit dropped from the
 # list) would pass a gate that only looks at what it finds.  k_fr_sum_rows: the combined check batch's row sum, enqueued on a
-# slot's stream between launch sequences that replay as graphs.
-REQUIRED = ("k_fr_sum_rows",)
+# slot's stream between launch sequences that replay as graphs.  k_fused_terms: the fused check batch's term scalars, likewise -- a
+# lane of ~400 dependent products that must keep its working set in registers.
+REQUIRED = ("k_fr_sum_rows", "k_fused_terms")
 
 
 def parse(path):

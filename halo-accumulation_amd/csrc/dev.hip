@@ -229,6 +229,10 @@ int halo_dev_hook(const char *name, long value) {
         if (value < 0 || value > 2) { set_error("dev_hook: check_combined_usum is 0 (by the member count), 1 (the host pool) or 2 (the device)"); return HALO_E_ARG; }
         h.combined_usum = (int)value;
     }
+    else if (!std::strcmp(name, "check_fused_chunk")) {
+        if (value != 0 && value < 8) { set_error("dev_hook: check_fused_chunk is 0 (the context's capacity) or at least 8 terms"); return HALO_E_ARG; }
+        h.fused_chunk = value > (1 << 30) ? (1 << 30) : (int)value;
+    }
     else if (!std::strcmp(name, "verifier_batch_min")) h.verifier_min = (int)value;
     else if (!std::strcmp(name, "decode_batch_min")) h.decode_min = value;
     else if (!std::strcmp(name, "table_slide_min")) h.slide_min = value > 0 && value < 4096 ? 4096 : value;
@@ -244,7 +248,7 @@ int halo_dev_hook(const char *name, long value) {
         h.poly_blocks = (int)value;
     }
     else if (!std::strcmp(name, "reset")) h = DevHooks();
-    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, open_batch_fold, commit_batch_group, check_combined_parts, check_combined_cap, check_combined_usum, verifier_batch_min, decode_batch_min, table_slide_min, pow_e, dot_blocks, poly_blocks, reset)"); return HALO_E_ARG; }
+    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, open_batch_fold, commit_batch_group, check_combined_parts, check_combined_cap, check_combined_usum, check_fused_chunk, verifier_batch_min, decode_batch_min, table_slide_min, pow_e, dot_blocks, poly_blocks, reset)"); return HALO_E_ARG; }
     return HALO_OK;
 }
 
@@ -374,6 +378,41 @@ int halo_dev_check_combined_scalars(halo_ctx *ctx, const uint64_t *xis, const ui
     hipError_t e = hipStreamSynchronize(ctx->stream);  // (also on failure: nothing of this call may be in flight when its buffer goes)
     if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
     if (!rc && (e = hipMemcpy(out, d + hcomb_rows_offset(A, lg_n, P, cap), n * 32, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d);
+    return rc;
+}
+
+// host only: the 2 A weights r_0, s_0, r_1, s_1, .. of the fused check batch as the product computes them (tests/test_check_fused_cpu.py
+// restates the rule)
+int halo_dev_check_fused_weights(const uint64_t *blobs, size_t stride_words, const size_t *idx, size_t A, size_t d, const uint8_t seed[32], uint64_t *out) {
+    if (A == 0) return HALO_OK;
+    if (!blobs || !idx || !out) { set_error("check_fused_weights: null pointer"); return HALO_E_ARG; }
+    if (!is_pow2(d + 1) || stride_words < instance_words(ilog2(d + 1))) { set_error("check_fused_weights: d + 1 is a power of two, the stride at least an Instance"); return HALO_E_ARG; }
+    std::vector<host::Fr> w;
+    check_fused_weights(blobs, stride_words, idx, A, d, seed, w);
+    for (size_t k = 0; k < 2 * A; ++k) w[k].store(out + 4 * k);
+    return HALO_OK;
+}
+
+// the fused check's term kernel on its own (tests/test_gpu_check_fused.py holds it against Python integers): M records of
+// lg_n + 6 Montgomery elements (xi_0 .. xi_lg | z | v | c | r | s) -> M x (2 lg_n + 2) canonical scalars and H's scalar; temporary
+// device buffers of this call only
+int halo_dev_check_fused_terms(halo_ctx *ctx, const uint64_t *recs, size_t M, size_t lg_n, uint64_t *scalars_out, uint64_t h_out[4]) {
+    HALO_CTX(ctx);
+    if (!recs || !scalars_out || !h_out) { set_error("check_fused_terms: null pointer"); return HALO_E_ARG; }
+    if (M < 1 || M > 65535) { set_error("check_fused_terms: 1..65535 members"); return HALO_E_ARG; }
+    if (lg_n < 1 || lg_n > 24) { set_error("check_fused_terms: lg n must be in 1..24"); return HALO_E_ARG; }
+    const size_t rw = (lg_n + 6) * 4, K = 2 * lg_n + 2;
+    uint64_t *d = nullptr;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d, (M * (rw + 4 + K * 4) + 4) * 8));
+    uint64_t *d_recs = d, *d_shares = d + M * rw, *d_sc = d_shares + M * 4, *d_h = d_sc + M * K * 4;
+    hipError_t e = hipMemcpy(d_recs, recs, M * rw * 8, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? fused_terms(ctx, d_recs, M, lg_n, d_sc, d_shares, d_h) : hip_fail(e, "hipMemcpy");
+    e = hipStreamSynchronize(ctx->stream);  // (also on failure: nothing of this call may be in flight when its buffer goes)
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    if (!rc && (e = hipMemcpy(scalars_out, d_sc, M * K * 32, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (!rc && (e = hipMemcpy(h_out, d_h, 32, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d);
     return rc;
 }

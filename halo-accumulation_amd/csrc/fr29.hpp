@@ -202,6 +202,57 @@ HALO_DEV Fs<1> fs_c266() {
     for (int i = 0; i < 9; i++) r.v[i] = C[i];
     return r;
 }
+// a - b + Kc r, Kc >= the bound of b (int32 limb sums: Kc L[i] + a.v[i] stays below 2^31 for Kc <= 2)
+template <int Kc, int Ka, int Kb>
+HALO_DEV Fs<Ka + Kc> fs_sub(const Fs<Ka> &a, const Fs<Kb> &b) {
+    static_assert(Kb <= Kc, "subtrahend may exceed the added multiple of r");
+    static_assert(Kc <= 2, "Kc L[i] + a.v[i] must fit an int32 limb sum");
+    static_assert(Ka + Kc <= 60, "value bound");
+    int32_t t[9];
+#pragma unroll
+    for (int i = 0; i < 9; i++) t[i] = (int32_t)a.v[i] - (int32_t)b.v[i] + Kc * (int32_t)R29::L[i];
+    Fs<Ka + Kc> r;
+    carry_pass(t, r.v);
+    return r;
+}
+// N(1) = 2^261 mod r: the one of the N-form (N(a) * N(b) = N(a b)); A(x) * fs_c266() = N(x), N(x) * fs_unit() = x itself
+HALO_DEV Fs<1> fs_n_one() {
+    constexpr uint32_t C[9] = {0x1fffff81, 0x68ad507, 0x100e85da, 0x1435ee7e, 0x1ffeefef, 0x1fffffff, 0x1fffffff, 0x1fffffff, 0x3fffff};
+    Fs<1> r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.v[i] = C[i];
+    return r;
+}
+HALO_DEV Fs<1> fs_unit() {
+    Fs<1> r = fs_zero<1>();
+    r.v[0] = 1;
+    return r;
+}
+
+// ---- the inverse: N(x) -> N(x^-1) = N(x)^(r - 2) in N-form products, the device's one Fr inversion (fused_lane.hpp: ONE per
+// lane, shared by Montgomery's trick).  A fixed chain for the constant r - 2: its 255 bits from the top, a square per bit and a
+// product with x at each of the 74 set bits -- 254 squares and 73 products whatever x is (no data-dependent trip count, as
+// decompress.hpp's square root); the exponent's words are literals of the unrolled outer loop, so nothing is indexed at run time.
+// x = 0 (any multiple of r) gives a multiple of r: 0.  Bounds: every product is fs_mul<2, 2> or fs_mul<2, K> (asserted there:
+// 2 K <= 120), every result an Fs<2>.
+template <int K>
+HALO_DEV Fs<2> fs_inv(const Fs<K> &x) {
+    static_assert(K <= 60, "fs_inv: the products x * acc need 2 K <= 120");
+    constexpr uint32_t E[8] = {0xffffffffu, 0x8c46eb20u, 0x0994a8ddu, 0x224698fcu, 0u, 0u, 0u, 0x40000000u};  // r - 2
+    static_assert(E[7] >> 30 == 1, "the chain starts at bit 254, the exponent's top bit");
+    Fs<2> acc = fs_mul(x, fs_n_one());  // bit 254: x itself, below 2 r
+#pragma unroll
+    for (int w = 7; w >= 0; w--) {
+        const uint32_t word = E[w];
+#pragma unroll 1
+        for (int bit = w == 7 ? 29 : 31; bit >= 0; bit--) {
+            acc = fs_mul(acc, acc);
+            if ((word >> bit) & 1u) acc = fs_mul(acc, x);  // (uniform: a bit of the constant)
+        }
+    }
+    return acc;
+}
+
 template <int K>
 HALO_DEV Fs<K> fs_shfl(const Fs<K> &a, int src_lane) {
     Fs<K> r;

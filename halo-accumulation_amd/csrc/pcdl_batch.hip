@@ -5,6 +5,7 @@
 // internal.hpp: idle_slots, StreamGuard, report_members.
 #include "curve.hpp"  // (AFF_STRIDE: the staged keys of the folded schedule)
 #include "fr_plan.hpp"
+#include "fused_lane.hpp"  // (the record and term layout of the fused check)
 #include "pcdl_internal.hpp"
 
 namespace halo {
@@ -42,14 +43,25 @@ size_t check_stage(halo_ctx *ctx, size_t want, size_t per_bytes) {
 
 // ------------------------------------------------------------------ the weights and the launch shape of the combined check
 // (pcdl_internal.hpp: the development library calls these too)
+// out[k] = SHA3-256(D || LE64(k)) mod r for k < count, D the digest of domain, seed, d, A and the members' indices and Instance words
+static void hashed_weights(const char *domain, size_t domain_len, const uint64_t *blobs, size_t stride, const size_t *idx, size_t A, size_t d,
+                           const uint8_t *seed, size_t count, std::vector<Fr> &out);
 void check_combined_weights(const uint64_t *blobs, size_t stride, const size_t *idx, size_t A, size_t d, const uint8_t *seed, std::vector<Fr> &out) {
     static const char kDomain[] = "halo-accumulation/check-batch-combined/v1";
+    hashed_weights(kDomain, sizeof(kDomain) - 1, blobs, stride, idx, A, d, seed, A, out);
+}
+void check_fused_weights(const uint64_t *blobs, size_t stride, const size_t *idx, size_t A, size_t d, const uint8_t *seed, std::vector<Fr> &out) {
+    static const char kDomain[] = "halo-accumulation/check-batch-fused/v1";
+    hashed_weights(kDomain, sizeof(kDomain) - 1, blobs, stride, idx, A, d, seed, 2 * A, out);  // r_a = out[2 a], s_a = out[2 a + 1]
+}
+static void hashed_weights(const char *domain, size_t domain_len, const uint64_t *blobs, size_t stride, const size_t *idx, size_t A, size_t d,
+                           const uint8_t *seed, size_t count, std::vector<Fr> &out) {
     static const uint8_t kZeros[32] = {};
     const size_t W = instance_words(ilog2(d + 1));
     const uint64_t d64 = d, A64 = A;
     uint8_t D[32];
     host::Sha3_256 h;
-    h.update(kDomain, sizeof(kDomain) - 1);
+    h.update(domain, domain_len);
     h.update(seed ? seed : kZeros, 32);
     h.update(&d64, 8);  // (the words of a blob are little-endian in memory on every host this library builds for)
     h.update(&A64, 8);
@@ -59,8 +71,8 @@ void check_combined_weights(const uint64_t *blobs, size_t stride, const size_t *
         h.update(blobs + idx[a] * stride, W * 8);
     }
     h.finalize(D);
-    out.resize(A);
-    for (size_t a = 0; a < A; ++a) {
+    out.resize(count);
+    for (size_t a = 0; a < count; ++a) {
         const uint64_t a64 = a;
         uint8_t dig[32];
         host::Sha3_256 g;
@@ -303,14 +315,159 @@ static int check_members_combined(halo_ctx *ctx, size_t d, const uint64_t *qs, s
     return HALO_OK;
 }
 
+// ------------------------------------------------------------------ ... and BOTH halves as one relation (halo_pcdl_check_batch_fused)
+// pcdl.rs:307-310 is as linear in the proof's points as :339.  With E_a = C'_a + sum_j (xi_(j+1)^-1 L_j + xi_(j+1) R_j) +
+// (v_a - c_a h_a(z_a)) xi_0 H - c_a U_a (relation_terms' form) and F_a = U_a - <h_a, G>, the M >= 2 members whose transcripts
+// held are checked as  sum_a r_a E_a + sum_a s_a F_a = 0  with the 2 M weights of check_fused_weights:
+//   right side  <sum_a s_a h_a, G>: h_combine_rows with the weights s_a and ONE n-point MSM over the key on the first idle slot,
+//               exactly the combined check's left side;
+//   left side   T = M (2 lg n + 2) + 1 terms over the CALLER's points: each member's C' | L_j | R_j | U, then H.  Their scalars
+//               come from k_fused_terms (fused_check.hip: one lane per member, H's scalar summed on the device), their points go
+//               from Jacobian words to native entries with batch_to_affine (infinity and Z != 1 included).  The workspaces are
+//               sized by the key, so the terms are cut into chunks of at most ctx_capacity points (the hook "check_fused_chunk":
+//               fewer), the last one filled up with zero scalars on points at infinity; up to MSM_MAX_BATCH chunks are the members of
+//               one batched launch sequence (MsmBatch::base_off: a chunk's own points), the sequences run one after the other
+//               on the second idle slot while the key's MSM runs on the first -- with one idle slot, after it -- and the
+//               chunks' sums are added on the host in chunk order.
+// *held = both sides are the same point.  If not -- or without the optional staging -- the caller runs the exact batch.
+static size_t fused_chunk_points(const halo_ctx *ctx, size_t T) {
+    size_t C = ctx_capacity(ctx);
+    const int forced = dev_hooks().fused_chunk;
+    if (forced >= 8 && (size_t)forced < C) C = (size_t)forced;
+    return C > T ? T : C;
+}
+static int check_members_fused(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t stride, const uint8_t *seed, const int *slots, int S,
+                               const std::vector<BatchCheck> &res, const std::vector<size_t> &ok, bool *held) {
+    const size_t n = d + 1, lg = ilog2(n), M = ok.size(), tw = (lg + 2) * 4;
+    *held = false;
+    if (lg > 24) { set_error("h_coeffs: lg_n > 24 unsupported"); return HALO_E_ARG; }
+    if (M > 65535) return HALO_OK;  // (h_combine_rows takes at most 65535 polynomials: the exact batch)
+    const size_t K = fused_term_count((int)lg), T = M * K + 1, rw = fused_rec_words((int)lg);
+    const size_t C = fused_chunk_points(ctx, T), chunks = (T + C - 1) / C, Tp = chunks * C;
+    if (Tp >= ((size_t)1 << 32)) return HALO_OK;  // (MsmBatch::base_off is 32 bits wide)
+    // the staging (words): records | shares | scalars Tp x 4 | Jacobian words Tp x 12 | native entries (128-byte aligned) | the right side's regions
+    const size_t o_rec = 0, o_share = o_rec + M * rw, o_sc = o_share + M * 4, o_jac = o_sc + Tp * 4;
+    const size_t o_nat = (o_jac + Tp * 12 + 15) & ~(size_t)15, o_h = o_nat + Tp * (AFF_STRIDE / 2);
+    const size_t cap = check_combined_cap(M);
+    size_t P = check_combined_parts(n, M);
+    for (;; P = (P + 1) / 2) {  // (fewer parts if the staging cannot hold their rows)
+        if (check_stage(ctx, 1, (o_h + hcomb_stage_words(M, lg, P, cap)) * 8) >= 1) break;
+        if (P == 1) return HALO_OK;
+    }
+    uint64_t *d_stage = ctx->d_check_stage;
+    std::vector<Fr> w;
+    check_fused_weights(qs, stride, ok.data(), M, d, seed, w);
+    // the right side: sum_a s_a h_a(X) over the key, asynchronous
+    {
+        std::vector<uint64_t> recs(M * tw);
+        for (size_t a = 0; a < M; ++a) {
+            for (size_t k = 0; k <= lg; ++k) res[ok[a]].st.xis[k].store(&recs[a * tw + 4 * k]);
+            w[2 * a + 1].store(&recs[a * tw + 4 * (lg + 1)]);
+        }
+        int rc;
+        {
+            StreamGuard on_slot(ctx, ctx->streams[slots[0]]);
+            rc = h_combine_rows(ctx, recs.data(), M, lg, P, cap, d_stage + o_h);
+        }
+        if (!rc) rc = msm_enqueue_batch(ctx, slots[0], ctx->d_bases, msm_one(d_stage + o_h + hcomb_rows_offset(M, lg, P, cap)), true, n);
+        if (rc) return rc;
+    }
+    Point right, left = Point::infinity();
+    bool right_done = false;
+    auto finish_right = [&]() { right_done = true; return msm_finish_batch(ctx, slots[0], &right, 1); };
+    int rc = HALO_OK;
+    if (S < 2) rc = finish_right();  // (one idle slot: the left side runs on it afterwards)
+    const int lslot = S < 2 ? slots[0] : slots[1];
+    // the left side's records and points
+    std::vector<uint64_t> recs(M * rw), jac(Tp * 12);
+    if (!rc) {
+        pool_run(M, [&](size_t a) {
+            const uint64_t *q = qs + ok[a] * stride, *proof = q + 21;
+            const SuccinctState &st = res[ok[a]].st;
+            uint64_t *r = &recs[a * rw], *p = &jac[a * K * 12];
+            for (size_t k = 0; k <= lg; ++k) st.xis[k].store(r + 4 * k);
+            std::memcpy(r + 4 * (lg + 1), q + 13, 64);                                          // z | v
+            std::memcpy(r + 4 * (lg + 3), pf_c(const_cast<uint64_t *>(proof), lg), 32);         // c
+            w[2 * a].store(r + 4 * (lg + 4));
+            w[2 * a + 1].store(r + 4 * (lg + 5));
+            st.C_prime.store(p);
+            std::memcpy(p + 12, pf_L(const_cast<uint64_t *>(proof), 0), lg * 96);               // L_0 .. (the blob's own words)
+            std::memcpy(p + 12 * (lg + 1), pf_R(const_cast<uint64_t *>(proof), lg, 0), lg * 96);  // R_0 ..
+            std::memcpy(p + 12 * (2 * lg + 1), pf_U(const_cast<uint64_t *>(proof), lg), 96);
+        });
+        static const Point kH = public_h_table().mul(Fr::one());
+        kH.store(&jac[(T - 1) * 12]);
+        for (size_t t = T; t < Tp; ++t) Point::infinity().store(&jac[t * 12]);
+        hipError_t e = hipMemcpy(d_stage + o_rec, recs.data(), recs.size() * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_stage + o_jac, jac.data(), jac.size() * 8, hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    }
+    if (!rc) {
+        StreamGuard on_slot(ctx, ctx->streams[lslot]);
+        rc = fused_terms(ctx, d_stage + o_rec, M, lg, d_stage + o_sc, d_stage + o_share, d_stage + o_sc + (T - 1) * 4);
+        if (!rc && Tp > T) {
+            hipError_t e = hipMemsetAsync(d_stage + o_sc + T * 4, 0, (Tp - T) * 32, ctx->stream);
+            if (e != hipSuccess) rc = hip_fail(e, "hipMemsetAsync");
+        }
+        if (!rc) rc = batch_to_affine(ctx, d_stage + o_jac, Tp, reinterpret_cast<uint32_t *>(d_stage + o_nat));
+    }
+    if (!rc) {
+        const size_t G = (size_t)group_size(ctx, C, 0, MSM_MAX_BATCH, 1);
+        rc = rotate_groups(
+            ctx, &lslot, 1, chunks, G < chunks ? G : chunks,
+            [&](size_t, size_t first, size_t cnt) -> int {
+                MsmBatch mb;
+                mb.count = (int)cnt;
+                for (size_t b = 0; b < cnt; ++b) {
+                    mb.scalars[b] = d_stage + o_sc + (first + b) * C * 4;
+                    mb.base_off[b] = (uint32_t)((first + b) * C);
+                }
+                return msm_enqueue_batch(ctx, lslot, reinterpret_cast<const uint32_t *>(d_stage + o_nat), mb, false, C);
+            },
+            [&](size_t, size_t cnt, const Point *pts) {
+                for (size_t b = 0; b < cnt; ++b) left = left + pts[b];
+            });
+    }
+    const std::string err = rc ? halo_last_error() : "";
+    if (!right_done) {  // (collected whatever happened to the left side: nothing stays in flight)
+        int rc_r = finish_right();
+        if (!rc) rc = rc_r;
+        else set_error(err);
+    }
+    if (rc) return rc;
+    *held = left == right;
+    return HALO_OK;
+}
+
 // blobs: m Instances (or Accumulators, whose Instance prefix is checked) at `stride` words, all of degree bound d (checked by
 // the caller); status[i] (nullable) = what halo_pcdl_check returns for member i alone
-// seed: the combined call's 32 bytes (or null); combined = false: the exact batch
-static int pcdl_check_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t stride, size_t m, int *status, bool combined = false,
+// seed: the combined / fused call's 32 bytes (or null)
+enum class CheckMode { exact, combined, fused };
+static int pcdl_check_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t stride, size_t m, int *status, CheckMode mode = CheckMode::exact,
                                  const uint8_t *seed = nullptr) {
     const size_t n = d + 1;
+    const bool combined = mode == CheckMode::combined;
     int slots[HALO_SLOTS], S = idle_slots(ctx, slots);
     if (!S) { set_error("check_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
+    if (mode == CheckMode::fused && m >= 2 && n >= 2) {  // (one member, or a constant: the exact path below)
+        // the transcripts alone, as succinct_challenges runs them (no relation: that is the fused relation's left side)
+        std::vector<BatchCheck> tr(m);
+        pool_run(m, [&](size_t i) {
+            const uint64_t *q = qs + i * stride;
+            tr[i].rc = succinct_challenges(ctx, Point::load(q), (size_t)q[12], Fr::load(q + 13), Fr::load(q + 17), q + 21, &tr[i].st, false);
+            if (tr[i].rc) tr[i].err = halo_last_error();
+        });
+        std::vector<size_t> acc;
+        for (size_t i = 0; i < m; ++i)
+            if (!tr[i].rc) acc.push_back(i);
+        bool fused_held = false;
+        if (acc.size() >= 2) {
+            int rc = check_members_fused(ctx, d, qs, stride, seed, slots, S, tr, acc, &fused_held);
+            if (rc) return rc;
+        }
+        if (fused_held) return report_members("instance", m, [&](size_t i) { return tr[i].rc; }, [&](size_t i) { return tr[i].err; }, status, [](size_t) {});
+        // the relation failed, or did not run: the exact batch decides, so a reject never depends on the weights
+    }
     // 1. the succinct half (pcdl.rs:333)
     std::vector<BatchCheck> res;
     int rc = succinct_half(ctx, d, [&](size_t i) { return qs + i * stride; }, m, res);
@@ -330,7 +487,7 @@ static int pcdl_check_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, si
     return report_members("instance", m, [&](size_t i) { return res[i].rc; }, [&](size_t i) { return res[i].err; }, status, [](size_t) {});
 }
 // the argument checks of both entry points (halo_pcdl_succinct_check_batch's), then the batch; acc: Accumulator blobs
-static int check_batch_entry(halo_ctx *ctx, size_t d, const uint64_t *blobs, size_t m, int *status, bool acc, bool combined = false,
+static int check_batch_entry(halo_ctx *ctx, size_t d, const uint64_t *blobs, size_t m, int *status, bool acc, CheckMode mode = CheckMode::exact,
                              const uint8_t *seed = nullptr) {
     if (m && !blobs) { set_error("check_batch: null pointer"); return HALO_E_ARG; }
     if (!is_pow2(d + 1)) return fail_reject("d+1 is not a power of 2!");
@@ -338,7 +495,7 @@ static int check_batch_entry(halo_ctx *ctx, size_t d, const uint64_t *blobs, siz
     for (size_t i = 0; i < m; ++i)
         if ((size_t)(blobs + i * stride)[12] != d || (blobs + i * stride)[22] != lg) return fail_reject("d_i != d");
     if (m == 0) return HALO_OK;
-    return pcdl_check_batch_host(ctx, d, blobs, stride, m, status, combined, seed);
+    return pcdl_check_batch_host(ctx, d, blobs, stride, m, status, mode, seed);
 }
 
 // ------------------------------------------------------------------ pcdl::commit of m polynomials at once
@@ -1401,7 +1558,14 @@ int halo_pcdl_check_batch(halo_ctx *ctx, size_t d, const uint64_t *instances, si
 // ... as one combined relation over the accepted members (see check_members_combined; the contract: include/halo_accumulation.h)
 int halo_pcdl_check_batch_combined(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, const uint8_t seed[32], int *status) {
     HALO_CTX(ctx);
-    return check_batch_entry(ctx, d, instances, m, status, false, true, seed);
+    return check_batch_entry(ctx, d, instances, m, status, false, CheckMode::combined, seed);
+}
+
+// ... and with the succinct relations in it too: ONE relation for the whole batch (see check_members_fused; the contract:
+// include/halo_accumulation.h)
+int halo_pcdl_check_batch_fused(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, const uint8_t seed[32], int *status) {
+    HALO_CTX(ctx);
+    return check_batch_entry(ctx, d, instances, m, status, false, CheckMode::fused, seed);
 }
 
 // acc::prover of k members at once (see acc_prover_batch_dev).  The argument checks are the whole call's and come before any work.
@@ -1437,7 +1601,12 @@ int halo_acc_decider_batch(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t
 
 int halo_acc_decider_batch_combined(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, const uint8_t seed[32], int *status) {
     HALO_CTX(ctx);
-    return check_batch_entry(ctx, d, accs, m, status, true, true, seed);
+    return check_batch_entry(ctx, d, accs, m, status, true, CheckMode::combined, seed);
+}
+
+int halo_acc_decider_batch_fused(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, const uint8_t seed[32], int *status) {
+    HALO_CTX(ctx);
+    return check_batch_entry(ctx, d, accs, m, status, true, CheckMode::fused, seed);
 }
 
 // pcdl::open of m polynomials at once (see open_batch_dev)

@@ -86,6 +86,9 @@ void check_combined_weights(const uint64_t *blobs, size_t stride, const size_t *
 // parts and tables per pass of the scalar step for A polynomials of n coefficients (the hooks "check_combined_parts" / "_cap" first)
 size_t check_combined_parts(size_t n, size_t A);
 size_t check_combined_cap(size_t A);
+// ---- pcdl_batch.hip: the fused check batch (halo_pcdl_check_batch_fused): the 2 A weights r_0, s_0, r_1, s_1, .. of the accepted
+// members, arguments as check_combined_weights, under the rule's own domain string (include/halo_accumulation.h), Montgomery form
+void check_fused_weights(const uint64_t *blobs, size_t stride, const size_t *idx, size_t A, size_t d, const uint8_t *seed, std::vector<host::Fr> &out);
 
 // ---- pcdl_acc.hip: acc.rs
 struct AccHPolys {  // acc.rs:61-66

@@ -232,6 +232,13 @@ def check_batch_combined(ctx, d, instances, seed=None):
     return _check_batch(ctx, lambda h, dd, qs, m, st: ctx.lib.halo_pcdl_check_batch_combined(h, dd, qs, m, _seed32(seed), st), d, instances)
 
 
+def check_batch_fused(ctx, d, instances, seed=None):
+    """check_batch as ONE relation, the succinct relations included (halo_pcdl_check_batch_fused: one MSM over the members' own points
+    beside the one over the key, two hashed weights per member; seed: 32 bytes of the caller's randomness or None) -> status list;
+    statuses and HaloReject as check_batch whenever a member is bad"""
+    return _check_batch(ctx, lambda h, dd, qs, m, st: ctx.lib.halo_pcdl_check_batch_fused(h, dd, qs, m, _seed32(seed), st), d, instances)
+
+
 def check_partial(ctx, Cm, d, z, v, pi, stride, offset):
     """One rank's half of pcdl::check over a cyclically sharded key (halo_pcdl_check_partial): -> (U, this rank's share of
     CM.Commit(ck, h)).  The caller adds the shares in rank order and accepts iff the sum is U (sharded.ShardedOpen.check)."""

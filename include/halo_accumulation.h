@@ -279,6 +279,45 @@ int halo_pcdl_check_batch(halo_ctx *ctx, size_t d, const uint64_t *instances, si
  * At m = 10 on those keys it is NOT faster than halo_pcdl_check_batch (the runs' ranges overlap). */
 int halo_pcdl_check_batch_combined(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, const uint8_t seed[32] /*nullable*/,
                                    int *status /*nullable*/);
+/* The same m checks as ONE relation, the succinct half included: pcdl.rs:307-310 is as linear in the proof's points as :339.  For
+ * a member a whose transcript was accepted (xi_a,0 .. xi_a,lg and C'_a as halo_pcdl_succinct_check computes them; c_a, z_a, v_a, U_a,
+ * L_a,j, R_a,j from its blob; hz_a = h_a(z_a)) let
+ *   E_a = C'_a + sum_j (xi_a,j+1^-1 L_a,j + xi_a,j+1 R_a,j) + (v_a - c_a hz_a) xi_a,0 H - c_a U_a      (0 iff :307-310 accepts)
+ *   F_a = U_a - <h_a, G>                                                                               (0 iff :339 accepts)
+ * and check  sum_a r_a E_a + sum_a s_a F_a = 0  with two independent hashed weights per member, i.e.
+ *   sum_a [ r_a C'_a + sum_j (r_a xi_a,j+1^-1 L_a,j + r_a xi_a,j+1 R_a,j) + (s_a - r_a c_a) U_a ] + (sum_a r_a (v_a - c_a hz_a) xi_a,0) H
+ *       ==  < sum_a s_a h_a , G >.
+ * Left: one variable-base MSM over M (2 lg + 2) + 1 points of the caller's; right: the combined call's n-point MSM over the key.
+ * (With s_a tied to r_a a shifted U whose two defects are in ratio -c_a : 1 would cancel: hence two weights.)  The contract:
+ *  1. Layouts, whole-call errors (null ctx, null blobs, d + 1 not a power of two, d_i != d, m = 0, no idle slot), the
+ *     "instance i: ..." message and the return rule are halo_pcdl_check_batch's.
+ *  2. Every member's structure and transcript run exactly as in halo_pcdl_succinct_check, on the host pool: validity of every point
+ *     and scalar, d, the proof length, a zero challenge.  A member rejected there gets that status and takes no further part.
+ *  3. M = the number of members accepted so far.  M <= 1 or d = 0: the exact path of halo_pcdl_check_batch.  M >= 2 (at most 65535,
+ *     lg <= 24; beyond: the exact path): the relation above.  The term scalars are computed on the device, one lane per member, with
+ *     one field inversion each; the left side's terms are cut into MSMs of at most the key's size, which run on a second idle slot
+ *     beside the key's MSM (one idle slot: after it), their sums added in order.
+ *  4. If the relation HOLDS, every such member's status is 0.
+ *  5. If it FAILS, the exact batch decides: the per-member relations and per-member MSMs of halo_pcdl_check_batch.  So a reject
+ *     never depends on the weights, and whenever any member is bad, status[], the return code and the message equal
+ *     halo_pcdl_check_batch's on the same blobs.
+ *  6. The one difference from the exact batch: a set of blobs with some E_a != 0 or F_a != 0 is wrongly accepted with probability
+ *     1/r (r = the group order, ~2^-254) per hash evaluation an adversary spends.
+ *  7. All device memory the call takes is optional staging (halo_set_memory_budget): without it the exact path runs and gives the
+ *     same statuses.  A multi-device context runs the call on its own device (devices[0]); a caller's MSM in flight on another slot
+ *     is left alone.
+ * Weight rule (fused).  lg, W and seed32 as above.
+ *   D   = SHA3-256("halo-accumulation/check-batch-fused/v1" || seed32 || LE64(d) || LE64(M) || for every member taking part, in
+ *         member order: LE64(i) || its W Instance words as little-endian bytes)      (i = its index among the m members)
+ *   r_a = (SHA3-256(D || LE64(2 a)) read as a little-endian integer) mod r,
+ *   s_a = (SHA3-256(D || LE64(2 a + 1)) read as a little-endian integer) mod r,      a = 0 .. M - 1 its position among them.
+ * When to call it (one MI355X, tools/time_decider_batch.py --fused --big, profiles/r19_check_fused.json; against
+ * halo_acc_decider_batch_combined in the same run, medians of 5): 1.36 to 1.54 times its speed at m = 10 and 1.28 to 1.37 times at
+ * m = 100 on keys of 2^9 .. 2^14 and of 2^20 points, 1.05 times at m = 1000, where the members' transcripts on the host are what
+ * remains.  Every fused run was faster than every combined run in each row but two, which are NOT won: 2^9 points with m = 100 and
+ * 2^14 points with m = 1000 (one fused run of five inside the combined call's range). */
+int halo_pcdl_check_batch_fused(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, const uint8_t seed[32] /*nullable*/,
+                                int *status /*nullable*/);
 /* One rank's half of pcdl::check over a key sharded cyclically (halo_ctx_create_urs_strided: point i on rank i mod stride,
  * offset = the rank): the succinct check (pcdl.rs:333, the same on every rank; d + 1 may be up to stride * the shard's size)
  * and this rank's share of CM.Commit(ck, h) (pcdl.rs:338) over its own points.  U_out = the proof's U after the succinct
@@ -341,6 +380,10 @@ int halo_acc_decider_batch(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t
  * words hashed into the weights are each accumulator's Instance prefix) */
 int halo_acc_decider_batch_combined(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, const uint8_t seed[32] /*nullable*/,
                                     int *status /*nullable*/);
+/* ... as one fused relation: halo_pcdl_check_batch_fused over the accumulators' Instance prefixes, with its contract (each
+ * accumulator's Instance prefix is what is read, and what is hashed into the weights) */
+int halo_acc_decider_batch_fused(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, const uint8_t seed[32] /*nullable*/,
+                                 int *status /*nullable*/);
 /* acc::verifier (acc.rs:223-243) of k accumulators at once: benches/acc.rs:64-74's loop in one call.  accs = k Accumulator blobs
  * at stride halo_accumulator_words(lg(d+1)); counts[j] = the number of Instances member j verifies against accs[j] (0 allowed);
  * instances = sum(counts) Instance blobs at stride halo_instance_words(lg(d+1)), member j's right after member j - 1's.

@@ -37,7 +37,9 @@ extern "C" {
  * scalars are cut into, >= 1, clamped to the accepted members; 0: a wave per SIMD), "check_combined_cap" (their tables per pass, >= 1;
  * 0: the default) -- the scalars are the same words under every value of the two --, "check_combined_usum" (the right side
  * sum r_a U_a of a combined check: 1 the host pool, 2 the device where a second slot is idle; 0: by the member count; another
- * value is HALO_E_ARG; "batch_stage_fail" makes the combined calls take the exact path), "reset" (all off).
+ * value is HALO_E_ARG; "batch_stage_fail" makes the combined and the fused calls take the exact path), "check_fused_chunk" (terms per
+ * MSM of the left side of halo_pcdl_check_batch_fused: at least 8, clamped to the context's size; 0: that size; 1..7 or a negative
+ * value is HALO_E_ARG -- the statuses are the same under every value), "reset" (all off).
  * The launch plan of the Fr kernels (csrc/fr_plan.hpp), each taken before the environment's value and the measured default, every
  * plan giving the same field elements: "pow_e" (elements per lane of k_powers, k_poly_eval_partial, k_h_coeffs and
  * k_h_accumulate_batch and of their batch forms: a power of two in [4, 64], the rule of HALO_POW_E), "dot_blocks" (block cap of
@@ -96,6 +98,16 @@ int halo_dev_check_weights(const uint64_t *blobs, size_t stride_words, const siz
  * and tables per pass are the product's (the hooks "check_combined_parts" / "check_combined_cap" first).  1 <= A <= 65535,
  * 1 <= lg_n, 2^lg_n <= the context's size (64 at least); temporary device buffers of this call only. */
 int halo_dev_check_combined_scalars(halo_ctx *ctx, const uint64_t *xis, const uint64_t *weights, size_t A, size_t lg_n, uint64_t *out);
+/* The weights of halo_pcdl_check_batch_fused / halo_acc_decider_batch_fused (the fused rule of include/halo_accumulation.h),
+ * arguments as halo_dev_check_weights: out = 2 A x 4 Montgomery words, r_0 | s_0 | r_1 | s_1 | ..  Host only, no context. */
+int halo_dev_check_fused_weights(const uint64_t *blobs, size_t stride_words, const size_t *idx, size_t A, size_t d,
+                                 const uint8_t seed[32] /*nullable*/, uint64_t *out);
+/* The term kernel of the fused check on its own (k_fused_terms, then the sum of H's shares: k_fr_sum_rows): recs = M records of
+ * lg_n + 6 elements of 4 Montgomery words (xi_0 .. xi_lg | z | v | c | r | s); scalars_out = M x (2 lg_n + 2) x 4 words, member a's
+ * scalars r | r xi_1^-1 .. r xi_lg^-1 | r xi_1 .. r xi_lg | s - r c as canonical integers below the group order (NOT Montgomery: what
+ * the left side's MSM reads); h_out = sum_a r_a (v_a - c_a h_a(z_a)) xi_a,0 likewise.  1 <= M <= 65535, 1 <= lg_n <= 24; a zero
+ * challenge gives zeros for its inverses.  Temporary device buffers of this call only. */
+int halo_dev_check_fused_terms(halo_ctx *ctx, const uint64_t *recs, size_t M, size_t lg_n, uint64_t *scalars_out, uint64_t h_out[4]);
 
 /* replay cached hipGraphs of the MSM launch sequence when the same shape repeats (default on) */
 int halo_set_graphs(halo_ctx *ctx, int on);  /* also: environment HALO_GRAPHS=0 at context creation; HALO_TRACE=1 logs every launch */

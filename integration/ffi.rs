@@ -54,6 +54,8 @@ extern "C" {
     // ... with one MSM for all accepted members (seed: 32 bytes or null; the contract is in the header)
     pub fn halo_pcdl_check_batch_combined(ctx: *mut HaloCtx, d: usize, instances: *const u64, m: usize, seed: *const u8, status: *mut c_int) -> c_int;
     pub fn halo_acc_decider_batch_combined(ctx: *mut HaloCtx, d: usize, accs: *const u64, m: usize, seed: *const u8, status: *mut c_int) -> c_int;
+    pub fn halo_pcdl_check_batch_fused(ctx: *mut HaloCtx, d: usize, instances: *const u64, m: usize, seed: *const u8, status: *mut c_int) -> c_int;
+    pub fn halo_acc_decider_batch_fused(ctx: *mut HaloCtx, d: usize, accs: *const u64, m: usize, seed: *const u8, status: *mut c_int) -> c_int;
     // acc::verifier of k accumulators at once (counts[j] instances for accs[j]; status may be null)
     pub fn halo_acc_verifier_batch(ctx: *mut HaloCtx, d: usize, instances: *const u64, counts: *const usize, k: usize, accs: *const u64, status: *mut c_int) -> c_int;
     // acc::prover of k members at once (counts[j] instances for member j; rng_state and status may be null)

@@ -10,7 +10,13 @@ JSON line; every time is the median of --reps alternating runs, in ms.
 (random_instance_batch + prover_batch: a decider's work does not depend on what its accumulator accumulated).  n in --sizes with k
 in {10, 100, 1000}; with --big n = 2^20 on its own context with k in {10, 100}.  Every row keeps median, least and greatest of
 --reps runs of each way, and says whether the combined call's range lies below the exact batch's.  Also the sweep of the combined
-call's right side (the development hook check_combined_usum: 1 the host pool, 2 the device) over the member count."""
+call's right side (the development hook check_combined_usum: 1 the host pool, 2 the device) over the member count.
+
+--fused: the four-way leg -- loop / exact batch / combined batch / fused batch (halo_acc_decider_batch_fused: the succinct
+relations in the one relation too), alternating in one process over the same k independent accumulators.  n in {2^9, 2^12, 2^14}
+(--sizes changes them) with k in {10, 100, 1000}; with --big n = 2^20 on its own context with k in {10, 100}.  The baseline is
+the combined call of the same run.  Every row keeps median, least and greatest of --reps runs (5 unless given) of each way and
+says whether the ranges of the fused and the combined call lie apart, and which way."""
 import argparse
 import ctypes as C
 import json
@@ -88,6 +94,15 @@ def combined(ctx, d, blob, k):
     return ms, list(st)
 
 
+def fused(ctx, d, blob, k):
+    st = (C.c_int * k)()
+    t = time.perf_counter()
+    rc = ctx.lib.halo_acc_decider_batch_fused(ctx.h, d, ptr(blob), k, None, st)
+    ms = (time.perf_counter() - t) * 1e3
+    assert rc == 0, ctx.lib.halo_last_error()
+    return ms, list(st)
+
+
 def stats(ms):
     return {"median": round(statistics.median(ms), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)}
 
@@ -119,6 +134,60 @@ def time_three(ctx, d, accs, k, reps):
     row["batch_faster_than_combined"] = max(ms["batch"]) < min(ms["combined"])
     row["batch_over_combined"] = round(statistics.median(ms["batch"]) / statistics.median(ms["combined"]), 2)
     return row
+
+
+def time_four(ctx, d, accs, k, reps):
+    """-> {"loop" | "batch" | "combined" | "fused": stats} of `reps` alternating runs after a warm-up of each, and how the fused
+    call's range lies against the combined call's"""
+    ptrs = [ptr(a) for a in accs[:k]]
+    blob = np.ascontiguousarray(np.concatenate(accs[:k]))
+    ways = {"loop": lambda: serial(ctx, ptrs), "batch": lambda: batched(ctx, d, blob, k), "combined": lambda: combined(ctx, d, blob, k),
+            "fused": lambda: fused(ctx, d, blob, k)}
+    ms = {w: [] for w in ways}
+    for fn in ways.values():
+        fn()
+    for _ in range(reps):
+        for w, fn in ways.items():
+            t, st = fn()
+            assert st == [0] * k, "a member was rejected"
+            ms[w].append(t)
+    row = {w: stats(v) for w, v in ms.items()}
+    row["fused_runs"] = [round(v, 3) for v in ms["fused"]]
+    row["combined_runs"] = [round(v, 3) for v in ms["combined"]]
+    row["every_fused_run_beats_every_combined_run"] = max(ms["fused"]) < min(ms["combined"])  # won: the ranges apart
+    row["every_combined_run_beats_every_fused_run"] = max(ms["combined"]) < min(ms["fused"])
+    row["combined_over_fused"] = round(statistics.median(ms["combined"]) / statistics.median(ms["fused"]), 2)
+    return row
+
+
+def main_fused(a):
+    rows = []
+    sizes = [int(x) for x in a.sizes.split(",")] if a.sizes_given else [1 << 9, 1 << 12, 1 << 14]
+    reps = a.reps if a.reps_given else 5
+    ctx = h._lib.Context(urs_n=1 << 14)
+    try:
+        for n in sizes:
+            accs = independent_accs(ctx, n, a.chain, 0x48414C4F00000500 + n)
+            for k in (10, 100, 1000):
+                if k <= len(accs):
+                    rows.append({"n": n, "k": k, **time_four(ctx, n - 1, accs, k, reps)})
+                    print(rows[-1], file=sys.stderr, flush=True)
+    finally:
+        ctx.close()
+    if a.big:
+        n = 1 << 20
+        c = h._lib.Context(urs_n=n)
+        try:
+            accs = independent_accs(c, n, 100, 0x48414C4F00000600)
+            for k in (10, 100):
+                rows.append({"n": n, "k": k, **time_four(c, n - 1, accs, k, reps)})
+                print(rows[-1], file=sys.stderr, flush=True)
+        finally:
+            c.close()
+    print(json.dumps({"tool": "tools/time_decider_batch.py --fused", "workload": "k x acc::decider over k independent accumulators, 1 GPU: "
+                      "the halo_acc_decider loop, halo_acc_decider_batch, halo_acc_decider_batch_combined and halo_acc_decider_batch_fused, "
+                      "alternating; contexts of 2^14 points (n = 2^20: its own); baseline = the combined call of the same run",
+                      "reps": reps, "unit": "ms", "rows": rows, "statuses": "all 0 in every run of every way"}))
 
 
 def usum_sweep(ctx, d, accs, reps):
@@ -181,12 +250,17 @@ def main_combined(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--combined", action="store_true", help="loop / exact batch / combined batch, three ways alternating (see the module text)")
+    ap.add_argument("--fused", action="store_true", help="loop / exact batch / combined batch / fused batch, four ways alternating (see the module text)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--chain", type=int, default=1000)
     ap.add_argument("--sizes", default=",".join(map(str, SIZES)))
     ap.add_argument("--sweep", type=int, default=1, help="members-per-launch sweep at k = 100 (0: off)")
     ap.add_argument("--big", action="store_true", help="add the 2^20-point leg (chain of 10)")
     a = ap.parse_args()
+    a.sizes_given = any(x == "--sizes" or x.startswith("--sizes=") for x in sys.argv[1:])
+    a.reps_given = any(x == "--reps" or x.startswith("--reps=") for x in sys.argv[1:])
+    if a.fused:
+        return main_fused(a)
     if a.combined:
         return main_combined(a)
     ctx = h._lib.Context(urs_n=1 << 14)
