@@ -665,7 +665,7 @@ class Context:
         check(self.lib.halo_dev_table_read(self.h, int(row), int(off), int(n), ptr(out)))
         return out
 
-    MSM_PLAN_FIELDS = ("pipeline", "c", "W", "B", "members", "sets", "pieces", "kmax", "form", "L", "logL", "nseg", "live_seg", "vw", "vw_bits")
+    MSM_PLAN_FIELDS = ("pipeline", "c", "W", "B", "members", "sets", "pieces", "kmax", "form", "L", "logL", "nseg", "live_seg")
 
     def msm_last_plan(self, slot=0) -> dict:
         """halo_dev_msm_last_plan: the plan of the launch enqueued last on `slot`, as its launch sequence noted it.  pipeline: 0 general,
@@ -674,7 +674,7 @@ class Context:
         out = (C.c_long * 16)()
         check(self.lib.halo_dev_msm_last_plan(self.h, int(slot), out))
         d = dict(zip(self.MSM_PLAN_FIELDS, [int(v) for v in out]))
-        rc = int(out[15])
+        rc = int(out[13])
         d.update(lg_rows=rc & 255, lg_cols=(rc >> 8) & 255, per=rc >> 16)
         return d
 

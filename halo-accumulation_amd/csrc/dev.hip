@@ -195,14 +195,12 @@ long halo_dev_tuning(const char *name) {
     if (!std::strcmp(name, "host_pieces")) return t.host_pieces;
     if (!std::strncmp(name, "host_split", 10) && name[10] >= '0' && name[10] <= '3' && !name[11]) return t.host_split[name[10] - '0'];
     if (!std::strcmp(name, "fold_table_after")) return t.fold_table_after;
-    if (!std::strcmp(name, "graph_cache")) return t.graph_cache;
     if (!std::strcmp(name, "pow_e")) return t.pow_e;
     if (!std::strcmp(name, "dot_blocks")) return t.dot_blocks;
     if (!std::strcmp(name, "spin_us")) return t.spin_us;
     if (!std::strcmp(name, "graphs")) return t.graphs;
     if (!std::strcmp(name, "memory_budget")) return t.memory_budget_set ? (long)(t.memory_budget >> 20) : -1;  // MiB
     if (!std::strcmp(name, "trace")) return t.trace ? 1 : 0;
-    if (!std::strcmp(name, "tagged")) return t.tagged ? 1 : 0;
     if (!std::strcmp(name, "commit_batch_group")) return dev_hooks().commit_group;  // (the hook as it stands: a CPU test sees "reset" clear it)
     if (!std::strcmp(name, "open_batch_fold")) return dev_hooks().open_fold;
     return -1;
@@ -876,9 +874,8 @@ static int msm_slot_idle(halo_ctx *ctx, int slot, const char *who) {
 // records the plan's launch left in h_winsum: what msm_combine_member walks over
 static size_t msm_winsum_records(const MsmPlan &p) {
     if (p.W == 0) return 0;
-    if (p.table_vw > 0 && p.table_rc)
+    if (p.pipeline >= 2)
         return (size_t)p.table_pieces * p.table_sets * 2 * (size_t)(((1 << p.table_rc_lg_cols) + (1 << p.table_rc_lg_rows)) / 64);
-    if (p.table_vw > 0) return (size_t)p.table_pieces * 2 * p.table_sets * p.table_vw;
     return (size_t)(p.w1 - p.w0) * p.batch;
 }
 int halo_dev_msm_last_plan(halo_ctx *ctx, int slot, long out[16]) {
@@ -888,8 +885,8 @@ int halo_dev_msm_last_plan(halo_ctx *ctx, int slot, long out[16]) {
     if (rc) return rc;
     const MsmPlan &p = ctx->wss[slot].plan;
     const long v[16] = {p.pipeline, p.c, p.W, (long)p.B, p.batch, p.table_sets, p.table_pieces, (long)p.kmax, p.winsum_form, (long)p.red_L, p.red_logL,
-                        (long)p.red_nseg, p.red_live_seg, p.table_vw, p.table_vw_bits,
-                        p.table_rc ? (long)p.table_rc_lg_rows | (long)p.table_rc_lg_cols << 8 | (long)p.table_rc_per << 16 : 0};
+                        (long)p.red_nseg, p.red_live_seg,
+                        p.pipeline >= 2 ? (long)p.table_rc_lg_rows | (long)p.table_rc_lg_cols << 8 | (long)p.table_rc_per << 16 : 0, 0, 0};
     for (int k = 0; k < 16; ++k) out[k] = v[k];
     return HALO_OK;
 }

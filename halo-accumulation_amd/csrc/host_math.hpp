@@ -18,10 +18,6 @@
 
 namespace halo {
 namespace host {
-// HALO_HOST_INV_FERMAT, read with the rest of the environment (tuning.hip).  Weak: a program built from this header alone
-// (tests/native) has no tuning() to ask and keeps the default.
-bool host_inv_fermat() __attribute__((weak));
-
 using u64 = uint64_t;
 using u128 = unsigned __int128;
 
@@ -317,8 +313,6 @@ struct Fp {
     // The limbs hold a = x R: the plain integer inverse of a is x^-1 R^-1, and one Montgomery product with R^3 makes it x^-1 R.
     Fp inv() const {
         if (is_zero()) return *this;
-        static const bool fermat = host_inv_fermat && host_inv_fermat();  // development switch for A/B runs (csrc/tuning.hpp)
-        if (fermat) return inv_fermat();
         static const Fp R3 = Fp{{P::R2[0], P::R2[1], P::R2[2], P::R2[3]}} * Fp{{P::R2[0], P::R2[1], P::R2[2], P::R2[3]}};
         Fp r;
         modinv::inverse(l, P::M, r.l);

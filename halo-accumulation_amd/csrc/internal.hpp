@@ -71,11 +71,10 @@ struct MsmPlan {
     uint32_t B;   // buckets per window = 2^(c-1)
     int batch;    // MSMs sharing the launch sequence (their windows are laid side by side: W * batch in all)
     int w0, w1;   // windows [w0, w1) of 0..W are computed (a window-sharded partial); the result carries 2^(c*w0)
-    int table_vw = 0;  // > 0: the fixed-base table pipeline ran; h_winsum holds table_vw weighted sums, then table_vw plain sums
-    int table_vw_bits = 15;  // log2 of the buckets per virtual window
-    int table_pieces = 1;    // a large table MSM runs as this many consecutive pieces: 2 * table_sets * table_vw sums each
+    // the fixed-base table pipeline (pipeline >= 2): window sums by rows and columns of the bucket index (msm_buckets.hip
+    // k_msm_reduce_rc); h_winsum holds (2^lg_cols + 2^lg_rows) / 64 pairs (S, T) per piece and set
+    int table_pieces = 1;    // a large table MSM runs as this many consecutive pieces
     int table_sets = 1;      // bucket sets side by side in a batched table launch (members, rounded up to a power of two)
-    bool table_rc = false;   // window sums by rows and columns of the bucket index (msm_buckets.hip k_msm_reduce_rc): (S, T) pairs per set
     int table_rc_lg_rows = 0, table_rc_lg_cols = 0;
     // the sliding odd-digit plan over the all-shifts table (TblPlan::slide): bucket index = range * 2^lg_cols + fine holds the
     // digits of magnitude 2 (fine * 2^lg_rows + range) + 1 -- other constants in msm_combine_member, same (S, T) pairs
@@ -87,17 +86,18 @@ struct MsmPlan {
     // What the launch sequence chose for its window sums, noted where it computes them.  Nothing in the product reads these: the
     // development library reports them (halo_dev_msm_last_plan), so that a test can assert the plan its case was built for.
     int pipeline = 0;          // 0 general, 1 small (smsm.hip), 2 table with fixed windows, 3 table sliding
-    int winsum_form = 0;       // 0 k_msm_reduce1 + k_smsm_final, 1 k_smsm_reduce (+ k_smsm_final, or fused), 2 k_msm_reduce_rc + k_rc_mid
+    int winsum_form = 0;       // 0 k_msm_reduce1 + k_smsm_final, 1 k_smsm_reduce (+ k_smsm_final beyond one segment), 2 k_msm_reduce_rc + k_rc_mid
     uint32_t kmax = 0;         // longest chain of the bucket kernel: a bucket of more entries is several tasks
     uint32_t red_L = 0, red_nseg = 0;  // forms 0, 1: buckets per lane / quad, segments per window
     int red_logL = 0, red_live_seg = 0;
     int table_rc_per = 0;      // form 2: buckets per lane of k_msm_reduce_rc
 };
 constexpr int MSM_MAX_BATCH = 8;
+constexpr size_t REDUCE_WAVES = 1024;  // most waves of k_msm_reduce1 / k_smsm_reduce: one per SIMD (msm_general.hip, smsm.hip)
 // fixed-base table plan of a context (msm_table.hip: table_plan)
 struct TblPlan {
-    int c, W, fbits, vw_bits;        // window bits, windows, fine-bucket bits of a coarse range, log2 buckets per virtual window
-    uint32_t B, ranges, vw, spread;  // buckets (2^(c-1)), coarse ranges, virtual windows, modulus of the top-window spread (0: none)
+    int c, W, fbits;                 // window bits, windows, fine-bucket bits of a coarse range
+    uint32_t B, ranges, spread;      // buckets (2^(c-1)), coarse ranges, modulus of the top-window spread (0: none)
     int fold_top;                    // scalars >= 2^254 are recoded as r - s with flipped signs (c = 17: the top window is full)
     // The table of a c = 20 key may hold EVERY shift, rows 0 .. 254 (`rows` = 255: T[j][i] = 2^j G_i) instead of the W rows 2^(c w) G_i.
     // slide > 0 (21): the launch recodes its scalars into sliding windows of at most `slide` bits that start at set bits only (odd
@@ -555,9 +555,8 @@ int msm_host_run(halo_ctx *ctx, size_t off, size_t n, const uint64_t *scalars, s
 int msm_end_slot(halo_ctx *ctx, int slot, size_t count, uint64_t *out);  // `count` results of whatever begin started `slot` (halo_msm_end_sharded)
 
 // ---- smsm.hip: the 4-launch pipeline for MSMs of up to 2^16 points (digits already in ws.d_canon)
-// (winsum / winsum_plain may be pinned host memory; done: the counter to publish to, or null)
-int quad_final_enqueue(halo_ctx *ctx, MsmWorkspace &ws, uint32_t Wt, uint32_t nseg, int k, uint64_t *winsum, uint64_t *winsum_plain,
-                       const uint32_t *seg = nullptr, uint32_t *done = nullptr);
+// (winsum may be pinned host memory; done: the counter to publish to, or null)
+int quad_final_enqueue(halo_ctx *ctx, MsmWorkspace &ws, uint32_t Wt, uint32_t nseg, int k, uint64_t *winsum, uint32_t *done = nullptr);
 int rc_mid_enqueue(halo_ctx *ctx, const uint32_t *entries, uint32_t blocks, uint64_t *winsum, uint32_t *done = nullptr, uint32_t *ticket = nullptr);
 // (offs: one base offset per member, in points; a block of k_smsm_sort sorts one window, so one member)
 int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MemberOffsets &offs, size_t n, MsmPlan &p, uint32_t Wt,

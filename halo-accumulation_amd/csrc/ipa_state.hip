@@ -158,8 +158,7 @@ static int ipa_round_lr_points(halo_ipa *st, host::Fr dots[2], host::Point *Lp_o
     // drain, and the H' terms, which need only the dot products, were computed after the MSMs instead of under them.  In
     // the late rounds (an MSM of a few 10^4 additions: the GPU is mostly idle) the MSM's launches go first instead: the
     // three API calls of the dot products would only delay its start.
-    const int dots_env = tuning().dots_first;  // development switch
-    const bool dots_first = dots_env >= 0 ? dots_env != 0 : (st->nofold ? st->M : m) > ((size_t)1 << 16);
+    const bool dots_first = (st->nofold ? st->M : m) > ((size_t)1 << 16);
     auto launch_dots = [&]() -> int {
         StreamGuard on_third(ctx, ctx->streams[2]);
         return fr_dot2_launch(ctx, st->buf.d_c + 4 * m, st->buf.d_z, st->buf.d_c, st->buf.d_z + 4 * m, m);
@@ -195,8 +194,7 @@ static int ipa_round_lr_points(halo_ipa *st, host::Fr dots[2], host::Point *Lp_o
             both.scalars[1] = st->buf.d_FR;
             // half of each scalar array is zero: over a 2^16-point key 23 windows of 11 bits beat the table's 20 of 13 (measured,
             // medians of 13 opens on one box: 15.40 / 15.42 -> 15.23 / 15.37 ms; 10, 12 and 14 bits are worse, other key sizes keep the table)
-            const bool hint_env = tuning().ipa_c_hint;  // development switch
-            if (hint_env && st->M == ((size_t)1 << 16)) both.c_hint = 11;
+            if (st->M == ((size_t)1 << 16)) both.c_hint = 11;
             rc = msm_enqueue_batch(ctx, 0, st->G_src, both, true, st->M);
             if (rc) return rc;
         } else {
@@ -431,8 +429,7 @@ int halo_ipa_finish(halo_ipa *st, uint64_t U[12], uint64_t c[4]) {
         st->fold_pending = false;
     }
     int rc;
-    const bool u_from_last_round = tuning().u_from_last_round;  // development switch
-    if (st->nofold && st->M > 1 && st->last_valid && st->last_folded && u_from_last_round && !st->last_c0.is_zero() && !st->last_c1.is_zero()) {
+    if (st->nofold && st->M > 1 && st->last_valid && st->last_folded && !st->last_c0.is_zero() && !st->last_c1.is_zero()) {
         // U = G_final[0] = sum_b s''[b] K[b] with s''[2t + u] = s[t] xi^u (the last fold): U = A + xi B, A / B = the sums of
         // s[t] K[2t] / s[t] K[2t + 1].  The last round had two coefficients left, so its MSMs were exactly L' = c1 A and
         // R' = c0 B (k_nofold_expand with m = 2: FL[2t] = c[1] s[t], FR[2t + 1] = c[0] s[t]): U = L' / c1 + (xi / c0) R' -- two

@@ -96,9 +96,9 @@ int msm_workspace_alloc(halo_ctx *ctx, size_t n, int slot) {
     }
     need.hist = (size_t)256 * 32768 + need.counts;  // W * nchunks <= 256 blocks of B <= 32768 counters
     need.windows = 64;
-    {   // the table pipeline runs a large MSM in pieces and keeps 2 x 16 window sums per piece
+    {   // the table pipeline runs a large MSM in pieces and keeps 24 (S, T) pairs per piece (k_msm_reduce_rc)
         size_t pieces = (n + TBL_PIECE - 1) / TBL_PIECE;
-        if (48 * pieces > need.windows) need.windows = 48 * pieces;  // (or 24 (S, T) pairs per piece: k_msm_reduce_rc)
+        if (48 * pieces > need.windows) need.windows = 48 * pieces;
         if (need.windows < 128) need.windows = 128;                  // (a batch of 8 of the small-key plan: 8 x 8 pairs)
     }
     alloc_epoch_bump(ctx);
@@ -124,11 +124,8 @@ int msm_run(halo_ctx *ctx, const uint32_t *d_bases, const uint64_t *d_scalars, b
 
 
 uint32_t msm_kmax(const halo_ctx *ctx, size_t n) {
-    const int small_env = tuning().smsm_kmax;  // development override
     if (ctx->task_len > 0) return (uint32_t)ctx->task_len;
-    if (small_env > 0 && n <= ((size_t)1 << 16)) return (uint32_t)small_env;
-    const int late_env = tuning().late_kmax;  // development override
-    if (n <= ((size_t)1 << 14)) return late_env > 0 ? (uint32_t)late_env : 8u;  // the IPA's late rounds: the chain is the round's latency (measured: 16 -> 8: -0.15 ms per open)
+    if (n <= ((size_t)1 << 14)) return 8u;  // the IPA's late rounds: the chain is the round's latency (measured: 16 -> 8: -0.15 ms per open)
     return n >= ((size_t)1 << 18) ? KMAX : 16u;
 }
 
@@ -141,7 +138,7 @@ static bool batch_need(const halo_ctx *ctx, const MsmWorkspace &ws, size_t n, in
     if (count > 1 && ctx->n < ((size_t)1 << 20) && ctx->n >= ((size_t)1 << 17)) {  // room for a batch through the small-key table plan
         size_t sets = 1;
         while (sets < (size_t)count) sets <<= 1;
-        if (Wt < 32 * sets) Wt = 32 * sets;          // 2 x 16 window sums per bucket set
+        if (Wt < 32 * sets) Wt = 32 * sets;          // (a bucket set leaves 8 (S, T) pairs, 16 records: table_rc_shape)
         if (sorted < n * 30 * (size_t)count) sorted = n * 30 * (size_t)count;  // 15 rows of u32 digits per member (d_canon holds 2 bytes per entry)
         if (total < sets << 16) total = sets << 16;
     }
@@ -229,8 +226,7 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
     // caller has nothing else in flight) the pieces ALTERNATE over this slot's workspace and stream and the neighbouring slot's:
     // piece k + 1 sorts and accumulates while piece k's window sums -- latency chains on a few hundred waves -- finish.
     int partner = -1;
-    if (ctx->may_borrow > 0 && members.count == 1 && ctx->d_table && ctx->tbl.c == 20 && n > TBL_PIECE && table_eligible(ctx, d_bases, members, n) &&
-        tuning().piece_alternate) {
+    if (ctx->may_borrow > 0 && members.count == 1 && ctx->d_table && ctx->tbl.c == 20 && n > TBL_PIECE && table_eligible(ctx, d_bases, members, n)) {
         int cand = slot ^ 1;
         if (!ctx->wss[cand].in_flight) {
             // the partner runs pieces of THIS launch: it needs this slot's capacities, which a forced task length may have grown
@@ -276,17 +272,15 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
         }
         ws.graph_epoch = ctx->alloc_epoch;
     }
-    const int cache_n = tuning().graph_cache;  // development switch: HALO_GRAPH_CACHE=1 is the single graph per slot of rounds 1-3
-    static_assert(MsmWorkspace::GRAPHS == 8, "tuning.hip clamps HALO_GRAPH_CACHE to 8");
     MsmWorkspace::CachedGraph *hit = nullptr;
-    for (int k = 0; k < cache_n; ++k)
+    for (int k = 0; k < MsmWorkspace::GRAPHS; ++k)
         if (ws.graphs[k].exec && key == ws.graphs[k].key) hit = &ws.graphs[k];
     if (graphs && hit) {
         if (debug_trace()) fprintf(stderr, "[halo] graph REPLAY ctx=%p slot=%d n=%zu\n", (void *)ctx, slot, n);
         HALO_HIP(hipGraphLaunch(hit->exec, ctx->streams[slot]));
         hit->used = ++ws.graph_clock;
         ws.plan = hit->plan;
-        ctx->last_table_plan = ws.plan.table_vw > 0 ? ws.plan.table_slide : -1;
+        ctx->last_table_plan = ws.plan.pipeline >= 2 ? ws.plan.table_slide : -1;
         ws.done_expect += (uint32_t)ws.plan.publishers;
         ws.in_flight = ws.launched = true;
         if (partner >= 0) { ws.borrowed = partner; ctx->wss[partner].in_flight = true; ctx->wss[partner].lent_from = slot; }
@@ -294,15 +288,14 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
     }
     bool capture = false;
     if (graphs) {
-        for (int k = 0; k < cache_n; ++k) capture = capture || key == ws.seen[k];
-        if (!capture) { ws.seen[ws.seen_at] = key; ws.seen_at = (ws.seen_at + 1) % cache_n; }
+        for (int k = 0; k < MsmWorkspace::SEEN; ++k) capture = capture || key == ws.seen[k];
+        if (!capture) { ws.seen[ws.seen_at] = key; ws.seen_at = (ws.seen_at + 1) % MsmWorkspace::SEEN; }
     }
     if (debug_trace()) fprintf(stderr, "[halo] msm enqueue ctx=%p slot=%d n=%zu batch=%d part=%d/%d capture=%d\n", (void *)ctx, slot, n, members.count, members.part, members.parts, (int)capture);
     if (capture) HALO_HIP(hipStreamBeginCapture(ctx->streams[slot], hipStreamCaptureModeRelaxed));
     // The launch's last kernel publishes its sums itself (smsm.hip publish(): pinned buffer + pinned counter) unless the event
-    // profiler brackets every launch or HALO_DIRECT_RESULTS=0 asks for the copy + stream wait of rounds 1-3 (development switch).
-    const bool direct = tuning().direct_results;
-    ctx->sink_done = direct && !ctx->prof.on ? ws.h_done : nullptr;
+    // profiler brackets every launch: then a copy and a stream wait.
+    ctx->sink_done = !ctx->prof.on ? ws.h_done : nullptr;
     ctx->sink_publishers = 0;
     int rc = msm_enqueue_launches(ctx, ws, d_bases, members, mont, n, partner);
     ctx->sink_done = nullptr;
@@ -313,7 +306,7 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
         if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
         if (e != hipSuccess) return hip_fail(e, "hipStreamEndCapture");
         MsmWorkspace::CachedGraph *victim = &ws.graphs[0];
-        for (int k = 0; k < cache_n; ++k)
+        for (int k = 0; k < MsmWorkspace::GRAPHS; ++k)
             if (!ws.graphs[k].exec) { victim = &ws.graphs[k]; break; }
             else if (ws.graphs[k].used < victim->used) victim = &ws.graphs[k];
         if (victim->exec) { drain(); (void)hipGraphExecDestroy(victim->exec); *victim = MsmWorkspace::CachedGraph(); }
@@ -333,7 +326,7 @@ int msm_enqueue_batch(halo_ctx *ctx, int slot, const uint32_t *d_bases, const Ms
         ws.done_expect = *(volatile uint32_t *)ws.h_done;
         return rc;
     }
-    ctx->last_table_plan = ws.plan.table_vw > 0 ? ws.plan.table_slide : -1;
+    ctx->last_table_plan = ws.plan.pipeline >= 2 ? ws.plan.table_slide : -1;
     ws.done_expect += (uint32_t)ws.plan.publishers;
     ws.in_flight = ws.launched = true;
     if (partner >= 0) { ws.borrowed = partner; ctx->wss[partner].in_flight = true; ctx->wss[partner].lent_from = slot; }
@@ -404,7 +397,7 @@ void msm_combine_member(halo_ctx *ctx, int slot, int b, host::Point *out) {
     MsmPlan p = ws.plan;
     *out = host::Point::infinity();
     if (p.W == 0) return;
-    if (p.table_vw > 0 && p.table_rc) {
+    if (p.pipeline >= 2) {  // the table pipeline: row / column sums (msm_buckets.hip k_msm_reduce_rc)
         // per piece and set: pairs (S_q, T_q) = (sum E, sum (Q + 1) E) over 64 entries each, the columns' first, then the rows'.
         //   sum_lo (lo + 1) C_lo = sum_q T_q + 64 sum_q q S_q;   sum_hi (hi + 1) R_hi likewise
         //   sum_b (b + 1) B_b = [columns] + 2^lg_cols ([rows] - sum_hi R_hi)
@@ -442,21 +435,6 @@ void msm_combine_member(halo_ctx *ctx, int slot, int b, host::Point *out) {
         host::Point rows = weighted(cblocks, rblocks, &s_rows) - s_rows;
         for (int k = 0; k < p.table_rc_lg_cols && !rows.is_inf(); ++k) rows = rows.dbl();
         *out = cols + rows;
-        return;
-    }
-    if (p.table_vw > 0) {
-        // virtual window v holds the buckets v 2^b + 1 .. (v + 1) 2^b (b = table_vw_bits): sum_v [ T_v + v 2^b S_v ];
-        // a piece (large MSM) or a batch stores sets * V weighted sums, then sets * V plain sums; member b owns set b
-        int V = p.table_vw, A = p.table_sets * V;
-        host::Point acc = host::Point::infinity(), run = host::Point::infinity(), tot = host::Point::infinity();
-        for (int k = 0; k < p.table_pieces; ++k)  // the pieces of a large MSM add up window by window
-            for (int v = 0; v < V; ++v) acc = acc + host::Point::load(ws.h_winsum + 12 * ((size_t)k * 2 * A + (size_t)b * V + v));
-        for (int v = V - 1; v >= 1; --v) {  // tot = sum_v v S_v by running sums
-            for (int k = 0; k < p.table_pieces; ++k) run = run + host::Point::load(ws.h_winsum + 12 * ((size_t)k * 2 * A + A + (size_t)b * V + v));
-            tot = tot + run;
-        }
-        for (int k = 0; k < p.table_vw_bits && !tot.is_inf(); ++k) tot = tot.dbl();
-        *out = acc + tot;
         return;
     }
     int Wm = p.w1 - p.w0;

@@ -43,19 +43,6 @@ MsmPlan msm_plan(size_t n, int forced_c) {
     // bits (c = 14, 12, 11, 9) are avoided: that window puts n/4 points into each of ~4 buckets.
     static const int table[] = {/*lg 10*/ 8, 8, 8, 10, 10, 13, 13, 15, 15, /*lg 19*/ 15};
     int c = forced_c > 0 ? forced_c : (lg >= 20 ? 16 : lg >= 10 ? table[lg - 10] : lg - 2);
-    // development override, e.g. HALO_PLAN="16:12,15:12": window bits for MSMs of 2^lg <= n < 2^(lg+1) points
-    const char *plan_env = tuning().plan;
-    if (plan_env && forced_c <= 0) {
-        for (const char *q = plan_env; *q;) {
-            int l = atoi(q);
-            const char *colon = strchr(q, ':');
-            if (!colon) break;
-            if (l == lg) c = atoi(colon + 1);
-            const char *comma = strchr(colon, ',');
-            if (!comma) break;
-            q = comma + 1;
-        }
-    }
     if (c < 4) c = 4;
     if (c > 16) c = 16;
     MsmPlan p;
@@ -540,12 +527,9 @@ int msm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_base
         L = p.B >= 16384 ? 8 : p.B >= 4096 ? 4 : p.B >= 1024 ? 2 : 1;
         nseg = p.B / (64 * L);
     }
-    {
-        // no more waves than SIMDs (one wave each): a SIMD that holds two runs both chains at about half speed and the kernel
-        // waits for it (development switch HALO_REDUCE1_WAVES, 0 = off)
-        const int waves_env = tuning().reduce1_waves;
-        while (waves_env > 0 && p.B > 64 && (size_t)Wt * nseg > (size_t)waves_env && nseg > 1 && L < 64) { L <<= 1; nseg >>= 1; }
-    }
+    // no more waves than SIMDs (one wave each): a SIMD that holds two runs both chains at about half speed and the kernel
+    // waits for it
+    while (p.B > 64 && (size_t)Wt * nseg > REDUCE_WAVES && nseg > 1 && L < 64) { L <<= 1; nseg >>= 1; }
     if (ctx->reduce_span > 0 && p.B > 64) {
         L = (uint32_t)ctx->reduce_span;
         while (64 * L > p.B) L >>= 1;
@@ -558,7 +542,7 @@ int msm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_base
     HALO_LAUNCH(ctx, "k_msm_reduce1", k_msm_reduce1, dim3((unsigned)(Wt * nseg)), dim3(64), 0, ws.d_buckets, ws.d_ntask, ws.d_toff,
                 ws.d_tblockoff, p.B, L, logL, nseg, ws.d_seg);
     {
-        int rc = quad_final_enqueue(ctx, ws, (uint32_t)Wt, nseg, logL + 6, ctx->sink_done ? ws.h_winsum : ws.d_winsum, nullptr, nullptr, ctx->sink_done);
+        int rc = quad_final_enqueue(ctx, ws, (uint32_t)Wt, nseg, logL + 6, ctx->sink_done ? ws.h_winsum : ws.d_winsum, ctx->sink_done);
         if (rc) return rc;
     }
     HALO_HIP(hipGetLastError());

@@ -17,16 +17,16 @@ namespace halo {
 //   * 13 n mixed additions instead of 16 n (the general pipeline cannot go past c = 16: every window would need its own
 //     2^(c-1) buckets reduced);
 //   * the weighted bucket sum is taken once over 2^19 buckets -- as many as 16 windows x 2^15 today -- and the host no longer
-//     runs a 240-doubling Horner chain: it combines 16 (plain, weighted) pairs with ~50 additions.
+//     runs a 240-doubling Horner chain: it combines 24 (plain, weighted) pairs with ~70 additions.
 // The sort is the two-level one (coarse: 512 bucket ranges, runs advance sequentially; fine: one block per range, 1024 buckets,
-// staged in LDS, which also writes the bucket kernel's task records); everything after it (k_msm_accumulate, combine, window
-// sums) is the general pipeline's, which sees 16 "virtual windows" of 2^15 buckets.
+// staged in LDS, which also writes the bucket kernel's task records); the bucket kernel and the combine behind it are the
+// general pipeline's, the window sums are taken over the rows and columns of the bucket index (k_msm_reduce_rc, table_rc_shape).
 //
 // Two plans (TblPlan, fixed when a context builds its table):
-//   key of >= 2^20 points: c = 20, 13 windows, 2^19 buckets, 512 coarse ranges of 1024 buckets, 16 virtual windows of 2^15;
+//   key of >= 2^20 points: c = 20, 13 windows, 2^19 buckets, 512 coarse ranges of 1024 buckets;
 //   key of 2^17 .. 2^19 points (a rank's index shard of a 2^20-point MSM): c = 17, 15 windows (15 x 17 = 255 bits exactly),
-//     2^16 buckets, n / 2048 coarse ranges (so that a range's 15 n / ranges entries fit the fine sort's LDS stage), 16 virtual
-//     windows of 2^12 -- 15 n additions against 16 n, an eighth of the buckets of the general plan's 16 x 2^15.
+//     2^16 buckets, n / 2048 coarse ranges (so that a range's 15 n / ranges entries fit the fine sort's LDS stage) -- 15 n
+//     additions against 16 n, an eighth of the buckets of the general plan's 16 x 2^15.
 //
 // Third plan, the default of a c = 20 key whose ALL-SHIFTS table could be had (255 rows T[j][i] = 2^j G_i, 255 x 128 B per point:
 // optional memory like the 13 rows): sliding windows of at most 21 bits that start at set bits only (slide_lane.hpp).  Every digit
@@ -41,9 +41,9 @@ TblPlan table_plan(size_t key_n) {
     TblPlan t{};
     t.row_step = 1; t.slide = 0;
     if (key_n >= table_slide_min()) {
-        t.c = 20; t.W = 13; t.B = 1u << 19; t.fbits = 10; t.vw_bits = 15; t.spread = 31; t.fold_top = 0;
+        t.c = 20; t.W = 13; t.B = 1u << 19; t.fbits = 10; t.spread = 31; t.fold_top = 0;
     } else {
-        t.c = 17; t.W = 15; t.B = 1u << 16; t.vw_bits = 12; t.spread = 0; t.fold_top = 1;
+        t.c = 17; t.W = 15; t.B = 1u << 16; t.spread = 0; t.fold_top = 1;
         uint32_t ranges = 64;
         while ((size_t)ranges * 2048 < key_n && ranges < 256) ranges <<= 1;
         t.fbits = 16;
@@ -52,7 +52,6 @@ TblPlan table_plan(size_t key_n) {
     t.ranges = t.B >> t.fbits;
     t.rbits = 0;
     while ((1u << t.rbits) < t.ranges) t.rbits++;
-    t.vw = t.B >> t.vw_bits;
     t.rows = t.W;
     return t;
 }
@@ -725,8 +724,7 @@ int table_build(halo_ctx *ctx) {
 // A tagged launch (MsmBatch::tagged) has no table-free form: the caller asks first and keeps its two plain launches otherwise
 // (no table yet -- the first MSM over the key builds it --, table mode off, a forced window size, the small-key plan).
 bool msm_tagged_ready(const halo_ctx *ctx, const uint32_t *d_bases, size_t n) {
-    const bool off = !tuning().tagged;  // development switch: never
-    if (off || !ctx->d_table || ctx->tbl.c != 20) return false;
+    if (!ctx->d_table || ctx->tbl.c != 20) return false;
     MsmBatch one;
     one.tagged = true;
     return table_eligible(ctx, d_bases, one, n);
@@ -800,25 +798,20 @@ bool table_eligible(const halo_ctx *ctx, const uint32_t *d_bases, const MsmBatch
     if (ctx->n < least || (n < least && !(members.sub && tp.c == 20 && n >= 4096)) || (tp.c != 20 && 2 * n < ctx->n) || n % 4 != 0 || rows * ctx->n >= ((size_t)1 << 31)) return false;
     return d_bases >= ctx->d_bases && d_bases + AFF_STRIDE * n <= ctx->d_bases + AFF_STRIDE * ctx->n;
 }
-// the shape of the row / column window sums (k_msm_reduce_rc) for a launch of `sets` bucket sets of B buckets each; per = 0: none
+// the shape of the row / column window sums (k_msm_reduce_rc) for a launch of `sets` bucket sets of B buckets each: every launch
+// table_eligible accepts has one (c = 20: one set, or the two of a tagged launch; c = 17: a power of two of at most 8)
 static RcShape table_rc_shape(int c, uint32_t B, uint32_t sets) {
-    const bool off = !tuning().reduce_rc;  // development switch: the older form
     RcShape r;
-    if (off) return r;
     if (c == 20 && (sets == 1 || sets == 2) && B == (1u << 19)) { r.lg_rows = 9; r.lg_cols = 10; r.per = 16; }  // (2 sets: a tagged launch, 2048 waves)
     else if (c == 17 && B == (1u << 16) && (sets == 1 || sets == 2 || sets == 4 || sets == 8)) { r.lg_rows = 8; r.lg_cols = 8; r.per = sets == 1 ? 4 : (int)(2 * sets); }
     return r;
 }
-// A batch is about throughput: its window sums take 2^15-bucket virtual windows (8 buckets per lane) like the large plan --
-// with 2^12 (one bucket per lane: the short chain a single MSM wants) the wave-wide step of k_msm_reduce1 cost as many
-// instructions as the bucket kernel itself.
 // A context whose table holds every shift slides (ctx->tbl.slide) -- one MSM in one piece with the row / column window sums; the
 // tagged launch, the pieces of a larger MSM and table mode 1 take the fixed windows on rows 20 w of the same table.
 static TblPlan table_launch_plan(const halo_ctx *ctx, const MsmBatch &members, size_t n) {
     const int count = members.count;
     TblPlan tp = ctx->tbl;
-    if (tp.rows == SLIDE_BITS && (members.tagged || count != 1 || n > TBL_PIECE || ctx->table_mode == 1 || !tuning().reduce_rc)) tp = table_plan_fixed_on(ctx->tbl, ctx->n);
-    if (count > 1 && tp.vw_bits < 15 && tp.B >= (1u << 15)) { tp.vw_bits = 15; tp.vw = tp.B >> 15; }
+    if (tp.rows == SLIDE_BITS && (members.tagged || count != 1 || n > TBL_PIECE || ctx->table_mode == 1)) tp = table_plan_fixed_on(ctx->tbl, ctx->n);
     return tp;
 }
 // task length of the bucket kernel for a table launch of `entries` digits: the chain bound per lane, the W n additions over the
@@ -835,27 +828,13 @@ static size_t tmsm_ovf_records(size_t entries, uint32_t kmax) { return (entries 
 // records of `order` a piece of `entries` digits over `buckets` buckets takes (tmsm_enqueue_piece: overflow region + one per bucket):
 // what the slot's cap_tasks has to hold, at the task length the piece will run with
 size_t tmsm_order_records(const halo_ctx *ctx, size_t entries, size_t buckets) { return tmsm_ovf_records(entries, tmsm_kmax(ctx, entries)) + buckets; }
-// What a piece of `entries` digits takes for its bucket kernel and -- without the row / column sums -- for k_msm_reduce1 over virtual
-// windows of 2^vw_bits buckets: computed here for the piece that launches and for the plan that reports it (MsmPlan, one place each).
-struct TblWinsum { uint32_t kmax, L, nseg; int logL; };
-static TblWinsum tmsm_winsum(const halo_ctx *ctx, const TblPlan &tp, size_t entries) {
-    TblWinsum w;
-    w.kmax = tmsm_kmax(ctx, entries);
-    const uint32_t vwB = 1u << tp.vw_bits;
-    w.L = vwB / 4096 ? vwB / 4096 : 1;
-    w.nseg = vwB / (64 * w.L);
-    if (tp.vw_bits == 15 && (ctx->reduce_span == 16 || ctx->reduce_span == 32 || ctx->reduce_span == 64)) { w.L = (uint32_t)ctx->reduce_span; w.nseg = 512 / w.L; }
-    w.logL = 0;
-    while ((1u << w.logL) < w.L) w.logL++;
-    return w;
-}
 int tmsm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MsmBatch &members, bool mont, size_t n, int partner) {
     const TblPlan tp = table_launch_plan(ctx, members, n);
     size_t pieces = tp.c == 20 ? (n + TBL_PIECE - 1) / TBL_PIECE : 1;
     uint32_t cpow = 1;  // a batch (small-key plan, one piece) lays its members' bucket sets side by side: a power of two of them
     while ((int)cpow < msm_outputs(members)) cpow <<= 1;
     const RcShape rcs = table_rc_shape(tp.c, tp.B, cpow);
-    if (2 * tp.vw * pieces * cpow > ws.cap_windows || rc_points(rcs) * cpow * pieces > ws.cap_windows) {
+    if (!rcs.per || rc_points(rcs) * cpow * pieces > ws.cap_windows) {
         set_error("msm: table plan exceeds workspace");
         return HALO_E_ARG;
     }
@@ -867,7 +846,7 @@ int tmsm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bas
     hipStream_t mine = ctx->stream;
     if (partner >= 0) {
         const size_t entries = (size_t)tp.W * len * members.count;
-        if (2 * tp.vw * cpow > ctx->wss[partner].cap_windows || rc_points(rcs) * cpow > ctx->wss[partner].cap_windows ||
+        if (rc_points(rcs) * cpow > ctx->wss[partner].cap_windows ||
             tmsm_ovf_records(entries, tmsm_kmax(ctx, entries)) + (size_t)tp.B * cpow > ctx->wss[partner].cap_tasks)
             partner = -1;  // (the pieces then run one after the other on this slot: same result)
     }
@@ -887,28 +866,21 @@ int tmsm_enqueue_launches(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bas
         HALO_HIP(hipStreamWaitEvent(mine, ctx->ev_piece[slot][1], 0));
     }
     MsmPlan p;
-    p.c = tp.c; p.W = tp.W; p.B = tp.B; p.batch = msm_outputs(members); p.w0 = 0; p.w1 = tp.W; p.table_vw = (int)tp.vw; p.table_vw_bits = tp.vw_bits;
+    p.c = tp.c; p.W = tp.W; p.B = tp.B; p.batch = msm_outputs(members); p.w0 = 0; p.w1 = tp.W;
     p.table_pieces = (int)pieces;
     p.table_sets = (int)cpow;
-    p.table_rc = rcs.per != 0;
     p.table_rc_lg_rows = rcs.lg_rows;
     p.table_rc_lg_cols = rcs.lg_cols;
     p.table_slide = tp.slide;
-    {   // the window sums every piece took (the pieces are of one length but for the last: the same task length class is noted from the first)
-        const TblWinsum w = tmsm_winsum(ctx, tp, (size_t)tp.W * (len < n ? len : n) * members.count);
-        p.pipeline = tp.slide ? 3 : 2;
-        p.kmax = w.kmax;
-        p.winsum_form = rcs.per ? 2 : 0;
-        p.table_rc_per = rcs.per;
-        if (!rcs.per) {
-            p.red_L = w.L; p.red_nseg = w.nseg; p.red_logL = w.logL;
-            for (p.red_live_seg = 1; (uint32_t)p.red_live_seg < w.nseg;) p.red_live_seg <<= 1;  // (quad_final_enqueue's)
-        }
-    }
+    // (the pieces are of one length but for the last: the task length class is noted from the first)
+    p.pipeline = tp.slide ? 3 : 2;
+    p.kmax = tmsm_kmax(ctx, (size_t)tp.W * (len < n ? len : n) * members.count);
+    p.winsum_form = 2;
+    p.table_rc_per = rcs.per;
     ws.plan = p;
     return HALO_OK;
 }
-// one piece: window sums to slot `piece` of d_winsum / h_winsum (sets * vw weighted sums, then sets * vw plain sums)
+// one piece: its (S, T) pairs to slot `piece` of d_winsum / h_winsum (rc_points(rcs) records per set)
 static int tmsm_enqueue_piece(halo_ctx *ctx, MsmWorkspace &ws, const TblPlan &plan, const uint32_t *d_bases, const MsmBatch &members, size_t soff, bool mont,
                               size_t n, int piece, uint64_t *h_dst) {
     TblPlan tp = plan;
@@ -929,15 +901,14 @@ static int tmsm_enqueue_piece(halo_ctx *ctx, MsmWorkspace &ws, const TblPlan &pl
                 members.tagged ? 1 : 0, (uint32_t)n, tp, d_digits, ws.d_meta, ws.d_blockoff, ws.d_tblockoff);
     // from here on: ONE MSM of rows = count * W digit rows over sets * B buckets
     const uint32_t rows = (uint32_t)tp.W * (uint32_t)members.count;
-    tp.B *= cpow; tp.ranges *= cpow; tp.vw *= cpow;
+    tp.B *= cpow; tp.ranges *= cpow;
     for (uint32_t k = cpow; k > 1; k >>= 1) tp.rbits++;
     uint32_t nchunks = 256u / rows;  // 19 (17) chunks per window: about one block per CU
     uint32_t chunk_len = (uint32_t)((n + nchunks - 1) / nchunks);
     chunk_len = (chunk_len + 3) / 4 * 4;
     dim3 gridc((unsigned)(rows * nchunks)), b1024(1024), b256(256);
     uint32_t *chist = ws.d_hist, *cstart = ws.d_hist + (size_t)rows * nchunks * tp.ranges;  // <= 255 * 512 + 513 words <= cap_hist
-    const TblWinsum wsum = tmsm_winsum(ctx, plan, entries);
-    const uint32_t kmax = wsum.kmax;
+    const uint32_t kmax = tmsm_kmax(ctx, entries);
     const bool wide = tp.ranges > TBL_MAX_RANGES;  // (two bucket sets of the c = 20 plan: 1024 coarse ranges)
     if (wide) HALO_LAUNCH(ctx, "k_tmsm_coarse_hist2", k_tmsm_coarse_hist2, gridc, b1024, 0, d_digits, (uint32_t)n, nchunks, chunk_len, tp, chist);
     else HALO_LAUNCH(ctx, "k_tmsm_coarse_hist", k_tmsm_coarse_hist, gridc, b1024, 0, d_digits, (uint32_t)n, nchunks, chunk_len, tp, chist);
@@ -960,33 +931,17 @@ static int tmsm_enqueue_piece(halo_ctx *ctx, MsmWorkspace &ws, const TblPlan &pl
                 reinterpret_cast<const uint4 *>(ws.d_order), ws.d_buckets);
     HALO_LAUNCH(ctx, "k_msm_combine", k_msm_combine, dim3(512 + 1024), dim3(64), 0, ws.d_ntask, ws.d_toff, ws.d_tblockoff, ws.d_meta, ws.d_biglist,
                 total, 512u, ws.d_buckets);
-    // window sums: the buckets as tp.vw virtual windows of 2^vw_bits, 64 segments each (c = 20: 8 buckets per lane; c = 17: 1)
+    // window sums by rows and columns of the bucket index (k_msm_reduce_rc): rows + columns entries per set, then blocks of 64
+    // entries -> (S, T) pairs, combined on the host (msm_combine_member)
     const RcShape rcs = table_rc_shape(tp.c, tp.B / cpow, cpow);
-    if (rcs.per) {
-        // rows and columns of the bucket index (k_msm_reduce_rc): rows + columns entries per set, then blocks of 64 entries ->
-        // (S, T) pairs, combined on the host (msm_combine_member)
-        const uint32_t pts = rc_points(rcs) * cpow, nb = (tp.B / cpow) / (64u * (uint32_t)rcs.per);
-        uint64_t *d_rc = ws.d_winsum + (size_t)piece * pts * 12;
-        HALO_LAUNCH(ctx, "k_msm_reduce_rc", k_msm_reduce_rc, dim3(cpow * 2 * nb), dim3(64), 0, ws.d_buckets, ws.d_ntask, ws.d_toff, ws.d_tblockoff, rcs, ws.d_seg);
-        uint64_t *h_rc = h_dst + (size_t)piece * pts * 12;
-        int rc = rc_mid_enqueue(ctx, ws.d_seg, pts / 2, ctx->sink_done ? h_rc : d_rc, ctx->sink_done, ws.d_meta + 255);
-        if (rc) return rc;
-        HALO_HIP(hipGetLastError());
-        if (!ctx->sink_done) HALO_HIP(hipMemcpyAsync(h_rc, d_rc, (size_t)pts * 96, hipMemcpyDeviceToHost, s));
-        return HALO_OK;
-    }
-    uint64_t *d_out = ws.d_winsum + (size_t)piece * 2 * tp.vw * 12;
-    const uint32_t vwB = 1u << tp.vw_bits, L = wsum.L, nseg = wsum.nseg;
-    const int logL = wsum.logL;
-    HALO_LAUNCH(ctx, "k_msm_reduce1", k_msm_reduce1, dim3(tp.vw * nseg), dim3(64), 0, ws.d_buckets, ws.d_ntask, ws.d_toff, ws.d_tblockoff, vwB, L, logL,
-                nseg, ws.d_seg);
-    {
-        uint64_t *out = ctx->sink_done ? h_dst + (size_t)piece * 2 * tp.vw * 12 : d_out;
-        int rc = quad_final_enqueue(ctx, ws, tp.vw, nseg, logL + 6, out, out + 12 * tp.vw, nullptr, ctx->sink_done);
-        if (rc) return rc;
-    }
+    const uint32_t pts = rc_points(rcs) * cpow, nb = (tp.B / cpow) / (64u * (uint32_t)rcs.per);
+    uint64_t *d_rc = ws.d_winsum + (size_t)piece * pts * 12;
+    HALO_LAUNCH(ctx, "k_msm_reduce_rc", k_msm_reduce_rc, dim3(cpow * 2 * nb), dim3(64), 0, ws.d_buckets, ws.d_ntask, ws.d_toff, ws.d_tblockoff, rcs, ws.d_seg);
+    uint64_t *h_rc = h_dst + (size_t)piece * pts * 12;
+    int rc = rc_mid_enqueue(ctx, ws.d_seg, pts / 2, ctx->sink_done ? h_rc : d_rc, ctx->sink_done, ws.d_meta + 255);
+    if (rc) return rc;
     HALO_HIP(hipGetLastError());
-    if (!ctx->sink_done) HALO_HIP(hipMemcpyAsync(h_dst + (size_t)piece * 2 * tp.vw * 12, d_out, (size_t)2 * tp.vw * 96, hipMemcpyDeviceToHost, s));
+    if (!ctx->sink_done) HALO_HIP(hipMemcpyAsync(h_rc, d_rc, (size_t)pts * 96, hipMemcpyDeviceToHost, s));
     return HALO_OK;
 }
 

@@ -897,7 +897,7 @@ struct OpenGroups {
     const int *slots;  // the slots idle at entry; S of them are used
     int S;
     size_t n, lg, G, ms;
-    bool draw, commit, hiding, accumulated, dev_rows, u_from_last_round;  // draw: p from the stream; commit: C = commit(p) rides in step 0's MSM
+    bool draw, commit, hiding, accumulated, dev_rows;  // draw: p from the stream; commit: C = commit(p) rides in step 0's MSM
     OpenStage st;
     size_t nofold;  // the key size from which on the rounds fold no more (>= n: never folded, the no-fold form throughout)
     // M: points of the key the group's MSMs run over -- n over the context's key until the first fold, then each member's own staged
@@ -1143,7 +1143,7 @@ struct OpenGroups {
     // :230-231 as halo_ipa_finish: U from the last round's MSMs where both coefficients are non-zero, else U = <s, G> (one more step)
     int finish_u(int j, bool *through) {
         Flight &f = fl[j];
-        auto from_last_round = [&](const OpenJob &jb) { return u_from_last_round && !jb.c0.is_zero() && !jb.c1.is_zero(); };
+        auto from_last_round = [&](const OpenJob &jb) { return !jb.c0.is_zero() && !jb.c1.is_zero(); };
         pool_run(f.cnt, [&](size_t b) {
             OpenJob &jb = jobs[f.first + b];
             if (!from_last_round(jb)) return;
@@ -1258,7 +1258,7 @@ static int open_batch_dev(halo_ctx *ctx, size_t d, std::vector<OpenJob> &jobs, b
     *ran = true;
     const OpenStage st{ctx->d_check_stage, ctx->h_open_pinned, per, n, ms, G, fold_off, keystride};
     // (hiding: the same for every member of a batch)
-    OpenGroups groups{ctx, jobs, slots_in, S, n, lg, G, ms, draw, commit, jobs[0].hiding, accumulated, jobs[0].dev_row, tuning().u_from_last_round, st, ctx->nofold_size, {}};
+    OpenGroups groups{ctx, jobs, slots_in, S, n, lg, G, ms, draw, commit, jobs[0].hiding, accumulated, jobs[0].dev_row, st, ctx->nofold_size, {}};
     return groups.run();
 }
 

@@ -364,14 +364,15 @@ HALO_DEV void block_weighted_sum(XyzzN &S, XyzzN &T, int k, uint32_t *xch, uint3
 }
 
 // grid = Wt * nseg blocks of 64 quads; block (w, s) reduces the buckets [s * 64 L, (s + 1) * 64 L) of window w.
-// seg: Wt * nseg records of (S, T); done: one ticket counter per window (zeroed by k_msm_recode).
-template <bool FUSED>
+// ONE_SEG (nseg == 1): the block's sum is the window sum, written to winsum and published; otherwise it leaves its (S, T)
+// record in seg (Wt * nseg of them) for k_smsm_final.  ticket: the launch's publish counter (zeroed by k_msm_recode).
+template <bool ONE_SEG>
 __global__ __launch_bounds__(256, 2) void k_smsm_reduce(uint32_t *__restrict__ partial, const uint32_t *__restrict__ bk_first,
                                                         const uint32_t *__restrict__ bk_nt, uint32_t B, uint32_t L, int logL, uint32_t nseg,
-                                                        int live_seg, uint32_t *__restrict__ seg, uint32_t *__restrict__ done,
+                                                        uint32_t *__restrict__ seg, uint32_t *__restrict__ ticket,
                                                         uint64_t *__restrict__ winsum, uint32_t *__restrict__ published) {
     __shared__ uint32_t xch[64 * XYZZ_WORDS], parkS[64 * XYZZ_WORDS], parkT[64 * XYZZ_WORDS];
-    __shared__ uint32_t heavy[64], heavy_n, ticket;
+    __shared__ uint32_t heavy[64], heavy_n;
     uint32_t w = blockIdx.x / nseg, s = blockIdx.x % nseg;
     int tid = threadIdx.x, ql = tid & 3, Q = tid >> 2;
     uint32_t first = s * 64 * L + (uint32_t)Q * L;
@@ -445,39 +446,23 @@ __global__ __launch_bounds__(256, 2) void k_smsm_reduce(uint32_t *__restrict__ p
     }
     XyzzN tot;
     block_weighted_sum(run, tot, logL, xch, parkS, parkT, Q, ql, 64);
-    uint32_t *rec = seg + 2 * XYZZ_WORDS * ((size_t)w * nseg + s);
-    if (nseg > 1) {
+    if (!ONE_SEG) {  // k_smsm_final combines the segments
+        uint32_t *rec = seg + 2 * XYZZ_WORDS * ((size_t)w * nseg + s);
         if (Q == 0) {
             xyzz_store_quad(rec, run, ql);
             xyzz_store_quad(rec + XYZZ_WORDS, tot, ql);
         }
-        if (!FUSED) return;  // k_smsm_final combines the segments
-        // the last block of this window to get here combines the window's segments
-        __threadfence();
-        __syncthreads();
-        if (tid == 0) ticket = atomicAdd(&done[w], 1u);
-        __syncthreads();
-        if (ticket != nseg - 1) return;
-        __threadfence();
-        XyzzN S = xyzz_inf(), T = xyzz_inf();
-        if ((uint32_t)Q < nseg) {
-            const uint32_t *o = seg + 2 * XYZZ_WORDS * ((size_t)w * nseg + (uint32_t)Q);
-            S = xyzz_load(o);
-            T = xyzz_load(o + XYZZ_WORDS);
-        }
-        park_put(parkT, Q, ql, T);
-        block_weighted_sum(S, T, logL + 6, xch, parkS, parkT, Q, ql, live_seg);
-        tot = T;
+        return;
     }
     if (tid == 0) {
         xyzz_store_jac_words(winsum + 12 * (size_t)w, tot);
-        publish(published, done + 191, gridDim.x / nseg);  // (done = d_meta + 64: word 255 of the launch's small state)
+        publish(published, ticket, gridDim.x);
     }
 }
 
 // one block per window: the segments' (S, T) -> the window sum
 __global__ __launch_bounds__(256, 2) void k_smsm_final(const uint32_t *__restrict__ seg, uint32_t nseg, int k, int live_seg, uint64_t *__restrict__ winsum,
-                                                       uint64_t *__restrict__ winsum_plain, uint32_t *__restrict__ published, uint32_t *__restrict__ ticket) {
+                                                       uint32_t *__restrict__ published, uint32_t *__restrict__ ticket) {
     __shared__ uint32_t xch[64 * XYZZ_WORDS], parkS[64 * XYZZ_WORDS], parkT[64 * XYZZ_WORDS];
     uint32_t w = blockIdx.x;
     int tid = threadIdx.x, ql = tid & 3, Q = tid >> 2;
@@ -491,7 +476,6 @@ __global__ __launch_bounds__(256, 2) void k_smsm_final(const uint32_t *__restric
     block_weighted_sum(S, T, k, xch, parkS, parkT, Q, ql, live_seg);
     if (tid == 0) {
         xyzz_store_jac_words(winsum + 12 * (size_t)w, T);
-        if (winsum_plain) xyzz_store_jac_words(winsum_plain + 12 * (size_t)w, S);  // the unweighted sum (table pipeline)
         publish(published, ticket, gridDim.x);
     }
 }
@@ -499,13 +483,10 @@ __global__ __launch_bounds__(256, 2) void k_smsm_final(const uint32_t *__restric
 // ------------------------------------------------------------------------------ launch sequence
 // Called from msm_enqueue_launches (msm_general.hip) after k_msm_recode; digits are in ws.d_canon.  Buffer reuse: d_sorted
 // (entries), d_starts (first task of a bucket), d_counts (tasks of a bucket), d_task_g (task records), d_buckets
-// (partials), d_seg, d_meta[0] (task count), d_meta[64 + w] (tickets), d_winsum.
+// (partials), d_seg, d_meta[0] (task count), d_meta[255] (publish ticket), d_winsum.
 int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const MemberOffsets &offs, size_t n, MsmPlan &p, uint32_t Wt,
                  uint32_t kmax) {
     const uint16_t *d_digits = reinterpret_cast<const uint16_t *>(ws.d_canon);
-    // entries per wave task: 8 per lane where the launch is throughput-bound, 2 per lane for the latency-bound small ones
-    const int wt_env = tuning().smsm_wave_task;  // development override
-    uint32_t wave_task = wt_env > 0 ? (uint32_t)wt_env : WAVE_TASK;
     // bucket ranges per window: enough blocks that one CU issues at most ~8K LDS atomics per pass
     uint32_t R = 1;
     while (R < 8 && p.B / (2 * R) >= 64 && n / R > 8192) R <<= 1;
@@ -527,12 +508,12 @@ int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const
             if (top_span - (R - 1) * top_rb > p.B / R) top_rb = (top_span + R - 1) / R;  // the last block's stretch must fit its histogram
         }
     }
-    HALO_LAUNCH(ctx, "k_smsm_sort", k_smsm_sort, dim3(Wt * R), dim3(1024), lds, d_digits, (uint32_t)n, p.B, R, kmax, wave_task, top_w, Wm, top_span, top_rb,
+    HALO_LAUNCH(ctx, "k_smsm_sort", k_smsm_sort, dim3(Wt * R), dim3(1024), lds, d_digits, (uint32_t)n, p.B, R, kmax, WAVE_TASK, top_w, Wm, top_span, top_rb,
                 offs, ws.d_sorted, ws.d_starts, ws.d_counts, ws.d_task_g, ws.d_order, ws.d_biglist, ws.d_meta);
     size_t max_tasks = (size_t)Wt * p.B + n * (size_t)Wt / kmax + 1;
     if (max_tasks > ws.cap_tasks || max_tasks > ws.cap_counts) { set_error("msm: small-path tasks exceed the workspace"); return HALO_E_ARG; }
     // wave tasks: one per bucket of more than 4 kmax entries plus one per further WAVE_TASK entries (3 words each in d_order)
-    size_t max_wave = (size_t)Wt * n / (4 * (size_t)kmax) + (size_t)Wt * n / wave_task + 1;
+    size_t max_wave = (size_t)Wt * n / (4 * (size_t)kmax) + (size_t)Wt * n / WAVE_TASK + 1;
     if (3 * max_wave > ws.cap_tasks) { set_error("msm: small-path wave tasks exceed the workspace"); return HALO_E_ARG; }
     unsigned lane_blocks = (unsigned)((max_tasks + 255) / 256), wave_blocks = (unsigned)((max_wave + 3) / 4);
     HALO_LAUNCH(ctx, "k_smsm_accumulate", k_smsm_accumulate, dim3(lane_blocks + wave_blocks), dim3(256), 0, d_bases, ws.d_sorted, ws.d_task_g,
@@ -540,12 +521,9 @@ int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const
     // 64 quads per block, L buckets per quad, at most 16 segments per window
     uint32_t L = 1;
     while ((size_t)64 * L * 16 < p.B) L <<= 1;
-    {
-        // ... and no more blocks than give every SIMD one wave (4 waves per block): with 1.6 waves per SIMD the SIMDs that
-        // hold two ran every step of the chain at half speed, and the kernel waits for them
-        const int waves_env = tuning().smsm_waves;  // development switch (0: off)
-        while (waves_env > 0 && L < 64 && (size_t)Wt * ((p.B + 64 * L - 1) / (64 * L)) * 4 > (size_t)waves_env && (size_t)64 * L < p.B) L <<= 1;
-    }
+    // ... and no more blocks than give every SIMD one wave (4 waves per block): with 1.6 waves per SIMD the SIMDs that
+    // hold two ran every step of the chain at half speed, and the kernel waits for them
+    while (L < 64 && (size_t)Wt * ((p.B + 64 * L - 1) / (64 * L)) * 4 > REDUCE_WAVES && (size_t)64 * L < p.B) L <<= 1;
     if (ctx->reduce_span > 0) {
         L = (uint32_t)ctx->reduce_span;
         while ((size_t)64 * L * 64 < p.B) L <<= 1;  // the final stage holds at most 64 segments
@@ -555,31 +533,28 @@ int smsm_enqueue(halo_ctx *ctx, MsmWorkspace &ws, const uint32_t *d_bases, const
     while ((1u << logL) < L) logL++;
     while ((uint32_t)live_seg < nseg) live_seg <<= 1;
     p.pipeline = 1; p.winsum_form = 1; p.kmax = kmax; p.red_L = L; p.red_nseg = nseg; p.red_logL = logL; p.red_live_seg = live_seg;
-    // (the fused form's per-window tickets are done[w] = d_meta[64 + w]: d_meta has 256 words, all zeroed by the recode, and word
-    // 255 is the publish ticket -- more than 191 windows keep the two-launch form)
-    const bool fused = tuning().smsm_fused && Wt <= 191;
-    // (one thread per window writes its sum: straight to the slot's pinned buffer when the launch publishes, see publish())
+    // (one thread per window writes its sum: straight to the slot's pinned buffer when the launch publishes, see publish();
+    // word 255 of the launch's small state is the publish ticket)
     uint64_t *out = ctx->sink_done ? ws.h_winsum : ws.d_winsum;
-    if (fused || nseg == 1) {
-        HALO_LAUNCH(ctx, "k_smsm_reduce", k_smsm_reduce<true>, dim3(Wt * nseg), dim3(256), 0, ws.d_buckets, ws.d_starts, ws.d_counts, p.B, L, logL, nseg,
-                    live_seg, ws.d_seg, ws.d_meta + 64, out, ctx->sink_done);
+    if (nseg == 1) {
+        HALO_LAUNCH(ctx, "k_smsm_reduce", k_smsm_reduce<true>, dim3(Wt), dim3(256), 0, ws.d_buckets, ws.d_starts, ws.d_counts, p.B, L, logL, nseg,
+                    ws.d_seg, ws.d_meta + 255, out, ctx->sink_done);
     } else {
         HALO_LAUNCH(ctx, "k_smsm_reduce", k_smsm_reduce<false>, dim3(Wt * nseg), dim3(256), 0, ws.d_buckets, ws.d_starts, ws.d_counts, p.B, L, logL, nseg,
-                    live_seg, ws.d_seg, ws.d_meta + 64, out, (uint32_t *)nullptr);
-        HALO_LAUNCH(ctx, "k_smsm_final", k_smsm_final, dim3(Wt), dim3(256), 0, ws.d_seg, nseg, logL + 6, live_seg, out, (uint64_t *)nullptr, ctx->sink_done, ws.d_meta + 255);
+                    ws.d_seg, ws.d_meta + 255, out, (uint32_t *)nullptr);
+        HALO_LAUNCH(ctx, "k_smsm_final", k_smsm_final, dim3(Wt), dim3(256), 0, ws.d_seg, nseg, logL + 6, live_seg, out, ctx->sink_done, ws.d_meta + 255);
     }
     if (ctx->sink_done) ctx->sink_publishers += 1;
     return HALO_OK;
 }
 
-// The last step of the sorted pipelines of msm_general.hip and msm_table.hip as well: the (S, T) records k_msm_reduce1 left per segment (nseg <= 64
+// The last step of the general pipeline (msm_general.hip) as well: the (S, T) records k_msm_reduce1 left per segment (nseg <= 64
 // per window, 2^k buckets each) -> window sums.  A chain of ~20 dependent point operations run by Wt blocks: the quad
 // form takes 80 us where one wave per window took 130.
-int quad_final_enqueue(halo_ctx *ctx, MsmWorkspace &ws, uint32_t Wt, uint32_t nseg, int k, uint64_t *winsum, uint64_t *winsum_plain,
-                       const uint32_t *seg, uint32_t *done) {
+int quad_final_enqueue(halo_ctx *ctx, MsmWorkspace &ws, uint32_t Wt, uint32_t nseg, int k, uint64_t *winsum, uint32_t *done) {
     int live_seg = 1;
     while ((uint32_t)live_seg < nseg) live_seg <<= 1;
-    HALO_LAUNCH(ctx, "k_smsm_final", k_smsm_final, dim3(Wt), dim3(256), 0, seg ? seg : ws.d_seg, nseg, k, live_seg, winsum, winsum_plain, done, ws.d_meta + 255);
+    HALO_LAUNCH(ctx, "k_smsm_final", k_smsm_final, dim3(Wt), dim3(256), 0, ws.d_seg, nseg, k, live_seg, winsum, done, ws.d_meta + 255);
     if (done) ctx->sink_publishers += 1;
     return HALO_OK;
 }

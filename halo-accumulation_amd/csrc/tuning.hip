@@ -16,7 +16,6 @@ size_t parse_bytes(const char *e) {  // "48G", "512M", plain bytes
     return v > 0 ? (size_t)v : 0;
 }
 int env_int(const char *name, int dflt) { const char *e = getenv(name); return e ? atoi(e) : dflt; }
-bool env_off(const char *name) { const char *e = getenv(name); return e && atoi(e) == 0; }  // "=0" switches a default-on path off
 Tuning read_env() {
     Tuning t;
     t.trace = getenv("HALO_TRACE") != nullptr;
@@ -44,10 +43,6 @@ Tuning read_env() {
         else fprintf(stderr, "[halo] HALO_HOST_SPLIT=%s ignored: 1 to 4 positive numbers of sixteenths that add up to 16\n", e);
     }
     t.fold_table_after = env_int("HALO_FOLD_TABLE_AFTER", t.fold_table_after);
-    t.plan = getenv("HALO_PLAN");
-    t.dots_first = env_int("HALO_DOTS_FIRST", -1);
-    t.ipa_c_hint = !env_off("HALO_IPA_C_HINT");
-    t.u_from_last_round = !env_off("HALO_U_FROM_LAST_ROUND");
     t.pow_e = env_int("HALO_POW_E", 0);
     if (t.pow_e != 0 && (t.pow_e < 4 || t.pow_e > 64 || (t.pow_e & (t.pow_e - 1)) != 0)) {
         // k_h_coeffs relies on a chain length that is a power of two (its mid * high factor is wave-uniform and changes every
@@ -62,20 +57,6 @@ Tuning read_env() {
         fprintf(stderr, "[halo] HALO_DOT_BLOCKS=%d clamped to %d: the block cap must be in [1, %d]\n", t.dot_blocks, clamped, FR_GRID_CAP);
         t.dot_blocks = clamped;
     }
-    t.smsm_kmax = env_int("HALO_SMSM_KMAX", 0);
-    t.late_kmax = env_int("HALO_LATE_KMAX", 0);
-    t.piece_alternate = !env_off("HALO_PIECE_ALTERNATE");
-    t.graph_cache = env_int("HALO_GRAPH_CACHE", t.graph_cache);
-    if (t.graph_cache < 1) t.graph_cache = 1;
-    if (t.graph_cache > 8) t.graph_cache = 8;
-    t.direct_results = !env_off("HALO_DIRECT_RESULTS");
-    t.tagged = !env_off("HALO_TAGGED");
-    t.reduce_rc = !env_off("HALO_REDUCE_RC");
-    t.reduce1_waves = env_int("HALO_REDUCE1_WAVES", t.reduce1_waves);
-    t.smsm_wave_task = env_int("HALO_SMSM_WAVE_TASK", 0);
-    t.smsm_waves = env_int("HALO_SMSM_WAVES", t.smsm_waves);
-    t.smsm_fused = env_int("HALO_SMSM_FUSED", 0) != 0;
-    t.host_inv_fermat = getenv("HALO_HOST_INV_FERMAT") != nullptr;
     t.spin_us = env_int("HALO_SPIN_US", t.spin_us);
     return t;
 }
@@ -85,7 +66,6 @@ const Tuning &tuning() {
     static const Tuning t = read_env();
     return t;
 }
-namespace host { bool host_inv_fermat() { return tuning().host_inv_fermat; } }  // (host_math.hpp Fp::inv)
 DevHooks &dev_hooks() {
     static DevHooks h;
     return h;

@@ -63,7 +63,7 @@ int halo_dev_fr_plan(halo_ctx *ctx, int which, size_t n, long out[4]);
  * rounds themselves only ever reach powers of two; m = 0 gives zeros. */
 int halo_dev_dot2_cross(halo_ctx *ctx, const uint64_t *c, const uint64_t *z, size_t m, uint64_t out[8]);
 /* What the library read from the environment at its first use (csrc/tuning.hip), by field: "host_split_set", "host_pieces", "host_split0".."host_split3",
- * "fold_table_after", "graph_cache", "pow_e", "dot_blocks", "spin_us", "graphs", "memory_budget" (MiB, -1 unset), "trace", "tagged"; -1 for an
+ * "fold_table_after", "pow_e", "dot_blocks", "spin_us", "graphs", "memory_budget" (MiB, -1 unset), "trace"; -1 for an
  * unknown name.  Also "commit_batch_group" and "open_batch_fold": those hooks of halo_dev_hook as they stand now (0 after "reset").
  * Host only. */
 long halo_dev_tuning(const char *name);
@@ -225,10 +225,11 @@ int halo_dev_table_read(halo_ctx *ctx, size_t row, size_t off, size_t count, uin
  *   [4] members  [5] sets          MSMs of the launch; bucket sets of a table launch (members rounded up to a power of two)
  *   [6] pieces                     consecutive pieces of a large table MSM
  *   [7] kmax                       longest chain of the bucket kernel: a bucket of more entries is several tasks
- *   [8] window-sum form: 0 k_msm_reduce1 + k_smsm_final, 1 k_smsm_reduce (+ k_smsm_final, or fused), 2 k_msm_reduce_rc + k_rc_mid
+ *   [8] window-sum form: 0 k_msm_reduce1 + k_smsm_final, 1 k_smsm_reduce (+ k_smsm_final beyond one segment), 2 k_msm_reduce_rc +
+ *       k_rc_mid (every table launch)
  *   [9] L  [10] logL  [11] nseg  [12] live_seg    forms 0 and 1: buckets per lane (quad), segments per window, the final stage's width
- *   [13] vw  [14] vw_bits          table with fixed windows: virtual windows per set, log2 of their buckets
- *   [15] form 2: lg_rows | lg_cols << 8 | per << 16 (rows x columns of the bucket index, buckets per lane); else 0
+ *   [13] form 2: lg_rows | lg_cols << 8 | per << 16 (rows x columns of the bucket index, buckets per lane); else 0
+ *   [14] [15] 0 (not used)
  * A launch of no points, or a window shard without windows, reports W = 0.  HALO_E_ARG: a slot out of range, a slot in flight, no
  * launch on the slot yet (or its last one refused), a null `out`. */
 int halo_dev_msm_last_plan(halo_ctx *ctx, int slot, long out[16]);
@@ -236,9 +237,7 @@ int halo_dev_msm_last_plan(halo_ctx *ctx, int slot, long out[16]);
  * points (X | Y | Z, Montgomery words, Z = 0: infinity), exactly what the host's combination (msm_combine_member) reads.  *count =
  * their number; by window-sum form of halo_dev_msm_last_plan:
  *   general and small pipeline   members x (w1 - w0) weighted sums sum_b (b + 1) B_b, [member][w]
- *   table, fixed windows         per piece: sets x vw weighted sums [set][v] (weights 1 .. 2^vw_bits inside virtual window v), then
- *                                sets x vw plain sums sum_b B_b in the same order
- *   table, rows and columns      per piece and set: the pairs (S, T) = (sum_Q E_Q, sum_Q (Q + 1) E_Q) of the 64-entry blocks of the
+ *   table (both pipelines)       per piece and set: the pairs (S, T) = (sum_Q E_Q, sum_Q (Q + 1) E_Q) of the 64-entry blocks of the
  *                                columns' plain sums C_lo (2^lg_cols / 64 pairs), then those of the rows' R_hi (2^lg_rows / 64 pairs)
  * HALO_E_ARG: a slot out of range, a slot in flight, no launch yet, a null pointer, cap_points below the number of records -- *count
  * is set in that case too. */

@@ -86,6 +86,30 @@ def test_general_pipeline_every_site_and_class(hal, c, span):
         ctx.close()
 
 
+@pytest.mark.parametrize("span,L,nseg", wc.REDUCE1_SPANS)
+def test_general_pipeline_at_2_15_buckets_per_window(hal, span, L, nseg):
+    """k_msm_reduce1 + k_smsm_final at c = 16, the plan of every table-free MSM of 2^20 points or more: 8 buckets per lane and 64
+    segments, and under reduce span 64 the reverse -- equal and opposite lane sums and segment sums at every level of both scans"""
+    launch = wc.reduce1_launch(span)
+    assert (launch.plan["L"], launch.plan["nseg"]) == (L, nseg)
+    for kern, live in ((wc.K_REDUCE1, 64), (wc.K_FINAL, nseg)):
+        off = 1
+        while off < live:
+            for cl in ("P+P", "P-P"):
+                assert launch.counts.get((kern, "scan/%d" % off, cl), 0), (kern, off, cl)
+            off <<= 1
+    key = wc.multiples_key(len(launch.ks), launch.ks)
+    ctx = hal.Context(key)
+    try:
+        ctx.set_small_path(0)
+        ctx.set_window_bits(wc.REDUCE1_C)
+        ctx.set_reduce_span(span)
+        run_three_times(ctx, key, launch.scalars, plan_fields(launch.plan, 8), launch.values)
+    finally:
+        reset_knobs(ctx)
+        ctx.close()
+
+
 @pytest.mark.parametrize("sort_mode", [0, 1])
 def test_combine_equal_opposite_and_infinite_partials(hal, sort_mode):
     """k_msm_combine under a task length of 8: buckets of 2, 8, 9, 64 and 65 equal tasks, the two-task P-P bucket, a cancellation at
@@ -366,43 +390,3 @@ def test_plan_and_window_sum_hooks_misuse_is_reported(hal):
         assert c.msm_last_plan(0)["W"] == 0 and c.msm_window_sums(0).shape == (0, 12)
     finally:
         c.close()
-
-
-# ---------------------------------------------------------------------------------------------------- the older table form
-VW_PLAN = dict(pipeline=2, form=0, c=20, W=13, B=1 << 19, members=1, sets=1, pieces=1, kmax=16, vw=16, vw_bits=15)
-
-
-def rc_off_main():
-    """(in a process of its own, started with HALO_REDUCE_RC=0: the library reads the switch once, when it loads)"""
-    import halo_accumulation_amd as h
-    hal = h._lib
-    hal.dev_hook("table_slide_min", 4096)
-    ks, launch = wc.fixed_launch()
-    key = wc.multiples_key(len(ks), ks)
-    ctx = hal.Context(key)
-    try:
-        for span, L in ((0, 8), (16, 16), (32, 32), (64, 64)):
-            ctx.set_reduce_span(span)
-            run_three_times(ctx, key, launch.scalars, dict(VW_PLAN, L=L, nseg=512 // L, live_seg=512 // L), [launch.values])
-            assert ctx.info(9) == FIXED
-        ctx.set_reduce_span(0)
-        for name, extra in wc.vw_extra_launches()[1]:  # the host's running sums, site by site
-            run_three_times(ctx, key, extra.scalars, dict(VW_PLAN, L=8, nseg=64, live_seg=64), [extra.values], same_words=False)
-    finally:
-        reset_knobs(ctx)
-        ctx.close()
-    print("rc-off ok")
-
-
-def test_virtual_window_form_of_the_table_plan():
-    """HALO_REDUCE_RC=0 (a development switch of the environment): the c = 20 plan's window sums as k_msm_reduce1 over 16 virtual
-    windows of 2^15 buckets (L = 8 and 64 segments; reduce spans 16, 32, 64) + k_smsm_final with its plain sums, and the host's
-    running sums over them -- equal and opposite lane and segment sums at every level, equal neighbouring plain sums"""
-    import os
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    code = "import sys; sys.path[:0] = [%r, %r, %r]; import test_gpu_window_sums as t; t.rc_off_main()" % (
-        os.path.dirname(here), os.path.join(os.path.dirname(here), "oracle"), here)
-    p = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, HALO_REDUCE_RC="0"), capture_output=True, text=True, timeout=300)
-    assert p.returncode == 0 and "rc-off ok" in p.stdout, p.stdout[-2000:] + p.stderr[-4000:]

@@ -30,7 +30,7 @@ def test_the_coverage_table_is_complete():
 
 def test_the_planted_launches_meet_every_class_at_every_site():
     """the launches planted by hand -- k_msm_combine, the partial loop and the heavy pre-sum of k_smsm_reduce, k_msm_reduce_rc in its
-    five shapes, the host's Horner, its row / column forms and its running sums over virtual windows -- meet P+P, P-P, inf+Q and
+    five shapes, the host's Horner and its row / column forms -- meet P+P, P-P, inf+Q and
     Q+inf at every site, with no exemption.  Cells marked * : the sort's atomics decide which task holds the odd entry, both
     placements are counted, and a run on the device meets one of the two (EITHER_SIDE)"""
     counts = wc.planted_counts()
@@ -46,7 +46,7 @@ def test_the_planted_launches_meet_every_class_at_every_site():
         assert all(("k_msm_reduce_rc", "%s tree/%d" % (name, 32 >> t)) in sites for t in range(6))
     assert all((wc.K_COMBINE, "tree/%d" % (32 >> t)) in sites and (wc.K_SREDUCE, "heavy tree/%d" % (32 >> t)) in sites for t in range(6))
     for site in ("cols t+=T", "cols run+=S", "cols tot+=run", "cols t+tot", "rows t+=T", "rows run+=S", "rows tot+=run", "rows t+tot", "cols - plain",
-                 "rows - plain", "cw + rw", "+ s_all", "cols + rows", "vw acc+=T", "vw run+=S", "vw tot+=run", "vw acc+tot", "horner"):
+                 "rows - plain", "cw + rw", "+ s_all", "cols + rows", "horner"):
         assert (wc.K_HOST, site) in sites, site
     missing = [(k, s, cl) for k, s in sites for cl in wc.EDGE if not counts.get((k, s, cl))]
     assert not missing, missing
@@ -113,8 +113,6 @@ def test_the_models_against_pallas_model(pipeline):
                 plan = dict(pipeline=pipe, form=2, lg_rows=lg_rows, lg_cols=lg_cols)
                 vals = values if pipe == 2 else {(c << lg_rows) + r: x for (r, c), x in cells.items()}
                 _replay(lambda rec, cv: wc.model_host_rc(rec, plan, vals, cv), to_point)
-            vw = {(int(rng.next_u64() % 4) << 3) + int(rng.next_u64() % 8): x for x in _small_values(rng, 12) if x}
-            _replay(lambda rec, cv: wc.model_host_vw(rec, dict(pipeline=2, form=0, vw=4, vw_bits=3), vw, cv), to_point)
         g, k = wc.COMBINE_G, wc.COMBINE_KMAX
         for tasks in ([k * g] * 65, [0] + [k * g] * 63, [k * g] * 127 + [-k * g], [-24 * g] + [k * g] * 63, [k * g, 0], [0, 0]):
             _replay(lambda rec, cv: wc.model_combine(rec, [cv(x) for x in tasks]), to_point)
@@ -140,7 +138,6 @@ def _records(plan, values):
 
 CHECKER_PLANS = [
     (dict(pipeline=0, form=0), [{0: 5, 3: -2}, {1: 7}, {}, {63: 1, 2: 9}]),
-    (dict(pipeline=2, form=0, vw=16, vw_bits=15), [{5: 3, (3 << 15) + 9: -4, (15 << 15) + 32767: 2}]),
     (dict(pipeline=3, form=2, lg_rows=9, lg_cols=10), [{5: 3, (700 << 9) + 300: -4, (1023 << 9) + 511: 2, 513: 6}]),
     (dict(pipeline=2, form=2, lg_rows=8, lg_cols=8), [{5: 3, 65535: 2}, {77: -1, 300: 8}]),
 ]
@@ -190,10 +187,11 @@ def test_the_planted_scalars_give_the_digits_claimed():
         for launch in launches:
             launch.ks = ks
             _check_digits(launch)
-    for launch in (wc.combine_launch(), wc.horner_launch(7), wc.horner_launch(13), wc.partials_launch(), wc.heavy_launch(), wc.strided_launch()):
+    for launch in (wc.combine_launch(), wc.horner_launch(7), wc.horner_launch(13), wc.partials_launch(), wc.heavy_launch(), wc.strided_launch(),
+                   wc.reduce1_launch(0), wc.reduce1_launch(64)):
         _check_digits(launch)
     # the fixed windows of the table plan: one digit in window 0
-    fixed = [wc.fixed_launch()[1]] + [l for _, l in wc.vw_extra_launches()[1] + wc.extra_host_launches("fixed")[1]] + [wc.slide_structure_launch("fixed")[1]]
+    fixed = [l for _, l in wc.extra_host_launches("fixed")[1]] + [wc.slide_structure_launch("fixed")[1]]
     for launch in fixed:
         for s in launch.scalars:
             dg = wc.recode_digits(s, 20)

@@ -23,8 +23,8 @@ the general pipeline, of k_smsm_reduce and k_smsm_final in the small one over si
 with the model counting what they meet: k_msm_combine (combine_launch), the partial loop and the heavy-bucket pre-sum of
 k_smsm_reduce (partials_launch, heavy_launch, strided_launch), k_msm_reduce_rc in its five shapes (structure_cells; small_key_batches for the 256 x
 256 shape of the small-key plan, one member and batches), the host's Horner (horner_launch), its row / column forms
-(slide_host_launches, extra_host_launches) and its running sums over virtual windows (fixed_launch, vw_extra_launches);
-planted_counts is their coverage table.  Where a bucket has several tasks the entries are
+(slide_host_launches, extra_host_launches) and k_msm_reduce1 + k_smsm_final at 2^15 buckets per window (reduce1_launch);
+planted_counts is the coverage table of the others.  Where a bucket has several tasks the entries are
 all equal, or one odd entry is sized so that the class falls on a known level whichever task receives it: the sorts place the
 entries of a bucket with atomics."""
 import numpy as np
@@ -1182,28 +1182,6 @@ def extra_host_launches(layout="slide"):
     return table_key()[0], out
 
 
-VW_CASES = [  # {(virtual window, bucket in it): m}: acc += T_v upwards; run += S_v, tot += run from the top down to 1; acc + 2^15 tot
-    ("acc+=T P+P", {(0, 0): 1, (1, 0): 1}), ("acc+=T P-P, acc + tot inf+Q", {(0, 0): -1, (1, 0): 1}), ("acc+=T Q+inf, acc + tot Q+inf", {(0, 0): 1}),
-    ("run+=S P-P, tot+=run Q+inf", {(15, 0): 1, (14, 0): -1}), ("tot+=run P+P", {(15, 0): 1}), ("tot+=run P-P", {(15, 0): 1, (14, 0): -2}),
-    ("acc + tot P+P", {(1, 32767): 1}), ("acc + tot P-P", {(1, 0): 1, (0, 32767): -1, (0, 0): -1}),
-]
-
-
-def vw_extra_launches():
-    """the host's running sums over the virtual windows, site by site (the form behind HALO_REDUCE_RC=0)"""
-    ks, lay = table_key()
-    out = []
-    for name, cells in VW_CASES:
-        plus = list(range(lay["plus"], lay["plus"] + T_PLUS))
-        minus = list(range(lay["minus"], lay["minus"] + T_MINUS))
-        buckets = {}
-        for (v, b), m in cells.items():
-            for i in _pattern(plus, minus, [1 if m > 0 else -1] * abs(m)):
-                buckets[i] = (v << 15) + b
-        out.append((name, TableLaunch(ks, buckets, fixed_scalar)))
-    return ks, out
-
-
 SMALL_KEY_N = 1 << 17        # the small-key plan (c = 17, 256 x 256) takes keys of 2^17 .. 2^20 points, whole or at least half
 
 
@@ -1320,24 +1298,35 @@ def strided_launch(c=10):
     return PlantedLaunch(plan, ks, digits, values, rec.counts)
 
 
-def fixed_launch():
-    """the fixed windows in their older form (HALO_REDUCE_RC=0, read when the library loads: k_msm_reduce1 over 16 virtual windows of
-    2^15 buckets + k_smsm_final + the host's running sums), planted by hand over points +-g G in the first bucket of a lane (bucket 8 l of a segment) or of a segment (512 s):
-    virtual window 0 the 64 lanes of segment 0 all equal, 1 .. 6 with the sign of bit 32 >> t of the lane; 7 the 64 segments all equal,
-    8 .. 13 with the sign of bit 32 >> t of the segment; 14 and 15 one equal point each: equal neighbouring plain sums S_v for the
-    host's running sums.  Under another reduce span the same buckets fall on other lanes and segments."""
-    ks, lay = table_key()
-    plus = list(range(lay["plus"], lay["plus"] + T_PLUS))
-    minus = list(range(lay["minus"], lay["minus"] + T_MINUS))
-    buckets = {}
-    for v in range(14):
-        step, t = (8, v) if v < 7 else (512, v - 7)
-        for k in range(64):
-            sg = 1 if t == 0 or not k & (64 >> t) else -1
-            buckets[_pattern(plus, minus, [sg])[0]] = (v << 15) + step * k
-    buckets[plus.pop()] = (14 << 15) + 77
-    buckets[plus.pop()] = (15 << 15) + 4099
-    return ks, TableLaunch(ks, buckets, fixed_scalar)
+REDUCE1_C = 16               # the general pipeline's plan for every table-free MSM of >= 2^20 points: 2^15 buckets per window
+REDUCE1_SPANS = [(0, 8, 64), (64, 64, 8)]   # (reduce span, L, nseg) of its k_msm_reduce1 + k_smsm_final
+
+
+def reduce1_launch(span):
+    """k_msm_reduce1 + k_smsm_final at 2^15 buckets per window, planted by hand over 64 points +g G and 64 points -g G, one point in
+    the first bucket of a lane (bucket L l of segment 0) or of a segment (64 L s).  Window 0: the 64 lanes all equal, windows 1 .. 6:
+    with the sign of bit 32 >> t of the lane -- equal and opposite lane sums at every level of the wave's scan and tree; then the
+    segments all equal and, one window per level of k_smsm_final, with the sign of bit nseg >> t of the segment.  Point l (64
+    + l for the minus sign) serves lane or segment l of every window: the key has 128 points."""
+    plan = general_plan(REDUCE1_C, span)
+    L, nseg, g = plan["L"], plan["nseg"], COMBINE_G
+    ks = [g] * 64 + [-g] * 64
+    digits, values = [dict() for _ in ks], []
+    levels = nseg.bit_length() - 1
+    for w in range(7 + 1 + levels):
+        step, units, t = (L, 64, w) if w < 7 else (64 * L, nseg, w - 7)
+        v = {}
+        for k in range(units):
+            neg = t > 0 and bool(k & (units >> t))
+            digits[64 + k if neg else k][w] = step * k + 1
+            v[step * k] = -g if neg else g
+        values.append(v)
+    assert len(values) <= plan["W"] - 1
+    rec = IntRec()
+    for w, v in enumerate(values):
+        model_window(rec, plan, [v.get(b, 0) for b in range(plan["B"])], w)
+    values += [{}] * (plan["W"] - len(values))
+    return PlantedLaunch(plan, ks, digits, values, rec.counts)
 
 
 # ---------------------------------------------------------------------------------------------------- the host's table forms
@@ -1380,32 +1369,14 @@ def model_host_rc(rec, plan, values, cv=lambda m: m):
     return rec.add(K_HOST, "cols + rows", wc_, rows)
 
 
-def model_host_vw(rec, plan, values, cv=lambda m: m):
-    """msm_combine_member over the virtual windows' weighted and plain sums of one set (one piece)"""
-    recs = [cv(m) for _, m in expected_records(dict(plan, pieces=1), [values])]
-    V = plan["vw"]
-    acc = run = tot = rec.zero
-    for v in range(V):
-        acc = rec.add(K_HOST, "vw acc+=T", acc, recs[v], v)
-    for v in range(V - 1, 0, -1):
-        run = rec.add(K_HOST, "vw run+=S", run, recs[V + v], v)
-        tot = rec.add(K_HOST, "vw tot+=run", tot, run, v)
-    for k in range(plan["vw_bits"]):
-        if not rec.is_inf(tot):
-            tot = rec.dbl(K_HOST, "vw dbl", tot)
-    return rec.add(K_HOST, "vw acc+tot", acc, tot)
-
-
 PLAN_OF_LAYOUT = {"slide": dict(pipeline=3, form=2, lg_rows=9, lg_cols=10), "fixed": dict(pipeline=2, form=2, lg_rows=9, lg_cols=10),
                   "small": dict(pipeline=2, form=2, lg_rows=8, lg_cols=8)}
-VW_MODEL_PLAN = dict(pipeline=2, form=0, vw=16, vw_bits=15)
 
 
 def planted_counts():
     """what the launches planted by hand meet, by the models: {(kernel, site, class): count}, over every launch of the GPU module --
     k_msm_combine (combine_launch), the partial loop and the heavy pre-sum of k_smsm_reduce (partials_launch, heavy_launch, strided_launch),
-    k_msm_reduce_rc in its five shapes, the host's Horner, its row / column forms over every table launch and its running sums over
-    the virtual windows.  Where the sort's atomics decide which task holds an odd entry the launch is counted with it first and with
+    k_msm_reduce_rc in its five shapes, the host's Horner and its row / column forms over every table launch.  Where the sort's atomics decide which task holds an odd entry the launch is counted with it first and with
     it last: the device meets one of the two."""
     rec = IntRec()
     for launch in (combine_launch(), partials_launch(), heavy_launch(), strided_launch(), horner_launch(7), horner_launch(13)):
@@ -1422,8 +1393,6 @@ def planted_counts():
                 tables.append(("small", l))
     for layout, l in tables:
         assert abs(model_host_rc(rec, PLAN_OF_LAYOUT[layout], l.values)) < LIMIT
-    for l in [fixed_launch()[1]] + [l for _, l in vw_extra_launches()[1]]:
-        model_host_vw(rec, VW_MODEL_PLAN, l.values)
     return {k: n for k, n in rec.counts.items() if k[0] in (K_COMBINE, K_HOST, "k_msm_reduce_rc") or k[1].startswith(("partial", "heavy"))}
 
 
@@ -1449,17 +1418,6 @@ def expected_records(plan, values):
             out.append(("window %d" % r, sum((b + 1) * x for b, x in v.items())))
         return out
     assert plan.get("pieces", 1) == 1
-    if plan["form"] == 0:  # table with fixed windows: sets x vw weighted sums, then sets x vw plain sums
-        bits, vw = plan["vw_bits"], plan["vw"]
-        weighted, plain = [], []
-        for s, v in enumerate(values):
-            T, S = [0] * vw, [0] * vw
-            for b, x in v.items():
-                T[b >> bits] += ((b & ((1 << bits) - 1)) + 1) * x
-                S[b >> bits] += x
-            weighted += [("set %d virtual window %d weighted" % (s, q), T[q]) for q in range(vw)]
-            plain += [("set %d virtual window %d plain" % (s, q), S[q]) for q in range(vw)]
-        return weighted + plain
     lg_rows, lg_cols = plan["lg_rows"], plan["lg_cols"]
     rows, cols = 1 << lg_rows, 1 << lg_cols
     for s, v in enumerate(values):

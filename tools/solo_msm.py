@@ -1,5 +1,5 @@
 """Latency of ONE halo_msm_dev call at n = 2^lg, nothing else in flight (median of K), and the result's first words.
-Usage: solo_msm.py LG [K=12]   (HALO_PIECE_ALTERNATE=0: the pieces of a large MSM one after the other)"""
+Usage: solo_msm.py LG [K=12]"""
 import sys, os, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
