@@ -189,6 +189,7 @@ _DEV_SIGS = {
     "halo_dev_small_msm_seg": (C.c_int, [C.c_void_p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, u64p]),
     "halo_dev_batch_small_msm": (C.c_int, [C.c_void_p, u64p, u64p, C.c_size_t, C.c_size_t, u64p]),
     "halo_dev_batch_to_affine": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p]),
+    "halo_dev_transcripts": (C.c_int, [C.c_void_p, C.c_size_t, u64p, C.c_size_t, C.c_int, u64p, u64p, C.POINTER(C.c_int)]),
     "halo_dev_fq_sqrt": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, u32p]),
     "halo_dev_fold_points": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_int, u64p, C.c_int, C.c_int, u64p]),
     "halo_dev_fold_points_batch": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_int, u64p, C.c_int, C.c_int, C.c_int, u64p]),
@@ -697,6 +698,18 @@ class Context:
         out = np.zeros((pts_jac.shape[0], 8), dtype=np.uint64)
         check(self.lib.halo_dev_batch_to_affine(self.h, ptr(pts_jac), pts_jac.shape[0], ptr(out)))
         return out
+
+    def transcripts(self, d, instances, on_device):
+        """halo_dev_transcripts: the succinct check's transcripts of m Instance blobs of degree bound d on the host pool or through
+        the device route -> (xis m x (lg + 1) x 4, C' m x 12 normalised, status m: 0 ok, 1 instance, 2 proof, 3 zero challenge,
+        4 header)"""
+        lg = (int(d) + 1).bit_length() - 1
+        instances = np.ascontiguousarray(instances, dtype=np.uint64).reshape(-1, 21 + 2 + 24 * lg + 32)
+        m = instances.shape[0]
+        xis, cp = np.zeros((m, lg + 1, 4), dtype=np.uint64), np.zeros((m, 12), dtype=np.uint64)
+        st = (C.c_int * max(m, 1))()
+        check(self.lib.halo_dev_transcripts(self.h, int(d), ptr(instances), m, int(bool(on_device)), ptr(xis), ptr(cp), st))
+        return xis, cp, np.array(list(st)[:m], dtype=np.int64)
 
     def batch_small_msm(self, points, scalars, K):
         """halo_dev_batch_small_msm: m sums of K terms (m K x 8 affine words, m K x 4 canonical scalar words) in one

@@ -16,7 +16,7 @@ import sys
 # list) would pass a gate that only looks at what it finds.  k_fr_sum_rows: the combined check batch's row sum, enqueued on a
 # slot's stream between launch sequences that replay as graphs.  k_fused_terms: the fused check batch's term scalars, likewise -- a
 # lane of ~400 dependent products that must keep its working set in registers.
-REQUIRED = ("k_fr_sum_rows", "k_fused_terms")
+REQUIRED = ("k_fr_sum_rows", "k_fused_terms", "k_transcript_points", "k_transcript_head", "k_transcript_chain")
 
 
 def parse(path):

@@ -203,6 +203,7 @@ long halo_dev_tuning(const char *name) {
     if (!std::strcmp(name, "trace")) return t.trace ? 1 : 0;
     if (!std::strcmp(name, "commit_batch_group")) return dev_hooks().commit_group;  // (the hook as it stands: a CPU test sees "reset" clear it)
     if (!std::strcmp(name, "open_batch_fold")) return dev_hooks().open_fold;
+    if (!std::strcmp(name, "transcript_min")) return dev_hooks().transcript_min;
     return -1;
 }
 
@@ -232,6 +233,10 @@ int halo_dev_hook(const char *name, long value) {
         h.fused_chunk = value > (1 << 30) ? (1 << 30) : (int)value;
     }
     else if (!std::strcmp(name, "verifier_batch_min")) h.verifier_min = (int)value;
+    else if (!std::strcmp(name, "transcript_min")) {
+        if (value < 0) { set_error("dev_hook: transcript_min is 0 (the measured default) or the member count, at least 1, from which transcripts run on the device"); return HALO_E_ARG; }
+        h.transcript_min = value;
+    }
     else if (!std::strcmp(name, "decode_batch_min")) h.decode_min = value;
     else if (!std::strcmp(name, "table_slide_min")) h.slide_min = value > 0 && value < 4096 ? 4096 : value;
     else if (!std::strcmp(name, "pow_e")) {
@@ -246,7 +251,7 @@ int halo_dev_hook(const char *name, long value) {
         h.poly_blocks = (int)value;
     }
     else if (!std::strcmp(name, "reset")) h = DevHooks();
-    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, open_batch_fold, commit_batch_group, check_combined_parts, check_combined_cap, check_combined_usum, check_fused_chunk, verifier_batch_min, decode_batch_min, table_slide_min, pow_e, dot_blocks, poly_blocks, reset)"); return HALO_E_ARG; }
+    else { set_error("dev_hook: unknown hook (table_fail, force_peer_copy, shard_fail_rank, shard_fail_at, batch_stage_fail, check_batch_group, open_batch_group, open_batch_fold, commit_batch_group, check_combined_parts, check_combined_cap, check_combined_usum, check_fused_chunk, verifier_batch_min, transcript_min, decode_batch_min, table_slide_min, pow_e, dot_blocks, poly_blocks, reset)"); return HALO_E_ARG; }
     return HALO_OK;
 }
 
@@ -467,6 +472,42 @@ int halo_dev_batch_small_msm(halo_ctx *ctx, const uint64_t *points, const uint64
     if (!rc && (e = hipMemcpy(out_jac, d_out, m * 96, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d);
     return rc;
+}
+
+// the succinct check's transcripts of m Instances on their own, on the host pool (succinct_challenges) or through the product's
+// transcripts_batch_dev whatever the threshold (tests/test_gpu_transcripts.py holds the two against each other word for word)
+int halo_dev_transcripts(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, int on_device, uint64_t *xis_out, uint64_t *cprime_out,
+                         int *status_out) {
+    HALO_CTX(ctx);
+    if (m == 0) return HALO_OK;
+    if (!instances || !xis_out || !cprime_out || !status_out) { set_error("dev_transcripts: null pointer"); return HALO_E_ARG; }
+    if (!is_pow2(d + 1)) { set_error("dev_transcripts: d + 1 is not a power of two"); return HALO_E_ARG; }
+    const size_t lg = ilog2(d + 1), iw = instance_words(lg);
+    const BlobAt blob_at = [&](size_t i) { return instances + i * iw; };
+    std::vector<BatchCheck> res;
+    if (on_device) {
+        int rc = transcripts_batch_dev(ctx, d, blob_at, m, res, false);
+        if (rc == kTranscriptNoStage) { set_error("dev_transcripts: the staging was refused"); return HALO_E_DEVICE; }
+        if (rc) return rc;
+    } else {
+        res.assign(m, BatchCheck());
+        pool_run(m, [&](size_t i) {
+            const uint64_t *q = blob_at(i);
+            res[i].rc = succinct_challenges(ctx, host::Point::load(q), (size_t)q[12], host::Fr::load(q + 13), host::Fr::load(q + 17), q + 21, &res[i].st, false);
+            if (res[i].rc) res[i].err = halo_last_error();
+        });
+    }
+    for (size_t i = 0; i < m; ++i) {
+        uint64_t *xs = xis_out + i * (lg + 1) * 4, *cp = cprime_out + i * 12;
+        std::memset(xs, 0, (lg + 1) * 32);
+        std::memset(cp, 0, 96);
+        const std::string &e = res[i].err;
+        status_out[i] = !res[i].rc ? 0 : !e.compare(0, 8, "instance") ? 1 : !e.compare(0, 11, "proof holds") ? 2 : !e.compare(0, 9, "challenge") ? 3 : 4;
+        if (res[i].rc) continue;
+        for (size_t k = 0; k <= lg; ++k) res[i].st.xis[k].store(xs + 4 * k);
+        res[i].st.C_prime.store_normalized(cp);
+    }
+    return HALO_OK;
 }
 
 // halo_msm_points' normalisation on its own (tests/test_gpu_point_paths.py holds every output against Python integers): upload,

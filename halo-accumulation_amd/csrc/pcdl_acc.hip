@@ -227,7 +227,8 @@ static void succinct_one(halo_ctx *ctx, size_t d, const uint64_t *q, BatchCheck 
 }
 
 // ------------------------------------------------------------------ batched succinct checks (acc.rs:158-170)
-// m instances at once: the transcripts (hashes, C') are computed by a bounded pool of host threads, then ONE launch evaluates
+// m instances at once: the transcripts (hashes, C') are computed by a bounded pool of host threads, or from transcript_min members on
+// by the device (transcripts_batch, transcript.hip), then ONE launch evaluates
 // the m polynomials h_i at their own z_i (k_h_eval_z) and ONE launch computes the m relations (k_batch_small_msm):
 //     C'_i + sum_j (xi_j^-1 L_j + xi_j R_j) + (v_i - c_i h_i(z_i)) xi_0 H - c_i U_i  ==  0        (pcdl.rs:288-310)
 // as 2 lg n + 2 scalar multiples per instance, compared with -C'_i on the host.  Per-instance outcome equals the host path's.
@@ -266,15 +267,12 @@ int succinct_check_batch(halo_ctx *ctx, size_t d, const BlobAt &blob_at, size_t 
     size_t lg = ilog2(d + 1), K = 2 * lg + 2;
     res.assign(m, BatchCheck());
     if (K > 64) { set_error("batched succinct check: lg n too large"); return HALO_E_ARG; }
-    pool_run(m, [&](size_t i) {
-        const uint64_t *q = blob_at(i);
-        res[i].rc = succinct_challenges(ctx, Point::load(q), (size_t)q[12], Fr::load(q + 13), Fr::load(q + 17), q + 21, &res[i].st, false);
-        if (res[i].rc) res[i].err = halo_last_error();
-    });
+    int rc = transcripts_batch(ctx, d, blob_at, m, res);  // (transcript.hip: the host pool, or the device from transcript_min members on)
+    if (rc) return rc;
     // staging layout (words): xis m (lg+1) 4 | zs m 4 | hz m 4 | points m K 8 | scalars m K 4 | out m 12
     size_t o_xis = 0, o_zs = o_xis + m * (lg + 1) * 4, o_hz = o_zs + m * 4, o_pts = o_hz + m * 4, o_sc = o_pts + m * K * 8, o_out = o_sc + m * K * 4,
            total = o_out + m * 12;
-    int rc = verify_staging(ctx, total);
+    rc = verify_staging(ctx, total);
     if (rc) return rc;
     std::vector<uint64_t> host(total, 0);
     for (size_t i = 0; i < m; ++i) {

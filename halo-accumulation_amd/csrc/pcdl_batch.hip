@@ -451,12 +451,9 @@ static int pcdl_check_batch_host(halo_ctx *ctx, size_t d, const uint64_t *qs, si
     if (!S) { set_error("check_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
     if (mode == CheckMode::fused && m >= 2 && n >= 2) {  // (one member, or a constant: the exact path below)
         // the transcripts alone, as succinct_challenges runs them (no relation: that is the fused relation's left side)
-        std::vector<BatchCheck> tr(m);
-        pool_run(m, [&](size_t i) {
-            const uint64_t *q = qs + i * stride;
-            tr[i].rc = succinct_challenges(ctx, Point::load(q), (size_t)q[12], Fr::load(q + 13), Fr::load(q + 17), q + 21, &tr[i].st, false);
-            if (tr[i].rc) tr[i].err = halo_last_error();
-        });
+        std::vector<BatchCheck> tr;
+        int rc_tr = transcripts_batch(ctx, d, [&](size_t i) { return qs + i * stride; }, m, tr);
+        if (rc_tr) return rc_tr;
         std::vector<size_t> acc;
         for (size_t i = 0; i < m; ++i)
             if (!tr[i].rc) acc.push_back(i);

@@ -79,6 +79,19 @@ int succinct_check_batch(halo_ctx *ctx, size_t d, const BlobAt &blob_at, size_t 
 int succinct_half(halo_ctx *ctx, size_t d, const BlobAt &blob_at, size_t m, std::vector<BatchCheck> &res);
 int verify_staging(halo_ctx *ctx, size_t words);  // ctx->d_verify holds at least `words`
 
+// ---- transcript.hip: the transcripts alone (no relation) of m Instance blobs of degree bound d: res[i].rc / err / st.{lg_n, C_prime,
+// xis, U} as succinct_challenges leaves them (C_prime normalised on the device route: the same point).  transcripts_batch: the rule
+// of every batched call -- the device from transcript_min members on (the hook "transcript_min", else kTranscriptMin) if
+// ctx->batch_verify and the optional staging is granted, else the host pool.  transcripts_batch_dev: the device route whatever m
+// is; kTranscriptNoStage if the staging is refused (nothing ran), else a device / argument error only.  need_relation_inputs: fill
+// st.U as well (the development library's twin needs the challenges and C' only).
+// measured (tools/time_transcripts.py, profiles/r20_transcripts.json): at k = 1000 every device run beats every host
+// run at 2^9 and 2^14 points in both timed calls; at k = 64 and 100 the host pool wins (the K = 3 ladder launch costs ~2 ms flat)
+constexpr size_t kTranscriptMin = 1000;
+constexpr int kTranscriptNoStage = 1;
+int transcripts_batch(halo_ctx *ctx, size_t d, const BlobAt &blob_at, size_t m, std::vector<BatchCheck> &res);
+int transcripts_batch_dev(halo_ctx *ctx, size_t d, const BlobAt &blob_at, size_t m, std::vector<BatchCheck> &res, bool need_relation_inputs);
+
 // ---- pcdl_batch.hip: the combined check batch (halo_pcdl_check_batch_combined; the development library runs its steps alone)
 // The weights r_a of the A accepted members idx[0 .. A) of the blobs at `stride` words, degree bound d, seed = 32 bytes or null
 // (32 zero bytes): the rule of include/halo_accumulation.h, Montgomery form

@@ -49,6 +49,7 @@ struct DevHooks {
     int combined_usum = 0;     // "check_combined_usum"  the right side sum r_a U_a of a combined check: 1 the host pool, 2 the device (0: by the member count)
     int fused_chunk = 0;       // "check_fused_chunk"    terms per MSM of a fused check's left side (>= 8, clamped to the context's capacity; 0: the capacity)
     int verifier_min = 0;      // "verifier_batch_min" relations from which halo_acc_verifier_batch launches (>= 1; 0: the measured default)
+    long transcript_min = 0;   // "transcript_min"     members from which a batched check's transcripts run on the device (>= 1; 0: the measured default)
     long slide_min = 0;        // "table_slide_min"    keys from this many points take the c = 20 table plans and the all-shifts table (>= 4096; 0: 2^20)
     long decode_min = 0;       // "decode_batch_min"   finite points from which halo_*_decode_batch decompresses on the device (>= 1; 0: the measured default)
     // the launch plan of the Fr kernels (fr_plan.hpp), each before the environment's value and the measured default; 0: not set

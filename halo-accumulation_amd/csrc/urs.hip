@@ -4,6 +4,7 @@
 #include <cstring>
 #include <thread>
 
+#include "keccak_lane.hpp"
 #include "msm_kernels.hpp"
 
 namespace halo {
@@ -40,58 +41,18 @@ __global__ __launch_bounds__(256) void k_native_to_aff(const uint32_t *__restric
 }
 // main.rs:18-32 on the device: canon[i] = SHA3-256(genesis || LE64(first_index + i * stride)) read as a little-endian
 // integer mod r (ark-ff from_le_bytes_mod_order), as 8 plain 32-bit words -- the scalar of generator i.  One lane per
-// hash: Keccak-f[1600] with the 25 lanes in registers (the 68-byte message is one block of the 136-byte rate).
+// hash: Keccak-f[1600] with the 25 lanes in registers (keccak_lane.hpp; the 68-byte message is one block of the 136-byte rate).
 // The host spent ~70-120 ms on the 2^20 hashes of a context; here they take tens of microseconds.
-HALO_DEV uint64_t rol64(uint64_t x, int n) { return (x << n) | (x >> (64 - n)); }
 __global__ __launch_bounds__(256) void k_urs_scalars(uint64_t first_index, uint64_t stride, uint32_t n, uint32_t *__restrict__ canon) {
     uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    constexpr uint64_t RC[24] = {0x0000000000000001ULL, 0x0000000000008082ULL, 0x800000000000808aULL, 0x8000000080008000ULL, 0x000000000000808bULL,
-                                 0x0000000080000001ULL, 0x8000000080008081ULL, 0x8000000000008009ULL, 0x000000000000008aULL, 0x0000000000000088ULL,
-                                 0x0000000080008009ULL, 0x000000008000000aULL, 0x000000008000808bULL, 0x800000000000008bULL, 0x8000000000008089ULL,
-                                 0x8000000000008003ULL, 0x8000000000008002ULL, 0x8000000000000080ULL, 0x000000000000800aULL, 0x800000008000000aULL,
-                                 0x8000000080008081ULL, 0x8000000000008080ULL, 0x0000000080000001ULL, 0x8000000080008008ULL};
-    constexpr int ROT[24] = {1, 3, 6, 10, 15, 21, 28, 36, 45, 55, 2, 14, 27, 41, 56, 8, 25, 43, 62, 18, 39, 61, 20, 44};
-    constexpr int PIL[24] = {10, 7, 11, 17, 18, 3, 5, 16, 8, 21, 24, 4, 15, 23, 19, 13, 12, 2, 20, 14, 22, 9, 6, 1};
     // "To understand recursion, one must first understand recursion" (60 bytes), then the index, 0x06 ... 0x80 padding
     uint64_t idx = first_index + (uint64_t)i * stride;
     uint64_t a[25] = {0x7265646e75206f54ULL, 0x657220646e617473ULL, 0x2c6e6f6973727563ULL, 0x73756d20656e6f20ULL, 0x2074737269662074ULL,
                       0x6174737265646e75ULL, 0x727563657220646eULL, 0x6e6f6973ULL | (idx << 32), (idx >> 32) | (0x06ULL << 32), 0, 0, 0, 0, 0, 0, 0,
                       0x8000000000000000ULL, 0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll 1
-    for (int r = 0; r < 24; r++) {
-        uint64_t c[5], t, bc;
-#pragma unroll
-        for (int x = 0; x < 5; x++) c[x] = a[x] ^ a[x + 5] ^ a[x + 10] ^ a[x + 15] ^ a[x + 20];
-#pragma unroll
-        for (int x = 0; x < 5; x++) {
-            t = c[(x + 4) % 5] ^ rol64(c[(x + 1) % 5], 1);
-#pragma unroll
-            for (int y = 0; y < 25; y += 5) a[y + x] ^= t;
-        }
-        t = a[1];
-#pragma unroll
-        for (int k = 0; k < 24; k++) {
-            bc = a[PIL[k]];
-            a[PIL[k]] = rol64(t, ROT[k]);
-            t = bc;
-        }
-#pragma unroll
-        for (int y = 0; y < 25; y += 5) {
-            uint64_t b0 = a[y], b1 = a[y + 1], b2 = a[y + 2], b3 = a[y + 3], b4 = a[y + 4];
-            a[y] = b0 ^ (~b1 & b2); a[y + 1] = b1 ^ (~b2 & b3); a[y + 2] = b2 ^ (~b3 & b4); a[y + 3] = b3 ^ (~b4 & b0); a[y + 4] = b4 ^ (~b0 & b1);
-        }
-        uint64_t rc = 0;
-#pragma unroll
-        for (int q = 0; q < 24; q++) rc = (q == r) ? RC[q] : rc;  // (no runtime-indexed constant array: that would live in scratch)
-        a[0] ^= rc;
-    }
-    Fe v;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { v.v[2 * k] = (uint32_t)a[k]; v.v[2 * k + 1] = (uint32_t)(a[k] >> 32); }
-    // 2^256 < 4 r: at most three subtractions bring the digest below r
-#pragma unroll 1
-    for (int q = 0; q < 3; q++) fe_cond_sub<FrCfg>(v);
+    keccak_f1600(a);
+    Fe v = keccak_digest_mod_r(a);
 #pragma unroll
     for (int k = 0; k < 8; k++) canon[8 * (size_t)i + k] = v.v[k];
 }

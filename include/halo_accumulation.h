@@ -313,8 +313,10 @@ int halo_pcdl_check_batch_combined(halo_ctx *ctx, size_t d, const uint64_t *inst
  *   s_a = (SHA3-256(D || LE64(2 a + 1)) read as a little-endian integer) mod r,      a = 0 .. M - 1 its position among them.
  * When to call it (one MI355X, tools/time_decider_batch.py --fused --big, profiles/r19_check_fused.json; against
  * halo_acc_decider_batch_combined in the same run, medians of 5): 1.36 to 1.54 times its speed at m = 10 and 1.28 to 1.37 times at
- * m = 100 on keys of 2^9 .. 2^14 and of 2^20 points, 1.05 times at m = 1000, where the members' transcripts on the host are what
- * remains.  Every fused run was faster than every combined run in each row but two, which are NOT won: 2^9 points with m = 100 and
+ * m = 100 on keys of 2^9 .. 2^14 and of 2^20 points, 1.05 times at m = 1000 (that run had the members' transcripts on the host
+ * pool; from 1000 members on they now run on the device, which takes 29.0 to 26.6 ms off halo_acc_decider_batch_fused at 2^9
+ * points and 38.7 to 37.4 ms at 2^14 -- tools/time_transcripts.py, profiles/r20_transcripts.json; the ratio against the combined
+ * call has not been measured again).  Every fused run was faster than every combined run in each row but two, which are NOT won: 2^9 points with m = 100 and
  * 2^14 points with m = 1000 (one fused run of five inside the combined call's range). */
 int halo_pcdl_check_batch_fused(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, const uint8_t seed[32] /*nullable*/,
                                 int *status /*nullable*/);

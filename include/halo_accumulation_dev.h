@@ -30,7 +30,11 @@ extern "C" {
  * no-fold size: 0 the measured default, 1 the folded schedule with member-batched key folds wherever it applies, 2 never: one member
  * at a time; another value is HALO_E_ARG), "commit_batch_group" (members per MSM launch of halo_pcdl_commit_batch / halo_pcdl_commit_dev_batch, 1..8; 0: the
  * rule of the check batch), "verifier_batch_min" (relations
- * from which halo_acc_verifier_batch runs its sums on the device, >= 1; 0: the measured default), "table_slide_min" (keys from this many points, >= 4096, take the c = 20 table plans and
+ * from which halo_acc_verifier_batch runs its sums on the device, >= 1; 0: the measured default), "transcript_min" (members from
+ * which the batched checks -- halo_pcdl_succinct_check_batch, halo_pcdl_check_batch and its _combined and _fused forms, the
+ * halo_acc_decider_batch calls, the succinct half of halo_acc_prover_batch -- run their Fiat-Shamir transcripts on the device,
+ * >= 1; 0: the measured default; a negative value is HALO_E_ARG; "batch_stage_fail" refuses its staging too: the host pool;
+ * codes, statuses, messages and outputs are the same under every value), "table_slide_min" (keys from this many points, >= 4096, take the c = 20 table plans and
  * the all-shifts table with its sliding-window recode; 0: 2^20), "decode_batch_min" (finite points
  * from which halo_*_decode_batch decompresses on the device, >= 1; 0: the measured default; "batch_stage_fail" refuses its staging
  * too: the host pool), "check_combined_parts" (parts the polynomials of halo_pcdl_check_batch_combined's
@@ -64,7 +68,7 @@ int halo_dev_fr_plan(halo_ctx *ctx, int which, size_t n, long out[4]);
 int halo_dev_dot2_cross(halo_ctx *ctx, const uint64_t *c, const uint64_t *z, size_t m, uint64_t out[8]);
 /* What the library read from the environment at its first use (csrc/tuning.hip), by field: "host_split_set", "host_pieces", "host_split0".."host_split3",
  * "fold_table_after", "pow_e", "dot_blocks", "spin_us", "graphs", "memory_budget" (MiB, -1 unset), "trace"; -1 for an
- * unknown name.  Also "commit_batch_group" and "open_batch_fold": those hooks of halo_dev_hook as they stand now (0 after "reset").
+ * unknown name.  Also "commit_batch_group", "open_batch_fold" and "transcript_min": those hooks of halo_dev_hook as they stand now (0 after "reset").
  * Host only. */
 long halo_dev_tuning(const char *name);
 
@@ -158,6 +162,17 @@ int halo_dev_small_msm_seg(halo_ctx *ctx, const uint64_t *points, const uint64_t
  * scalars = m x K x 4 canonical words, out_jac = m x 12 Jacobian words.  m = 0 is HALO_OK.  HALO_E_ARG: a null pointer, m above
  * 65535, K outside 1..64 (the product's message). */
 int halo_dev_batch_small_msm(halo_ctx *ctx, const uint64_t *points, const uint64_t *scalars, size_t m, size_t K, uint64_t *out_jac);
+
+/* The transcripts of pcdl::succinct_check (pcdl.rs:272-296) for m Instance blobs of degree bound d on their own, no relation:
+ * on_device = 0 on the host pool, as every single call runs them; on_device != 0 through the device route of the batched checks
+ * (k_transcript_points, k_transcript_head, k_batch_small_msm with K = 3, k_transcript_chain) whatever "transcript_min" says.
+ * xis_out = m x (lg + 1) x 4 Montgomery words (xi_0 .. xi_lg), cprime_out = m x 12 words (C', normalised), both zero in the rows
+ * of a rejected member; status_out[i] = 0 accepted, 1 the instance holds an invalid point or scalar, 2 the proof does, 3 a challenge
+ * is zero, 4 the member's d or proof length does not fit d.  A member with a point that is not normalised (Z neither 0 nor 1) is
+ * finished on the host pool before the call returns.  m = 0 is HALO_OK.  HALO_E_ARG: a null pointer, d + 1 not a power of two;
+ * HALO_E_DEVICE: on_device and the staging refused ("batch_stage_fail", the memory budget). */
+int halo_dev_transcripts(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, int on_device, uint64_t *xis_out, uint64_t *cprime_out,
+                         int *status_out);
 
 /* halo_msm_points' normalisation on its own: upload, the product's batch_to_affine (k_batch_to_affine: four points per lane, one
  * shared inversion), k_native_to_aff, download.  pts_jac = m x 12 arkworks Jacobian words (any Z; Z = 0 is infinity whatever X
