@@ -7,7 +7,8 @@
 //
 // It links AGAINST libhalo_hip.so (one copy of the library's state in the process) and holds nothing the product path calls:
 // `nm -D libhalo_hip.so` shows no halo_test_* / halo_bench_* / halo_dev_* symbol, and the product library reads no fault
-// injector from the environment (tests/test_abi_cpu.py checks both).
+// injector from the environment (tests/test_abi_cpu.py checks both).  What this file calls in the product is the reach that
+// product.map exports, name by name: a call to another internal fails this library's link until the map lists it.
 #include <cstring>
 
 #include "../../include/halo_accumulation_dev.h"
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(256) void k_lazy_point_quad(int op, const uint32_t 
     }
 }
 
-int test_field_op(halo_ctx *ctx, int field, int op, const uint64_t *d_a, const uint64_t *d_b, size_t n, uint64_t *d_out) {
+static int test_field_op(halo_ctx *ctx, int field, int op, const uint64_t *d_a, const uint64_t *d_b, size_t n, uint64_t *d_out) {
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
     if (field == 2) HALO_LAUNCH(ctx, "k_test_field29", k_test_field29, grid, block, 0, op, d_a, d_b, (uint32_t)n, d_out);
     else if (field == 0) HALO_LAUNCH(ctx, "k_test_field", k_test_field<FqCfg>, grid, block, 0, op, d_a, d_b, (uint32_t)n, d_out);
@@ -169,7 +170,7 @@ int test_field_op(halo_ctx *ctx, int field, int op, const uint64_t *d_a, const u
     HALO_HIP(hipGetLastError());
     return HALO_OK;
 }
-int test_point_op(halo_ctx *ctx, int op, const uint64_t *d_a, const uint64_t *d_b, size_t n, uint64_t *d_out) {
+static int test_point_op(halo_ctx *ctx, int op, const uint64_t *d_a, const uint64_t *d_b, size_t n, uint64_t *d_out) {
     dim3 grid((unsigned)((n + 255) / 256)), block(256);
     if (op >= 4) {
         HALO_LAUNCH(ctx, "k_test_point_quad", k_test_point_quad, dim3((unsigned)((4 * n + 255) / 256)), block, 0, op, d_a, d_b, (uint32_t)n, d_out);

@@ -287,6 +287,7 @@ struct IpaBuffers {
     bool in_use = false;
 };
 
+namespace halo {
 // What the contexts over ONE resident key have in common (halo_ctx_clone): the key, its fixed-base MSM table and its fold
 // table -- immutable once built -- and the optional-memory bytes they hold on the device's books.  Every context owns a
 // reference (a context that was never cloned is the only user of its own); the last one to go frees the memory.  `mu` guards
@@ -297,7 +298,7 @@ struct KeyShare {
     int users = 1;
     uint32_t *d_bases = nullptr;
     uint32_t *d_table = nullptr;
-    halo::TblPlan tbl{};
+    TblPlan tbl{};
     double table_build_ms = 0;  // build of d_table (kernels, without the allocation)
     uint32_t *d_foldtab = nullptr;
     size_t foldtab_bytes = 0;
@@ -307,10 +308,11 @@ struct KeyShare {
     long full_opens = 0;     // full-size opens over this key by any of its contexts while no fold table existed (the automatic mode builds from tuning().fold_table_after on)
     size_t budget_held = 0;  // bytes of optional memory reserved for this key (budget.hip table_budget_*)
 };
+}  // namespace halo
 
 struct halo_ctx {
     int device = 0;
-    std::shared_ptr<KeyShare> share;  // d_bases / d_table / d_foldtab below are this context's view of it
+    std::shared_ptr<halo::KeyShare> share;  // d_bases / d_table / d_foldtab below are this context's view of it
     hipStream_t stream = nullptr;      // stream the launch macro uses (= streams[slot in use])
     hipStream_t streams[HALO_SLOTS] = {};
     size_t n = 0;
@@ -511,13 +513,11 @@ inline void pool_run(size_t m, const std::function<void(size_t)> &fn) {
     worker();
     for (auto &t : th) t.join();
 }
-// ---- urs.hip (key generation and the affine layouts), dev.hip (the test_* kernels)
+// ---- urs.hip (key generation and the affine layouts)
 int urs_generate(halo_ctx *ctx, uint64_t first_index, uint64_t stride, size_t n, uint32_t *d_out_native);
 int batch_to_affine(halo_ctx *ctx, const uint64_t *d_jac_words, size_t n, uint32_t *d_out_native);
 int aff_words_to_native(halo_ctx *ctx, const uint64_t *d_in, size_t n, uint32_t *d_out);
 int aff_native_to_words(halo_ctx *ctx, const uint32_t *d_in, size_t n, uint64_t *d_out);
-int test_field_op(halo_ctx *ctx, int field, int op, const uint64_t *d_a, const uint64_t *d_b, size_t n, uint64_t *d_out);
-int test_point_op(halo_ctx *ctx, int op, const uint64_t *d_a, const uint64_t *d_b, size_t n, uint64_t *d_out);
 
 // ---- budget.hip: the budget for OPTIONAL device memory (the MSM fixed-base table, the fold table and its temporary), per device and
 // process-wide: reserve() succeeds if what all contexts of this process hold on ctx's device plus `bytes` stays within the

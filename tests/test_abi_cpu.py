@@ -65,6 +65,45 @@ def test_development_library_is_separate(hal):
     assert lib.halo_dev_hook(b"no_such_hook", 1) == hal._lib.HALO_E_ARG
 
 
+def dynamic_symbols(path, which):
+    """{name: type letter} over EVERY line of `nm -D` (which: --defined-only or --undefined-only), versions stripped"""
+    import subprocess
+    out = {}
+    for line in subprocess.check_output(["nm", "-D", which, path], text=True).splitlines():
+        fields = line.split()
+        if len(fields) >= 2:
+            out[fields[-1].split("@")[0]] = fields[-2]
+    return out
+
+
+def test_libraries_export_their_headers_and_the_reach_only(hal):
+    """The whole dynamic symbol table, not only its ` T halo_` lines: csrc/c_abi.map seals the development and the RCCL library
+    to their headers, csrc/product.map the product to its header plus the reach R -- the internals the development library
+    imports.  R is exactly what that library leaves undefined and the product defines (nothing is exported for it that it does
+    not use), holds no more than the 39 names it imported before the seal, and no kernel stub or kernel handle."""
+    import subprocess
+    from halo_accumulation_amd import rccl
+    defined, undefined = "--defined-only", "--undefined-only"
+    dev = dynamic_symbols(hal._lib.DEV_LIB_PATH, defined)
+    assert sorted(dev) == header_symbols("halo_accumulation_dev.h"), "the development library exports exactly what its header declares"
+    if rccl.available():
+        assert sorted(dynamic_symbols(rccl.LIB_PATH, defined)) == header_symbols("halo_rccl.h")
+    prod = dynamic_symbols(hal._lib.LIB_PATH, defined)
+    header = set(header_symbols())
+    assert header <= set(prod)
+    reach = set(prod) - header
+    assert not [s for s in reach if s.startswith("halo_")]
+    imported = {s for s in dynamic_symbols(hal._lib.DEV_LIB_PATH, undefined) if s in prod and not s.startswith("halo_")}
+    assert reach == imported, "exported for the development library but not used by it: %s" % sorted(reach - imported)
+    assert 0 < len(reach) <= 39
+    for s in sorted(reach):
+        assert prod[s] == "T", s + ": the reach holds functions only (a kernel handle is an object)"
+        assert "__device_stub__" not in s and not re.match(r"_ZN4halo\d+k_", s), s + ": a kernel's stub or handle"
+    # what the development library imports of C symbols are the product's own (halo_last_error), and it still links against it
+    assert {s for s in dynamic_symbols(hal._lib.DEV_LIB_PATH, undefined) if s.startswith("halo_")} <= header
+    assert "libhalo_hip.so" in subprocess.check_output(["readelf", "-d", hal._lib.DEV_LIB_PATH], text=True)
+
+
 def test_environment_is_parsed_once_and_strictly(hal):
     """csrc/tuning.hip: defaults, a valid HALO_HOST_SPLIT, invalid ones (ignored with a line on stderr, the default stays), clamps."""
     import subprocess, sys
