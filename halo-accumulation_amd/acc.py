@@ -5,7 +5,7 @@ import numpy as np
 
 from halo_accumulation_amd import _lib
 from halo_accumulation_amd._lib import check, ptr
-from halo_accumulation_amd.pcdl import _a, _check_batch, _pack_polys, _pack_rows, _seed32, lg_of
+from halo_accumulation_amd.pcdl import _a, _check_batch, _check_batch_mixed, _pack_polys, _pack_rows, _seed32, lg_of
 
 
 def _cat(qs):
@@ -171,3 +171,15 @@ def decider_batch_fused(ctx, d, accs, seed=None):
     """decider_batch as ONE relation, the succinct relations included (halo_acc_decider_batch_fused; seed: 32 bytes or None) ->
     status list; statuses and HaloReject as decider_batch whenever a member is bad"""
     return _check_batch(ctx, lambda h, dd, qs, m, st: ctx.lib.halo_acc_decider_batch_fused(h, dd, qs, m, _seed32(seed), st), d, accs)
+
+
+def decider_batch_mixed(ctx, accs):
+    """acc::decider of m accumulators, each of its own degree bound (read from the blob's word 12), in one call
+    (halo_acc_decider_batch_mixed) -> status list; raises HaloReject as pcdl.check_batch does"""
+    return _check_batch_mixed(ctx, ctx.lib.halo_acc_decider_batch_mixed, accs)
+
+
+def decider_batch_mixed_combined(ctx, accs, seed=None):
+    """decider_batch_mixed with ONE MSM for the accepted members of every size (halo_acc_decider_batch_mixed_combined; seed: 32 bytes
+    or None) -> status list; statuses and HaloReject as decider_batch_mixed whenever a member is bad"""
+    return _check_batch_mixed(ctx, lambda h, ds, ps, m, st: ctx.lib.halo_acc_decider_batch_mixed_combined(h, ds, ps, m, _seed32(seed), st), accs)

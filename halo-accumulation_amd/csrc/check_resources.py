@@ -15,8 +15,10 @@ import sys
 # Kernels the gate must have SEEN: one whose remarks are missing (renamed, compiled out, its translation unit dropped from the
 # list) would pass a gate that only looks at what it finds.  k_fr_sum_rows: the combined check batch's row sum, enqueued on a
 # slot's stream between launch sequences that replay as graphs.  k_fused_terms: the fused check batch's term scalars, likewise -- a
-# lane of ~400 dependent products that must keep its working set in registers.
-REQUIRED = ("k_fr_sum_rows", "k_fused_terms", "k_transcript_points", "k_transcript_head", "k_transcript_chain")
+# lane of ~400 dependent products that must keep its working set in registers.  k_h_tables_mixed, k_h_accumulate_mixed: the mixed
+# combined check batch's scalar step, enqueued like k_fr_sum_rows.
+REQUIRED = ("k_fr_sum_rows", "k_fused_terms", "k_transcript_points", "k_transcript_head", "k_transcript_chain", "k_h_tables_mixed",
+            "k_h_accumulate_mixed")
 
 
 def parse(path):

@@ -386,6 +386,51 @@ int halo_dev_check_combined_scalars(halo_ctx *ctx, const uint64_t *xis, const ui
     return rc;
 }
 
+// host only: the weights of the mixed combined check batch as the product computes them (tests/test_check_mixed_cpu.py restates the rule)
+int halo_dev_check_mixed_weights(const uint64_t *const *blobs, const size_t *ds, const size_t *idx, size_t A, const uint8_t seed[32], uint64_t *out) {
+    if (A == 0) return HALO_OK;
+    if (!blobs || !ds || !idx || !out) { set_error("check_mixed_weights: null pointer"); return HALO_E_ARG; }
+    for (size_t a = 0; a < A; ++a) {
+        if (!blobs[idx[a]]) { set_error("check_mixed_weights: null pointer"); return HALO_E_ARG; }
+        if (!is_pow2(ds[idx[a]] + 1)) { set_error("check_mixed_weights: every d + 1 is a power of two"); return HALO_E_ARG; }
+    }
+    std::vector<host::Fr> r;
+    check_mixed_weights(blobs, ds, idx, A, seed, r);
+    for (size_t a = 0; a < A; ++a) r[a].store(out + 4 * a);
+    return HALO_OK;
+}
+
+// the mixed combined check's scalar step on its own (tests/test_gpu_check_mixed.py holds it against Python integers): the tables in
+// the caller's order -- the launcher sorts --, temporary device buffers of this call only
+int halo_dev_check_mixed_scalars(halo_ctx *ctx, const uint64_t *xis, const size_t *lgs, const uint64_t *weights, size_t A, uint64_t *out) {
+    HALO_CTX(ctx);
+    if (!xis || !lgs || !weights || !out) { set_error("check_mixed_scalars: null pointer"); return HALO_E_ARG; }
+    if (A < 1 || A > 65535) { set_error("check_mixed_scalars: 1..65535 polynomials"); return HALO_E_ARG; }
+    size_t lg_max = 0;
+    for (size_t a = 0; a < A; ++a) {
+        if (lgs[a] < 1 || lgs[a] > 24 || ((size_t)1 << lgs[a]) > ctx_capacity(ctx)) { set_error("check_mixed_scalars: 2^lg_n exceeds context size"); return HALO_E_ARG; }
+        if (lgs[a] > lg_max) lg_max = lgs[a];
+    }
+    const size_t n = (size_t)1 << lg_max, xw = (lg_max + 1) * 4, tw = xw + 4;
+    const size_t P = check_combined_parts(n, A), cap = check_combined_cap(A);
+    std::vector<uint64_t> recs(A * tw, 0);
+    std::vector<uint32_t> lg32(A);
+    for (size_t a = 0; a < A; ++a) {
+        lg32[a] = (uint32_t)lgs[a];
+        std::memcpy(&recs[a * tw], xis + a * xw, (lgs[a] + 1) * 32);
+        std::memcpy(&recs[a * tw + (lgs[a] + 1) * 4], weights + 4 * a, 32);
+    }
+    uint64_t *d = nullptr;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d, hmix_stage_words(A, lg_max, P, cap) * 8));
+    int rc = h_combine_rows_mixed(ctx, recs.data(), lg32.data(), A, lg_max, P, cap, d);
+    hipError_t e = hipStreamSynchronize(ctx->stream);  // (also on failure: nothing of this call may be in flight when its buffer goes)
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    if (!rc && (e = hipMemcpy(out, d + hmix_rows_offset(A, lg_max, P, cap), n * 32, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d);
+    return rc;
+}
+
 // host only: the 2 A weights r_0, s_0, r_1, s_1, .. of the fused check batch as the product computes them (tests/test_check_fused_cpu.py
 // restates the rule)
 int halo_dev_check_fused_weights(const uint64_t *blobs, size_t stride_words, const size_t *idx, size_t A, size_t d, const uint8_t seed[32], uint64_t *out) {

@@ -1,6 +1,8 @@
 // h(X) of pcdl.rs:56-91 and pcdl.rs:496-505: its coefficients from three 256-entry tables (K7), the sum of several scaled
 // polynomials per member (K7b, acc.rs:85-94) and HPoly::eval, one polynomial per lane (K8).  The launch plan of the coefficient
 // kernels is fr_plan.hpp's plan_h_coeffs.
+#include <algorithm>
+
 #include "fr29.hpp"
 #include "fr_plan.hpp"
 #include "internal.hpp"
@@ -42,9 +44,8 @@ __global__ __launch_bounds__(256) void k_h_coeffs_batch(const uint64_t *__restri
 // mid and high levels are N-form multipliers (32 x, five doublings), the low one A-form.
 // scaled = 1: a record is lg_n + 2 elements, the last one the polynomial's scale (alpha^(i+1) of acc.rs:85-94), folded into the
 // high table exactly as h_coeffs_dev(xis, lg_n, scale, ..) folds it on the host.
-__global__ __launch_bounds__(256) void k_h_tables(const uint64_t *__restrict__ xis, int lg_n, int scaled, uint64_t *__restrict__ tabs) {
-    const uint64_t *x = xis + (size_t)blockIdx.x * 4 * (size_t)(lg_n + 1 + scaled);
-    uint64_t *tab = tabs + (size_t)blockIdx.x * H_TAB_WORDS;
+// h_tables_block: one block's work for the record x; the two kernels differ only in where a record stands and where its lg comes from.
+HALO_DEV void h_tables_block(const uint64_t *__restrict__ x, int lg_n, int scaled, uint64_t *__restrict__ tab) {
     const uint32_t k = threadIdx.x;
 #pragma unroll 1
     for (int level = 0; level < 3; level++) {
@@ -63,6 +64,17 @@ __global__ __launch_bounds__(256) void k_h_tables(const uint64_t *__restrict__ x
         }
         fe_store(tab + 4 * (size_t)(256 * level + k), t);
     }
+}
+__global__ __launch_bounds__(256) void k_h_tables(const uint64_t *__restrict__ xis, int lg_n, int scaled, uint64_t *__restrict__ tabs) {
+    h_tables_block(xis + (size_t)blockIdx.x * 4 * (size_t)(lg_n + 1 + scaled), lg_n, scaled, tabs + (size_t)blockIdx.x * H_TAB_WORDS);
+}
+// The same with a length per polynomial (halo_pcdl_check_batch_mixed_combined): records at the fixed stride of lg_max + 1 + scaled
+// elements, record t's own lg in lgs[t]; its lgs[t] + 1 challenges (and the scale behind them) stand at the record's start as in a
+// record of k_h_tables for that lg, the rest of the record is not read.  A table depends on its own record alone, so it is word
+// for word what k_h_tables builds for lgs[t].
+__global__ __launch_bounds__(256) void k_h_tables_mixed(const uint64_t *__restrict__ xis, const uint32_t *__restrict__ lgs, int lg_max, int scaled,
+                                                        uint64_t *__restrict__ tabs) {
+    h_tables_block(xis + (size_t)blockIdx.x * 4 * (size_t)(lg_max + 1 + scaled), (int)lgs[blockIdx.x], scaled, tabs + (size_t)blockIdx.x * H_TAB_WORDS);
 }
 
 // ------------------------------------------------------------------ K7b: h(X) = h_0 + sum_i alpha^(i+1) h_i(X) of several members
@@ -108,6 +120,54 @@ __global__ __launch_bounds__(256) void k_h_accumulate_batch(const uint64_t *__re
             h_acc_step(a1, tab, k + 64, hm);
             h_acc_step(a2, tab, k + 128, hm);
             h_acc_step(a3, tab, k + 192, hm);
+        }
+        h_acc_store(out, rec, mode, k, n, a0);
+        h_acc_store(out, rec, mode, k + 64, n, a1);
+        h_acc_store(out, rec, mode, k + 128, n, a2);
+        h_acc_store(out, rec, mode, k + 192, n, a3);
+    }
+}
+
+// The same sum over tables of DIFFERENT lengths (halo_pcdl_check_batch_mixed_combined): s = sum_t pad(h_t), a shorter polynomial
+// zero-padded to the row's n coefficients.  lgs[t] = table t's lg; blockIdx.y = part, its record as above.  The tables of a
+// launch stand in order of DECREASING length, so within a part too.  The four steps of a lane cover one 256-aligned block
+// [kk, kk + 256) of coefficients:
+//   - a table with n_t <= kk adds nothing to the block, and neither does any table behind it: the table loop ends there.  kk is
+//     wave-uniform, so the exit is;
+//   - a table with n_t >= 256 that reaches the block covers all of it (n_t is a power of two, kk a multiple of 256);
+//   - a table shorter than 256 reaches block 0 only, and there a step adds its product only where k < n_t.  The product is
+//     computed for every lane (entries of the low table past 2^lg are one, mid[0] and high[0] valid): only the add is selected,
+//     no divergence around the multiplies.  For the longer tables the selection is always true.
+// Every coefficient below n is stored once, canonical; a block no table of the part reaches stores zeros (mode 1) or stays (mode 2).
+HALO_DEV void h_acc_step_below(Fs<2> &acc, const uint64_t *__restrict__ tab, uint32_t k, uint32_t n_t, const Fs<4> &hm) {
+    const Fs<2> sum = fs_tighten(fs_add(acc, fs_mul(fs_load(tab + 4 * (size_t)(k & 255u)), hm)));
+    const bool take = k < n_t;
+#pragma unroll
+    for (int i = 0; i < 9; i++) acc.v[i] = take ? sum.v[i] : acc.v[i];  // (same bound on both sides: limbs copied within Fs<2>)
+}
+__global__ __launch_bounds__(256) void k_h_accumulate_mixed(const uint64_t *__restrict__ tabs, const uint32_t *__restrict__ lgs,
+                                                            const uint64_t *__restrict__ recs, uint32_t n, int E, uint64_t *__restrict__ outs,
+                                                            uint64_t out_stride) {
+    const uint64_t *rec = recs + HACC_REC_WORDS * (size_t)blockIdx.y;
+    const uint32_t first = (uint32_t)rec[0], count = (uint32_t)(rec[0] >> 32), mode = (uint32_t)rec[1];
+    if (mode == 0) return;
+    uint64_t *out = outs + (size_t)blockIdx.y * out_stride;
+    const uint32_t wave = (blockIdx.x * 256 + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+    uint32_t k = wave * (64u * (uint32_t)E) + lane;
+#pragma unroll 1
+    for (int j = 0; j < E && k < n; j += 4, k += 256) {  // (E is a multiple of four: pow_chain_len)
+        const uint32_t kk = __builtin_amdgcn_readfirstlane(k);  // wave-uniform: the block's start is kk & ~255
+        Fs<2> a0 = fs_zero<2>(), a1 = fs_zero<2>(), a2 = fs_zero<2>(), a3 = fs_zero<2>();
+#pragma unroll 1
+        for (uint32_t t = 0; t < count; t++) {
+            const uint32_t n_t = 1u << __builtin_amdgcn_readfirstlane(lgs[first + t]);
+            if (n_t <= (kk & ~255u)) break;  // (decreasing lengths: no later table reaches this block)
+            const uint64_t *tab = tabs + (size_t)(first + t) * H_TAB_WORDS;
+            const Fs<4> hm = fs_widen<4>(fs_mul(fs_load(tab + 4 * (size_t)(256 + ((kk >> 8) & 255u))), fs_load(tab + 4 * (size_t)(512 + ((kk >> 16) & 255u)))));
+            h_acc_step_below(a0, tab, k, n_t, hm);
+            h_acc_step_below(a1, tab, k + 64, n_t, hm);
+            h_acc_step_below(a2, tab, k + 128, n_t, hm);
+            h_acc_step_below(a3, tab, k + 192, n_t, hm);
         }
         h_acc_store(out, rec, mode, k, n, a0);
         h_acc_store(out, rec, mode, k + 64, n, a1);
@@ -271,6 +331,69 @@ int h_combine_rows(halo_ctx *ctx, const uint64_t *h_recs, size_t A, size_t lg_n,
         HALO_LAUNCH(ctx, "k_h_tables", k_h_tables, dim3((unsigned)T), dim3(256), 0, d_recs + pass * cap * tw, (int)lg_n, 1, d_tabs);
         HALO_LAUNCH(ctx, "k_h_accumulate_batch", k_h_accumulate_batch, dim3(p.blocks, (unsigned)P), dim3(256), 0, d_tabs, d_parts + pass * P * HACC_REC_WORDS,
                     (uint32_t)n, p.E, d_rows, (uint64_t)(n * 4));
+    }
+    HALO_HIP(hipGetLastError());
+    return fr_sum_rows(ctx, d_rows, n * 4, P, n);
+}
+
+// s = sum_a r_a pad(h_a)(X) over A polynomials of their own lengths (halo_pcdl_check_batch_mixed_combined): n = 2^lg_max canonical
+// elements in row 0, a polynomial of 2^lgs[a] < n coefficients zero-padded.  h_combine_rows with three differences:
+//   - h_recs: A records at the fixed stride of lg_max + 2 elements in the CALLER's order, record a = its lgs[a] + 1 challenges,
+//     then r_a.  They are sorted here by decreasing length (stable) and staged in that order with their lgs, which is what
+//     k_h_accumulate_mixed's early loop end needs; a pass takes the next `cap` tables of the sorted order;
+//   - the parts of a pass are cut by summed table LENGTH, not by table count -- in sorted order equal counts would put all the
+//     long tables into the first parts: table j of the pass, with the lengths before it summing to s_j of L, goes to part
+//     s_j P / L (monotone in j, so a part is a stretch of tables; a part may be empty and then writes zeros in the first pass);
+//   - the launches are k_h_tables_mixed and k_h_accumulate_mixed.
+// Field sums are exact and every stored element canonical, so the words of s depend neither on P, on cap nor on the cuts.
+// d_stage (hmix_stage_words): the A records | their lgs | passes x P part records | cap tables | P rows.
+int h_combine_rows_mixed(halo_ctx *ctx, const uint64_t *h_recs, const uint32_t *lgs, size_t A, size_t lg_max, size_t P, size_t cap, uint64_t *d_stage) {
+    if (lg_max > 24) { set_error("h_coeffs: lg_n > 24 unsupported"); return HALO_E_ARG; }
+    if (A == 0 || A > 65535 || P == 0 || P > A || cap == 0) { set_error("h_combine: 1..65535 polynomials, 1..A parts, at least one table"); return HALO_E_ARG; }
+    for (size_t a = 0; a < A; ++a)
+        if (lgs[a] > lg_max) { set_error("h_combine: a polynomial longer than the row"); return HALO_E_ARG; }
+    if (cap > A) cap = A;
+    const size_t n = (size_t)1 << lg_max, tw = (lg_max + 2) * 4, passes = (A + cap - 1) / cap;
+    const FrPlan p = plan_h_coeffs(n);
+    uint64_t *d_recs = d_stage, *d_lgs64 = d_recs + A * tw, *d_parts = d_lgs64 + hmix_lg_words(A), *d_tabs = d_parts + hcomb_part_words(A, P, cap),
+             *d_rows = d_tabs + cap * H_TAB_WORDS;
+    const uint32_t *d_lgs = reinterpret_cast<const uint32_t *>(d_lgs64);
+    std::vector<size_t> order(A);
+    for (size_t a = 0; a < A; ++a) order[a] = a;
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return lgs[x] > lgs[y]; });
+    std::vector<uint64_t> recs(A * tw);
+    std::vector<uint32_t> slg(A);
+    for (size_t j = 0; j < A; ++j) {
+        std::memcpy(&recs[j * tw], h_recs + order[j] * tw, tw * 8);
+        slg[j] = lgs[order[j]];
+    }
+    std::vector<uint64_t> parts(passes * P * HACC_REC_WORDS, 0);  // (h_0 = 0 in every record)
+    for (size_t pass = 0; pass < passes; ++pass) {
+        const size_t lo = pass * cap, T = A - lo < cap ? A - lo : cap;
+        uint64_t L = 0;
+        for (size_t j = 0; j < T; ++j) L += (uint64_t)1 << slg[lo + j];
+        std::vector<size_t> cnt(P, 0), start(P, 0);
+        uint64_t s = 0;
+        for (size_t j = 0; j < T; ++j) {
+            const size_t q = (size_t)(s * P / L);  // (s < L, so q < P)
+            if (cnt[q]++ == 0) start[q] = j;
+            s += (uint64_t)1 << slg[lo + j];
+        }
+        for (size_t q = 0; q < P; ++q) {
+            uint64_t *rec = &parts[(pass * P + q) * HACC_REC_WORDS];
+            rec[0] = (uint64_t)start[q] | ((uint64_t)cnt[q] << 32);
+            rec[1] = pass == 0 ? 1 : (cnt[q] ? 2 : 0);
+        }
+    }
+    HALO_HIP(hipMemcpy(d_recs, recs.data(), A * tw * 8, hipMemcpyHostToDevice));
+    HALO_HIP(hipMemcpy(d_lgs64, slg.data(), A * 4, hipMemcpyHostToDevice));
+    HALO_HIP(hipMemcpy(d_parts, parts.data(), parts.size() * 8, hipMemcpyHostToDevice));
+    for (size_t pass = 0; pass < passes; ++pass) {
+        const size_t T = A - pass * cap < cap ? A - pass * cap : cap;
+        HALO_LAUNCH(ctx, "k_h_tables_mixed", k_h_tables_mixed, dim3((unsigned)T), dim3(256), 0, d_recs + pass * cap * tw, d_lgs + pass * cap, (int)lg_max, 1,
+                    d_tabs);
+        HALO_LAUNCH(ctx, "k_h_accumulate_mixed", k_h_accumulate_mixed, dim3(p.blocks, (unsigned)P), dim3(256), 0, d_tabs, d_lgs + pass * cap,
+                    d_parts + pass * P * HACC_REC_WORDS, (uint32_t)n, p.E, d_rows, (uint64_t)(n * 4));
     }
     HALO_HIP(hipGetLastError());
     return fr_sum_rows(ctx, d_rows, n * 4, P, n);

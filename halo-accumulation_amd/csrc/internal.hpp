@@ -621,6 +621,13 @@ inline size_t hcomb_rows_offset(size_t A, size_t lg_n, size_t P, size_t cap) {
 }
 inline size_t hcomb_stage_words(size_t A, size_t lg_n, size_t P, size_t cap) { return hcomb_rows_offset(A, lg_n, P, cap) + P * (((size_t)1 << lg_n) * 4); }
 int h_combine_rows(halo_ctx *ctx, const uint64_t *h_recs, size_t A, size_t lg_n, size_t P, size_t cap, uint64_t *d_stage);
+// ... over polynomials of their own lengths 2^lgs[a] <= 2^lg_max, zero-padded to the row (halo_pcdl_check_batch_mixed_combined): the
+// records at the fixed stride of lg_max + 2 elements in the caller's order, sorted by decreasing length inside; the staging holds
+// the A lgs (32 bits each, rounded up to 32 bytes) behind the records, else the layout above
+inline size_t hmix_lg_words(size_t A) { return ((A + 1) / 2 + 3) & ~(size_t)3; }
+inline size_t hmix_rows_offset(size_t A, size_t lg_max, size_t P, size_t cap) { return hcomb_rows_offset(A, lg_max, P, cap) + hmix_lg_words(A); }
+inline size_t hmix_stage_words(size_t A, size_t lg_max, size_t P, size_t cap) { return hcomb_stage_words(A, lg_max, P, cap) + hmix_lg_words(A); }
+int h_combine_rows_mixed(halo_ctx *ctx, const uint64_t *h_recs, const uint32_t *lgs, size_t A, size_t lg_max, size_t P, size_t cap, uint64_t *d_stage);
 // fr_vec.hip: rows[0] = the sum of P rows of n elements at `stride` words (k_fr_sum_rows; P = 1 launches nothing), on ctx->stream
 int fr_sum_rows(halo_ctx *ctx, uint64_t *d_rows, size_t stride, size_t P, size_t n);
 int h_eval_batch(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg_n, const host::Fr &z, uint64_t *d_out);

@@ -46,6 +46,19 @@ size_t check_stage(halo_ctx *ctx, size_t want, size_t per_bytes) {
 // out[k] = SHA3-256(D || LE64(k)) mod r for k < count, D the digest of domain, seed, d, A and the members' indices and Instance words
 static void hashed_weights(const char *domain, size_t domain_len, const uint64_t *blobs, size_t stride, const size_t *idx, size_t A, size_t d,
                            const uint8_t *seed, size_t count, std::vector<Fr> &out);
+// the second stage of every rule: out[k] = SHA3-256(D || LE64(k)) mod r
+static void weights_from_digest(const uint8_t D[32], size_t count, std::vector<Fr> &out) {
+    out.resize(count);
+    for (size_t a = 0; a < count; ++a) {
+        const uint64_t a64 = a;
+        uint8_t dig[32];
+        host::Sha3_256 g;
+        g.update(D, 32);
+        g.update(&a64, 8);
+        g.finalize(dig);
+        out[a] = Fr::from_le_bytes_mod_order(dig);
+    }
+}
 void check_combined_weights(const uint64_t *blobs, size_t stride, const size_t *idx, size_t A, size_t d, const uint8_t *seed, std::vector<Fr> &out) {
     static const char kDomain[] = "halo-accumulation/check-batch-combined/v1";
     hashed_weights(kDomain, sizeof(kDomain) - 1, blobs, stride, idx, A, d, seed, A, out);
@@ -71,35 +84,29 @@ static void hashed_weights(const char *domain, size_t domain_len, const uint64_t
         h.update(blobs + idx[a] * stride, W * 8);
     }
     h.finalize(D);
-    out.resize(count);
-    for (size_t a = 0; a < count; ++a) {
-        const uint64_t a64 = a;
-        uint8_t dig[32];
-        host::Sha3_256 g;
-        g.update(D, 32);
-        g.update(&a64, 8);
-        g.finalize(dig);
-        out[a] = Fr::from_le_bytes_mod_order(dig);
+    weights_from_digest(D, count, out);
+}
+// The weights of the mixed combined check (halo_pcdl_check_batch_mixed_combined; the rule: include/halo_accumulation.h): a domain of
+// its own, and every member's index and degree bound hashed in front of its Instance words, so no digest of a uniform call can be
+// replayed.  blobs[idx[a]] = member idx[a]'s blob, ds[idx[a]] its degree bound.
+void check_mixed_weights(const uint64_t *const *blobs, const size_t *ds, const size_t *idx, size_t A, const uint8_t *seed, std::vector<Fr> &out) {
+    static const char kDomain[] = "halo-accumulation/check-batch-mixed-combined/v1";
+    static const uint8_t kZeros[32] = {};
+    const uint64_t A64 = A;
+    uint8_t D[32];
+    host::Sha3_256 h;
+    h.update(kDomain, sizeof(kDomain) - 1);
+    h.update(seed ? seed : kZeros, 32);
+    h.update(&A64, 8);
+    for (size_t a = 0; a < A; ++a) {
+        const uint64_t i64 = idx[a], d64 = ds[idx[a]];
+        h.update(&i64, 8);
+        h.update(&d64, 8);
+        h.update(blobs[idx[a]], instance_words(ilog2(ds[idx[a]] + 1)) * 8);
     }
+    h.finalize(D);
+    weights_from_digest(D, A, out);
 }
-// P: one row of parts is plan_h_coeffs(n).blocks x 4 waves; enough parts for a wave per SIMD (1024) where the members allow
-size_t check_combined_parts(size_t n, size_t A) {
-    const int forced = dev_hooks().combined_parts;
-    size_t P;
-    if (forced >= 1) P = (size_t)forced;
-    else {
-        const size_t waves = (size_t)plan_h_coeffs(n).blocks * 4;
-        P = (1024 + waves - 1) / waves;
-    }
-    return P > A ? A : (P < 1 ? 1 : P);
-}
-// tables per pass: 256 x 24 KiB = 6 MiB of staging, and a pass of 256 tables is long enough to hide the next launch
-size_t check_combined_cap(size_t A) {
-    const int forced = dev_hooks().combined_cap;
-    const size_t cap = forced >= 1 ? (size_t)forced : 256;
-    return cap > A ? A : cap;
-}
-
 namespace {  // (everything below is local to this file; the entry points at the end are the way in)
 
 // Members per batched launch: the forced size (the development library's sweeps) if it lies in 1 .. max, else max; then as many
@@ -262,6 +269,34 @@ static int combined_usum_device(halo_ctx *ctx, int slot, const std::vector<Batch
     return rc;
 }
 
+// The right side T = sum_a r_a U_a of a combined relation whose left side's MSM is in flight on slots[0] -- on the host pool, or
+// (usum_dev) on slots[1] through d_region -- then the left side collected; *held = the two sides are the same point
+static int combined_sides_agree(halo_ctx *ctx, const int *slots, bool usum_dev, const std::vector<BatchCheck> &res, const std::vector<size_t> &ok,
+                                const std::vector<Fr> &r, uint64_t *d_region, bool *held) {
+    const size_t A = ok.size();
+    Point T = Point::infinity();
+    int rc_t = HALO_OK;
+    if (usum_dev) rc_t = combined_usum_device(ctx, slots[1], res, ok, r, d_region, &T);
+    else {  // one multi-scalar sum per pool thread
+        const size_t chunks = A < 16 ? A : 16;
+        std::vector<Point> part(chunks, Point::infinity());
+        pool_run(chunks, [&](size_t c) {
+            std::vector<Point> p;
+            std::vector<Fr> k;
+            for (size_t a = c * A / chunks; a < (c + 1) * A / chunks; ++a) { p.push_back(res[ok[a]].st.U); k.push_back(r[a]); }
+            part[c] = host::small_msm(p, k);
+        });
+        for (const Point &q : part) T = T + q;
+    }
+    const std::string err_t = rc_t ? halo_last_error() : "";
+    Point left;
+    int rc = msm_finish_batch(ctx, slots[0], &left, 1);  // (collected whatever happened to the right side: nothing stays in flight)
+    if (rc_t) { set_error(err_t); return rc_t; }
+    if (rc) return rc;
+    *held = left == T;
+    return HALO_OK;
+}
+
 static int check_members_combined(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t stride, const uint8_t *seed, const int *slots, int S,
                                   const std::vector<BatchCheck> &res, const std::vector<size_t> &ok, bool *held) {
     const size_t n = d + 1, lg = ilog2(n), A = ok.size(), tw = (lg + 2) * 4;
@@ -292,27 +327,52 @@ static int check_members_combined(halo_ctx *ctx, size_t d, const uint64_t *qs, s
     }
     if (!rc) rc = msm_enqueue_batch(ctx, slots[0], ctx->d_bases, msm_one(ctx->d_check_stage + hcomb_rows_offset(A, lg, P, cap)), true, n);  // asynchronous
     if (rc) return rc;
-    Point T = Point::infinity();
-    int rc_t = HALO_OK;
-    if (usum_dev) rc_t = combined_usum_device(ctx, slots[1], res, ok, r, ctx->d_check_stage + u_off, &T);
-    else {  // one multi-scalar sum per pool thread
-        const size_t chunks = A < 16 ? A : 16;
-        std::vector<Point> part(chunks, Point::infinity());
-        pool_run(chunks, [&](size_t c) {
-            std::vector<Point> p;
-            std::vector<Fr> k;
-            for (size_t a = c * A / chunks; a < (c + 1) * A / chunks; ++a) { p.push_back(res[ok[a]].st.U); k.push_back(r[a]); }
-            part[c] = host::small_msm(p, k);
-        });
-        for (const Point &q : part) T = T + q;
+    return combined_sides_agree(ctx, slots, usum_dev, res, ok, r, ctx->d_check_stage + u_off, held);
+}
+
+// ------------------------------------------------------------------ ... over members of SEVERAL degree bounds (halo_pcdl_check_batch_mixed_combined)
+// A commitment of degree bound d_a lives on the prefix G[0 .. n_a) of the one key (pcdl.rs:99-110, :338), and a shorter h_a is a
+// zero-padded vector over it: <sum_a r_a pad(h_a), G[0 .. n_max)> = sum_a r_a U_a, ONE MSM of n_max = the largest accepted n_a
+// points whatever the members' sizes.  check_members_combined with the scalars from h_combine_rows_mixed (a length per table), the
+// weights of check_mixed_weights and everything sized by lg_max; the right side is the same code.  blob_of / ds: the call's
+// members, ok: the accepted ones with d >= 1 in member order.
+static int check_members_mixed_combined(halo_ctx *ctx, const uint64_t *const *blob_of, const size_t *ds, const uint8_t *seed, const int *slots, int S,
+                                        const std::vector<BatchCheck> &res, const std::vector<size_t> &ok, bool *held) {
+    const size_t A = ok.size();
+    *held = false;
+    if (A > 65535) return HALO_OK;  // (h_combine_rows_mixed takes at most 65535 polynomials: the exact path)
+    std::vector<uint32_t> lgs(A);
+    size_t lg = 0;
+    for (size_t a = 0; a < A; ++a) {
+        lgs[a] = (uint32_t)ilog2(ds[ok[a]] + 1);
+        if (lgs[a] > lg) lg = lgs[a];
     }
-    const std::string err_t = rc_t ? halo_last_error() : "";
-    Point left;
-    rc = msm_finish_batch(ctx, slots[0], &left, 1);  // (collected whatever happened to the right side: nothing stays in flight)
-    if (rc_t) { set_error(err_t); return rc_t; }
+    if (lg > 24) return HALO_OK;  // (the exact path reports it)
+    const size_t n = (size_t)1 << lg, tw = (lg + 2) * 4;
+    const int forced = dev_hooks().combined_usum;
+    const bool usum_dev = S >= 2 && A <= ctx_capacity(ctx) && (forced ? forced == 2 : A >= kCombinedUsumDeviceMin);
+    const size_t cap = check_combined_cap(A);
+    size_t P = check_combined_parts(n, A), u_off = 0;
+    for (;; P = (P + 1) / 2) {  // (fewer parts if the staging cannot hold their rows)
+        u_off = (hmix_stage_words(A, lg, P, cap) + 15) & ~(size_t)15;
+        if (check_stage(ctx, 1, (u_off + (usum_dev ? A * (AFF_STRIDE / 2 + 16) : 0)) * 8) >= 1) break;
+        if (P == 1) return HALO_OK;
+    }
+    std::vector<Fr> r;
+    check_mixed_weights(blob_of, ds, ok.data(), A, seed, r);
+    std::vector<uint64_t> recs(A * tw, 0);
+    for (size_t a = 0; a < A; ++a) {
+        for (size_t k = 0; k <= lgs[a]; ++k) res[ok[a]].st.xis[k].store(&recs[a * tw + 4 * k]);
+        r[a].store(&recs[a * tw + 4 * (lgs[a] + 1)]);
+    }
+    int rc;
+    {
+        StreamGuard on_slot(ctx, ctx->streams[slots[0]]);
+        rc = h_combine_rows_mixed(ctx, recs.data(), lgs.data(), A, lg, P, cap, ctx->d_check_stage);
+    }
+    if (!rc) rc = msm_enqueue_batch(ctx, slots[0], ctx->d_bases, msm_one(ctx->d_check_stage + hmix_rows_offset(A, lg, P, cap)), true, n);  // asynchronous
     if (rc) return rc;
-    *held = left == T;
-    return HALO_OK;
+    return combined_sides_agree(ctx, slots, usum_dev, res, ok, r, ctx->d_check_stage + u_off, held);
 }
 
 // ------------------------------------------------------------------ ... and BOTH halves as one relation (halo_pcdl_check_batch_fused)
@@ -493,6 +553,70 @@ static int check_batch_entry(halo_ctx *ctx, size_t d, const uint64_t *blobs, siz
         if ((size_t)(blobs + i * stride)[12] != d || (blobs + i * stride)[22] != lg) return fail_reject("d_i != d");
     if (m == 0) return HALO_OK;
     return pcdl_check_batch_host(ctx, d, blobs, stride, m, status, mode, seed);
+}
+
+// ------------------------------------------------------------------ ... of m instances of SEVERAL degree bounds (halo_pcdl_check_batch_mixed, .._combined)
+// Member i is the blob blobs[i] of degree bound ds[i] (checked by the caller).  The members are grouped into classes of equal d, in
+// the order of their first member.  Each class runs the succinct half of the uniform call (succinct_half) and -- the exact form,
+// d = 0, and whenever the combined relation did not hold or did not run -- check_members_exact over its accepted members; the
+// results sit in member order throughout (res[i]), a class is a list of member indices.  The combined form puts the accepted
+// members with d >= 1 of ALL classes into one relation (check_members_mixed_combined).
+static int pcdl_check_mixed_host(halo_ctx *ctx, const size_t *ds, const uint64_t *const *blobs, size_t m, int *status, bool combined, const uint8_t *seed) {
+    int slots[HALO_SLOTS], S = idle_slots(ctx, slots);
+    if (!S) { set_error("check_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
+    std::vector<std::vector<size_t>> classes;  // member indices, ascending
+    {
+        std::vector<size_t> seen;  // the classes' degree bounds (a call holds a handful)
+        for (size_t i = 0; i < m; ++i) {
+            size_t c = 0;
+            while (c < seen.size() && seen[c] != ds[i]) ++c;
+            if (c == seen.size()) { seen.push_back(ds[i]); classes.emplace_back(); }
+            classes[c].push_back(i);
+        }
+    }
+    // 1. the succinct half, class by class (pcdl.rs:333)
+    std::vector<BatchCheck> res(m);
+    for (const std::vector<size_t> &cls : classes) {
+        std::vector<BatchCheck> part;
+        int rc = succinct_half(ctx, ds[cls[0]], [&](size_t j) { return blobs[cls[j]]; }, cls.size(), part);
+        if (rc) return rc;
+        for (size_t j = 0; j < cls.size(); ++j) res[cls[j]] = std::move(part[j]);
+    }
+    // 2. one relation over the accepted members of every class (a constant has nothing to combine)
+    bool held = false;
+    if (combined) {
+        std::vector<size_t> ok;
+        for (size_t i = 0; i < m; ++i)
+            if (!res[i].rc && ds[i] >= 1) ok.push_back(i);
+        if (ok.size() >= 2) {
+            int rc = check_members_mixed_combined(ctx, blobs, ds, seed, slots, S, res, ok, &held);
+            if (rc) return rc;
+        }
+    }
+    // 3. the exact path, class by class: every class if the relation failed or did not run -- which members fail never depends on
+    // the weights --, else the constants alone
+    for (const std::vector<size_t> &cls : classes) {
+        const size_t d = ds[cls[0]];
+        if (held && d >= 1) continue;
+        std::vector<size_t> ok;
+        for (size_t i : cls)
+            if (!res[i].rc) ok.push_back(i);
+        int rc = check_members_exact(ctx, d + 1, slots, S, res, ok);
+        if (rc) return rc;
+    }
+    return report_members("instance", m, [&](size_t i) { return res[i].rc; }, [&](size_t i) { return res[i].err; }, status, [](size_t) {});
+}
+// the whole-call checks of the four mixed entry points, then the batch
+static int check_mixed_entry(halo_ctx *ctx, const size_t *ds, const uint64_t *const *blobs, size_t m, int *status, bool combined, const uint8_t *seed) {
+    if (m && (!ds || !blobs)) { set_error("check_batch: null pointer"); return HALO_E_ARG; }
+    for (size_t i = 0; i < m; ++i)
+        if (!blobs[i]) { set_error("check_batch: null pointer"); return HALO_E_ARG; }
+    for (size_t i = 0; i < m; ++i)
+        if (!is_pow2(ds[i] + 1)) return fail_reject("d+1 is not a power of 2!");
+    for (size_t i = 0; i < m; ++i)
+        if ((size_t)blobs[i][12] != ds[i] || blobs[i][22] != ilog2(ds[i] + 1)) return fail_reject("d_i != d");
+    if (m == 0) return HALO_OK;
+    return pcdl_check_mixed_host(ctx, ds, blobs, m, status, combined, seed);
 }
 
 // ------------------------------------------------------------------ pcdl::commit of m polynomials at once
@@ -1565,6 +1689,18 @@ int halo_pcdl_check_batch_fused(halo_ctx *ctx, size_t d, const uint64_t *instanc
     return check_batch_entry(ctx, d, instances, m, status, false, CheckMode::fused, seed);
 }
 
+// ... of m instances each with its own degree bound, exact and as one combined relation (see pcdl_check_mixed_host; the contract:
+// include/halo_accumulation.h)
+int halo_pcdl_check_batch_mixed(halo_ctx *ctx, const size_t *ds, const uint64_t *const *instances, size_t m, int *status) {
+    HALO_CTX(ctx);
+    return check_mixed_entry(ctx, ds, instances, m, status, false, nullptr);
+}
+
+int halo_pcdl_check_batch_mixed_combined(halo_ctx *ctx, const size_t *ds, const uint64_t *const *instances, size_t m, const uint8_t seed[32], int *status) {
+    HALO_CTX(ctx);
+    return check_mixed_entry(ctx, ds, instances, m, status, true, seed);
+}
+
 // acc::prover of k members at once (see acc_prover_batch_dev).  The argument checks are the whole call's and come before any work.
 int halo_acc_prover_batch(halo_ctx *ctx, uint64_t *rng_state, size_t d, const uint64_t *instances, const size_t *counts, size_t k, uint64_t *accs_out,
                           int *status) {
@@ -1604,6 +1740,17 @@ int halo_acc_decider_batch_combined(halo_ctx *ctx, size_t d, const uint64_t *acc
 int halo_acc_decider_batch_fused(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, const uint8_t seed[32], int *status) {
     HALO_CTX(ctx);
     return check_batch_entry(ctx, d, accs, m, status, true, CheckMode::fused, seed);
+}
+
+// ... of m accumulators each with its own degree bound: the mixed check batch over their Instance prefixes
+int halo_acc_decider_batch_mixed(halo_ctx *ctx, const size_t *ds, const uint64_t *const *accs, size_t m, int *status) {
+    HALO_CTX(ctx);
+    return check_mixed_entry(ctx, ds, accs, m, status, false, nullptr);
+}
+
+int halo_acc_decider_batch_mixed_combined(halo_ctx *ctx, const size_t *ds, const uint64_t *const *accs, size_t m, const uint8_t seed[32], int *status) {
+    HALO_CTX(ctx);
+    return check_mixed_entry(ctx, ds, accs, m, status, true, seed);
 }
 
 // pcdl::open of m polynomials at once (see open_batch_dev)

@@ -1,6 +1,7 @@
 // Shared by the pcdl / acc level of the library: pcdl_acc.hip (the single calls, the sharded open and check), pcdl_batch.hip (the
 // batched calls) and, for the blob layout alone, wire.hip; for the transcript's hashes open_host.hip, for is_pow2 ipa_state.hip.
 #pragma once
+#include "fr_plan.hpp"  // (plan_h_coeffs: the parts of the combined checks' scalar step)
 #include "internal.hpp"
 
 namespace halo {
@@ -96,9 +97,28 @@ int transcripts_batch_dev(halo_ctx *ctx, size_t d, const BlobAt &blob_at, size_t
 // The weights r_a of the A accepted members idx[0 .. A) of the blobs at `stride` words, degree bound d, seed = 32 bytes or null
 // (32 zero bytes): the rule of include/halo_accumulation.h, Montgomery form
 void check_combined_weights(const uint64_t *blobs, size_t stride, const size_t *idx, size_t A, size_t d, const uint8_t *seed, std::vector<host::Fr> &out);
-// parts and tables per pass of the scalar step for A polynomials of n coefficients (the hooks "check_combined_parts" / "_cap" first)
-size_t check_combined_parts(size_t n, size_t A);
-size_t check_combined_cap(size_t A);
+// parts and tables per pass of the scalar step for A polynomials of n coefficients (the hooks "check_combined_parts" / "_cap" first;
+// the mixed call: n = the longest polynomial's).  Inline: the development library's twins of the scalar step use the same rule.
+// P: one row of parts is plan_h_coeffs(n).blocks x 4 waves; enough parts for a wave per SIMD (1024) where the members allow
+inline size_t check_combined_parts(size_t n, size_t A) {
+    const int forced = dev_hooks().combined_parts;
+    size_t P;
+    if (forced >= 1) P = (size_t)forced;
+    else {
+        const size_t waves = (size_t)plan_h_coeffs(n).blocks * 4;
+        P = (1024 + waves - 1) / waves;
+    }
+    return P > A ? A : (P < 1 ? 1 : P);
+}
+// tables per pass: 256 x 24 KiB = 6 MiB of staging, and a pass of 256 tables is long enough to hide the next launch
+inline size_t check_combined_cap(size_t A) {
+    const int forced = dev_hooks().combined_cap;
+    const size_t cap = forced >= 1 ? (size_t)forced : 256;
+    return cap > A ? A : cap;
+}
+// ---- pcdl_batch.hip: the mixed combined check batch (halo_pcdl_check_batch_mixed_combined): the weights r_a of the accepted members
+// idx[0 .. A) of a call whose member i is the blob blobs[i] of degree bound ds[i], under the rule's own domain, Montgomery form
+void check_mixed_weights(const uint64_t *const *blobs, const size_t *ds, const size_t *idx, size_t A, const uint8_t *seed, std::vector<host::Fr> &out);
 // ---- pcdl_batch.hip: the fused check batch (halo_pcdl_check_batch_fused): the 2 A weights r_0, s_0, r_1, s_1, .. of the accepted
 // members, arguments as check_combined_weights, under the rule's own domain string (include/halo_accumulation.h), Montgomery form
 void check_fused_weights(const uint64_t *blobs, size_t stride, const size_t *idx, size_t A, size_t d, const uint8_t *seed, std::vector<host::Fr> &out);

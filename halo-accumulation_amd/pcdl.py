@@ -239,6 +239,43 @@ def check_batch_fused(ctx, d, instances, seed=None):
     return _check_batch(ctx, lambda h, dd, qs, m, st: ctx.lib.halo_pcdl_check_batch_fused(h, dd, qs, m, _seed32(seed), st), d, instances)
 
 
+def _pack_mixed(blobs):
+    """-> (the blobs as contiguous uint64 arrays -- keep them alive over the call --, ds from each blob's word 12, the pointer array)"""
+    keep = [np.ascontiguousarray(b, dtype=np.uint64).reshape(-1) for b in blobs]
+    for b in keep:
+        if b.size < 23:
+            raise ValueError("a blob is shorter than an Instance's head")
+    m = len(keep)
+    ds = (C.c_size_t * max(m, 1))(*[int(b[12]) for b in keep])
+    ptrs = (C.c_void_p * max(m, 1))(*[b.ctypes.data for b in keep])
+    return keep, ds, ptrs
+
+
+def _check_batch_mixed(ctx, fn, blobs):
+    keep, ds, ptrs = _pack_mixed(blobs)
+    m = len(keep)
+    status = (C.c_int * max(m, 1))()
+    rc = fn(ctx.h, ds, ptrs, m, status)
+    st = [status[i] for i in range(m)]
+    if rc == _lib.HALO_E_REJECT:
+        raise _lib.HaloReject(ctx.lib.halo_last_error().decode(), st)
+    check(rc)
+    return st
+
+
+def check_batch_mixed(ctx, instances):
+    """pcdl::check of m instances, each of its own degree bound (read from the blob's word 12), in one call
+    (halo_pcdl_check_batch_mixed) -> status list; statuses and HaloReject as check_batch"""
+    return _check_batch_mixed(ctx, ctx.lib.halo_pcdl_check_batch_mixed, instances)
+
+
+def check_batch_mixed_combined(ctx, instances, seed=None):
+    """check_batch_mixed with ONE MSM for the accepted members of every size (halo_pcdl_check_batch_mixed_combined: a shorter h is a
+    zero-padded vector over the same key; seed: 32 bytes of the caller's randomness or None) -> status list; statuses and
+    HaloReject as check_batch_mixed whenever a member is bad"""
+    return _check_batch_mixed(ctx, lambda h, ds, ps, m, st: ctx.lib.halo_pcdl_check_batch_mixed_combined(h, ds, ps, m, _seed32(seed), st), instances)
+
+
 def check_partial(ctx, Cm, d, z, v, pi, stride, offset):
     """One rank's half of pcdl::check over a cyclically sharded key (halo_pcdl_check_partial): -> (U, this rank's share of
     CM.Commit(ck, h)).  The caller adds the shares in rank order and accepts iff the sum is U (sharded.ShardedOpen.check)."""

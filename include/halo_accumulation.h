@@ -320,6 +320,52 @@ int halo_pcdl_check_batch_combined(halo_ctx *ctx, size_t d, const uint64_t *inst
  * 2^14 points with m = 1000 (one fused run of five inside the combined call's range). */
 int halo_pcdl_check_batch_fused(halo_ctx *ctx, size_t d, const uint64_t *instances, size_t m, const uint8_t seed[32] /*nullable*/,
                                 int *status /*nullable*/);
+/* pcdl::check of m instances, EACH WITH ITS OWN degree bound: pcdl::check takes d per call, and a commitment of degree bound d
+ * lives on the prefix G[0 .. d + 1) of the one key (pcdl.rs:99-110, :338), so a verifier that holds one key sees proofs of several
+ * sizes.  instances[i] points at one Instance blob of halo_instance_words(lg(ds[i] + 1)) words; the blobs need be neither
+ * contiguous nor ordered.  The contract:
+ *  - Whole-call errors, before any work, status not written.  A null ctx, or a null ds, a null `instances` or a null instances[i]
+ *    with m > 0: HALO_E_ARG.  Some ds[i] + 1 not a power of two: HALO_E_REJECT ("d+1 is not a power of 2!").  A blob whose d word
+ *    (word 12) or proof lg word (word 22) disagrees with ds[i]: HALO_E_REJECT ("d_i != d").  m = 0: HALO_OK.  No idle slot:
+ *    HALO_E_ARG.
+ *  - Per member.  status[i] (nullable) = what halo_pcdl_check returns for member i alone -- a member whose d + 1 exceeds the key
+ *    included: it gets the single call's reject.  Returns 0, or the first non-zero status in member order with halo_last_error() =
+ *    "instance i: <the single call's message>", i the index in THIS call.
+ *  - The members are grouped into classes of equal d.  Each class runs the succinct half and the exact per-member MSMs of
+ *    halo_pcdl_check_batch, with its staging rule; the results are scattered back to member order. */
+int halo_pcdl_check_batch_mixed(halo_ctx *ctx, const size_t *ds, const uint64_t *const *instances, size_t m, int *status /*nullable*/);
+/* The same with ONE MSM for the members of every size: <h_a, G[0 .. n_a)> = U_a is linear in h_a, and a shorter h_a is a
+ * zero-padded vector over the same key, so the accepted members are checked as
+ *   < sum_a r_a pad(h_a), G[0 .. n_max) >  =  sum_a r_a U_a,        n_max = the largest accepted n_a.
+ * Arguments, whole-call errors, message and return rule are halo_pcdl_check_batch_mixed's.  It carries points 1 - 6 of
+ * halo_pcdl_check_batch_combined's contract with these changes:
+ *  1. The succinct half runs per class of equal d.
+ *  2. A = the accepted members with d_i >= 1, over ALL classes.  A <= 1: the exact path.  A >= 2 (at most 65535, lg <= 24; beyond:
+ *     the exact path): the relation above -- the scalars formed on the device from tables of their own lengths, ONE n_max-point
+ *     MSM over the key (the fixed-base table where the key has one and n_max reaches it), sum_a r_a U_a on the host pool or as a
+ *     small MSM on a second idle slot, by the uniform call's rule.  Members with d_i = 0 always take their class's exact path.
+ *  3. If the relation HOLDS, every such member's status is 0.
+ *  4. If it FAILS -- or the optional staging is refused -- the per-class exact path decides, so a reject never depends on the
+ *     weights and status[], code and message equal halo_pcdl_check_batch_mixed's on the same blobs.
+ *  5., 6. as there (soundness 1/r per hash evaluation; optional staging; devices[0] of a multi-device context; a caller's MSM in
+ *     flight on another slot is left alone).
+ * Weight rule (mixed): a domain of its own, and every member's index and degree bound in the hash, so no digest of a uniform call
+ * can be replayed.  W_i = halo_instance_words(lg(d_i + 1)), seed32 as above.
+ *   D   = SHA3-256("halo-accumulation/check-batch-mixed-combined/v1" || seed32 || LE64(A) || for every accepted member in member
+ *         order: LE64(i) || LE64(d_i) || its W_i Instance words as little-endian bytes)
+ *   r_a = (SHA3-256(D || LE64(a)) read as a little-endian integer) mod r,  a = 0 .. A - 1 its position among the accepted ones.
+ * There is no fused form for mixed sizes: the fused call's term kernel, its record layout and its term count are per lg.
+ * When to call it (one MI355X, tools/time_check_mixed.py --big, profiles/r21_check_mixed.json; members spread evenly over lg 9 .. 14,
+ * on the 2^20-point key 1 to 4 members of lg 20 as well; against the members sorted by d and one halo_pcdl_check_batch_combined, or
+ * one halo_pcdl_check_batch_fused, per size; alternating runs, medians of 5): when the alternative is a combined call per size
+ * it is never slower -- 1.02 to 1.28 times the per-size calls' speed -- and it spares the caller the sort, but only two of the
+ * eight rows are WON against them with the ranges apart (2^14 points with 600 members, 1.05 times; 2^20 points with 13 members,
+ * 1.28 times); in the other six the ranges overlap: NOT won.  Against a fused call per size it wins that one 2^20 row (13 members,
+ * 1.31 times) and the median of the 12-member row at 2^14 (1.15 times, ranges overlapping: NOT won); from 60 members on the
+ * per-size fused calls are faster on both keys, 0.61 to 0.79 times their speed: NOT won.  At those counts sort by d and call
+ * halo_pcdl_check_batch_fused per size. */
+int halo_pcdl_check_batch_mixed_combined(halo_ctx *ctx, const size_t *ds, const uint64_t *const *instances, size_t m,
+                                         const uint8_t seed[32] /*nullable*/, int *status /*nullable*/);
 /* One rank's half of pcdl::check over a key sharded cyclically (halo_ctx_create_urs_strided: point i on rank i mod stride,
  * offset = the rank): the succinct check (pcdl.rs:333, the same on every rank; d + 1 may be up to stride * the shard's size)
  * and this rank's share of CM.Commit(ck, h) (pcdl.rs:338) over its own points.  U_out = the proof's U after the succinct
@@ -386,6 +432,12 @@ int halo_acc_decider_batch_combined(halo_ctx *ctx, size_t d, const uint64_t *acc
  * accumulator's Instance prefix is what is read, and what is hashed into the weights) */
 int halo_acc_decider_batch_fused(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, const uint8_t seed[32] /*nullable*/,
                                  int *status /*nullable*/);
+/* acc::decider of m accumulators, each with its own degree bound: halo_pcdl_check_batch_mixed / .._mixed_combined over the
+ * accumulators' Instance prefixes, with their contracts.  accs[i] points at one Accumulator blob of
+ * halo_accumulator_words(lg(ds[i] + 1)) words; its Instance prefix is what is checked and what is hashed into the weights. */
+int halo_acc_decider_batch_mixed(halo_ctx *ctx, const size_t *ds, const uint64_t *const *accs, size_t m, int *status /*nullable*/);
+int halo_acc_decider_batch_mixed_combined(halo_ctx *ctx, const size_t *ds, const uint64_t *const *accs, size_t m,
+                                          const uint8_t seed[32] /*nullable*/, int *status /*nullable*/);
 /* acc::verifier (acc.rs:223-243) of k accumulators at once: benches/acc.rs:64-74's loop in one call.  accs = k Accumulator blobs
  * at stride halo_accumulator_words(lg(d+1)); counts[j] = the number of Instances member j verifies against accs[j] (0 allowed);
  * instances = sum(counts) Instance blobs at stride halo_instance_words(lg(d+1)), member j's right after member j - 1's.

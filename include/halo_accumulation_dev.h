@@ -39,7 +39,7 @@ extern "C" {
  * from which halo_*_decode_batch decompresses on the device, >= 1; 0: the measured default; "batch_stage_fail" refuses its staging
  * too: the host pool), "check_combined_parts" (parts the polynomials of halo_pcdl_check_batch_combined's
  * scalars are cut into, >= 1, clamped to the accepted members; 0: a wave per SIMD), "check_combined_cap" (their tables per pass, >= 1;
- * 0: the default) -- the scalars are the same words under every value of the two --, "check_combined_usum" (the right side
+ * 0: the default) -- the scalars are the same words under every value of the two; the mixed combined calls read both hooks too --, "check_combined_usum" (the right side
  * sum r_a U_a of a combined check: 1 the host pool, 2 the device where a second slot is idle; 0: by the member count; another
  * value is HALO_E_ARG; "batch_stage_fail" makes the combined and the fused calls take the exact path), "check_fused_chunk" (terms per
  * MSM of the left side of halo_pcdl_check_batch_fused: at least 8, clamped to the context's size; 0: that size; 1..7 or a negative
@@ -102,6 +102,20 @@ int halo_dev_check_weights(const uint64_t *blobs, size_t stride_words, const siz
  * and tables per pass are the product's (the hooks "check_combined_parts" / "check_combined_cap" first).  1 <= A <= 65535,
  * 1 <= lg_n, 2^lg_n <= the context's size (64 at least); temporary device buffers of this call only. */
 int halo_dev_check_combined_scalars(halo_ctx *ctx, const uint64_t *xis, const uint64_t *weights, size_t A, size_t lg_n, uint64_t *out);
+/* The weights of halo_pcdl_check_batch_mixed_combined / halo_acc_decider_batch_mixed_combined (the mixed rule of
+ * include/halo_accumulation.h) for the A accepted members idx[0 .. A) of a call whose member i is the blob blobs[i] of degree bound
+ * ds[i], seed = 32 bytes or NULL: out = A x 4 Montgomery words.  Host only, no context.  HALO_E_ARG: a null pointer, a null
+ * blobs[idx[a]], some ds[idx[a]] + 1 not a power of two. */
+int halo_dev_check_mixed_weights(const uint64_t *const *blobs, const size_t *ds, const size_t *idx, size_t A, const uint8_t seed[32] /*nullable*/,
+                                 uint64_t *out);
+/* The scalar step of the mixed combined check on its own (k_h_tables_mixed, k_h_accumulate_mixed over the parts, k_fr_sum_rows): A
+ * polynomials in the CALLER's order, polynomial a of 2^lgs[a] coefficients (the launcher sorts them by decreasing length).  With
+ * lg_max = the largest lgs[a]: xis = A records at the fixed stride of (lg_max + 1) x 4 Montgomery words, record a's first lgs[a] + 1
+ * elements its challenges (the rest is not read); weights = A x 4; out = 2^lg_max x 4 words, out[k] = the sum of weights_a h_a[k]
+ * over the a with k < 2^lgs[a], canonical.  Parts and tables per pass as in halo_dev_check_combined_scalars, for 2^lg_max
+ * coefficients.  1 <= A <= 65535, 1 <= lgs[a], 2^lg_max <= the context's size (64 at least); temporary device buffers of this call
+ * only. */
+int halo_dev_check_mixed_scalars(halo_ctx *ctx, const uint64_t *xis, const size_t *lgs, const uint64_t *weights, size_t A, uint64_t *out);
 /* The weights of halo_pcdl_check_batch_fused / halo_acc_decider_batch_fused (the fused rule of include/halo_accumulation.h),
  * arguments as halo_dev_check_weights: out = 2 A x 4 Montgomery words, r_0 | s_0 | r_1 | s_1 | ..  Host only, no context. */
 int halo_dev_check_fused_weights(const uint64_t *blobs, size_t stride_words, const size_t *idx, size_t A, size_t d,

@@ -56,6 +56,12 @@ extern "C" {
     pub fn halo_acc_decider_batch_combined(ctx: *mut HaloCtx, d: usize, accs: *const u64, m: usize, seed: *const u8, status: *mut c_int) -> c_int;
     pub fn halo_pcdl_check_batch_fused(ctx: *mut HaloCtx, d: usize, instances: *const u64, m: usize, seed: *const u8, status: *mut c_int) -> c_int;
     pub fn halo_acc_decider_batch_fused(ctx: *mut HaloCtx, d: usize, accs: *const u64, m: usize, seed: *const u8, status: *mut c_int) -> c_int;
+    // ... of m blobs each with its own degree bound (ds[i]; instances[i] / accs[i] point at one blob each), exact and with one MSM for
+    // the accepted members of every size (seed: 32 bytes or null; the contract is in the header)
+    pub fn halo_pcdl_check_batch_mixed(ctx: *mut HaloCtx, ds: *const usize, instances: *const *const u64, m: usize, status: *mut c_int) -> c_int;
+    pub fn halo_pcdl_check_batch_mixed_combined(ctx: *mut HaloCtx, ds: *const usize, instances: *const *const u64, m: usize, seed: *const u8, status: *mut c_int) -> c_int;
+    pub fn halo_acc_decider_batch_mixed(ctx: *mut HaloCtx, ds: *const usize, accs: *const *const u64, m: usize, status: *mut c_int) -> c_int;
+    pub fn halo_acc_decider_batch_mixed_combined(ctx: *mut HaloCtx, ds: *const usize, accs: *const *const u64, m: usize, seed: *const u8, status: *mut c_int) -> c_int;
     // acc::verifier of k accumulators at once (counts[j] instances for accs[j]; status may be null)
     pub fn halo_acc_verifier_batch(ctx: *mut HaloCtx, d: usize, instances: *const u64, counts: *const usize, k: usize, accs: *const u64, status: *mut c_int) -> c_int;
     // acc::prover of k members at once (counts[j] instances for member j; rng_state and status may be null)
