@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "fq29.hpp"
+#include "fq29s.hpp"
 
 namespace halo {
 
@@ -172,6 +173,99 @@ HALO_DEV void xyzz_add(XyzzN &acc, const XyzzN &q) {
     acc.zz = fq_mul(fq_mul(acc.zz, q.zz), PP);
     acc.zzz = fq_mul(fq_mul(acc.zzz, q.zzz), PPP);
 }
+
+// ---------------------------------------------------------------- XYZZ in registers, on the signed field layer (fq29s.hpp)
+// XyzzS : the accumulator of the bucket kernel and of the window sums while it stays in registers: |X|, |Y| < 8p and
+//         |ZZ|, |ZZZ| < 2p, signed normalised.  ZZ with all-zero limbs = infinity.  The formulas, the bounds and the exceptional
+//         cases are those of xyzz_madd / xyzz_add; the two subtractions, Q - x3 and the negation are nine instructions each and
+//         only x3 is carried.  The memory formats do not know this type: xyzs_from_xyzz reads a stored point as it is,
+//         xyzs_to_xyzz brings the coordinates to [0, 2p) once, before the store.
+//         ZZ is never negative: it starts as a stored value and is only ever multiplied by ZZ's and squares, and a Montgomery
+//         product of non-negative factors is non-negative; so it leaves as it is.
+struct XyzzS { Fqs<8> x, y; Fqs<2> zz, zzz; };
+
+HALO_DEV bool xyzs_is_inf(const XyzzS &p) { return fqs_limbs_zero(p.zz); }
+HALO_DEV XyzzS xyzs_inf() {
+    XyzzS r; r.x = fqs_zero<8>(); r.y = fqs_zero<8>(); r.zz = fqs_zero<2>(); r.zzz = fqs_zero<2>(); return r;
+}
+HALO_DEV XyzzS xyzs_from_xyzz(const XyzzN &p) {
+    XyzzS r; r.x = fqs_from_fq<8>(p.x); r.y = fqs_from_fq<8>(p.y); r.zz = fqs_from_fq<2>(p.zz); r.zzz = fqs_from_fq<2>(p.zzz); return r;
+}
+HALO_DEV XyzzN xyzs_to_xyzz(const XyzzS &p) {
+    XyzzN r;
+    r.x = fq_widen<8>(fqs_tighten(p.x)); r.y = fq_widen<8>(fqs_tighten(p.y)); r.zzz = fqs_tighten(p.zzz);
+#pragma unroll
+    for (int i = 0; i < 9; i++) r.zz.v[i] = (uint32_t)p.zz.v[i];
+    if (xyzs_is_inf(p)) return xyzz_inf();  // infinity keeps its all-zero limbs (a tightened 0 reads p)
+    return r;
+}
+HALO_DEV XyzzS xyzs_from_aff(const AffN &a) { return xyzs_from_xyzz(xyzz_from_aff(a)); }
+// dbl-2008-s-1 as xyzz_dbl, on signed operands as they stand (no way back to the stored form first: that way the rare doubling
+// inside an addition set the register count of the window-sum kernels).  y3 = M (S - x3) - W Y is one reduction.
+HALO_DEV XyzzS xyzs_dbl(const XyzzS &p) {
+    Fqs<8> V = fqs_from_fq<8>(fq_muls<4>(fqs_sqr(p.y)));
+    Fqs<4> W = fqs_muls2(fqs_mul(p.y, V));
+    Fqs<2> S = fqs_mul(p.x, V);
+    Fqs<6> M = fqs_from_fq<6>(fq_muls<3>(fqs_sqr(p.x)));
+    XyzzS r;
+    Fqs<6> x3 = fqs_sub_sub2(fqs_from_fq<2>(fqs_sqr(M)), fqs_zero<0>(), S);
+    r.x = fqs_widen<8>(x3);
+    r.y = fqs_widen<8>(fqs_mul_add_mul(M, fqs_sub(S, x3), fqs_neg(W), p.y));
+    r.zz = fqs_mul(V, p.zz);
+    r.zzz = fqs_mul(W, p.zzz);
+    if (xyzs_is_inf(p)) return xyzs_inf();
+    return r;
+}
+// acc += q (affine): madd-2008-s, 8M + 2S, one carry pass
+HALO_DEV void xyzs_madd(XyzzS &acc, const AffN &q) {
+    if (aff_is_inf(q)) return;
+    if (xyzs_is_inf(acc)) { acc = xyzs_from_aff(q); return; }
+    Fqs<2> U2 = fqs_mul(fqs_from_fq<2>(q.x), acc.zz);
+    Fqs<2> S2 = fqs_mul(fqs_from_fq<2>(q.y), acc.zzz);
+    Fqd<10> Pd = fqs_sub(U2, acc.x);
+    Fqd<10> Rd = fqs_sub(S2, acc.y);
+    if (fqd_is_zero_modp(Pd)) {
+        if (fqd_is_zero_modp(Rd)) acc = xyzs_dbl(xyzs_from_aff(q));
+        else acc = xyzs_inf();
+        return;
+    }
+    Fqs<2> PP = fqs_from_fq<2>(fqs_sqr(Pd));
+    Fqs<2> PPP = fqs_mul(Pd, PP);
+    Fqs<2> Qv = fqs_mul(acc.x, PP);
+    Fqs<8> x3 = fqs_sub_sub2(fqs_from_fq<2>(fqs_sqr(Rd)), PPP, Qv);
+    // y3 = R (Q - x3) - Y1 PPP as ONE reduction
+    Fqs<2> y3 = fqs_mul_add_mul(Rd, fqs_sub(Qv, x3), fqs_neg(acc.y), PPP);
+    acc.x = x3;
+    acc.y = fqs_widen<8>(y3);
+    acc.zz = fqs_mul(acc.zz, PP);
+    acc.zzz = fqs_mul(acc.zzz, PPP);
+}
+// acc += q: add-2008-s, 12M + 2S, one carry pass
+HALO_DEV void xyzs_add(XyzzS &acc, const XyzzS &q) {
+    if (xyzs_is_inf(q)) return;
+    if (xyzs_is_inf(acc)) { acc = q; return; }
+    Fqs<2> U1 = fqs_mul(acc.x, q.zz);
+    Fqs<2> U2 = fqs_mul(q.x, acc.zz);
+    Fqs<2> S1 = fqs_mul(acc.y, q.zzz);
+    Fqs<2> S2 = fqs_mul(q.y, acc.zzz);
+    Fqd<4> Pd = fqs_sub(U2, U1);
+    Fqd<4> Rd = fqs_sub(S2, S1);
+    if (fqd_is_zero_modp(Pd)) {
+        if (fqd_is_zero_modp(Rd)) acc = xyzs_dbl(acc);
+        else acc = xyzs_inf();
+        return;
+    }
+    Fqs<2> PP = fqs_from_fq<2>(fqs_sqr(Pd));
+    Fqs<2> PPP = fqs_mul(Pd, PP);
+    Fqs<2> Qv = fqs_mul(U1, PP);
+    Fqs<8> x3 = fqs_sub_sub2(fqs_from_fq<2>(fqs_sqr(Rd)), PPP, Qv);
+    Fqs<2> y3 = fqs_mul_add_mul(Rd, fqs_sub(Qv, x3), fqs_neg(S1), PPP);
+    acc.x = x3;
+    acc.y = fqs_widen<8>(y3);
+    acc.zz = fqs_mul(fqs_mul(acc.zz, q.zz), PP);
+    acc.zzz = fqs_mul(fqs_mul(acc.zzz, q.zzz), PPP);
+}
+
 // native XYZZ in memory: x | y | zz | zzz, 10 words each
 HALO_DEV void xyzz_store(uint32_t *o, const XyzzN &p) {
     fq_store_native(o, p.x); fq_store_native(o + 10, p.y); fq_store_native(o + 20, p.zz); fq_store_native(o + 30, p.zzz);
@@ -188,6 +282,8 @@ HALO_DEV XyzzN xyzz_load(const uint32_t *o) {
     p.x = fq_load_native<8>(o); p.y = fq_load_native<8>(o + 10); p.zz = fq_load_native<2>(o + 20); p.zzz = fq_load_native<2>(o + 30);
     return p;
 }
+HALO_DEV void xyzs_store(uint32_t *o, const XyzzS &p) { xyzz_store(o, xyzs_to_xyzz(p)); }
+HALO_DEV XyzzS xyzs_load(const uint32_t *o) { return xyzs_from_xyzz(xyzz_load(o)); }
 // (X, Y, ZZ, ZZZ) -> arkworks Jacobian words with Z = ZZZ: X*ZZ^2, Y*ZZZ^2, ZZZ   (ZZ^3 = ZZZ^2)
 HALO_DEV void xyzz_store_jac_words(uint64_t *o, const XyzzN &p) {
     if (xyzz_is_inf(p)) {
@@ -339,6 +435,15 @@ HALO_DEV XyzzN xyzz_shfl(const XyzzN &p, int src_lane) {
     XyzzN r;
     r.x = fq_shfl(p.x, src_lane); r.y = fq_shfl(p.y, src_lane);
     r.zz = fq_shfl(p.zz, src_lane); r.zzz = fq_shfl(p.zzz, src_lane);
+    return r;
+}
+HALO_DEV XyzzS xyzs_shfl(const XyzzS &p, int src_lane) {
+    XyzzS r;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        r.x.v[i] = __shfl(p.x.v[i], src_lane, 64); r.y.v[i] = __shfl(p.y.v[i], src_lane, 64);
+        r.zz.v[i] = __shfl(p.zz.v[i], src_lane, 64); r.zzz.v[i] = __shfl(p.zzz.v[i], src_lane, 64);
+    }
     return r;
 }
 HALO_DEV Fe fe_shfl(const Fe &a, int src_lane) {

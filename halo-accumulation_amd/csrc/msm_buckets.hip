@@ -157,7 +157,7 @@ __global__ __launch_bounds__(256) void k_msm_accumulate(const uint32_t *__restri
     uint4 rec = order[tid];
     if (rec.z == 0) return;
     uint32_t t = rec.x, st = rec.y, cnt = rec.z;
-    XyzzN acc = xyzz_inf();
+    XyzzS acc = xyzs_inf();  // signed limbs while it stays in registers (curve.hpp)
     // the next point's coordinates are fetched before the current mixed add is issued, and ITS index one add earlier
     // still: index -> gather is a dependent pair of loads, and with the index fetched in the same iteration the wave
     // sat in s_waitcnt for a whole memory latency per addition (17 % of the kernel's wave cycles parked:
@@ -173,9 +173,9 @@ __global__ __launch_bounds__(256) void k_msm_accumulate(const uint32_t *__restri
         e = e1;
         if (k + 1 < cnt) nxt = aff_load_signed(bases + AFF_STRIDE * (size_t)(e & 0x7fffffffu), (e >> 31) != 0);
         e1 = sorted[st + (k + 2 < last ? k + 2 : last)];
-        xyzz_madd(acc, p);
+        xyzs_madd(acc, p);
     }
-    xyzz_store(partial + XYZZ_WORDS * (size_t)t, acc);
+    xyzs_store(partial + XYZZ_WORDS * (size_t)t, acc);
 }
 
 // Folds the partials of multi-task buckets into the first one.  Blocks [0, small_blocks): one lane per bucket with 2..8
@@ -189,39 +189,39 @@ __global__ __launch_bounds__(64) void k_msm_combine(const uint32_t *__restrict__
         for (uint32_t b = blockIdx.x * 64 + lane; b < meta[140]; b += small_blocks * 64) {
             uint32_t g = biglist[total - 1 - b];
             uint32_t nt = ntask[g], t0 = scan_at(toff, tblockoff, g);
-            XyzzN acc = xyzz_load(partial + XYZZ_WORDS * (size_t)t0);
+            XyzzS acc = xyzs_load(partial + XYZZ_WORDS * (size_t)t0);
 #pragma unroll 1
             for (uint32_t j = 1; j < nt; j++) {
-                XyzzN q = xyzz_load(partial + XYZZ_WORDS * (size_t)(t0 + j));
-                xyzz_add(acc, q);
+                XyzzS q = xyzs_load(partial + XYZZ_WORDS * (size_t)(t0 + j));
+                xyzs_add(acc, q);
             }
-            xyzz_store(partial + XYZZ_WORDS * (size_t)t0, acc);
+            xyzs_store(partial + XYZZ_WORDS * (size_t)t0, acc);
         }
         return;
     }
     for (uint32_t b = blockIdx.x - small_blocks; b < meta[1]; b += gridDim.x - small_blocks) {
         uint32_t g = biglist[b];
         uint32_t nt = ntask[g], t0 = scan_at(toff, tblockoff, g);
-        XyzzN acc = xyzz_inf();
+        XyzzS acc = xyzs_inf();
 #pragma unroll 1
         for (uint32_t j = lane; j < nt; j += 64) {
-            XyzzN q = xyzz_load(partial + XYZZ_WORDS * (size_t)(t0 + j));
-            xyzz_add(acc, q);
+            XyzzS q = xyzs_load(partial + XYZZ_WORDS * (size_t)(t0 + j));
+            xyzs_add(acc, q);
         }
 #pragma unroll 1
         for (int off = 32; off >= 1; off >>= 1) {
-            XyzzN o = xyzz_shfl(acc, (lane + off) & 63);
-            if ((int)lane < off) xyzz_add(acc, o);
+            XyzzS o = xyzs_shfl(acc, (lane + off) & 63);
+            if ((int)lane < off) xyzs_add(acc, o);
         }
-        if (lane == 0) xyzz_store(partial + XYZZ_WORDS * (size_t)t0, acc);
+        if (lane == 0) xyzs_store(partial + XYZZ_WORDS * (size_t)t0, acc);
     }
 }
 
 // value of bucket g after the combine pass
-HALO_DEV XyzzN bucket_value(const uint32_t *__restrict__ partial, const uint32_t *__restrict__ ntask, const uint32_t *__restrict__ toff,
+HALO_DEV XyzzS bucket_value(const uint32_t *__restrict__ partial, const uint32_t *__restrict__ ntask, const uint32_t *__restrict__ toff,
                             const uint32_t *__restrict__ tblockoff, uint32_t g) {
-    if (ntask[g] == 0) return xyzz_inf();
-    return xyzz_load(partial + XYZZ_WORDS * (size_t)scan_at(toff, tblockoff, g));
+    if (ntask[g] == 0) return xyzs_inf();
+    return xyzs_load(partial + XYZZ_WORDS * (size_t)scan_at(toff, tblockoff, g));
 }
 
 // ------------------------------------------------------------------------------ reduce
@@ -232,40 +232,43 @@ HALO_DEV XyzzN bucket_value(const uint32_t *__restrict__ partial, const uint32_t
 // wave of k_msm_accumulate; forcing 256 made it spill, and that spill -- scratch inside a replayed hipGraph after the
 // queue's scratch had been re-assigned -- is what faulted on ROCm 7.2 in round 1 (build gate:
 // csrc/check_resources.py).
-HALO_DEV void wave_weighted_sum(XyzzN &S, XyzzN &T, int k, uint32_t *park, int live = 64) {
+HALO_DEV void wave_weighted_sum(XyzzS &S, XyzzS &T, int k, uint32_t *park, int live = 64) {
     int lane = threadIdx.x & 63;
     {
         uint32_t *mine = park + lane;  // word j of lane l at park[64 * j + l]: conflict-free
 #pragma unroll
         for (int j = 0; j < 9; j++) {
-            mine[64 * j] = T.x.v[j]; mine[64 * (9 + j)] = T.y.v[j]; mine[64 * (18 + j)] = T.zz.v[j]; mine[64 * (27 + j)] = T.zzz.v[j];
+            mine[64 * j] = (uint32_t)T.x.v[j]; mine[64 * (9 + j)] = (uint32_t)T.y.v[j];
+            mine[64 * (18 + j)] = (uint32_t)T.zz.v[j]; mine[64 * (27 + j)] = (uint32_t)T.zzz.v[j];
         }
     }
     // inclusive suffix scan: S_l <- sum_{j >= l} S_j   (lanes >= live hold infinity: their steps are skipped)
 #pragma unroll 1
     for (int off = 1; off < live; off <<= 1) {
-        XyzzN o = xyzz_shfl(S, (lane + off) & 63);
-        if (lane + off < 64) xyzz_add(S, o);
+        XyzzS o = xyzs_shfl(S, (lane + off) & 63);
+        if (lane + off < 64) xyzs_add(S, o);
     }
     // sum_{l>=1} suffix_l = sum_l l * S_l
-    XyzzN V = (lane >= 1) ? S : xyzz_inf();
+    XyzzN Vn = (lane >= 1) ? xyzs_to_xyzz(S) : xyzz_inf();
 #pragma unroll 1
-    for (int i = 0; i < k; i++) V = xyzz_dbl(V);
+    for (int i = 0; i < k; i++) Vn = xyzz_dbl(Vn);
+    XyzzS V = xyzs_from_xyzz(Vn);
     {
         const uint32_t *mine = park + lane;
 #pragma unroll
         for (int j = 0; j < 9; j++) {
-            T.x.v[j] = mine[64 * j]; T.y.v[j] = mine[64 * (9 + j)]; T.zz.v[j] = mine[64 * (18 + j)]; T.zzz.v[j] = mine[64 * (27 + j)];
+            T.x.v[j] = (int32_t)mine[64 * j]; T.y.v[j] = (int32_t)mine[64 * (9 + j)];
+            T.zz.v[j] = (int32_t)mine[64 * (18 + j)]; T.zzz.v[j] = (int32_t)mine[64 * (27 + j)];
         }
     }
-    xyzz_add(T, V);
+    xyzs_add(T, V);
     int top = 32;
     while (top >= live && top > 1) top >>= 1;  // first offset that still pairs two live lanes
     if (live <= 1) top = 0;
 #pragma unroll 1
     for (int off = top; off >= 1; off >>= 1) {
-        XyzzN o = xyzz_shfl(T, (lane + off) & 63);
-        if (lane < off) xyzz_add(T, o);
+        XyzzS o = xyzs_shfl(T, (lane + off) & 63);
+        if (lane < off) xyzs_add(T, o);
     }
 }
 
@@ -278,20 +281,20 @@ __global__ __launch_bounds__(64) void k_msm_reduce1(const uint32_t *__restrict__
     uint32_t w = blockIdx.x / nseg, s = blockIdx.x % nseg;
     uint32_t lane = threadIdx.x;
     uint32_t first = s * 64 * L + lane * L;
-    XyzzN run = xyzz_inf(), tot = xyzz_inf();
+    XyzzS run = xyzs_inf(), tot = xyzs_inf();
 #pragma unroll 1
     for (int j = (int)L - 1; j >= 0; j--) {
         uint32_t idx = first + (uint32_t)j;
-        XyzzN b = xyzz_inf();
+        XyzzS b = xyzs_inf();
         if (idx < B) b = bucket_value(partial, ntask, toff, tblockoff, w * B + idx);
-        xyzz_add(run, b);
-        xyzz_add(tot, run);
+        xyzs_add(run, b);
+        xyzs_add(tot, run);
     }
     wave_weighted_sum(run, tot, logL, park);
     if (lane == 0) {
         uint32_t *o = seg + 2 * XYZZ_WORDS * ((size_t)w * nseg + s);
-        xyzz_store(o, run);
-        xyzz_store(o + XYZZ_WORDS, tot);
+        xyzs_store(o, run);
+        xyzs_store(o + XYZZ_WORDS, tot);
     }
 }
 // The segments of a window are combined by k_smsm_final (smsm.hip, quad-parallel): see quad_final_enqueue.
@@ -328,22 +331,22 @@ __global__ __launch_bounds__(64) void k_msm_reduce_rc(const uint32_t *__restrict
         g0 = ((lane & (width - 1)) << sh.lg_cols) + col; stride = width << sh.lg_cols; slot = col;
     }
     g0 += set * (rows << sh.lg_cols);
-    XyzzN acc = xyzz_inf();
-    XyzzN b = bucket_value(partial, ntask, toff, tblockoff, g0);
+    XyzzS acc = xyzs_inf();
+    XyzzS b = bucket_value(partial, ntask, toff, tblockoff, g0);
 #pragma unroll 1
     for (uint32_t i = 0; i < per; i++) {
-        XyzzN nb2 = xyzz_inf();
+        XyzzS nb2 = xyzs_inf();
         if (i + 1 < per) nb2 = bucket_value(partial, ntask, toff, tblockoff, g0 + (i + 1) * stride);  // in flight during the addition
-        xyzz_add(acc, b);
+        xyzs_add(acc, b);
         b = nb2;
     }
     const uint32_t sub = lane & (width - 1);
 #pragma unroll 1
     for (uint32_t off = width >> 1; off >= 1; off >>= 1) {
-        XyzzN o = xyzz_shfl(acc, (int)((lane + off) & 63));
-        if (sub < off) xyzz_add(acc, o);
+        XyzzS o = xyzs_shfl(acc, (int)((lane + off) & 63));
+        if (sub < off) xyzs_add(acc, o);
     }
-    if (sub == 0) xyzz_store(ent + XYZZ_WORDS * ((size_t)set * (rows + cols) + slot), acc);
+    if (sub == 0) xyzs_store(ent + XYZZ_WORDS * ((size_t)set * (rows + cols) + slot), acc);
 }
 
 }  // namespace halo
