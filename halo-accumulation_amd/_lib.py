@@ -106,6 +106,8 @@ _SIGS = {
     "halo_pcdl_check_batch_mixed_combined": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.c_size_t, C.c_char_p, C.POINTER(C.c_int)]),
     "halo_acc_decider_batch_mixed": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.c_size_t, C.POINTER(C.c_int)]),
     "halo_acc_decider_batch_mixed_combined": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.c_size_t, C.c_char_p, C.POINTER(C.c_int)]),
+    "halo_pcdl_check_batch_mixed_fused": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.c_size_t, C.c_char_p, C.POINTER(C.c_int)]),
+    "halo_acc_decider_batch_mixed_fused": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_void_p), C.c_size_t, C.c_char_p, C.POINTER(C.c_int)]),
     "halo_pcdl_check_partial": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p, u64p, u64p, C.c_uint64, C.c_uint64, u64p, u64p]),
     "halo_pcdl_open_sharded": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), u64p, C.c_size_t, C.c_size_t, u64p, C.c_size_t,
                                          u64p, u64p, C.c_void_p, C.c_void_p, u64p, u64p]),
@@ -192,6 +194,8 @@ _DEV_SIGS = {
     "halo_dev_check_mixed_scalars": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_size_t), u64p, C.c_size_t, u64p]),
     "halo_dev_check_fused_weights": (C.c_int, [u64p, C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t, C.c_size_t, C.c_char_p, u64p]),
     "halo_dev_check_fused_terms": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_size_t, u64p, u64p]),
+    "halo_dev_check_mixed_fused_weights": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_size_t, C.c_char_p, u64p]),
+    "halo_dev_check_mixed_terms": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_size_t), C.c_size_t, u64p, u64p]),
     "halo_dev_small_msm_seg": (C.c_int, [C.c_void_p, u64p, u64p, C.POINTER(C.c_size_t), C.c_size_t, u64p]),
     "halo_dev_batch_small_msm": (C.c_int, [C.c_void_p, u64p, u64p, C.c_size_t, C.c_size_t, u64p]),
     "halo_dev_batch_to_affine": (C.c_int, [C.c_void_p, u64p, C.c_size_t, u64p]),

@@ -183,3 +183,10 @@ def decider_batch_mixed_combined(ctx, accs, seed=None):
     """decider_batch_mixed with ONE MSM for the accepted members of every size (halo_acc_decider_batch_mixed_combined; seed: 32 bytes
     or None) -> status list; statuses and HaloReject as decider_batch_mixed whenever a member is bad"""
     return _check_batch_mixed(ctx, lambda h, ds, ps, m, st: ctx.lib.halo_acc_decider_batch_mixed_combined(h, ds, ps, m, _seed32(seed), st), accs)
+
+
+def decider_batch_mixed_fused(ctx, accs, seed=None):
+    """decider_batch_mixed as ONE relation over the members of every size, the succinct relations included
+    (halo_acc_decider_batch_mixed_fused; seed: 32 bytes or None) -> status list; statuses and HaloReject as decider_batch_mixed
+    whenever a member is bad"""
+    return _check_batch_mixed(ctx, lambda h, ds, ps, m, st: ctx.lib.halo_acc_decider_batch_mixed_fused(h, ds, ps, m, _seed32(seed), st), accs)

@@ -16,9 +16,10 @@ import sys
 # list) would pass a gate that only looks at what it finds.  k_fr_sum_rows: the combined check batch's row sum, enqueued on a
 # slot's stream between launch sequences that replay as graphs.  k_fused_terms: the fused check batch's term scalars, likewise -- a
 # lane of ~400 dependent products that must keep its working set in registers.  k_h_tables_mixed, k_h_accumulate_mixed: the mixed
-# combined check batch's scalar step, enqueued like k_fr_sum_rows.
+# combined check batch's scalar step, enqueued like k_fr_sum_rows.  k_mixed_terms: the mixed fused check batch's term scalars, the
+# lane of k_fused_terms at a size per member.
 REQUIRED = ("k_fr_sum_rows", "k_fused_terms", "k_transcript_points", "k_transcript_head", "k_transcript_chain", "k_h_tables_mixed",
-            "k_h_accumulate_mixed")
+            "k_h_accumulate_mixed", "k_mixed_terms")
 
 
 def parse(path):

@@ -16,6 +16,7 @@
 #include "dev_lazy_ops.hpp"
 #include "fr_plan.hpp"
 #include "internal.hpp"
+#include "mixed_terms_lane.hpp"  // (the descriptors of halo_dev_check_mixed_terms)
 #include "pcdl_internal.hpp"
 
 namespace halo {
@@ -457,10 +458,54 @@ int halo_dev_check_fused_terms(halo_ctx *ctx, const uint64_t *recs, size_t M, si
     HALO_HIP(hipMalloc(&d, (M * (rw + 4 + K * 4) + 4) * 8));
     uint64_t *d_recs = d, *d_shares = d + M * rw, *d_sc = d_shares + M * 4, *d_h = d_sc + M * K * 4;
     hipError_t e = hipMemcpy(d_recs, recs, M * rw * 8, hipMemcpyHostToDevice);
-    int rc = e == hipSuccess ? fused_terms(ctx, d_recs, M, lg_n, d_sc, d_shares, d_h) : hip_fail(e, "hipMemcpy");
+    int rc = e == hipSuccess ? fused_terms(ctx, d_recs, M, lg_n, nullptr, d_sc, d_shares, d_h) : hip_fail(e, "hipMemcpy");
     e = hipStreamSynchronize(ctx->stream);  // (also on failure: nothing of this call may be in flight when its buffer goes)
     if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
     if (!rc && (e = hipMemcpy(scalars_out, d_sc, M * K * 32, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    if (!rc && (e = hipMemcpy(h_out, d_h, 32, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    (void)hipFree(d);
+    return rc;
+}
+
+// host only: the 2 A weights of the mixed fused check batch as the product computes them (tests/test_check_mixed_fused_cpu.py restates
+// the rule)
+int halo_dev_check_mixed_fused_weights(const uint64_t *const *blobs, const size_t *ds, const size_t *idx, size_t A, const uint8_t seed[32], uint64_t *out) {
+    if (A == 0) return HALO_OK;
+    if (!blobs || !ds || !idx || !out) { set_error("check_mixed_fused_weights: null pointer"); return HALO_E_ARG; }
+    for (size_t a = 0; a < A; ++a) {
+        if (!blobs[idx[a]]) { set_error("check_mixed_fused_weights: null pointer"); return HALO_E_ARG; }
+        if (!is_pow2(ds[idx[a]] + 1)) { set_error("check_mixed_fused_weights: every d + 1 is a power of two"); return HALO_E_ARG; }
+    }
+    std::vector<host::Fr> w;
+    check_mixed_fused_weights(blobs, ds, idx, A, seed, w);
+    for (size_t k = 0; k < 2 * A; ++k) w[k].store(out + 4 * k);
+    return HALO_OK;
+}
+
+// the mixed fused check's term kernel on its own (tests/test_gpu_check_mixed_fused.py holds it against Python integers): M dense
+// records of lgs[a] + 6 Montgomery elements -> the members' dense scalars and H's scalar; temporary device buffers of this call only
+int halo_dev_check_mixed_terms(halo_ctx *ctx, const uint64_t *recs, const size_t *lgs, size_t M, uint64_t *scalars_out, uint64_t h_out[4]) {
+    HALO_CTX(ctx);
+    if (!recs || !lgs || !scalars_out || !h_out) { set_error("check_mixed_terms: null pointer"); return HALO_E_ARG; }
+    if (M < 1 || M > 65535) { set_error("check_mixed_terms: 1..65535 members"); return HALO_E_ARG; }
+    std::vector<uint32_t> lg32(M), desc(M * MIXED_DESC_WORDS);
+    for (size_t a = 0; a < M; ++a) {
+        if (lgs[a] < 1 || lgs[a] > (size_t)FUSED_MAX_LG) { set_error("check_mixed_terms: lg n must be in 1..24"); return HALO_E_ARG; }
+        lg32[a] = (uint32_t)lgs[a];
+    }
+    size_t rw = 0, terms = 0;
+    mixed_terms_describe(lg32.data(), M, desc.data(), &rw, &terms);
+    const size_t dw = ((desc.size() + 1) / 2 + 3) & ~(size_t)3;  // the descriptors in 64-bit words, the regions behind them 32-byte aligned
+    uint64_t *d = nullptr;
+    alloc_epoch_bump(ctx);
+    HALO_HIP(hipMalloc(&d, (rw + M * 4 + dw + terms * 4 + 4) * 8));
+    uint64_t *d_recs = d, *d_shares = d + rw, *d_desc = d_shares + M * 4, *d_sc = d_desc + dw, *d_h = d_sc + terms * 4;
+    hipError_t e = hipMemcpy(d_recs, recs, rw * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_desc, desc.data(), desc.size() * 4, hipMemcpyHostToDevice);
+    int rc = e == hipSuccess ? fused_terms(ctx, d_recs, M, 0, reinterpret_cast<const uint32_t *>(d_desc), d_sc, d_shares, d_h) : hip_fail(e, "hipMemcpy");
+    e = hipStreamSynchronize(ctx->stream);  // (also on failure: nothing of this call may be in flight when its buffer goes)
+    if (!rc && e != hipSuccess) rc = hip_fail(e, "hipStreamSynchronize");
+    if (!rc && (e = hipMemcpy(scalars_out, d_sc, terms * 32, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     if (!rc && (e = hipMemcpy(h_out, d_h, 32, hipMemcpyDeviceToHost)) != hipSuccess) rc = hip_fail(e, "hipMemcpy");
     (void)hipFree(d);
     return rc;

@@ -635,7 +635,10 @@ int h_eval_batch(halo_ctx *ctx, const uint64_t *d_xis, size_t m, size_t lg_n, co
 int h_eval_each(halo_ctx *ctx, const uint64_t *d_xis, const uint64_t *d_zs, size_t m, size_t lg_n, uint64_t *d_out);
 // ---- fused_check.hip: the term scalars of the fused check batch (k_fused_terms + the sum of H's shares), on ctx->stream; the record
 // and scalar layouts are fused_lane.hpp's (lg + 6 Montgomery elements in, 2 lg + 2 canonical scalars out per member)
-int fused_terms(halo_ctx *ctx, const uint64_t *d_recs, size_t M, size_t lg, uint64_t *d_scalars, uint64_t *d_shares, uint64_t *d_h);
+// d_desc (nullable): the members' own sizes and offsets, mixed_terms_lane.hpp's descriptors -- the mixed fused check batch, whose
+// records and scalars lie dense (mixed_terms.hip: k_mixed_terms in k_fused_terms' place; mixed_terms_launch is the launch alone)
+int fused_terms(halo_ctx *ctx, const uint64_t *d_recs, size_t M, size_t lg, const uint32_t *d_desc, uint64_t *d_scalars, uint64_t *d_shares, uint64_t *d_h);
+int mixed_terms_launch(halo_ctx *ctx, const uint64_t *d_recs, const uint32_t *d_desc, size_t M, uint64_t *d_scalars, uint64_t *d_shares);
 // ---- small_sums.hip: m sums of K scalar multiples (canonical scalars, affine points) -> m Jacobian points
 int batch_small_msm(halo_ctx *ctx, const uint64_t *d_points, const uint64_t *d_scalars, size_t m, size_t K, uint64_t *d_out);
 // sums of 1..64 terms each, several to a wave (k_small_msm_seg): sum s holds terms sum_off[s] .. sum_off[s + 1] (same term

@@ -5,7 +5,7 @@
 // internal.hpp: idle_slots, StreamGuard, report_members.
 #include "curve.hpp"  // (AFF_STRIDE: the staged keys of the folded schedule)
 #include "fr_plan.hpp"
-#include "fused_lane.hpp"  // (the record and term layout of the fused check)
+#include "mixed_terms_lane.hpp"  // (the record and term layout of the fused checks: fused_lane.hpp, and the mixed call's descriptors)
 #include "pcdl_internal.hpp"
 
 namespace halo {
@@ -88,14 +88,20 @@ static void hashed_weights(const char *domain, size_t domain_len, const uint64_t
 }
 // The weights of the mixed combined check (halo_pcdl_check_batch_mixed_combined; the rule: include/halo_accumulation.h): a domain of
 // its own, and every member's index and degree bound hashed in front of its Instance words, so no digest of a uniform call can be
-// replayed.  blobs[idx[a]] = member idx[a]'s blob, ds[idx[a]] its degree bound.
-void check_mixed_weights(const uint64_t *const *blobs, const size_t *ds, const size_t *idx, size_t A, const uint8_t *seed, std::vector<Fr> &out) {
-    static const char kDomain[] = "halo-accumulation/check-batch-mixed-combined/v1";
+// replayed.  blobs[idx[a]] = member idx[a]'s blob, ds[idx[a]] its degree bound.  The mixed fused check
+// (halo_pcdl_check_batch_mixed_fused) hashes the same under its own domain and draws two weights per member: r_a = out[2 a],
+// s_a = out[2 a + 1].
+void check_mixed_weights_rule(MixedRule rule, const uint64_t *const *blobs, const size_t *ds, const size_t *idx, size_t A, const uint8_t *seed,
+                              std::vector<Fr> &out) {
+    static const char kCombined[] = "halo-accumulation/check-batch-mixed-combined/v1";
+    static const char kFused[] = "halo-accumulation/check-batch-mixed-fused/v1";
     static const uint8_t kZeros[32] = {};
+    const bool fused = rule == MixedRule::fused;
     const uint64_t A64 = A;
     uint8_t D[32];
     host::Sha3_256 h;
-    h.update(kDomain, sizeof(kDomain) - 1);
+    if (fused) h.update(kFused, sizeof(kFused) - 1);
+    else h.update(kCombined, sizeof(kCombined) - 1);
     h.update(seed ? seed : kZeros, 32);
     h.update(&A64, 8);
     for (size_t a = 0; a < A; ++a) {
@@ -105,7 +111,7 @@ void check_mixed_weights(const uint64_t *const *blobs, const size_t *ds, const s
         h.update(blobs[idx[a]], instance_words(ilog2(ds[idx[a]] + 1)) * 8);
     }
     h.finalize(D);
-    weights_from_digest(D, A, out);
+    weights_from_digest(D, fused ? 2 * A : A, out);
 }
 namespace {  // (everything below is local to this file; the entry points at the end are the way in)
 
@@ -396,22 +402,130 @@ static size_t fused_chunk_points(const halo_ctx *ctx, size_t T) {
     if (forced >= 8 && (size_t)forced < C) C = (size_t)forced;
     return C > T ? T : C;
 }
+// The left side is one body for the uniform call and for the mixed one (halo_pcdl_check_batch_mixed_fused, below): what differs is
+// where a member's record and terms lie -- constant strides, or prefix sums over members of their own sizes -- and which kernel
+// computes the scalars.  FusedMember: one taking-part member as the body packs it; FusedLeft: the terms' count, their cut into
+// chunks and the staging (words):
+//   records | shares | descriptors (the mixed call's) | scalars Tp x 4 | Jacobian words Tp x 12 | native entries (128-byte aligned)
+// with the right side's regions behind them at o_h.
+struct FusedMember {
+    const uint64_t *q;       // its blob
+    const SuccinctState *st;  // its accepted transcript
+    size_t lg, rec_off, term_off;  // its size; where its record starts (words) and its first term lies (terms)
+    const Fr *r, *s;         // its two weights
+};
+struct FusedLeft {
+    size_t M, T, C, chunks, Tp;  // members; terms, H included; terms per chunk; chunks; terms with the last chunk filled up
+    size_t o_rec, o_share, o_desc, o_sc, o_jac, o_nat, o_h;
+};
+// rec_words: all records; terms: the members' terms (H not counted); desc_words: 64-bit words of descriptors (0: none).  false: Tp
+// does not fit MsmBatch::base_off's 32 bits (the exact path)
+static bool fused_left_layout(const halo_ctx *ctx, size_t M, size_t rec_words, size_t terms, size_t desc_words, FusedLeft *L) {
+    L->M = M;
+    L->T = terms + 1;
+    L->C = fused_chunk_points(ctx, L->T);
+    L->chunks = (L->T + L->C - 1) / L->C;
+    L->Tp = L->chunks * L->C;
+    if (L->Tp >= ((size_t)1 << 32)) return false;
+    L->o_rec = 0;
+    L->o_share = L->o_rec + rec_words;
+    L->o_desc = L->o_share + M * 4;
+    L->o_sc = L->o_desc + ((desc_words + 3) & ~(size_t)3);
+    L->o_jac = L->o_sc + L->Tp * 4;
+    L->o_nat = (L->o_jac + L->Tp * 12 + 15) & ~(size_t)15;
+    L->o_h = L->o_nat + L->Tp * (AFF_STRIDE / 2);
+    return true;
+}
+// The left side of a fused relation whose right side's MSM is in flight on slots[0], through the context's check staging as L lays
+// it out: the members' records and points packed on the host pool (member_at(a) -> FusedMember), H and the padding at infinity
+// behind them, one upload; terms(d_recs, d_scalars, d_shares, d_h) computes the scalars on the current stream; the padding's
+// scalars are zeroed, the points go to native entries, and the chunks run in batched sequences on the second idle slot (one idle
+// slot: on it, after the right side).  The right side is collected whatever happened: nothing stays in flight.  *held = both
+// sides are the same point.
+template <class MemberAt, class Terms>
+static int fused_sides_agree(halo_ctx *ctx, const int *slots, int S, const FusedLeft &L, MemberAt member_at, Terms terms, bool *held) {
+    const size_t M = L.M, T = L.T, C = L.C, Tp = L.Tp;
+    uint64_t *d_stage = ctx->d_check_stage;
+    Point right, left = Point::infinity();
+    bool right_done = false;
+    auto finish_right = [&]() { right_done = true; return msm_finish_batch(ctx, slots[0], &right, 1); };
+    int rc = HALO_OK;
+    if (S < 2) rc = finish_right();  // (one idle slot: the left side runs on it afterwards)
+    const int lslot = S < 2 ? slots[0] : slots[1];
+    // the left side's records and points
+    std::vector<uint64_t> recs(L.o_share - L.o_rec), jac(Tp * 12);
+    if (!rc) {
+        pool_run(M, [&](size_t a) {
+            const FusedMember m = member_at(a);
+            const size_t lg = m.lg;
+            uint64_t *proof = const_cast<uint64_t *>(m.q) + 21;
+            uint64_t *r = &recs[m.rec_off], *p = &jac[m.term_off * 12];
+            for (size_t k = 0; k <= lg; ++k) m.st->xis[k].store(r + 4 * k);
+            std::memcpy(r + 4 * (lg + 1), m.q + 13, 64);                   // z | v
+            std::memcpy(r + 4 * (lg + 3), pf_c(proof, lg), 32);            // c
+            m.r->store(r + 4 * (lg + 4));
+            m.s->store(r + 4 * (lg + 5));
+            m.st->C_prime.store(p);
+            std::memcpy(p + 12, pf_L(proof, 0), lg * 96);                  // L_0 .. (the blob's own words)
+            std::memcpy(p + 12 * (lg + 1), pf_R(proof, lg, 0), lg * 96);   // R_0 ..
+            std::memcpy(p + 12 * (2 * lg + 1), pf_U(proof, lg), 96);
+        });
+        static const Point kH = public_h_table().mul(Fr::one());
+        kH.store(&jac[(T - 1) * 12]);
+        for (size_t t = T; t < Tp; ++t) Point::infinity().store(&jac[t * 12]);
+        hipError_t e = hipMemcpy(d_stage + L.o_rec, recs.data(), recs.size() * 8, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(d_stage + L.o_jac, jac.data(), jac.size() * 8, hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    }
+    if (!rc) {
+        StreamGuard on_slot(ctx, ctx->streams[lslot]);
+        rc = terms(d_stage + L.o_rec, d_stage + L.o_sc, d_stage + L.o_share, d_stage + L.o_sc + (T - 1) * 4);
+        if (!rc && Tp > T) {
+            hipError_t e = hipMemsetAsync(d_stage + L.o_sc + T * 4, 0, (Tp - T) * 32, ctx->stream);
+            if (e != hipSuccess) rc = hip_fail(e, "hipMemsetAsync");
+        }
+        if (!rc) rc = batch_to_affine(ctx, d_stage + L.o_jac, Tp, reinterpret_cast<uint32_t *>(d_stage + L.o_nat));
+    }
+    if (!rc) {
+        const size_t G = (size_t)group_size(ctx, C, 0, MSM_MAX_BATCH, 1);
+        rc = rotate_groups(
+            ctx, &lslot, 1, L.chunks, G < L.chunks ? G : L.chunks,
+            [&](size_t, size_t first, size_t cnt) -> int {
+                MsmBatch mb;
+                mb.count = (int)cnt;
+                for (size_t b = 0; b < cnt; ++b) {
+                    mb.scalars[b] = d_stage + L.o_sc + (first + b) * C * 4;
+                    mb.base_off[b] = (uint32_t)((first + b) * C);
+                }
+                return msm_enqueue_batch(ctx, lslot, reinterpret_cast<const uint32_t *>(d_stage + L.o_nat), mb, false, C);
+            },
+            [&](size_t, size_t cnt, const Point *pts) {
+                for (size_t b = 0; b < cnt; ++b) left = left + pts[b];
+            });
+    }
+    const std::string err = rc ? halo_last_error() : "";
+    if (!right_done) {  // (collected whatever happened to the left side: nothing stays in flight)
+        int rc_r = finish_right();
+        if (!rc) rc = rc_r;
+        else set_error(err);
+    }
+    if (rc) return rc;
+    *held = left == right;
+    return HALO_OK;
+}
 static int check_members_fused(halo_ctx *ctx, size_t d, const uint64_t *qs, size_t stride, const uint8_t *seed, const int *slots, int S,
                                const std::vector<BatchCheck> &res, const std::vector<size_t> &ok, bool *held) {
     const size_t n = d + 1, lg = ilog2(n), M = ok.size(), tw = (lg + 2) * 4;
     *held = false;
     if (lg > 24) { set_error("h_coeffs: lg_n > 24 unsupported"); return HALO_E_ARG; }
     if (M > 65535) return HALO_OK;  // (h_combine_rows takes at most 65535 polynomials: the exact batch)
-    const size_t K = fused_term_count((int)lg), T = M * K + 1, rw = fused_rec_words((int)lg);
-    const size_t C = fused_chunk_points(ctx, T), chunks = (T + C - 1) / C, Tp = chunks * C;
-    if (Tp >= ((size_t)1 << 32)) return HALO_OK;  // (MsmBatch::base_off is 32 bits wide)
-    // the staging (words): records | shares | scalars Tp x 4 | Jacobian words Tp x 12 | native entries (128-byte aligned) | the right side's regions
-    const size_t o_rec = 0, o_share = o_rec + M * rw, o_sc = o_share + M * 4, o_jac = o_sc + Tp * 4;
-    const size_t o_nat = (o_jac + Tp * 12 + 15) & ~(size_t)15, o_h = o_nat + Tp * (AFF_STRIDE / 2);
+    const size_t K = fused_term_count((int)lg), rw = fused_rec_words((int)lg);
+    FusedLeft L;
+    if (!fused_left_layout(ctx, M, M * rw, M * K, 0, &L)) return HALO_OK;
     const size_t cap = check_combined_cap(M);
     size_t P = check_combined_parts(n, M);
     for (;; P = (P + 1) / 2) {  // (fewer parts if the staging cannot hold their rows)
-        if (check_stage(ctx, 1, (o_h + hcomb_stage_words(M, lg, P, cap)) * 8) >= 1) break;
+        if (check_stage(ctx, 1, (L.o_h + hcomb_stage_words(M, lg, P, cap)) * 8) >= 1) break;
         if (P == 1) return HALO_OK;
     }
     uint64_t *d_stage = ctx->d_check_stage;
@@ -427,76 +541,79 @@ static int check_members_fused(halo_ctx *ctx, size_t d, const uint64_t *qs, size
         int rc;
         {
             StreamGuard on_slot(ctx, ctx->streams[slots[0]]);
-            rc = h_combine_rows(ctx, recs.data(), M, lg, P, cap, d_stage + o_h);
+            rc = h_combine_rows(ctx, recs.data(), M, lg, P, cap, d_stage + L.o_h);
         }
-        if (!rc) rc = msm_enqueue_batch(ctx, slots[0], ctx->d_bases, msm_one(d_stage + o_h + hcomb_rows_offset(M, lg, P, cap)), true, n);
+        if (!rc) rc = msm_enqueue_batch(ctx, slots[0], ctx->d_bases, msm_one(d_stage + L.o_h + hcomb_rows_offset(M, lg, P, cap)), true, n);
         if (rc) return rc;
     }
-    Point right, left = Point::infinity();
-    bool right_done = false;
-    auto finish_right = [&]() { right_done = true; return msm_finish_batch(ctx, slots[0], &right, 1); };
-    int rc = HALO_OK;
-    if (S < 2) rc = finish_right();  // (one idle slot: the left side runs on it afterwards)
-    const int lslot = S < 2 ? slots[0] : slots[1];
-    // the left side's records and points
-    std::vector<uint64_t> recs(M * rw), jac(Tp * 12);
-    if (!rc) {
-        pool_run(M, [&](size_t a) {
-            const uint64_t *q = qs + ok[a] * stride, *proof = q + 21;
-            const SuccinctState &st = res[ok[a]].st;
-            uint64_t *r = &recs[a * rw], *p = &jac[a * K * 12];
-            for (size_t k = 0; k <= lg; ++k) st.xis[k].store(r + 4 * k);
-            std::memcpy(r + 4 * (lg + 1), q + 13, 64);                                          // z | v
-            std::memcpy(r + 4 * (lg + 3), pf_c(const_cast<uint64_t *>(proof), lg), 32);         // c
-            w[2 * a].store(r + 4 * (lg + 4));
-            w[2 * a + 1].store(r + 4 * (lg + 5));
-            st.C_prime.store(p);
-            std::memcpy(p + 12, pf_L(const_cast<uint64_t *>(proof), 0), lg * 96);               // L_0 .. (the blob's own words)
-            std::memcpy(p + 12 * (lg + 1), pf_R(const_cast<uint64_t *>(proof), lg, 0), lg * 96);  // R_0 ..
-            std::memcpy(p + 12 * (2 * lg + 1), pf_U(const_cast<uint64_t *>(proof), lg), 96);
-        });
-        static const Point kH = public_h_table().mul(Fr::one());
-        kH.store(&jac[(T - 1) * 12]);
-        for (size_t t = T; t < Tp; ++t) Point::infinity().store(&jac[t * 12]);
-        hipError_t e = hipMemcpy(d_stage + o_rec, recs.data(), recs.size() * 8, hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(d_stage + o_jac, jac.data(), jac.size() * 8, hipMemcpyHostToDevice);
-        if (e != hipSuccess) rc = hip_fail(e, "hipMemcpy");
+    return fused_sides_agree(
+        ctx, slots, S, L, [&](size_t a) { return FusedMember{qs + ok[a] * stride, &res[ok[a]].st, lg, a * rw, a * K, &w[2 * a], &w[2 * a + 1]}; },
+        [&](const uint64_t *d_recs, uint64_t *d_sc, uint64_t *d_shares, uint64_t *d_h) { return fused_terms(ctx, d_recs, M, lg, nullptr, d_sc, d_shares, d_h); },
+        held);
+}
+
+// ------------------------------------------------------------------ ... and that over members of SEVERAL degree bounds (halo_pcdl_check_batch_mixed_fused)
+// check_members_fused with a size per member.  Right side: <sum_a s_a pad(h_a), G[0 .. n_max)>, the mixed combined check's scalars
+// (h_combine_rows_mixed) with the weights s_a and ONE n_max-point MSM over the key.  Left side: the same body; the members' records
+// and terms lie dense in member order, fused_rec_words(lg_a) words and 2 lg_a + 2 terms each, so the chunked MSMs see T = sum_a
+// (2 lg_a + 2) + 1 terms with nothing between members, and k_mixed_terms (mixed_terms.hip) finds each member's through its
+// descriptor {lg_a, record offset, term offset}.  blob_of / ds: the call's members, ok: those whose transcripts held with d >= 1,
+// in member order; tr: the transcripts in member order.
+static int check_members_mixed_fused(halo_ctx *ctx, const uint64_t *const *blob_of, const size_t *ds, const uint8_t *seed, const int *slots, int S,
+                                     const std::vector<BatchCheck> &tr, const std::vector<size_t> &ok, bool *held) {
+    const size_t M = ok.size();
+    *held = false;
+    if (M > 65535) return HALO_OK;  // (h_combine_rows_mixed and fr_sum_rows take at most 65535 rows: the exact path)
+    std::vector<uint32_t> lgs(M);
+    size_t lg = 0;
+    for (size_t a = 0; a < M; ++a) {
+        lgs[a] = (uint32_t)ilog2(ds[ok[a]] + 1);
+        if (lgs[a] > lg) lg = lgs[a];
     }
-    if (!rc) {
-        StreamGuard on_slot(ctx, ctx->streams[lslot]);
-        rc = fused_terms(ctx, d_stage + o_rec, M, lg, d_stage + o_sc, d_stage + o_share, d_stage + o_sc + (T - 1) * 4);
-        if (!rc && Tp > T) {
-            hipError_t e = hipMemsetAsync(d_stage + o_sc + T * 4, 0, (Tp - T) * 32, ctx->stream);
-            if (e != hipSuccess) rc = hip_fail(e, "hipMemsetAsync");
+    if (lg > (size_t)FUSED_MAX_LG) return HALO_OK;  // (the exact path reports it)
+    std::vector<uint32_t> desc(M * MIXED_DESC_WORDS + 1);
+    size_t rec_words = 0, terms = 0;
+    mixed_terms_describe(lgs.data(), M, desc.data(), &rec_words, &terms);
+    const size_t desc_words = (M * MIXED_DESC_WORDS + 1) / 2;
+    FusedLeft L;
+    if (!fused_left_layout(ctx, M, rec_words, terms, desc_words, &L)) return HALO_OK;
+    const size_t n = (size_t)1 << lg, tw = (lg + 2) * 4;
+    const size_t cap = check_combined_cap(M);
+    size_t P = check_combined_parts(n, M);
+    for (;; P = (P + 1) / 2) {  // (fewer parts if the staging cannot hold their rows)
+        if (check_stage(ctx, 1, (L.o_h + hmix_stage_words(M, lg, P, cap)) * 8) >= 1) break;
+        if (P == 1) return HALO_OK;
+    }
+    uint64_t *d_stage = ctx->d_check_stage;
+    std::vector<Fr> w;
+    check_mixed_fused_weights(blob_of, ds, ok.data(), M, seed, w);
+    // the right side: sum_a s_a pad(h_a)(X) over the key, asynchronous
+    {
+        std::vector<uint64_t> recs(M * tw, 0);
+        for (size_t a = 0; a < M; ++a) {
+            for (size_t k = 0; k <= lgs[a]; ++k) tr[ok[a]].st.xis[k].store(&recs[a * tw + 4 * k]);
+            w[2 * a + 1].store(&recs[a * tw + 4 * (lgs[a] + 1)]);
         }
-        if (!rc) rc = batch_to_affine(ctx, d_stage + o_jac, Tp, reinterpret_cast<uint32_t *>(d_stage + o_nat));
+        int rc;
+        {
+            StreamGuard on_slot(ctx, ctx->streams[slots[0]]);
+            rc = h_combine_rows_mixed(ctx, recs.data(), lgs.data(), M, lg, P, cap, d_stage + L.o_h);
+        }
+        if (!rc) rc = msm_enqueue_batch(ctx, slots[0], ctx->d_bases, msm_one(d_stage + L.o_h + hmix_rows_offset(M, lg, P, cap)), true, n);
+        if (rc) return rc;
     }
-    if (!rc) {
-        const size_t G = (size_t)group_size(ctx, C, 0, MSM_MAX_BATCH, 1);
-        rc = rotate_groups(
-            ctx, &lslot, 1, chunks, G < chunks ? G : chunks,
-            [&](size_t, size_t first, size_t cnt) -> int {
-                MsmBatch mb;
-                mb.count = (int)cnt;
-                for (size_t b = 0; b < cnt; ++b) {
-                    mb.scalars[b] = d_stage + o_sc + (first + b) * C * 4;
-                    mb.base_off[b] = (uint32_t)((first + b) * C);
-                }
-                return msm_enqueue_batch(ctx, lslot, reinterpret_cast<const uint32_t *>(d_stage + o_nat), mb, false, C);
-            },
-            [&](size_t, size_t cnt, const Point *pts) {
-                for (size_t b = 0; b < cnt; ++b) left = left + pts[b];
-            });
-    }
-    const std::string err = rc ? halo_last_error() : "";
-    if (!right_done) {  // (collected whatever happened to the left side: nothing stays in flight)
-        int rc_r = finish_right();
-        if (!rc) rc = rc_r;
-        else set_error(err);
-    }
-    if (rc) return rc;
-    *held = left == right;
-    return HALO_OK;
+    return fused_sides_agree(
+        ctx, slots, S, L,
+        [&](size_t a) {
+            const uint32_t *da = &desc[MIXED_DESC_WORDS * a];
+            return FusedMember{blob_of[ok[a]], &tr[ok[a]].st, da[0], da[1], da[2], &w[2 * a], &w[2 * a + 1]};
+        },
+        [&](const uint64_t *d_recs, uint64_t *d_sc, uint64_t *d_shares, uint64_t *d_h) -> int {
+            uint32_t *d_desc = reinterpret_cast<uint32_t *>(d_stage + L.o_desc);
+            HALO_HIP(hipMemcpy(d_desc, desc.data(), M * MIXED_DESC_WORDS * 4, hipMemcpyHostToDevice));
+            return fused_terms(ctx, d_recs, M, 0, d_desc, d_sc, d_shares, d_h);
+        },
+        held);
 }
 
 // blobs: m Instances (or Accumulators, whose Instance prefix is checked) at `stride` words, all of degree bound d (checked by
@@ -555,13 +672,19 @@ static int check_batch_entry(halo_ctx *ctx, size_t d, const uint64_t *blobs, siz
     return pcdl_check_batch_host(ctx, d, blobs, stride, m, status, mode, seed);
 }
 
-// ------------------------------------------------------------------ ... of m instances of SEVERAL degree bounds (halo_pcdl_check_batch_mixed, .._combined)
+// ------------------------------------------------------------------ ... of m instances of SEVERAL degree bounds (halo_pcdl_check_batch_mixed, .._combined, .._fused)
 // Member i is the blob blobs[i] of degree bound ds[i] (checked by the caller).  The members are grouped into classes of equal d, in
 // the order of their first member.  Each class runs the succinct half of the uniform call (succinct_half) and -- the exact form,
 // d = 0, and whenever the combined relation did not hold or did not run -- check_members_exact over its accepted members; the
 // results sit in member order throughout (res[i]), a class is a list of member indices.  The combined form puts the accepted
 // members with d >= 1 of ALL classes into one relation (check_members_mixed_combined).
-static int pcdl_check_mixed_host(halo_ctx *ctx, const size_t *ds, const uint64_t *const *blobs, size_t m, int *status, bool combined, const uint8_t *seed) {
+//
+// The fused form (halo_pcdl_check_batch_mixed_fused) runs the transcripts alone per class first (transcripts_batch: a class of its
+// own size takes the device route by the uniform rule), then ONE relation over the members of every class whose transcripts held
+// with d >= 1 (check_members_mixed_fused).  If it held, the transcripts' outcomes are the call's; if it failed or did not run --
+// or constants are among the members -- the exact path below runs from the top.
+static int pcdl_check_mixed_host(halo_ctx *ctx, const size_t *ds, const uint64_t *const *blobs, size_t m, int *status, CheckMode mode, const uint8_t *seed) {
+    const bool combined = mode == CheckMode::combined;
     int slots[HALO_SLOTS], S = idle_slots(ctx, slots);
     if (!S) { set_error("check_batch: every slot has an MSM in flight"); return HALO_E_ARG; }
     std::vector<std::vector<size_t>> classes;  // member indices, ascending
@@ -574,9 +697,38 @@ static int pcdl_check_mixed_host(halo_ctx *ctx, const size_t *ds, const uint64_t
             classes[c].push_back(i);
         }
     }
-    // 1. the succinct half, class by class (pcdl.rs:333)
+    // the classes the fused relation settled: their members' outcomes are in res already (constants never are)
+    bool fused_held = false;
     std::vector<BatchCheck> res(m);
+    if (mode == CheckMode::fused) {
+        size_t taking = 0;  // members with d >= 1
+        for (size_t i = 0; i < m; ++i) taking += ds[i] >= 1;
+        if (taking >= 2) {
+            // the transcripts alone, as succinct_challenges runs them (no relation: that is the fused relation's left side)
+            std::vector<BatchCheck> tr(m);
+            for (const std::vector<size_t> &cls : classes) {
+                if (ds[cls[0]] == 0) continue;
+                std::vector<BatchCheck> part;
+                int rc = transcripts_batch(ctx, ds[cls[0]], [&](size_t j) { return blobs[cls[j]]; }, cls.size(), part);
+                if (rc) return rc;
+                for (size_t j = 0; j < cls.size(); ++j) tr[cls[j]] = std::move(part[j]);
+            }
+            std::vector<size_t> acc;
+            for (size_t i = 0; i < m; ++i)
+                if (ds[i] >= 1 && !tr[i].rc) acc.push_back(i);
+            if (acc.size() >= 2) {
+                int rc = check_members_mixed_fused(ctx, blobs, ds, seed, slots, S, tr, acc, &fused_held);
+                if (rc) return rc;
+            }
+            if (fused_held)
+                for (size_t i = 0; i < m; ++i)
+                    if (ds[i] >= 1) res[i] = std::move(tr[i]);
+            // else the relation failed, or did not run: the exact path decides, so a reject never depends on the weights
+        }
+    }
+    // 1. the succinct half, class by class (pcdl.rs:333)
     for (const std::vector<size_t> &cls : classes) {
+        if (fused_held && ds[cls[0]] >= 1) continue;
         std::vector<BatchCheck> part;
         int rc = succinct_half(ctx, ds[cls[0]], [&](size_t j) { return blobs[cls[j]]; }, cls.size(), part);
         if (rc) return rc;
@@ -597,7 +749,7 @@ static int pcdl_check_mixed_host(halo_ctx *ctx, const size_t *ds, const uint64_t
     // the weights --, else the constants alone
     for (const std::vector<size_t> &cls : classes) {
         const size_t d = ds[cls[0]];
-        if (held && d >= 1) continue;
+        if ((held || fused_held) && d >= 1) continue;
         std::vector<size_t> ok;
         for (size_t i : cls)
             if (!res[i].rc) ok.push_back(i);
@@ -606,8 +758,8 @@ static int pcdl_check_mixed_host(halo_ctx *ctx, const size_t *ds, const uint64_t
     }
     return report_members("instance", m, [&](size_t i) { return res[i].rc; }, [&](size_t i) { return res[i].err; }, status, [](size_t) {});
 }
-// the whole-call checks of the four mixed entry points, then the batch
-static int check_mixed_entry(halo_ctx *ctx, const size_t *ds, const uint64_t *const *blobs, size_t m, int *status, bool combined, const uint8_t *seed) {
+// the whole-call checks of the six mixed entry points, then the batch
+static int check_mixed_entry(halo_ctx *ctx, const size_t *ds, const uint64_t *const *blobs, size_t m, int *status, CheckMode mode, const uint8_t *seed) {
     if (m && (!ds || !blobs)) { set_error("check_batch: null pointer"); return HALO_E_ARG; }
     for (size_t i = 0; i < m; ++i)
         if (!blobs[i]) { set_error("check_batch: null pointer"); return HALO_E_ARG; }
@@ -616,7 +768,7 @@ static int check_mixed_entry(halo_ctx *ctx, const size_t *ds, const uint64_t *co
     for (size_t i = 0; i < m; ++i)
         if ((size_t)blobs[i][12] != ds[i] || blobs[i][22] != ilog2(ds[i] + 1)) return fail_reject("d_i != d");
     if (m == 0) return HALO_OK;
-    return pcdl_check_mixed_host(ctx, ds, blobs, m, status, combined, seed);
+    return pcdl_check_mixed_host(ctx, ds, blobs, m, status, mode, seed);
 }
 
 // ------------------------------------------------------------------ pcdl::commit of m polynomials at once
@@ -1693,12 +1845,18 @@ int halo_pcdl_check_batch_fused(halo_ctx *ctx, size_t d, const uint64_t *instanc
 // include/halo_accumulation.h)
 int halo_pcdl_check_batch_mixed(halo_ctx *ctx, const size_t *ds, const uint64_t *const *instances, size_t m, int *status) {
     HALO_CTX(ctx);
-    return check_mixed_entry(ctx, ds, instances, m, status, false, nullptr);
+    return check_mixed_entry(ctx, ds, instances, m, status, CheckMode::exact, nullptr);
 }
 
 int halo_pcdl_check_batch_mixed_combined(halo_ctx *ctx, const size_t *ds, const uint64_t *const *instances, size_t m, const uint8_t seed[32], int *status) {
     HALO_CTX(ctx);
-    return check_mixed_entry(ctx, ds, instances, m, status, true, seed);
+    return check_mixed_entry(ctx, ds, instances, m, status, CheckMode::combined, seed);
+}
+
+// ... and as one fused relation over the members of every size (see check_members_mixed_fused; the contract: include/halo_accumulation.h)
+int halo_pcdl_check_batch_mixed_fused(halo_ctx *ctx, const size_t *ds, const uint64_t *const *instances, size_t m, const uint8_t seed[32], int *status) {
+    HALO_CTX(ctx);
+    return check_mixed_entry(ctx, ds, instances, m, status, CheckMode::fused, seed);
 }
 
 // acc::prover of k members at once (see acc_prover_batch_dev).  The argument checks are the whole call's and come before any work.
@@ -1745,12 +1903,17 @@ int halo_acc_decider_batch_fused(halo_ctx *ctx, size_t d, const uint64_t *accs, 
 // ... of m accumulators each with its own degree bound: the mixed check batch over their Instance prefixes
 int halo_acc_decider_batch_mixed(halo_ctx *ctx, const size_t *ds, const uint64_t *const *accs, size_t m, int *status) {
     HALO_CTX(ctx);
-    return check_mixed_entry(ctx, ds, accs, m, status, false, nullptr);
+    return check_mixed_entry(ctx, ds, accs, m, status, CheckMode::exact, nullptr);
 }
 
 int halo_acc_decider_batch_mixed_combined(halo_ctx *ctx, const size_t *ds, const uint64_t *const *accs, size_t m, const uint8_t seed[32], int *status) {
     HALO_CTX(ctx);
-    return check_mixed_entry(ctx, ds, accs, m, status, true, seed);
+    return check_mixed_entry(ctx, ds, accs, m, status, CheckMode::combined, seed);
+}
+
+int halo_acc_decider_batch_mixed_fused(halo_ctx *ctx, const size_t *ds, const uint64_t *const *accs, size_t m, const uint8_t seed[32], int *status) {
+    HALO_CTX(ctx);
+    return check_mixed_entry(ctx, ds, accs, m, status, CheckMode::fused, seed);
 }
 
 // pcdl::open of m polynomials at once (see open_batch_dev)

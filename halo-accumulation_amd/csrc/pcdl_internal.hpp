@@ -118,7 +118,19 @@ inline size_t check_combined_cap(size_t A) {
 }
 // ---- pcdl_batch.hip: the mixed combined check batch (halo_pcdl_check_batch_mixed_combined): the weights r_a of the accepted members
 // idx[0 .. A) of a call whose member i is the blob blobs[i] of degree bound ds[i], under the rule's own domain, Montgomery form
-void check_mixed_weights(const uint64_t *const *blobs, const size_t *ds, const size_t *idx, size_t A, const uint8_t *seed, std::vector<host::Fr> &out);
+// ... and of the mixed fused check batch (halo_pcdl_check_batch_mixed_fused): the 2 A weights r_0, s_0, r_1, s_1, .. under that rule's
+// domain.  The two rules hash the same things, so they are one function behind two names (one name in the development library's
+// reach, product.map).
+enum class MixedRule { combined, fused };
+void check_mixed_weights_rule(MixedRule rule, const uint64_t *const *blobs, const size_t *ds, const size_t *idx, size_t A, const uint8_t *seed,
+                              std::vector<host::Fr> &out);
+inline void check_mixed_weights(const uint64_t *const *blobs, const size_t *ds, const size_t *idx, size_t A, const uint8_t *seed, std::vector<host::Fr> &out) {
+    check_mixed_weights_rule(MixedRule::combined, blobs, ds, idx, A, seed, out);
+}
+inline void check_mixed_fused_weights(const uint64_t *const *blobs, const size_t *ds, const size_t *idx, size_t A, const uint8_t *seed,
+                                      std::vector<host::Fr> &out) {
+    check_mixed_weights_rule(MixedRule::fused, blobs, ds, idx, A, seed, out);
+}
 // ---- pcdl_batch.hip: the fused check batch (halo_pcdl_check_batch_fused): the 2 A weights r_0, s_0, r_1, s_1, .. of the accepted
 // members, arguments as check_combined_weights, under the rule's own domain string (include/halo_accumulation.h), Montgomery form
 void check_fused_weights(const uint64_t *blobs, size_t stride, const size_t *idx, size_t A, size_t d, const uint8_t *seed, std::vector<host::Fr> &out);

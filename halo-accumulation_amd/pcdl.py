@@ -276,6 +276,13 @@ def check_batch_mixed_combined(ctx, instances, seed=None):
     return _check_batch_mixed(ctx, lambda h, ds, ps, m, st: ctx.lib.halo_pcdl_check_batch_mixed_combined(h, ds, ps, m, _seed32(seed), st), instances)
 
 
+def check_batch_mixed_fused(ctx, instances, seed=None):
+    """check_batch_mixed as ONE relation over the members of every size, the succinct relations included
+    (halo_pcdl_check_batch_mixed_fused; seed: 32 bytes of the caller's randomness or None) -> status list; statuses and HaloReject
+    as check_batch_mixed whenever a member is bad"""
+    return _check_batch_mixed(ctx, lambda h, ds, ps, m, st: ctx.lib.halo_pcdl_check_batch_mixed_fused(h, ds, ps, m, _seed32(seed), st), instances)
+
+
 def check_partial(ctx, Cm, d, z, v, pi, stride, offset):
     """One rank's half of pcdl::check over a cyclically sharded key (halo_pcdl_check_partial): -> (U, this rank's share of
     CM.Commit(ck, h)).  The caller adds the shares in rank order and accepts iff the sum is U (sharded.ShardedOpen.check)."""

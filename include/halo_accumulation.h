@@ -354,7 +354,8 @@ int halo_pcdl_check_batch_mixed(halo_ctx *ctx, const size_t *ds, const uint64_t 
  *   D   = SHA3-256("halo-accumulation/check-batch-mixed-combined/v1" || seed32 || LE64(A) || for every accepted member in member
  *         order: LE64(i) || LE64(d_i) || its W_i Instance words as little-endian bytes)
  *   r_a = (SHA3-256(D || LE64(a)) read as a little-endian integer) mod r,  a = 0 .. A - 1 its position among the accepted ones.
- * There is no fused form for mixed sizes: the fused call's term kernel, its record layout and its term count are per lg.
+ * This call itself has no fused form for mixed sizes inside it (its succinct half stays exact, per class); the fused relation over
+ * mixed sizes is halo_pcdl_check_batch_mixed_fused below, whose term kernel takes a length per member.
  * When to call it (one MI355X, tools/time_check_mixed.py --big, profiles/r21_check_mixed.json; members spread evenly over lg 9 .. 14,
  * on the 2^20-point key 1 to 4 members of lg 20 as well; against the members sorted by d and one halo_pcdl_check_batch_combined, or
  * one halo_pcdl_check_batch_fused, per size; alternating runs, medians of 5): when the alternative is a combined call per size
@@ -362,10 +363,54 @@ int halo_pcdl_check_batch_mixed(halo_ctx *ctx, const size_t *ds, const uint64_t 
  * eight rows are WON against them with the ranges apart (2^14 points with 600 members, 1.05 times; 2^20 points with 13 members,
  * 1.28 times); in the other six the ranges overlap: NOT won.  Against a fused call per size it wins that one 2^20 row (13 members,
  * 1.31 times) and the median of the 12-member row at 2^14 (1.15 times, ranges overlapping: NOT won); from 60 members on the
- * per-size fused calls are faster on both keys, 0.61 to 0.79 times their speed: NOT won.  At those counts sort by d and call
- * halo_pcdl_check_batch_fused per size. */
+ * per-size fused calls are faster on both keys, 0.61 to 0.79 times their speed: NOT won.  At every count
+ * halo_pcdl_check_batch_mixed_fused below is faster than either (profiles/r22_check_mixed_fused.json): no sort by d is needed. */
 int halo_pcdl_check_batch_mixed_combined(halo_ctx *ctx, const size_t *ds, const uint64_t *const *instances, size_t m,
                                          const uint8_t seed[32] /*nullable*/, int *status /*nullable*/);
+/* The same as ONE relation over the members of every size, the succinct half included: halo_pcdl_check_batch_fused's relation with
+ * a size per member.  With E_a and F_a as there, each at its own lg_a, and F_a = U_a - <pad(h_a), G[0 .. n_max)>:
+ *   sum_a [ r_a C'_a + sum_j (r_a xi_a,j+1^-1 L_a,j + r_a xi_a,j+1 R_a,j) + (s_a - r_a c_a) U_a ] + (sum_a r_a (v_a - c_a hz_a) xi_a,0) H
+ *       ==  < sum_a s_a pad(h_a) , G[0 .. n_max) >.
+ * Left: one variable-base MSM over T = sum_a (2 lg_a + 2) + 1 points of the caller's; right: the mixed combined call's one
+ * n_max-point MSM over the key.  The contract:
+ *  1. Arguments, whole-call errors (before any work, status not written), the "instance i: ..." message and the return rule are
+ *     halo_pcdl_check_batch_mixed's.
+ *  2. Every member's structure and transcript run exactly as in halo_pcdl_succinct_check, per class of equal d (a class of 1000
+ *     members or more on the device, by the uniform call's rule).  A member rejected there gets that status and takes no further
+ *     part -- a member whose d + 1 exceeds the key included: it gets what halo_pcdl_check_batch_mixed reports for it.
+ *  3. M = the number of members accepted so far with d_i >= 1, over ALL classes.  Members with d_i = 0 always take their class's
+ *     exact path.  M <= 1: the exact path of halo_pcdl_check_batch_mixed.  M >= 2 (at most 65535, every lg <= 24, fewer than 2^32
+ *     terms with the last chunk filled up; beyond: the exact path): the relation above.  The term scalars are computed on the
+ *     device, one lane per member at the member's own size, with one field inversion each; the members' terms lie one behind the
+ *     other with nothing between them, are cut into MSMs of at most the key's size and run in batched sequences on a second idle
+ *     slot beside the key's MSM (one idle slot: after it), their sums added in order.  The right side's scalars are formed from
+ *     tables of their own lengths; its MSM is the fixed-base table's where the key has one and n_max reaches it.
+ *  4. If the relation HOLDS, every such member's status is 0.
+ *  5. If it FAILS -- or the optional staging is refused -- halo_pcdl_check_batch_mixed's exact path decides: the succinct half
+ *     per class, then the per-member MSMs.  So a reject never depends on the weights, and status[], the return code and the
+ *     message equal halo_pcdl_check_batch_mixed's on the same blobs.
+ *  6. The one difference from the exact call: a set of blobs with some E_a != 0 or F_a != 0 is wrongly accepted with probability
+ *     1/r (r = the group order, ~2^-254) per hash evaluation an adversary spends.  Two independent weights per member, for the
+ *     reason halo_pcdl_check_batch_fused gives.
+ *  7. All device memory the call takes is optional staging (halo_set_memory_budget): without it the exact path runs and gives the
+ *     same statuses.  A multi-device context runs the call on its own device (devices[0]); a caller's MSM in flight on another slot
+ *     is left alone; no idle slot: HALO_E_ARG.
+ * Weight rule (mixed fused): a domain of its own, and every member's index and degree bound in the hash.
+ * W_i = halo_instance_words(lg(d_i + 1)), seed32 as above.
+ *   D   = SHA3-256("halo-accumulation/check-batch-mixed-fused/v1" || seed32 || LE64(M) || for every member taking part, in member
+ *         order: LE64(i) || LE64(d_i) || its W_i Instance words as little-endian bytes)
+ *   r_a = (SHA3-256(D || LE64(2 a)) read as a little-endian integer) mod r,
+ *   s_a = (SHA3-256(D || LE64(2 a + 1)) read as a little-endian integer) mod r,      a = 0 .. M - 1 its position among them.
+ * When to call it (one MI355X, tools/time_check_mixed.py --big, profiles/r22_check_mixed_fused.json; the workloads of
+ * halo_pcdl_check_batch_mixed_combined above; against one halo_pcdl_check_batch_fused per size and against
+ * halo_pcdl_check_batch_mixed_combined in the same alternating runs, medians of 5): whenever members of several sizes are checked.
+ * Against a fused call per size, 2^14 points: 2.40, 1.94, 1.82 and 1.22 times its speed at 12, 60, 120 and 600 members, all four
+ * rows WON (every run below every run of the per-size calls); 2^20 points: 2.64, 1.92 and 1.69 times at 13, 62 and 123 members,
+ * WON, and 1.20 times at 604 members, NOT won (one run of five inside the per-size calls' range).  Against
+ * halo_pcdl_check_batch_mixed_combined 1.44 to 2.91 times, and against a combined call per size 1.61 to 3.11 times, all eight
+ * rows WON.  At 600 members the transcripts on the host pool are what remains of every way. */
+int halo_pcdl_check_batch_mixed_fused(halo_ctx *ctx, const size_t *ds, const uint64_t *const *instances, size_t m,
+                                      const uint8_t seed[32] /*nullable*/, int *status /*nullable*/);
 /* One rank's half of pcdl::check over a key sharded cyclically (halo_ctx_create_urs_strided: point i on rank i mod stride,
  * offset = the rank): the succinct check (pcdl.rs:333, the same on every rank; d + 1 may be up to stride * the shard's size)
  * and this rank's share of CM.Commit(ck, h) (pcdl.rs:338) over its own points.  U_out = the proof's U after the succinct
@@ -432,12 +477,14 @@ int halo_acc_decider_batch_combined(halo_ctx *ctx, size_t d, const uint64_t *acc
  * accumulator's Instance prefix is what is read, and what is hashed into the weights) */
 int halo_acc_decider_batch_fused(halo_ctx *ctx, size_t d, const uint64_t *accs, size_t m, const uint8_t seed[32] /*nullable*/,
                                  int *status /*nullable*/);
-/* acc::decider of m accumulators, each with its own degree bound: halo_pcdl_check_batch_mixed / .._mixed_combined over the
- * accumulators' Instance prefixes, with their contracts.  accs[i] points at one Accumulator blob of
+/* acc::decider of m accumulators, each with its own degree bound: halo_pcdl_check_batch_mixed / .._mixed_combined / .._mixed_fused
+ * over the accumulators' Instance prefixes, with their contracts.  accs[i] points at one Accumulator blob of
  * halo_accumulator_words(lg(ds[i] + 1)) words; its Instance prefix is what is checked and what is hashed into the weights. */
 int halo_acc_decider_batch_mixed(halo_ctx *ctx, const size_t *ds, const uint64_t *const *accs, size_t m, int *status /*nullable*/);
 int halo_acc_decider_batch_mixed_combined(halo_ctx *ctx, const size_t *ds, const uint64_t *const *accs, size_t m,
                                           const uint8_t seed[32] /*nullable*/, int *status /*nullable*/);
+int halo_acc_decider_batch_mixed_fused(halo_ctx *ctx, const size_t *ds, const uint64_t *const *accs, size_t m,
+                                       const uint8_t seed[32] /*nullable*/, int *status /*nullable*/);
 /* acc::verifier (acc.rs:223-243) of k accumulators at once: benches/acc.rs:64-74's loop in one call.  accs = k Accumulator blobs
  * at stride halo_accumulator_words(lg(d+1)); counts[j] = the number of Instances member j verifies against accs[j] (0 allowed);
  * instances = sum(counts) Instance blobs at stride halo_instance_words(lg(d+1)), member j's right after member j - 1's.

@@ -39,10 +39,10 @@ extern "C" {
  * from which halo_*_decode_batch decompresses on the device, >= 1; 0: the measured default; "batch_stage_fail" refuses its staging
  * too: the host pool), "check_combined_parts" (parts the polynomials of halo_pcdl_check_batch_combined's
  * scalars are cut into, >= 1, clamped to the accepted members; 0: a wave per SIMD), "check_combined_cap" (their tables per pass, >= 1;
- * 0: the default) -- the scalars are the same words under every value of the two; the mixed combined calls read both hooks too --, "check_combined_usum" (the right side
+ * 0: the default) -- the scalars are the same words under every value of the two; the mixed combined and the mixed fused calls read both hooks too --, "check_combined_usum" (the right side
  * sum r_a U_a of a combined check: 1 the host pool, 2 the device where a second slot is idle; 0: by the member count; another
- * value is HALO_E_ARG; "batch_stage_fail" makes the combined and the fused calls take the exact path), "check_fused_chunk" (terms per
- * MSM of the left side of halo_pcdl_check_batch_fused: at least 8, clamped to the context's size; 0: that size; 1..7 or a negative
+ * value is HALO_E_ARG; "batch_stage_fail" makes the combined and the fused calls, the mixed ones included, take the exact path), "check_fused_chunk" (terms per
+ * MSM of the left side of halo_pcdl_check_batch_fused and of halo_pcdl_check_batch_mixed_fused: at least 8, clamped to the context's size; 0: that size; 1..7 or a negative
  * value is HALO_E_ARG -- the statuses are the same under every value), "reset" (all off).
  * The launch plan of the Fr kernels (csrc/fr_plan.hpp), each taken before the environment's value and the measured default, every
  * plan giving the same field elements: "pow_e" (elements per lane of k_powers, k_poly_eval_partial, k_h_coeffs and
@@ -126,6 +126,17 @@ int halo_dev_check_fused_weights(const uint64_t *blobs, size_t stride_words, con
  * the left side's MSM reads); h_out = sum_a r_a (v_a - c_a h_a(z_a)) xi_a,0 likewise.  1 <= M <= 65535, 1 <= lg_n <= 24; a zero
  * challenge gives zeros for its inverses.  Temporary device buffers of this call only. */
 int halo_dev_check_fused_terms(halo_ctx *ctx, const uint64_t *recs, size_t M, size_t lg_n, uint64_t *scalars_out, uint64_t h_out[4]);
+/* The weights of halo_pcdl_check_batch_mixed_fused / halo_acc_decider_batch_mixed_fused (the mixed fused rule of
+ * include/halo_accumulation.h), arguments and errors as halo_dev_check_mixed_weights: out = 2 A x 4 Montgomery words, r_0 | s_0 |
+ * r_1 | s_1 | ..  Host only, no context. */
+int halo_dev_check_mixed_fused_weights(const uint64_t *const *blobs, const size_t *ds, const size_t *idx, size_t A,
+                                       const uint8_t seed[32] /*nullable*/, uint64_t *out);
+/* The term kernel of the mixed fused check on its own (k_mixed_terms, then the sum of H's shares: k_fr_sum_rows): M members of their
+ * own sizes lgs[a].  recs = their records one behind the other, member a's of lgs[a] + 6 elements laid out as for
+ * halo_dev_check_fused_terms; scalars_out = their scalars one behind the other, (2 lgs[a] + 2) x 4 words for member a, canonical;
+ * h_out = the sum of their shares of H's scalar.  The descriptors (offsets as prefix sums) are the product's.  1 <= M <= 65535,
+ * 1 <= lgs[a] <= 24, no null pointer: else HALO_E_ARG.  Temporary device buffers of this call only. */
+int halo_dev_check_mixed_terms(halo_ctx *ctx, const uint64_t *recs, const size_t *lgs, size_t M, uint64_t *scalars_out, uint64_t h_out[4]);
 
 /* replay cached hipGraphs of the MSM launch sequence when the same shape repeats (default on) */
 int halo_set_graphs(halo_ctx *ctx, int on);  /* also: environment HALO_GRAPHS=0 at context creation; HALO_TRACE=1 logs every launch */

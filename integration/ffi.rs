@@ -62,6 +62,9 @@ extern "C" {
     pub fn halo_pcdl_check_batch_mixed_combined(ctx: *mut HaloCtx, ds: *const usize, instances: *const *const u64, m: usize, seed: *const u8, status: *mut c_int) -> c_int;
     pub fn halo_acc_decider_batch_mixed(ctx: *mut HaloCtx, ds: *const usize, accs: *const *const u64, m: usize, status: *mut c_int) -> c_int;
     pub fn halo_acc_decider_batch_mixed_combined(ctx: *mut HaloCtx, ds: *const usize, accs: *const *const u64, m: usize, seed: *const u8, status: *mut c_int) -> c_int;
+    // ... and as one fused relation over the members of every size, the succinct relations included
+    pub fn halo_pcdl_check_batch_mixed_fused(ctx: *mut HaloCtx, ds: *const usize, instances: *const *const u64, m: usize, seed: *const u8, status: *mut c_int) -> c_int;
+    pub fn halo_acc_decider_batch_mixed_fused(ctx: *mut HaloCtx, ds: *const usize, accs: *const *const u64, m: usize, seed: *const u8, status: *mut c_int) -> c_int;
     // acc::verifier of k accumulators at once (counts[j] instances for accs[j]; status may be null)
     pub fn halo_acc_verifier_batch(ctx: *mut HaloCtx, d: usize, instances: *const u64, counts: *const usize, k: usize, accs: *const u64, status: *mut c_int) -> c_int;
     // acc::prover of k members at once (counts[j] instances for member j; rng_state and status may be null)

@@ -1,14 +1,17 @@
-"""Members of SEVERAL degree bounds checked three ways, alternating in one process after a warm-up of each:
+"""Members of SEVERAL degree bounds checked four ways, alternating in one process after a warm-up of each:
 
-  mixed      ONE halo_pcdl_check_batch_mixed_combined over all the members (one MSM of the largest size for all of them);
-  combined   the best a caller could do before it: the members sorted by d, one halo_pcdl_check_batch_combined per size;
-  fused      the same with one halo_pcdl_check_batch_fused per size.
+  mixed        ONE halo_pcdl_check_batch_mixed_combined over all the members (one MSM of the largest size for all of them);
+  combined     the best a caller could do before it: the members sorted by d, one halo_pcdl_check_batch_combined per size;
+  fused        the same with one halo_pcdl_check_batch_fused per size;
+  mixed_fused  ONE halo_pcdl_check_batch_mixed_fused over all the members (the succinct relations in the same relation).
 
 Workloads: a key of 2^14 points with the members spread evenly over lg 9 .. 14, and (--big) a key of 2^20 points with the same
 members plus 1 .. 4 of lg 20; totals of 12, 60, 120 and 600 members.  The members are honest Instances (random_instance_batch: a
 check's work does not depend on what was opened); every way must accept all of them.  Every row keeps median, least and
-greatest of --reps runs (5 unless given) of each way, in ms, and says whether the mixed call's range lies below both others'
-("won"), or which ranges overlap or lie below it ("not won").  Prints one JSON line; --out writes the same to a file."""
+greatest of --reps runs (5 unless given) of each way, in ms, and says whether the mixed call's range lies below the two per-size
+ways' ("won"), or which ranges overlap or lie below it ("not won"); and the same for the mixed fused call against each of the three
+other ways ("mixed_fused_won": every one of its runs below every run of that way).  Prints one JSON line; --out writes the same to a
+file."""
 import argparse
 import ctypes as C
 import json
@@ -43,7 +46,7 @@ def members_of(ctx, total, seed, extra_lg20=0):
 
 
 class Shapes:
-    """the three ways' arguments, built once per workload (packing is not what is timed)"""
+    """the four ways' arguments, built once per workload (packing is not what is timed)"""
 
     def __init__(self, ctx, members):
         self.ctx, self.m = ctx, len(members)
@@ -55,13 +58,19 @@ class Shapes:
             mine = [q for q in members if int(q[12]) == d]
             self.classes.append((d, np.ascontiguousarray(np.concatenate(mine)), len(mine)))
 
-    def mixed(self):
+    def one_call(self, fn):
         st = (C.c_int * self.m)()
         t = time.perf_counter()
-        rc = self.ctx.lib.halo_pcdl_check_batch_mixed_combined(self.ctx.h, self.ds, self.ptrs, self.m, None, st)
+        rc = fn(self.ctx.h, self.ds, self.ptrs, self.m, None, st)
         ms = (time.perf_counter() - t) * 1e3
         assert rc == 0 and not any(st), self.ctx.lib.halo_last_error()
         return ms
+
+    def mixed(self):
+        return self.one_call(self.ctx.lib.halo_pcdl_check_batch_mixed_combined)
+
+    def mixed_fused(self):
+        return self.one_call(self.ctx.lib.halo_pcdl_check_batch_mixed_fused)
 
     def per_class(self, fn):
         t = time.perf_counter()
@@ -79,7 +88,7 @@ class Shapes:
 
 
 def row_of(shape, reps):
-    ways = (("mixed", shape.mixed), ("combined", shape.combined), ("fused", shape.fused))
+    ways = (("mixed", shape.mixed), ("combined", shape.combined), ("fused", shape.fused), ("mixed_fused", shape.mixed_fused))
     for _, fn in ways:  # warm-up of each shape
         fn()
     runs = {name: [] for name, _ in ways}
@@ -92,6 +101,10 @@ def row_of(shape, reps):
     row["not_below"] = lost  # the ways whose range overlaps the mixed call's, or lies below it
     row["speedup_vs_combined"] = round(row["combined"]["median"] / row["mixed"]["median"], 2)
     row["speedup_vs_fused"] = round(row["fused"]["median"] / row["mixed"]["median"], 2)
+    # the mixed fused call against each other way: won = every one of its runs below every run of that way
+    others = ("fused", "mixed", "combined")
+    row["mixed_fused_won"] = {name: row["mixed_fused"]["max"] < row[name]["min"] for name in others}
+    row["mixed_fused_speedup"] = {name: round(row[name]["median"] / row["mixed_fused"]["median"], 2) for name in others}
     return row
 
 
